@@ -20,7 +20,10 @@ slab of the configuration's length (N = 8 on c4: a 512^3 x 256 series in eight s
 (N = 8 on c4 is BASELINE.json's literal `moving_extremum_3d 512^3 x 32, 8xMI355X` case: 4 timesteps + 1 halo slice per rank).
 `--timesteps T` overrides the series length.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and `cpu_baseline` objects.
+Prints ONE JSON line on rank 0 (contract in the task statement) with a `roofline` object.  A plain run sets up, warms up, times
+the K steps and prints that line; `--full` adds what the headline figure does not need (the `cpu_baseline` objects, the other
+configurations, the streaming tracker, pass 2 and the `check` of the result, ...).  `--dump-outputs DIR` writes what the last
+timed step returned (records, factors) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -107,6 +110,28 @@ def check_records(name, case, dims, nt, recs, paths, want_paths):
         ok = ok and err < 1e-6 and out["types"] == [2] and crossed and len(recs) >= 2 * nt - 1
     out["ok"] = bool(ok)
     return out
+
+
+DUMP_MAX_BYTES = 64 * 10**6
+
+
+def dump_outputs(out_dir, recs, factors):
+    """--dump-outputs: what the last timed step handed its caller -- the records (ftkx_cp_t, one file per field) and the quantisation
+    factors -- as float64 .npy files, so that two builds can be compared output for output.  64-bit integers (tags, factors) go as their
+    high and low 32 bits, each exact in float64.  A record set above DUMP_MAX_BYTES: a fixed, seeded sample of its rows (records_row)."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(recs)
+    per_row = 8 * 12
+    rows = np.arange(n)
+    if n * per_row > DUMP_MAX_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_BYTES // per_row, replace=False))
+    r = recs[rows]
+    tag, factors = r["tag"].astype(np.uint64), np.asarray(factors, dtype=np.uint64)
+    arrays = {"records_x": r["x"], "records_t": r["t"], "records_scalar": r["scalar"], "records_type": r["type"], "records_aux": r["aux"],
+              "records_tag_hi": tag >> np.uint64(32), "records_tag_lo": tag & np.uint64(0xFFFFFFFF), "records_row": rows,
+              "n_records": np.array([n]), "factors_hi": factors >> np.uint64(32), "factors_lo": factors & np.uint64(0xFFFFFFFF)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def glibc_version():
@@ -681,6 +706,13 @@ def main():
     ap.add_argument("--no-other-configs", action="store_true", help="N = 1: skip the few passes of the other BASELINE configurations that follow the timed region")
     ap.add_argument("--dump-merged", default=None, help="rank 0 writes the merged records and the curves traced from them (npz)")
     ap.add_argument("--no-sustained", action="store_true", help="N = 1: skip the >= 1.2 s repetition of the timed loop that follows it")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need (off by default): the >= 1.2 s repetition, the single-pass latency, "
+                         "the per-kernel times, pass 2 and the check of the result, the other configurations, the streaming tracker, the boundary call, "
+                         "the patched reference tracker, the CPU baselines; N > 1: the other scaling and the other halo convention.  The --no-* options "
+                         "above still leave parts of it out")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps: write what the last timed step handed its caller (records, factors) as DIR/<name>.npy, float64")
     ap.add_argument("--rank-timeout", type=int, default=900, help="--gpus N without a launcher: seconds the N child processes get before they are ended")
     ap.add_argument("--fail-rank", type=int, default=-1, help=argparse.SUPPRESS)      # (tests: this rank exits with code 7 before it joins the process group)
     args = ap.parse_args()
@@ -720,11 +752,11 @@ def main():
 
     env = (torch, dist, ftk_amd, synthetic, tslab, world, rank, local_rank, dev, multi)
     out = job(args, env)
-    if world > 1 and args.scaling == "strong" and not args.no_other_scaling:
+    if world > 1 and args.scaling == "strong" and args.full and not args.no_other_scaling:
         # the other way to scale, for the record: every rank a slab of the configuration's whole length (weak scaling), a few passes
         import copy
         a2 = copy.copy(args)
-        a2.scaling, a2.steps, a2.warmup, a2.light = "weak", min(args.steps, 3), 1, True
+        a2.scaling, a2.steps, a2.warmup, a2.light, a2.dump_outputs = "weak", min(args.steps, 3), 1, True, None
         o2 = job(a2, env)
         if rank == 0:
             out["other"] = {k: o2[k] for k in ("scaling", "steps", "ms_per_step", "value", "config", "halo_exchange", "roofline_end_to_end")}
@@ -737,7 +769,7 @@ def main():
 def job(args, env):
     """one measurement: set-up, warm-up, timed passes, the JSON line's dictionary (rank 0; None elsewhere)"""
     torch, dist, ftk_amd, synthetic, tslab, world, rank, local_rank, dev, multi = env
-    light = getattr(args, "light", False)
+    light = getattr(args, "light", False) or not args.full     # (without --full: the headline measurement alone)
     nd, nv, case, dims, nt = CONFIGS[args.config]
     if args.timesteps > 0:
         nt = args.timesteps
@@ -949,6 +981,7 @@ def job(args, env):
     recs, st = passes(args.steps)
     barrier()
     elapsed = time.perf_counter() - tt0
+    recs, last_factors = np.array(recs), np.array(getattr(one_pass, "factors", factors))      # (the records lie in the library's host buffer, which the next pass reuses)
     per_pass_ms = np.diff(np.array([tt0] + pass_stamps[:args.steps])) * 1e3      # (pipelined: the time between consecutive completions)
     timed_paths = list(path_list)
     own_elapsed = elapsed
@@ -1001,7 +1034,7 @@ def job(args, env):
                       "slab_host": ("C++ (include/ftkx_slab.h) over " + slab.transport) if slab is not None else "host-driven sequence (Python)",
                       "distinct_devices": len(set(e["pci_bus_id"] for e in everyone)), "per_rank": everyone}
     latency_ms = None
-    if pipelined:
+    if pipelined and args.full:
         # the same pass on its own (ftkx_sweep_series, nothing else in flight): what one call takes from its first launch to the records
         saved = list(host_ms)
         ctx.set_profiling(0)
@@ -1013,7 +1046,7 @@ def job(args, env):
         latency_ms = (time.perf_counter() - tl0) / 3 * 1e3
         host_ms[0], host_ms[1], host_ms[2] = saved
     ktimes_all, k_all = None, 3
-    if not args.no_kernel_events and not (multi and args.compact_halo):
+    if args.full and not args.no_kernel_events and not (multi and args.compact_halo):
         ctx.set_profiling(1)
         for _ in range(k_all):
             one_pass()
@@ -1022,7 +1055,7 @@ def job(args, env):
         ctx.set_profiling(0)
 
     if slab is not None:
-        npass = args.steps + (3 if pipelined else 0)      # (the latency passes behind the timed region count as well)
+        npass = args.steps + (3 if latency_ms is not None else 0)      # (the latency passes behind the timed region count as well)
         compact_bytes[0], compact_bytes[1], compact_bytes[3] = slab.bytes_sent * args.steps / npass, slab.bytes_received * args.steps / npass, slab.fallbacks
         compact_bytes[2] = max(getattr(slab, "last_asked", 0), 0) * args.steps
         halo_info["protocol"] = "queued on the stream between the stages of the slab pass (ftkx_series_dist_*): all_gather of 4 doubles per rank, masks, request, reply"
@@ -1052,10 +1085,14 @@ def job(args, env):
     # ---- after the timed region: merge the slabs' hit buffers on rank 0 and run pass 2 on the merged set ("host merge of
     # hit buffers into the union_find / trace stage"; critical_point_tracker.hh:689-717).  Curves cross slab boundaries.
     tm0 = time.perf_counter()
-    merged = tslab.gather_records(np.array(recs), 0) if multi else np.array(recs)
+    merged = None
+    if args.full or args.dump_merged or args.dump_outputs:
+        merged = tslab.gather_records(recs, 0) if multi else recs
     tm1 = time.perf_counter()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, merged, last_factors)
     pass2 = None
-    if rank == 0:
+    if rank == 0 and (args.full or args.dump_merged):
         ftk_amd.pass2(nd, dom, merged, ctx)               # (first call: the worker threads start, the candidate tables go up)
         curves, loop, nspecial, trajs, ms_trace, ms_post = ftk_amd.pass2(nd, dom, merged, ctx)
         _c, _l, _n, _t, ms_trace_host, _p = ftk_amd.pass2(nd, dom, merged)
@@ -1071,7 +1108,7 @@ def job(args, env):
     # the result itself against what the configuration must give (cheap, size-independent): the device-driven form was what ran, tags
     # ascending and unique, the expected count / type histogram (c1, c2, c5) or the single extremum on x0 + dir * t (c3, c4)
     check = {"hits": n_hits}
-    if rank == 0 and not args.exact_only:
+    if rank == 0 and args.full and not args.exact_only:
         if (not multi or slab is not None) and not args.host_driven:
             # ((1, 64): the fused tail declined late -- few coarse cells with more records than it orders -- and the chain took the pass: device-driven
             # all the same; only the small test configurations see it)
@@ -1100,7 +1137,10 @@ def job(args, env):
         avg_ms = dom_ms / max(1, dom_n)
         slices_per_launch = len(own) * args.steps / max(1, dom_n)
         alg_bytes_launch = (8.0 * c * n_vertex) * slices_per_launch + 72.0 * len(recs) * args.steps / max(1, dom_n)
-        achieved = alg_bytes_launch / (avg_ms * 1e-3) / 1e9
+        # (no timed launch of the dominant kernel -- a pass without a mask kernel, and no extra passes without --full: no figure)
+        achieved = alg_bytes_launch / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else None
+        frac = achieved / HBM_PEAK_GBS if achieved else None
+        frac_stream = achieved / STREAM_CEILING_GBS if achieved else None
         kt_break = ktimes_all if ktimes_all else ktimes
         n_break = k_all if ktimes_all else args.steps
         all_ms = sum(v[0] for v in kt_break.values()) / n_break
@@ -1143,14 +1183,14 @@ def job(args, env):
                                else "host-driven batch (slices_prepare, host factors, enqueue, collect)",
                        "split_pass": (ctx.series_split_decision() if slab is None and series_paths else None),
                        "input_resident": "the field the tracker API is given (S, or V for vector input) in HBM; gradient/Jacobian evaluated in flight"},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": frac,
                          "traffic": traffic, "traffic_source": traffic_source,
                          "traffic_ratio": (traffic / alg_bytes_launch) if traffic else None,     # HBM bytes moved / algorithmic bytes: > 1 = re-reads
-                         "streaming_ceiling": STREAM_CEILING_GBS, "frac_of_streaming_ceiling": achieved / STREAM_CEILING_GBS, "kernel": kernel_symbol, "kernel_family": "ftkx::%s<%d>" % (domk, nd), "avg_launch_ms": avg_ms, "launches_timed": int(dom_n),
+                         "streaming_ceiling": STREAM_CEILING_GBS, "frac_of_streaming_ceiling": frac_stream, "kernel": kernel_symbol, "kernel_family": "ftkx::%s<%d>" % (domk, nd), "avg_launch_ms": avg_ms, "launches_timed": int(dom_n),
                          "algorithmic_bytes_per_launch": alg_bytes_launch, "slices_per_launch": slices_per_launch,
-                         "all_kernels_ms_per_pass": all_ms, "achieved_all_kernels": alg_bytes_pass / (all_ms * 1e-3) / 1e9,
+                         "all_kernels_ms_per_pass": all_ms, "achieved_all_kernels": alg_bytes_pass / (all_ms * 1e-3) / 1e9 if all_ms > 0 else None,
                          "kernel_ms_per_pass": {k: v[0] / n_break for k, v in kt_break.items()},
-                         "kernel_ms_note": "avg_launch_ms: events around the mask kernel only, inside the timed region; kernel_ms_per_pass: %d extra passes with events around every kernel family (cull = coarse cull + factors; exact = everything behind them)" % n_break},
+                         "kernel_ms_note": "avg_launch_ms: events around the mask kernel only, inside the timed region; kernel_ms_per_pass: %s" % ("%d extra passes with events around every kernel family (cull = coarse cull + factors; exact = everything behind them)" % n_break if ktimes_all else "the timed passes (--full: every kernel family)")},
             # the factor pre-pass is inside the timed region now (fused into the mask kernel): nothing of the sweep is left outside
             "prepass_ms": 0.0,
             "end_to_end_ms": elapsed / args.steps * 1e3,
@@ -1180,8 +1220,8 @@ def job(args, env):
             for name in ("c1", "c2", "c3", "c4", "c5"):
                 if name == args.config:
                     others[name] = {"workload": out["config"]["workload"], "steps": args.steps, "ms_per_step": out["ms_per_step"], "value": out["value"],
-                                    "kernel": kernel_symbol, "kernel_avg_launch_ms": avg_ms, "frac": achieved / HBM_PEAK_GBS,
-                                    "frac_of_streaming_ceiling": achieved / STREAM_CEILING_GBS,
+                                    "kernel": kernel_symbol, "kernel_avg_launch_ms": avg_ms, "frac": frac,
+                                    "frac_of_streaming_ceiling": frac_stream,
                                     "end_to_end_frac": out["roofline_end_to_end"]["frac"], "hits": n_hits, "check": check, "headline": True, **spread(per_pass_ms)}
                     continue
                 try:

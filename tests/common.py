@@ -65,6 +65,22 @@ def by_tag(recs):
     return recs[np.argsort(recs["tag"], kind="stable")]
 
 
+def records_digest(recs):
+    """SHA-256 of a record set in the form assert_records_equal(..., coord_tol=0.0) compares it: ordered by tag; tag, type, ordinal,
+    timestep, x, t and the first scalar, every NaN alike and -0.0 == 0.0 (tests/golden/fuzz_reference.json holds such digests)"""
+    import hashlib
+    r = by_tag(recs)
+    h = hashlib.sha256()
+    for f, dt in (("tag", "<u8"), ("type", "<u4"), ("ordinal", "<i4"), ("timestep", "<i4")):
+        h.update(np.ascontiguousarray(r[f], dtype=dt).tobytes())
+    s = r["scalar"][:, 0] if r["scalar"].ndim == 2 else r["scalar"]
+    for a in (r["x"], r["t"], s):
+        a = np.array(a, dtype="<f8") + 0.0
+        a[np.isnan(a)] = np.nan
+        h.update(a.tobytes())
+    return h.hexdigest()
+
+
 def assert_records_equal(got, ref, *, coord_tol=0.0, what=""):
     """tag / type / (ordinal, timestep when present) exact; coordinates and scalar within coord_tol
     (0.0 = bit-identical, NaN == NaN).  `got` and `ref` are structured arrays with fields

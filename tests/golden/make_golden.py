@@ -13,6 +13,7 @@ import os
 import subprocess
 import sys
 import tempfile
+import zipfile
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -59,6 +60,14 @@ def run_file(out, steps, nd, nv, env=None):
     os.unlink(inp)
 
 
+def savez_lzma(path, **arrays):
+    """np.savez_compressed with LZMA in place of deflate (np.load reads either): the largest fixtures stay below 1 MiB"""
+    with zipfile.ZipFile(path, "w", compression=zipfile.ZIP_LZMA) as z:
+        for k, v in arrays.items():
+            with z.open(k + ".npy", "w") as f:
+                np.lib.format.write_array(f, np.asanyarray(v), allow_pickle=False)
+
+
 def save(name, d, extra=None):
     meta = dict(nd=d["nd"], nv=d["nv"], dims=np.array(d["dims"]), DT=d["DT"])
     meta.update(extra or {})
@@ -73,7 +82,7 @@ def save(name, d, extra=None):
         allp = np.concatenate([c[1] for c in d["pp"]]) if d["pp"] else np.zeros(0, dtype=[("tag", "<u8"), ("type", "<u4"), ("_pad", "<u4"), ("t", "<f8")])
         meta["pp_tags"] = allp["tag"]; meta["pp_types"] = allp["type"]; meta["pp_t"] = allp["t"]
         meta["pp_loop"] = np.array([c[0] for c in d["pp"]], dtype=np.int32)
-    np.savez_compressed(os.path.join(HERE, name + ".npz"), steps=d["steps"], factors=d["factors"], records=d["records"], **meta)
+    savez_lzma(os.path.join(HERE, name + ".npz"), steps=d["steps"], factors=d["factors"], records=d["records"], **meta)
     types, counts = np.unique(d["records"]["type"], return_counts=True)
     print(f"{name}: {len(d['records'])} records ({int(d['records']['ordinal'].sum())} ordinal) types "
           f"{dict(zip(types.tolist(), counts.tolist()))} factors {sorted(set(d['factors'].tolist()))} "

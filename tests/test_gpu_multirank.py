@@ -21,7 +21,7 @@ def _free_port():
 
 
 def _bench(n, cfg, extra=(), dump=None, env=None):
-    common = ["bench.py", "--gpus", str(n), "--config", cfg, "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-other-configs", "--no-streaming-tracker", *extra]
+    common = ["bench.py", "--gpus", str(n), "--config", cfg, "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-other-configs", "--no-streaming-tracker", *extra]
     if dump:
         common += ["--dump-merged", str(dump)]
     if n == 1:
@@ -118,7 +118,7 @@ def test_the_collectives_run_on_rccl(tmp_path):
     the driver's 8-GPU run makes -- and the result is the plain single-rank one."""
     one = _bench(1, "small3", dump=tmp_path / "one.npz")
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()), RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
-    cmd = [sys.executable, "bench.py", "--gpus", "1", "--config", "small3", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--force-dist", "--backend", "nccl",
+    cmd = [sys.executable, "bench.py", "--gpus", "1", "--config", "small3", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--force-dist", "--backend", "nccl",
            "--dump-merged", str(tmp_path / "rccl.npz")]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -141,7 +141,7 @@ def test_bench_launches_its_own_ranks(tmp_path):
     the merged records are the single-rank ones byte for byte.  A rank that dies ends the run at once, the others are not waited for."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     one = _bench(1, "small3", dump=tmp_path / "one.npz")
-    cmd = [sys.executable, "bench.py", "--gpus", "3", "--backend", "gloo", "--single-device", "--config", "small3", "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, "bench.py", "--gpus", "3", "--backend", "gloo", "--single-device", "--config", "small3", "--steps", "2", "--warmup", "1", "--full",
            "--no-other-scaling", "--dump-merged", str(tmp_path / "three.npz")]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-3000:]

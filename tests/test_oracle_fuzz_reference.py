@@ -1,19 +1,17 @@
 """The oracle against THE REFERENCE ITSELF on seeded random series (not gpu): oracle/_ref/ftk_ref_driver -- hguo/ftk's own trackers
-compiled from its headers by oracle/Makefile -- tracks each series in `file` mode; the C restatement must give the same records
-(bit for bit), factors included.  Pins the oracle beyond the committed fixtures; skipped where the binary was not built."""
+compiled from its headers by oracle/Makefile -- tracked each series in `file` mode; the C restatement must give the same records
+(bit for bit), factors included.  Pins the oracle beyond the committed fixtures.  What the reference returned is recorded in
+tests/golden/fuzz_reference.json (tests/golden/make_golden_fuzz.py: record counts, factors, digests of the records)."""
+import json
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
-from common import assert_records_equal
-from refdump import read_dump, write_input
+from common import GOLDEN, records_digest
 from test_gpu_fuzz import _field, _vector_series, KINDS
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DRIVER = os.path.join(ROOT, "oracle", "_ref", "ftk_ref_driver")
+SEEDS = range(12)
 
 
 @pytest.fixture(scope="module")
@@ -23,9 +21,14 @@ def oracle():
     return pyoracle
 
 
-@pytest.mark.skipif(not os.path.exists(DRIVER), reason="oracle/_ref/ftk_ref_driver not built")
-@pytest.mark.parametrize("seed", range(12))
-def test_oracle_equals_the_real_reference_on_random_series(oracle, seed):
+@pytest.fixture(scope="module")
+def recorded():
+    with open(os.path.join(GOLDEN, "fuzz_reference.json")) as f:
+        return json.load(f)["seeds"]
+
+
+def fuzz_cases(seed):
+    """the four random series of a seed -> (steps, nd, nv, the reference driver's environment, the oracle's options, what)"""
     rng = np.random.default_rng(7000 + seed)
     for case in range(4):
         nd = int(rng.choice([2, 3]))
@@ -48,13 +51,17 @@ def test_oracle_equals_the_real_reference_on_random_series(oracle, seed):
             env["FTK_REF_TYPE_FILTER"] = str(type_filter)
         if degrees:
             env["FTK_REF_DEGREES"] = "1"
-        with tempfile.TemporaryDirectory() as tmp:
-            inp, out = os.path.join(tmp, "in.bin"), os.path.join(tmp, "out.bin")
-            write_input(inp, steps, nd, nv)
-            e = dict(os.environ); e.update(env)
-            subprocess.run([DRIVER, "file", inp, out, "8"], check=True, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, env=e, timeout=300)
-            ref = read_dump(out)
-        got, gf, _ = oracle.track(steps, nd, nv, robust=robust, type_filter=type_filter, compute_degrees=degrees, tag_mode=oracle.TAG_REFERENCE, nthreads=8)
         what = f"seed {seed} case {case}: nd {nd} nv {nv} dims {dims} nt {nt} {kind} robust {robust} filter {type_filter} degrees {degrees}"
-        assert np.array_equal(gf, ref["factors"]), what + f": factors {gf} vs {ref['factors']}"
-        assert_records_equal(got, ref["records"], coord_tol=0.0, what=what)
+        yield steps, nd, nv, env, dict(robust=robust, type_filter=type_filter, compute_degrees=degrees), what
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_oracle_equals_the_real_reference_on_random_series(oracle, recorded, seed):
+    want = recorded[str(seed)]
+    cases = list(fuzz_cases(seed))
+    assert len(cases) == len(want)
+    for (steps, nd, nv, _env, opts, what), ref in zip(cases, want):
+        got, gf, _ = oracle.track(steps, nd, nv, **opts, tag_mode=oracle.TAG_REFERENCE, nthreads=8)
+        assert [int(f) for f in gf] == ref["factors"], what + f": factors {gf} vs {ref['factors']}"
+        assert len(got) == ref["records"], what + f": {len(got)} records, the reference returned {ref['records']}"
+        assert records_digest(got) == ref["records_sha256"], what + ": the records are not bit-identical to the reference's"

@@ -3,6 +3,7 @@ sections 2-4) -- as an artefact that is checked: it applies cleanly to the refer
 this repository), the line ranges INTEGRATION.md cites still hold what it says they hold, and oracle/_ref/ftk_shim_driver -- which
 tests/test_shim.py runs on the GPU against the CPU fixtures of the same reference -- was built from the PATCHED headers plus the patch's
 new source file, with no update_timestep() override of its own."""
+import hashlib
 import os
 import shutil
 import subprocess
@@ -103,7 +104,15 @@ def test_shim_driver_is_the_patched_reference():
     drv = os.path.join(ROOT, "oracle", "_ref", "ftk_shim_driver")
     if not os.path.exists(drv):
         pytest.skip("oracle/_ref/ftk_shim_driver not built (make -C oracle shim, after ftk_amd/libftkx.so)")
-    assert os.path.getmtime(drv) >= os.path.getmtime(PATCH), "rebuild: make -C oracle shim"
+    # made from the sources in this tree: oracle/Makefile records their SHA-256 beside the driver (by content -- a checkout resets file times)
+    made_from = {}
+    if os.path.exists(drv + ".sha256"):
+        for line in open(drv + ".sha256"):
+            digest, name = line.split(None, 1)
+            made_from[os.path.normpath(os.path.join(ROOT, "oracle", name.strip()))] = digest
+    assert os.path.normpath(PATCH) in made_from, "rebuild: make -C oracle shim"
+    for path, digest in made_from.items():
+        assert hashlib.sha256(open(path, "rb").read()).hexdigest() == digest, f"rebuild: make -C oracle shim ({path} changed)"
     defined = subprocess.run(["nm", "-C", "--defined-only", drv], capture_output=True, text=True).stdout
     undefined = subprocess.run(["nm", "-C", "--undefined-only", drv], capture_output=True, text=True).stdout
     assert "extract_cp2dt_hip(" in defined and "extract_cp3dt_hip(" in defined            # the patch's new source file is linked in

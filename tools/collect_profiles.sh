@@ -4,7 +4,7 @@
 CFG=${1:-c4}; TAG=${2:-r03}
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 OUT=gpurun_out/profiles_${TAG}_${CFG}; rm -rf $OUT; mkdir -p $OUT
-LIGHT="--no-cpu-baseline --no-other-configs --no-streaming-tracker --no-sustained"
+LIGHT="--full --no-cpu-baseline --no-other-configs --no-streaming-tracker --no-sustained"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py --config $CFG --steps 5 --warmup 2 $LIGHT > $OUT/bench_under_trace.log 2>&1
 # (bench.py's passes under the trace: 3 warm-up + 5 timed with two in flight, then 3 on their own (latency) and 3 with events around every kernel:
 # --skip 7 = a timed pass with another one in flight; --skip 4 = a pass on its own)

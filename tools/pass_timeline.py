@@ -2,7 +2,7 @@
 """Timeline of ONE pass of bench.py out of a rocprofv3 --kernel-trace CSV: every dispatch of the last pass with its start offset,
 duration and the idle gap in front of it (what the fixed tail of a pass is made of).
 
-    rocprofv3 --kernel-trace --output-format csv -d DIR -- python3 bench.py --config c2 --steps 5 --warmup 1 --no-cpu-baseline
+    rocprofv3 --kernel-trace --output-format csv -d DIR -- python3 bench.py --config c2 --steps 5 --warmup 1 --full --no-cpu-baseline
     python3 tools/pass_timeline.py DIR [--first KERNEL_SUBSTRING] [--skip N]
 
 A pass starts at the dispatch whose name contains --first (default: init_red_kernel, the first launch of ftkx_slices_prepare /
