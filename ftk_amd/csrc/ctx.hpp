@@ -36,10 +36,9 @@ void launch_scatter_packed(const u64 *hdr, const unsigned *idx, const u64 *words
                            size_t mask_words, u64 *bad, hipStream_t st);
 void launch_sparse_cells(const Mesh &m, const Fields *d_steps, const u64 *d_list, u64 cap, const double *sparse, u64 *cells, u64 cells_cap, hipStream_t st);
 void launch_patches(const Mesh &m, bool scatter, const u64 *cells, size_t n, int ncomp, double *field, double *patches, hipStream_t st);
-bool masks_have_summary(const Mesh &m);
+bool masks_have_summary(const Mesh &m);      // these three: readers of the mask plan (mask_plan.hpp)
 int mask_summary_rows(const Mesh &m);
 bool march2_supported(const Mesh &m);
-bool masks_fuse_reduction(const Mesh &m);
 void launch_reduce_march(const Mesh &m, const MaskJob *d_jobs, int njobs, hipStream_t stream);
 void launch_cull_two_level(const Mesh &m, const Fields *d_steps, int nsteps, u64 *d_refine, u64 refine_cap, u64 *d_list, u64 cap, hipStream_t stream);
 void launch_resolution_scalar(const Mesh &m, const double *S, u64 *out2, hipStream_t stream);

@@ -12,7 +12,8 @@ void set_global_error(const char *msg);
 namespace ftkx {
 // The library's test hooks come in two families, one environment variable each, "name=value,name=value" (DESIGN.md section 8):
 // FTKX_SERIES_HOOKS (small, short, fold, split, one, rank_max: which forms of the device-driven pass are taken) and FTKX_MASK_PLAN (swizzle,
-// yg, zchunk, lmin, lcap, order, rows, lean: launch geometry of the mask kernels).  Read at every use: tests switch them inside one process.
+// yg, zchunk, lmin, lcap, order, rows, lean: launch geometry of the mask kernels; parsed by read_mask_hooks, mask_plan.hpp).  Read at every use: tests switch them
+// inside one process.  env_hook reads one knob of the first family.
 inline long env_hook(const char *var, const char *name, long dflt)
 {
   const char *e = getenv(var);

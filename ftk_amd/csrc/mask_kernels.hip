@@ -1,8 +1,10 @@
 // The MASK kernels of the fast path (gfx950): one pass over a slice -- S, 8 bytes per vertex, the gradient evaluated in flight, or V for
 // vector input -- writes a sign-mask byte per vertex, the block summaries and the reduction update_vector_field_scaling_factor needs
-// (critical_point_tracker.hh:850-864, ndarray.hh:770-778).  HBM-bound; which kernel takes which mesh: launch_masks_impl at the end.
+// (critical_point_tracker.hh:850-864, ndarray.hh:770-778).  HBM-bound; which kernel takes which mesh, with what launch geometry: plan_masks (mask_plan.hpp).
 // (Split from sweep_kernels.hip in round 6.)
+#include <atomic>
 #include "internal.hpp"
+#include "mask_plan.hpp"
 #include "sweep_device.hpp"
 #include "series_device.hpp"
 
@@ -141,7 +143,7 @@ __global__ __launch_bounds__(kThreads) void mask_vec_kernel(const Mesh m, const 
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// The same walk as mask_march2_kernel<ND, EDGE = true, REDUCE> on a VALU diet.  rocprofv3 showed the kernel above issue-bound
+// The 128-column marching kernels: the walk of their predecessor (a kernel of rounds 1-3, gone since) on a VALU diet.  rocprofv3 showed it issue-bound
 // (VALUBusy 72 %, 2.96e9 VALU instructions per 512^3 x 32 launch) rather than HBM-bound, so this version removes instructions
 // that do no arithmetic for the result:
 //   * the four plane buffers rotate by NAME (the z loop is unrolled four times) instead of being copied every plane;
@@ -181,7 +183,7 @@ __device__ inline void remap_block(int swizzle, unsigned &bx, unsigned &by, unsi
     b = xcd * per + (xcd < rem ? xcd : rem) + k;
     bx = b % gridDim.x; by = (b / gridDim.x) % gridDim.y; bz = b / (gridDim.x * gridDim.y);
   }
-  if (swizzle & 8) {   // grouped placement, see mask_march2_kernel
+  if (swizzle & 8) {   // grouped placement (plan_masks, mask_plan.hpp: what it buys, and how the group height YG gets into bits 8-15)
     const unsigned YG = ((unsigned)swizzle >> 8) & 0xffu;
     const unsigned nb = gridDim.x * gridDim.y * gridDim.z, G = gridDim.x * YG;
     const unsigned b = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
@@ -356,7 +358,7 @@ __device__ inline unsigned guard_and_reduce(unsigned a0, unsigned a1, double dx0
 // (The diet alone, on the kernel above's linear walk: 0.744 -> 0.742 ms -- the kernel was not waiting for its arithmetic.)
 // Same fused reduction and records as mask_vec_kernel; the same mask words wherever both write them (tests/test_gpu_properties.py:
 // fields with NaNs, infinities, big values and plateaus).  Needs rows of at least 64 groups and byte offsets that fit 31 bits:
-// vec_lean() below.
+// plan_masks (mask_plan.hpp).
 // ---------------------------------------------------------------------------------------------------------------
 template <int ND>
 __device__ inline void push_vertex_signs(unsigned &S, unsigned &G, const double *x, double thr)
@@ -752,7 +754,7 @@ __global__ __launch_bounds__((ND == 2 || (PD == 1 && RY <= 4)) ? 768 : 512) void
 // In 2D that kernel's wavefront takes 8 rows x 128 columns -- 8 KB of input -- and leaves: ten row loads issued at once and all of them
 // waited for before the first row is classified, one set-up and one pair of reduction atomics per 8 KB.  Here a wavefront takes `groups`
 // consecutive groups of 8 rows of its 128 columns: the set-up once, the loads of group g + 1 on their way while group g is classified (two
-// register sets that rotate by name).  Faster on WIDE slices only (launch_masks_impl has the numbers): most of the scalar instructions of
+// register sets that rotate by name).  Faster on WIDE slices only (plan_masks has the numbers): most of the scalar instructions of
 // either kernel are the per-row uniform tests inside the step, not the set-up.
 // Same mask words, summaries and reductions as the kernel above, bit for bit (tests/test_gpu_properties.py::test_mask_kernel_generations_agree
 // runs them against each other: FTKX_MASK_PLAN rows=0 takes the kernel above).
@@ -998,19 +1000,7 @@ __device__ inline void wait_plane_landed(int s)
 #undef FTKX_WAIT_VM
 }
 
-// The z extent of a slice in PIECES of unequal length, the same for every tile column: blockIdx.z = piece * njobs + slice, pieces in
-// order of decreasing length.  The hardware hands workgroups out in order of their index as slots free up -- a queue --, so the long
-// pieces (up to half a column) go out first and the launch ends on pieces of a few planes: the device stays full until a few
-// microseconds before the end whatever the size of the series (equal chunks of 32 planes: 256^3 x 16 is 5.3 rounds of workgroups, a
-// 512^3 slice on its own 2.7), and the two start-up planes of a march are paid per piece -- 7 pieces per 512 planes on 512^3 x 32
-// instead of 16 chunks.  (Persistent workgroups pulling such pieces from a queue of their own were built and measured: the loop state
-// costs the kernel 36 more SGPR spills and 12 VGPRs of scratch at three wavefronts per SIMD -- 7.6 ms against 5.7 on 512^3 x 32.)
-// Equal chunks (launches of a dozen rounds and more) go out slice by slice instead: neighbouring chunks of a slice then run at the same
-// time and find each other's start-up planes in the caches.
-struct ZPlan {
-  unsigned npieces;
-  unsigned z0[47], len[47];
-};
+// (ZPlan, the z extent of a slice in pieces of unequal length: mask_plan.hpp)
 
 template <int NS, int CY, int RY, bool TWOB>
 __device__ __forceinline__ void march6_body(const Mesh &m, const MaskJob *__restrict__ jobs, int swizzle, int njobs, const ZPlan &plan)
@@ -1382,25 +1372,16 @@ __global__ __launch_bounds__(kThreads) void resolution_scalar_kernel(const Mesh 
 // kernel family so that its roofline line can be matched with the profiler's summary
 static const char *g_last_mask_kernel = "";
 const char *last_mask_kernel() { return g_last_mask_kernel; }
-// Which mask kernel took how many launches in this process: launch_masks_impl picks one of six by the mesh (3D scalar: march6; 2D scalar: march4,
-// rows2 for rows of 32 KB and more; vector input: vec2 with block summaries, vec without; everything else: the generic kernel), and the GPU
-// suite is meant to reach every one of them (tests/conftest.py writes the table; profiles/r06_mask_kernel_coverage.json).
-static unsigned long long g_mask_launches[kMaskKernels] = {0, 0, 0, 0, 0, 0, 0};
+// Which mask kernel took how many launches in this process, by MaskFamily (mask_plan.hpp: plan_masks picks one by the mesh); the GPU suite is
+// meant to reach every one of them (tests/conftest.py writes the table; profiles/r06_mask_kernel_coverage.json).
+static_assert(MASK_FAMILIES == kMaskKernels && kMaskThreads == kThreads, "mask_plan.hpp restates these two");
+static std::atomic<unsigned long long> g_mask_launches[kMaskKernels];
 static const char *const g_mask_names[kMaskKernels] = {"mask_march6_kernel (3D scalar)", "mask_march4_kernel (2D scalar)", "mask_rows2_kernel (2D scalar, long rows)",
                                                        "mask_march4_kernel<reduce> (stand-alone reduction)", "mask_vec2_kernel (vector input, block summaries)",
                                                        "mask_vec_kernel (vector input)", "mask_kernel (generic)"};
-void mask_kernel_launches(unsigned long long *out, const char **names) { for (int i = 0; i < kMaskKernels; i ++) { if (out) out[i] = g_mask_launches[i]; if (names) names[i] = g_mask_names[i]; } }
-
-void launch_masks_impl(const Mesh &m, const MaskJob *d_jobs, int njobs, bool reduce, hipStream_t stream);
-bool masks_have_summary(const Mesh &m);
-int mask_summary_rows(const Mesh &m);
-
-// can the 128-column marching kernels (which also carry the exact pre-pass reduction) walk this mesh? (which carries the fused reduction) walk this mesh?
-bool march2_supported(const Mesh &m)
+void mask_kernel_launches(unsigned long long *out, const char **names)
 {
-  const int DD = m.nd == 3 ? m.ext_sz[2] : 1;
-  const size_t slice_bytes = (size_t)m.ext_sz[0] * m.ext_sz[1] * DD * 8;
-  return m.scalar_mode && (m.ext_sz[0] % 2) == 0 && m.ext_sz[0] >= 2 && slice_bytes < (1ull << 32);
+  for (int i = 0; i < kMaskKernels; i ++) { if (out) out[i] = g_mask_launches[i].load(std::memory_order_relaxed); if (names) names[i] = g_mask_names[i]; }
 }
 
 void launch_resolution_scalar(const Mesh &m, const double *S, u64 *out2, hipStream_t stream)
@@ -1426,188 +1407,46 @@ void launch_calib_read(const void *p, size_t bytes, double *scratch, hipStream_t
   hipLaunchKernelGGL(calib_read_kernel, dim3(256 * 16), dim3(kThreads), 0, stream, (const double2 *)p, bytes / 16, scratch);
 }
 
-// does this mesh take the fast vector-input kernel?
-static bool vec_fast(const Mesh &m) { return !m.scalar_mode && m.ext_sz[0] >= 8 && (m.ext_sz[0] % 8) == 0; }
-// ... its form with block summaries (mask_vec2_kernel)?  Rows of at least 64 groups, byte offsets that fit 31 bits.  FTKX_MASK_PLAN lean=0: never
-static bool vec_lean(const Mesh &m)
+// The plan of this mesh under the hooks as they stand now (mask_plan.hpp), and what the rest of the library asks of it
+static MaskPlan plan_of(const Mesh &m, int njobs = 1, bool reduce = false)
 {
-  if (!vec_fast(m) || m.ext_sz[0] < 256) return false;
-  if (env_hook("FTKX_MASK_PLAN", "lean", 1) == 0) return false;
-  const size_t n = (size_t)m.ext_sz[1] * (m.nd == 3 ? (size_t)m.ext_sz[2] : 1);
-  return (size_t)m.ext_sz[0] * n * 8 * (size_t)m.nd < (1ull << 31) && (size_t)m.mask_pitch * n < (1ull << 31);
+  return plan_masks(MaskShape{m.nd, m.scalar_mode, {m.ext_sz[0], m.ext_sz[1], m.ext_sz[2]}, m.mask_pitch}, read_mask_hooks(), njobs, reduce);
 }
+bool march2_supported(const Mesh &m) { return plan_of(m).march2; }
+bool masks_have_summary(const Mesh &m) { return plan_of(m).has_summary; }
+int mask_summary_rows(const Mesh &m) { return plan_of(m).u_rows; }
 
-void launch_masks_impl(const Mesh &m, const MaskJob *d_jobs, int njobs, bool reduce, hipStream_t stream)
+static void launch_masks_impl(const Mesh &m, const MaskJob *d_jobs, int njobs, bool reduce, hipStream_t stream)
 {
   if (njobs <= 0) return;
-  if (m.scalar_mode && march2_supported(m)) {
-    // scalar slices with an even row length below 4 GiB: the marching kernels on 128-column, line-aligned tiles
-    const int DW = m.ext_sz[0], DD = m.nd == 3 ? m.ext_sz[2] : 1;
-    int swizzle = 8;   // grouped placement -- the x tiles of some row groups on one XCD -- cuts the fabric reads from 47.7 to 41.4 GB per 512^3 x 32 launch
-    // 2D: the rows of a wavefront's block that no other wavefront reads (all but its first and last two) are loaded non-temporally -- they are
-    // read once, and keeping them out of the caches leaves the halo rows there for the neighbours: woven 1024^2 x 64 0.115 -> 0.102 ms (all
-    // loads non-temporal: 0.106; 3D, where the planes are re-read by the z march: 256^3 x 16 -1 %, 512^3 x 32 +1.3 %: left as it is.  The
-    // vector-input kernel, whose every value is read once, does NOT like non-temporal loads: double_gyre 0.73 -> 1.30 ms)
-    if (m.nd == 2) swizzle |= 16;
-    swizzle = (int)env_hook("FTKX_MASK_PLAN", "swizzle", swizzle);
-    int zchunk = 32;
-    bool zforced = false;
-    if (env_hook("FTKX_MASK_PLAN", "zchunk", 0) > 0) { zchunk = (int)env_hook("FTKX_MASK_PLAN", "zchunk", 0); zforced = true; }
-    if (m.nd == 3 && !reduce) {
-      // 3D: mask_march6_kernel -- 128 x 16 tiles as four wavefronts of 4 rows that all load (LDS-DMA) and classify, TWO row slots in
-      // LDS (37 KB: three workgroups = twelve wavefronts per CU, which its 164 VGPRs allow), one barrier per plane; grouped placement:
-      // 16 row groups (all of a 256^2 plane's, half of a 512^2 plane's tiles) of one piece of planes share an XCD's L2 (4: +3.5 %, 8: +0.5 %)
-      int yg_want = 16;
-      if (env_hook_set("FTKX_MASK_PLAN", "yg")) yg_want = env_hook("FTKX_MASK_PLAN", "yg", 16) > 0 ? (int)env_hook("FTKX_MASK_PLAN", "yg", 16) : 1;
-      if (yg_want > 255) yg_want = 255;
-      // The pieces a tile column is marched in (ZPlan): at most 24 planes, at most half of what is left of the column, at least 6,
-      // multiples of 3 (the march is unrolled three planes deep), handed out longest first.  Measured, not derived (tools/ab_mask.py,
-      // interleaved on one box): against equal chunks of 32 planes 256^3 x 16 0.418 -> 0.405 ms, one 512^3 slice 0.206 -> 0.197, four
-      // 0.756 -> 0.748, 512^3 x 32 5.72 -> 5.69.  LONGER marches are slower although they pay fewer start-up planes (caps of 28 / 32 / 48:
-      // +9 / +5 / +1..2 % on 512^3 x 32; half columns +3.7 %: the tiles of a group drift apart and stop sharing their halo rows in the L2),
-      // equal chunks swing by +-3 % with their length (24: 5.89, 27: 5.68, 30: 5.98, 32: 5.72, 33: 5.84 ms -- what is left over at a
-      // column's top decides).  Order of the workgroups: slice by slice where a slice alone fills the device (neighbouring pieces of a
-      // slice then run together and find each other's start-up planes in the caches: 512^3 x 32 5.59 against 5.85 ms piece by piece),
-      // piece by piece over all slices otherwise (256^3 x 16: 0.379 against 0.399).
-      // FTKX_MASK_PLAN (test hooks): zchunk=n: equal chunks of n planes; lcap / lmin: the two bounds; order=0 / 1
-      ZPlan plan = ZPlan();
-      bool planned = false;
-      {
-        int lmin = 6, lcap = 24;
-        planned = !zforced;
-        if (env_hook("FTKX_MASK_PLAN", "lmin", 0) >= 1) lmin = (int)env_hook("FTKX_MASK_PLAN", "lmin", 0);
-        if (env_hook("FTKX_MASK_PLAN", "lcap", 0) >= 1) lcap = (int)env_hook("FTKX_MASK_PLAN", "lcap", 0);
-        if (lcap < lmin) lcap = lmin;
-        std::vector<int> lens;
-        int rem = DD;
-        if (!planned) while (rem > 0) { const int l = rem < zchunk ? rem : zchunk; lens.push_back(l); rem -= l; }
-        while (rem > 0) {
-          int l = (rem + 1) / 2;
-          if (l > lcap) l = lcap;
-          if (l < lmin) l = lmin;
-          if (l >= 3) l -= l % 3;      // (the march is unrolled three planes deep: a length that is no multiple of 3 pays for up to two empty steps)
-          if (l > rem || rem - l < (lmin + 1) / 2) l = rem;
-          lens.push_back(l); rem -= l;
-        }
-        while (lens.size() > 47) { const int l = lens.back(); lens.pop_back(); lens.back() += l; }      // (more pieces than the table holds: merged from the end)
-        std::stable_sort(lens.begin(), lens.end(), [](int a, int b) { return a > b; });
-        plan.npieces = (unsigned)lens.size();
-        int z = 0;
-        for (size_t i = 0; i < lens.size(); i ++) { plan.z0[i] = (unsigned)z; plan.len[i] = (unsigned)lens[i]; z += lens[i]; }
-      }
-      constexpr int NS6 = 2, CY6 = 4, RY6 = 4, rows = CY6 * RY6;
-      g_last_mask_kernel = "ftkx::mask_march6_kernel<2, 4, 4, false>"; g_mask_launches[0] ++;
-      dim3 grid6((unsigned)((DW + 127) / 128), (unsigned)((m.ext_sz[1] + rows - 1) / rows), plan.npieces * (unsigned)njobs);
-      int sw = swizzle;
-      // grouped placement needs a y extent that is a multiple of the group height: pad it (workgroups past the last row leave at once)
-      if (sw & 8) { int yg = yg_want; if (yg > (int)grid6.y) yg = (int)grid6.y; grid6.y = (grid6.y + (unsigned)yg - 1) / (unsigned)yg * (unsigned)yg; sw = (sw & 0xff) | (yg << 8); }
-      const unsigned bytes = (unsigned)NS6 * (unsigned)(rows + 2) * 1024u + (unsigned)(NS6 + 1) * 256u + 128u;   // row slots, edge ring, the summaries' exchange
-      (void)hipFuncSetAttribute((const void *)mask_march6_kernel<NS6, CY6, RY6, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-      bool slice_major = (size_t)grid6.x * ((m.ext_sz[1] + rows - 1) / rows) * plan.npieces >= 768;      // a slice alone fills the device (three workgroups per CU)
-      if (env_hook_set("FTKX_MASK_PLAN", "order")) slice_major = env_hook("FTKX_MASK_PLAN", "order", 0) == 0;
-      hipLaunchKernelGGL((mask_march6_kernel<NS6, CY6, RY6, false>), grid6, dim3(64u * CY6), bytes, stream, m, d_jobs, sw, slice_major ? -njobs : njobs, plan);
-      return;
-    }
-    // 2D, and the exact stand-alone reduction (ftkx_slice_resolution) of either dimension: mask_march4_kernel -- every wavefront loads
-    // its rows into registers (4 wavefronts of 8 rows in 2D, of 4 rows marching along z in 3D)
-    const int RY = (m.nd == 3) ? 4 : 8, wpb = 4;
-    if (m.nd == 2 && !reduce) {
-      // mask_rows2_kernel: a wavefront marches down `groups` groups of 8 rows (FTKX_MASK_PLAN rows=n, test hook; rows=0: the kernel below).
-      // Measured (tools/ab_mask.py, interleaved on one box, 4 groups against the kernel below): 4096^2 x 16 0.428 -> 0.384 ms, 2048^2 x 64
-      // 0.412 -> 0.397 (8 groups: 0.390), but 1024^2 x 64 0.096 -> 0.109 and 1024^2 x 256 0.379 -> 0.399: with rows of 8 KB the short
-      // wavefronts of the kernel below, whose neighbours in x run together, read whole rows; taken for rows of 32 KB and more
-      int groups = (DW >= 4096 && m.ext_sz[1] >= 512) ? 4 : 0;
-      if (env_hook_set("FTKX_MASK_PLAN", "rows")) groups = (int)env_hook("FTKX_MASK_PLAN", "rows", groups);
-      if (groups > 64) groups = 64;
-      if (groups >= 1) {
-        dim3 gridr((unsigned)((DW + 127) / 128), (unsigned)((m.ext_sz[1] + wpb * RY * groups - 1) / (wpb * RY * groups)), (unsigned)njobs);
-        int sw = swizzle;
-        if (sw & 8) {
-          int yg = 4;
-          if (env_hook_set("FTKX_MASK_PLAN", "yg")) { const long v = env_hook("FTKX_MASK_PLAN", "yg", 4); yg = v > 0 ? (v > 255 ? 255 : (int)v) : 1; }
-          while (yg > 1 && gridr.y % (unsigned)yg) yg --;
-          sw = (sw & 0xff) | (yg << 8);
-        }
-        g_last_mask_kernel = "ftkx::mask_rows2_kernel<8>"; g_mask_launches[2] ++;
-        hipLaunchKernelGGL(mask_rows2_kernel<8>, gridr, dim3((unsigned)(64 * wpb)), 0, stream, m, d_jobs, groups, sw);
-        return;
-      }
-    }
-    const int nzc = m.nd == 3 ? (DD + zchunk - 1) / zchunk : 1;
-    const dim3 grid4((unsigned)((DW + 127) / 128), (unsigned)((m.ext_sz[1] + wpb * RY - 1) / (wpb * RY)), (unsigned)(nzc * njobs));
-    if (swizzle & 8) {     // (the group height must divide the grid's y extent)
-      int yg = 4;
-      if (env_hook_set("FTKX_MASK_PLAN", "yg")) { const long v = env_hook("FTKX_MASK_PLAN", "yg", 4); yg = v > 0 ? (v > 255 ? 255 : (int)v) : 1; }
-      while (yg > 1 && grid4.y % (unsigned)yg) yg --;
-      swizzle = (swizzle & 0xff) | (yg << 8);
-    }
-    const dim3 blk((unsigned)(64 * wpb));
-#define FTKX_M4(ND_, R_, PD_, RY_) do { if (!reduce) g_last_mask_kernel = "ftkx::mask_march4_kernel<" #ND_ ", " #R_ ", " #PD_ ", " #RY_ ">"; g_mask_launches[reduce ? 3 : 1] ++; \
-      hipLaunchKernelGGL((mask_march4_kernel<ND_, R_, PD_, RY_>), grid4, blk, 0, stream, m, d_jobs, zchunk, swizzle); } while (0)
-    if (reduce) { if (m.nd == 2) FTKX_M4(2, true, 1, 8); else FTKX_M4(3, true, 1, 4); }
-    else FTKX_M4(2, false, 1, 8);
-#undef FTKX_M4
-    return;
+  const MaskPlan p = plan_of(m, njobs, reduce);
+  g_mask_launches[p.family].fetch_add(1, std::memory_order_relaxed);
+  if (p.family != MASK_REDUCE) g_last_mask_kernel = p.name;
+  const dim3 grid(p.grid[0], p.grid[1], p.grid[2]), block(p.block);
+  switch (p.family) {
+  case MASK_MARCH6:
+    (void)hipFuncSetAttribute((const void *)mask_march6_kernel<2, 4, 4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
+    hipLaunchKernelGGL((mask_march6_kernel<2, 4, 4, false>), grid, block, p.lds_bytes, stream, m, d_jobs, p.swizzle, p.njobs, p.z);
+    break;
+  case MASK_ROWS2: hipLaunchKernelGGL(mask_rows2_kernel<8>, grid, block, 0, stream, m, d_jobs, p.groups, p.swizzle); break;
+  case MASK_REDUCE:
+    if (m.nd == 2) hipLaunchKernelGGL((mask_march4_kernel<2, true, 1, 8>), grid, block, 0, stream, m, d_jobs, p.zchunk, p.swizzle);
+    else hipLaunchKernelGGL((mask_march4_kernel<3, true, 1, 4>), grid, block, 0, stream, m, d_jobs, p.zchunk, p.swizzle);
+    break;
+  case MASK_MARCH4: hipLaunchKernelGGL((mask_march4_kernel<2, false, 1, 8>), grid, block, 0, stream, m, d_jobs, p.zchunk, p.swizzle); break;
+  case MASK_VEC2:
+    if (m.nd == 2) hipLaunchKernelGGL(mask_vec2_kernel<2>, grid, block, 0, stream, m, d_jobs);
+    else hipLaunchKernelGGL(mask_vec2_kernel<3>, grid, block, 0, stream, m, d_jobs);
+    break;
+  case MASK_VEC:
+    if (m.nd == 2) hipLaunchKernelGGL(mask_vec_kernel<2>, grid, block, 0, stream, m, d_jobs);
+    else hipLaunchKernelGGL(mask_vec_kernel<3>, grid, block, 0, stream, m, d_jobs);
+    break;
+  default:
+    if (m.nd == 2) hipLaunchKernelGGL(mask_kernel<2>, grid, block, 0, stream, m, d_jobs);
+    else hipLaunchKernelGGL(mask_kernel<3>, grid, block, 0, stream, m, d_jobs);
   }
-  const size_t DDv = m.nd == 3 ? (size_t)m.ext_sz[2] : 1;
-  if (vec_fast(m)) {
-    const size_t groups = (size_t)(m.ext_sz[0] / 4) * m.ext_sz[1] * DDv;
-    size_t bx = (groups + kThreads - 1) / kThreads;
-    if (bx > 2048) bx = 2048;               // grid-stride the rest: 8 workgroups per CU per job
-    // ... and at least four groups per lane where the slice has them: the per-wavefront fixed costs (index arithmetic, the two
-    // reduction atomics) are paid per 16 KB instead of per 4 KB (double_gyre 2048 x 1024 x 128: 0.795 -> 0.746 ms)
-    while (bx > 256 && bx * kThreads * 4 > groups) bx /= 2;
-    const dim3 grid((unsigned)bx, (unsigned)njobs);
-    // mask_vec2_kernel (units of 4 rows x 64 groups, one summary byte per 8 x 4 block): where the mesh carries block summaries
-    if (m.u_rows == 4 && vec_lean(m)) {
-      const size_t units = (size_t)((m.ext_sz[0] / 4 + 63) / 64) * ((m.ext_sz[1] + 3) / 4) * DDv;
-      size_t bx2 = (units + 7) / 8;             // two units (32 KB) per wavefront where the slice has them (four: +1.3 %, one: +0.3 % on double_gyre 2048 x 1024 x 128)
-      if (bx2 > 2048) bx2 = 2048;
-      const dim3 grid((unsigned)bx2, (unsigned)njobs);
-      g_last_mask_kernel = m.nd == 2 ? "ftkx::mask_vec2_kernel<2>" : "ftkx::mask_vec2_kernel<3>"; g_mask_launches[4] ++;
-      if (m.nd == 2) hipLaunchKernelGGL(mask_vec2_kernel<2>, grid, dim3(kThreads), 0, stream, m, d_jobs);
-      else hipLaunchKernelGGL(mask_vec2_kernel<3>, grid, dim3(kThreads), 0, stream, m, d_jobs);
-      return;
-    }
-    g_last_mask_kernel = m.nd == 2 ? "ftkx::mask_vec_kernel<2>" : "ftkx::mask_vec_kernel<3>"; g_mask_launches[5] ++;
-    if (m.nd == 2) hipLaunchKernelGGL(mask_vec_kernel<2>, grid, dim3(kThreads), 0, stream, m, d_jobs);
-    else hipLaunchKernelGGL(mask_vec_kernel<3>, grid, dim3(kThreads), 0, stream, m, d_jobs);
-    return;
-  }
-  // the one generic form (odd row lengths, slices of 4 GiB and more, vector rows that are not a multiple of 8): one lane per mask byte
-  const size_t n = (size_t)m.mask_pitch * m.ext_sz[1] * DDv;
-  size_t bx = (n + kThreads - 1) / kThreads;
-  if (bx > 4096) bx = 4096;                 // grid-stride the rest
-  const dim3 grid((unsigned)bx, (unsigned)njobs);
-  g_last_mask_kernel = m.nd == 2 ? "ftkx::mask_kernel<2>" : "ftkx::mask_kernel<3>"; g_mask_launches[6] ++;
-  if (m.nd == 2) hipLaunchKernelGGL(mask_kernel<2>, grid, dim3(kThreads), 0, stream, m, d_jobs);
-  else hipLaunchKernelGGL(mask_kernel<3>, grid, dim3(kThreads), 0, stream, m, d_jobs);
 }
-
-// Rows a summary byte stands for.  mask_march6_kernel with four rows per wavefront writes ONE byte per 8 x 4 block of vertices
-// (aligned in y): a quarter of the summary bytes to write (what they cost: DESIGN.md) and for the coarse cull to read.  Everything
-// else writes one byte per word of 8.  The same decision as launch_masks_impl's choice of kernel (same environment knobs).
-int mask_summary_rows(const Mesh &m)
-{
-  if (!masks_have_summary(m)) return 1;
-  int want = 0;
-  if (const char *e = getenv("FTKX_U_ROWS")) want = atoi(e);
-  if (want == 1) return 1;
-  if (!m.scalar_mode) return vec_lean(m) ? 4 : 1;              // mask_vec2_kernel / mask_vec_kernel
-  if (m.nd == 3) return want == 4 ? 4 : 16;                    // mask_march6_kernel: the workgroup's sixteen rows (FTKX_U_ROWS=4: a wavefront's four)
-  return 4;                                                    // mask_march4_kernel<2, ...>: a wavefront's rows in blocks of four
-}
-
-// does launch_masks produce the per-word summaries for this mesh?  (the 128-column marching kernels and the fast vector kernel do)
-bool masks_have_summary(const Mesh &m)
-{
-  if (const char *e = getenv("FTKX_U_ROWS")) if (atoi(e) < 0) return false;      // (FTKX_U_ROWS=-1: no summaries at all, the one-level cull)
-  if (!m.scalar_mode) return vec_fast(m);
-  return march2_supported(m) && (m.ext_sz[0] % 8) == 0;
-}
-
-// are the reduction slots of MaskJob::red filled by launch_masks (the fused one-pass form)?  All mask kernels do.
-bool masks_fuse_reduction(const Mesh &) { return true; }
 
 void launch_masks(const Mesh &m, const MaskJob *d_jobs, int njobs, hipStream_t stream) { launch_masks_impl(m, d_jobs, njobs, false, stream); }
 // pre-pass: only valid when march2_supported(m)

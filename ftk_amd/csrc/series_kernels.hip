@@ -279,7 +279,7 @@ __device__ __forceinline__ void series_small_body(const Mesh &m, const Mesh &mc,
                                                   int report_decline /* nothing is queued behind this kernel: if it declines, it says so itself */)
 {
   constexpr int N = ND + 1, NVC = 1 << N, G = kThreads / NVC, NTYPES = fan_table<N>::NTYPES;
-  constexpr unsigned LIST_CAP = kSmallPer * 128, PASS_CAP = 2048;   // a coarse cell is 8 x u_rows corners, u_rows <= 16 (mask_summary_rows)
+  constexpr unsigned LIST_CAP = kSmallPer * 128, PASS_CAP = 2048;   // a coarse cell is 8 x u_rows corners, u_rows <= 16 (mask_plan.hpp)
   __shared__ unsigned s_rank[kSmallRank];
   static_assert(G * NTYPES <= (int)PASS_CAP / 2, "a batch's worst case must fit twice");
   __shared__ u64 s_list[LIST_CAP];

@@ -32,7 +32,7 @@ struct Mesh {
   int mask_pitch;            // row pitch (bytes) of the vertex-mask arrays: roundup8(ext_sz[0]) + 8
   int u_pitch;               // row pitch of the per-8-vertex summary arrays: roundup8(ceil(ext_sz[0] / 8)) + 8
   int u_rows;                // rows a summary byte stands for: 1 (a word of 8 vertices) or 4 (the 8 x 4 block of aligned rows; row
-                             // index of U = y / u_rows, ceil(ext_sz[1] / u_rows) rows per plane) -- mask_summary_rows()
+                             // index of U = y / u_rows, ceil(ext_sz[1] / u_rows) rows per plane) -- MaskPlan::u_rows (mask_plan.hpp)
   int jacobian_symmetric, robust, use_type_filter;
   unsigned type_filter;
   int compute_degrees, tag_mode;
@@ -77,7 +77,7 @@ struct Fields {
   int scope_mask;            // FTKX_SCOPE_*
 };
 
-constexpr int kMaskKernels = 7;      // mask-kernel families launch_masks picks from (mask_kernels.hip: mask_kernel_launches)
+constexpr int kMaskKernels = 7;      // mask-kernel families plan_masks picks from (mask_plan.hpp: MaskFamily)
 
 // tile kernel (exact_only / non-robust / overflow regime, and small jobs)
 struct TileParams {

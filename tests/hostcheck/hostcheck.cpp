@@ -4,6 +4,7 @@
 #include "../../ftk_amd/csrc/cp_device.hpp"
 #include "../../ftk_amd/csrc/fan_tables.hpp"
 #include "../../ftk_amd/csrc/split_policy.hpp"
+#include "../../ftk_amd/csrc/mask_plan.hpp"
 
 using namespace ftkx;
 
@@ -81,5 +82,18 @@ int hc_split_state(void *k, int forced, double *median_order, double *median_spl
   const ftkxh::split_cal &K = *(const ftkxh::split_cal *)k;
   *median_order = K.median_order; *median_split = K.median_split; *phase = K.phase; *countdown = K.countdown;
   return ftkxh::split_state(K, forced);
+}
+
+// ---- the mask kernels' launch plan (ftk_amd/csrc/mask_plan.hpp), computed without a device: tests/test_mask_plan.py ----
+// shape = {nd, scalar_mode, DW, DH, DD, mask_pitch}; hooks as the two environment variables would hold them (NULL: not set) ->
+// out[14 + 2 * 47] = family, march2, has_summary, u_rows, grid[3], block, lds_bytes, swizzle, zchunk, groups, njobs, npieces, then (z0, len) per piece; name[64]
+void hc_mask_plan(const int *shape, const char *mask_plan, const char *u_rows, int njobs, int reduce, long long *out, char *name)
+{
+  const MaskShape s{shape[0], shape[1], {shape[2], shape[3], shape[4]}, shape[5]};
+  const MaskPlan p = plan_masks(s, parse_mask_hooks(mask_plan, u_rows), njobs, reduce != 0);
+  const long long head[14] = {p.family, p.march2, p.has_summary, p.u_rows, p.grid[0], p.grid[1], p.grid[2], p.block, p.lds_bytes, p.swizzle, p.zchunk, p.groups, p.njobs, p.z.npieces};
+  for (int i = 0; i < 14; i ++) out[i] = head[i];
+  for (int i = 0; i < 47; i ++) { out[14 + 2 * i] = p.z.z0[i]; out[15 + 2 * i] = p.z.len[i]; }
+  strncpy(name, p.name, 63); name[63] = 0;
 }
 }
