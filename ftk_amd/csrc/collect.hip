@@ -285,23 +285,23 @@ int run_batch(ftkx_ctx *c, const double *sparse_field, bool cull_done)
     // the survivor list is shared by the sub-batches of one collect: the exact kernel of sub-batch i must not re-test the
     // survivors of sub-batch i-1, so each sub-batch gets its own list segment by resetting the list counter in between
     if (i > 0) {
-      HIP_TRY(c, hipMemsetAsync(c->d_counters + ftkx::CNT_SURVIVOR_LIST, 0, sizeof(u64), c->stream));
-      HIP_TRY(c, hipMemsetAsync(c->d_counters + ftkx::CNT_REFINE_LIST, 0, sizeof(u64), c->stream));
+      HIP_TRY(c, hipMemsetAsync(c->sr_tail[0].counters + ftkx::CNT_SURVIVOR_LIST, 0, sizeof(u64), c->stream));
+      HIP_TRY(c, hipMemsetAsync(c->sr_tail[0].counters + ftkx::CNT_REFINE_LIST, 0, sizeof(u64), c->stream));
     }
     if (cull_done) {    // the survivor list of exactly these steps is on the device already (cull-ahead, see ftkx_ctx::ahead)
       if (subs.size() != 1 || !sb.jobs.empty()) return fail(c, FTKX_E_DEVICE, "internal: cull-ahead taken over by a batch that rebuilds masks");
     } else {
       ev_begin(c, K_CULL);
-      if (two_level) ftkx::launch_cull_two_level(m, d_steps, (int)sb.steps.size(), c->d_refine, c->refine_capacity, c->d_list, c->list_capacity, c->stream);
-      else ftkx::launch_cull(m, d_steps, (int)sb.steps.size(), c->d_list, c->list_capacity, c->stream);
+      if (two_level) ftkx::launch_cull_two_level(m, d_steps, (int)sb.steps.size(), c->sr_tail[0].refine, c->sr_tail[0].refine_capacity, c->sr_tail[0].list, c->sr_tail[0].list_capacity, c->stream);
+      else ftkx::launch_cull(m, d_steps, (int)sb.steps.size(), c->sr_tail[0].list, c->sr_tail[0].list_capacity, c->stream);
       ev_end(c);
     }
     if (cull_only) {
       // (the exact kernel is what publishes the list peak; without it the host reads the list counter itself)
-      ftkx::launch_sparse_cells(m, d_steps, c->d_list, c->list_capacity, sparse_field, c->d_cells, c->cells_cap, c->stream);
+      ftkx::launch_sparse_cells(m, d_steps, c->sr_tail[0].list, c->sr_tail[0].list_capacity, sparse_field, c->d_cells, c->cells_cap, c->stream);
       continue;
     }
-    ev_begin(c, K_EXACT); ftkx::launch_exact(m, d_steps, (int)step_base[i], c->d_list, c->list_capacity, c->stream); ev_end(c);
+    ev_begin(c, K_EXACT); ftkx::launch_exact(m, d_steps, (int)step_base[i], c->sr_tail[0].list, c->sr_tail[0].list_capacity, c->stream); ev_end(c);
   }
   if (cull_only) { HIP_TRY(c, hipGetLastError()); return FTKX_OK; }
   if (!tiles.empty()) {
@@ -400,7 +400,7 @@ int ftkx_sweep_collect(ftkx_ctx *c, const ftkx_cp_t **out, size_t *n_out)
   if (c->pending.empty()) return FTKX_OK;
   int rc;
   if ((rc = ensure_hit_buffer(c, std::max<u64>(c->capacity, 1u << 16)))) { c->pending.clear(); return rc; }
-  if (c->nd == 3 && (rc = ensure_fragile(c, std::max<u64>(c->fragile_capacity, 1u << 12)))) { c->pending.clear(); return rc; }
+  if (c->nd == 3 && (rc = ensure_fragile(c, c->sr_tail[0], std::max<u64>(c->sr_tail[0].fragile_capacity, 1u << 12)))) { c->pending.clear(); return rc; }
   bool any_fast = false;
   u64 fast_cells = 0;
   {
@@ -409,8 +409,8 @@ int ftkx_sweep_collect(ftkx_ctx *c, const ftkx_cp_t **out, size_t *n_out)
     for (const Request &r : c->pending) if (r.mode == MODE_FAST) { any_fast = true; fast_cells += cells; }
   }
   if (c->dense_collects > 0) c->dense_collects --;          // the fast path is probed again after a while
-  if (any_fast && (rc = ensure_list(c, std::max<u64>(c->list_capacity, 1u << 20)))) { c->pending.clear(); return rc; }
-  if (any_fast && (rc = ensure_refine(c, std::max<u64>(c->refine_capacity, 1u << 20)))) { c->pending.clear(); return rc; }
+  if (any_fast && (rc = ensure_list(c, c->sr_tail[0], std::max<u64>(c->sr_tail[0].list_capacity, 1u << 20)))) { c->pending.clear(); return rc; }
+  if (any_fast && (rc = ensure_refine(c, c->sr_tail[0], std::max<u64>(c->sr_tail[0].refine_capacity, 1u << 20)))) { c->pending.clear(); return rc; }
   // upper bound of the tags this batch can emit -> number of key bits for the device sort
   int key_bits = 64;
   if (c->opt.tag_mode != FTKX_TAG_REFERENCE) {            // REFERENCE tags go through int32 products and may wrap to anything
@@ -432,17 +432,17 @@ int ftkx_sweep_collect(ftkx_ctx *c, const ftkx_cp_t **out, size_t *n_out)
   }
   for (int attempt = 0; ; attempt ++) {
     // (cull-ahead: the counters were zeroed before that cull and hold its list counts)
-    if (!use_ahead) HIP_TRY(c, hipMemsetAsync(c->d_counters, 0, ftkx::CNT_N * sizeof(u64), c->stream));
+    if (!use_ahead) HIP_TRY(c, hipMemsetAsync(c->sr_tail[0].counters, 0, ftkx::CNT_N * sizeof(u64), c->stream));
     if ((rc = run_batch(c, nullptr, use_ahead))) { c->pending.clear(); return rc; }
     use_ahead = false;
-    HIP_TRY(c, hipMemcpyAsync(c->h_counters, c->d_counters, ftkx::CNT_N * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->h_counters, c->sr_tail[0].counters, ftkx::CNT_N * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     c->ahead_staged = false;
     // (records <= simplices that passed: the 2D type filter may drop some; the pass list shares the hit buffer's capacity)
     const u64 hits = std::max(c->h_counters[ftkx::CNT_HITS], c->h_counters[ftkx::CNT_PASS]);
     const u64 listed = c->h_counters[ftkx::CNT_LIST_PEAK], refined = c->h_counters[ftkx::CNT_REFINE_PEAK];
     const u64 fragile = c->h_counters[ftkx::CNT_FRAGILE];
-    if (hits <= c->capacity && listed <= c->list_capacity && refined <= c->refine_capacity && fragile <= c->fragile_capacity) { ev_harvest(c); break; }
+    if (hits <= c->capacity && listed <= c->sr_tail[0].list_capacity && refined <= c->sr_tail[0].refine_capacity && fragile <= c->sr_tail[0].fragile_capacity) { ev_harvest(c); break; }
     // a buffer was too small (records / survivors beyond capacity were only counted): grow to what this batch needs, replay it
     for (auto &e : c->events) { ev_give(c, e.second.first); ev_give(c, e.second.second); }
     c->events.clear();
@@ -450,7 +450,7 @@ int ftkx_sweep_collect(ftkx_ctx *c, const ftkx_cp_t **out, size_t *n_out)
     // Most cells survive the cull (data whose quantised magnitudes can overflow the determinants almost everywhere):
     // a survivor list would be as large as the input.  Such a batch goes through the tile kernel instead, which stages each
     // tile's vertices once and applies the same cull rule in LDS.
-    if (any_fast && (listed > c->list_capacity || refined > c->refine_capacity) && (listed > fast_cells / 8 || refined * 8 > fast_cells / 8)) {
+    if (any_fast && (listed > c->sr_tail[0].list_capacity || refined > c->sr_tail[0].refine_capacity) && (listed > fast_cells / 8 || refined * 8 > fast_cells / 8)) {
       for (const Request &r : c->pending) {
         auto a = c->slices.find(r.t), b = c->slices.find(r.t + 1);
         if ((a != c->slices.end() && a->second.sparse) || ((r.scope & FTKX_SCOPE_INTERVAL) && b != c->slices.end() && b->second.sparse)) {
@@ -464,11 +464,11 @@ int ftkx_sweep_collect(ftkx_ctx *c, const ftkx_cp_t **out, size_t *n_out)
       if (hits > c->capacity && (rc = ensure_hit_buffer(c, 2 * hits + 1024))) { c->pending.clear(); return rc; }
       continue;
     }
-    if (fragile > c->fragile_capacity && (rc = ensure_fragile(c, fragile + fragile / 8 + 1024))) { c->pending.clear(); return rc; }
-    if (refined > c->refine_capacity && (rc = ensure_refine(c, refined + refined / 8 + 1024))) { c->pending.clear(); return rc; }
-    if (listed > c->list_capacity && (rc = ensure_list(c, listed + listed / 8 + 1024))) { c->pending.clear(); return rc; }
+    if (fragile > c->sr_tail[0].fragile_capacity && (rc = ensure_fragile(c, c->sr_tail[0], fragile + fragile / 8 + 1024))) { c->pending.clear(); return rc; }
+    if (refined > c->sr_tail[0].refine_capacity && (rc = ensure_refine(c, c->sr_tail[0], refined + refined / 8 + 1024))) { c->pending.clear(); return rc; }
+    if (listed > c->sr_tail[0].list_capacity && (rc = ensure_list(c, c->sr_tail[0], listed + listed / 8 + 1024))) { c->pending.clear(); return rc; }
     // with a truncated survivor list the hit count is a lower bound: leave generous room
-    const u64 want_hits = std::max<u64>(hits + hits / 8 + 1024, (listed > c->list_capacity || refined > c->refine_capacity) ? 2 * hits + 1024 : 0);
+    const u64 want_hits = std::max<u64>(hits + hits / 8 + 1024, (listed > c->sr_tail[0].list_capacity || refined > c->sr_tail[0].refine_capacity) ? 2 * hits + 1024 : 0);
     if (want_hits > c->capacity && (rc = ensure_hit_buffer(c, want_hits))) { c->pending.clear(); return rc; }
   }
   c->pending.clear();
@@ -482,7 +482,7 @@ int ftkx_sweep_collect(ftkx_ctx *c, const ftkx_cp_t **out, size_t *n_out)
   // exactly singular Hessian takes plateaus or lattice-aligned data -- and then one small round trip.
   if (const u64 nf = c->h_counters[ftkx::CNT_FRAGILE]) {
     std::vector<u64> frag((size_t)nf * 10), pairs((size_t)nf * 2);
-    HIP_TRY(c, hipMemcpyAsync(frag.data(), c->d_fragile, frag.size() * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(frag.data(), c->sr_tail[0].fragile, frag.size() * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     for (size_t i = 0; i < (size_t)nf; i ++) {
       double A[3][3];

@@ -124,15 +124,15 @@ enum { K_MASK = 0, K_CULL = 1, K_EXACT = 2, K_TILE = 3, K_N = 4 };
 }  // namespace ftkxh
 
 // A series pass that has been queued (ftkx_sweep_series_submit) and not yet collected (ftkx_sweep_series_complete): what the second half
-// of the call needs.  Two may be open at a time: the host prepares and queues pass N + 1 while the device still works on pass N, and the
-// records of pass N cross PCIe (a copy engine, not a kernel) while the mask kernel of pass N + 1 runs.
+// of the call needs.  Up to ftkx_ctx::kPlaces (three) may be open at a time: the host prepares and queues pass N + 1 while the device still
+// works on pass N, and the records of pass N cross PCIe (a copy engine, not a kernel) while the mask kernel of pass N + 1 runs.
 struct ftkx_series_pending {
   bool open = false;
   bool by_host = false;             // not queued: the host-driven batch sweeps it when it is collected
   std::vector<int> ts, scopes, slice_ts, red_index;
   std::vector<unsigned long long> gen;   // per slice: Slice::mask_gen as this pass left it
   int n = 0, buf = 0;
-  size_t k = 0, nwords = 0, nbins = 0, total_desc = 0;
+  size_t k = 0, nwords = 0, nbins = 0;
   unsigned long long hint = 0;
   bool two_level = false, short_chain = false, small_now = false, to_device = false;
   bool copy_pending = false;        // to_device: the copy kernel has not been queued yet (it goes behind the descriptor fetch of the next pass, or is queued when the pass is collected)
@@ -145,19 +145,18 @@ struct ftkx_series_pending {
   size_t off_steps = 0, off_slices = 0, off_sinfo = 0, ntodo = 0;
   int shift = 0;                    // order key -> bucket
   const u64 *running_from = nullptr;   // a results block on the device whose SR_RUNNING word this pass continues from (the pass before it, or a slab pass's stub)
-  bool pipelined = false;
   bool refined = false;             // the refine kernel has been queued already (a slab pass lists the halo's cells from its output)
   // split pass (series.hip, "the tail next to the next mask kernel"): begin + masks on the context's stream, the tail -- counters, cull + factors,
   // the kernel chain -- on the tail stream behind an event, next to the mask kernel of the pass queued behind it
   bool split = false;
   int before_buf = -1;              // the place of the split pass that was open when this one was planned (its factor job is waited for by this pass's tail), or -1
   int cal_kind = 0;                 // a pass of the split calibration: 1 measured in order, 2 measured split
-  int tail_set = 0;                 // 0: the context's own counters and lists, 1: sr_set1
+  int tail_set = 0;                 // which of ftkx_ctx::sr_tail its tail works on (series.hip: tail_of): 0 unless it is every other split pass of a short mask launch
   bool split_sparse = false;        // ... of a sparse pass: few workgroups per chain kernel, 2^10 buckets
   bool one = false;                 // the one-launch pass for small series (one_kernel.hip)
   std::vector<std::pair<unsigned char *, unsigned char *>> retired;   // (M, U) arrays this pass still reads, replaced in their slices by the pass queued behind it
   std::vector<ftkxh::Slice> parked;        // slices dropped (or replaced) while this split pass was the newest one open: its tail -- on a stream of its own -- may still read
-                                    // their arrays, which go back to the pools when it has been completed (free_slice)
+                                    // their arrays, which go back to the pools when it has been completed (release_retired)
   // slab pass (ftkx_series_dist_*): one rank's part of a series cut into timestep slabs, queued in stages with the caller's collectives between them
   bool dist = false;
   int dist_stage = 0;               // 1 begun (masks, contribution, outgoing masks), 2 culled (request written), 3 served (reply written), 4 finished = open
@@ -167,7 +166,7 @@ struct ftkx_series_pending {
   u64 *request_out = nullptr;       // device: this rank's request to its upper neighbour (count, cells)
 };
 
-// what one of the (two) passes in flight writes that the host reads, or that a copy engine reads after the pass
+// what one of the passes in flight writes that the host reads, or that a copy engine reads after the pass
 struct ftkx_series_buffers {
   u64 *results = nullptr, *h_results = nullptr;       // device block; coherent pinned copy with the flag word behind it
   size_t results_cap = 0, h_results_cap = 0;
@@ -183,6 +182,24 @@ struct ftkx_series_buffers {
   u64 *dist_block = nullptr;                           // slab pass: DB_N words (sweep_params.hpp)
 };
 
+// What the tail of a sweep works on, and the stream a SPLIT pass's tail runs on.  The context has two (ftkx_ctx::sr_tail).  Set 0 is what the
+// host-driven batch (collect.hip, prepare.hip, halo.hip) and every pass that is not split work on, in the order of the context's stream.  Set 1
+// (same capacities: ensure_set1) is for every other split pass of a short mask launch, so that the tails of two passes can run at the same time --
+// a mask launch shorter than one tail next to it (a single 512^3 slice) then still hides half a tail behind every mask kernel.
+struct ftkx_tail_set {
+  u64 *counters = nullptr;          // CNT_N counters + 128 words (64 {min, max} slots) for the resolution reduction + 8
+  u64 *list = nullptr;              // surviving corners of the fast path
+  u64 *refine = nullptr;            // words the summary level could not rule out (two-level cull)
+  u64 *pass = nullptr;              // simplices that passed the integer test, awaiting the record kernel
+  u64 *fragile = nullptr;           // 3D records to be re-classified on the host (slot, J[9]): cp_device.hpp, classify3
+  u64 *bucketed = nullptr, *sorted = nullptr;   // series pass: the order keys by bucket, and ranked
+  unsigned *hist = nullptr, *boff = nullptr;    // series pass: bucket counts and offsets
+  // `capacity` is the set's own copy of ftkx_ctx::capacity (which stays the capacity of d_hits / h_hits and of Mesh::capacity): how far THIS
+  // set's pass array has followed it
+  u64 capacity = 0, list_capacity = 0, refine_capacity = 0, fragile_capacity = 0, order_capacity = 0, bins_cap = 0;
+  hipStream_t stream = nullptr;     // the tail of a split pass on this set; created where the first such pass is planned
+};
+
 struct ftkx_ctx {
   int nd = 0, device = 0;
   hipStream_t own_stream = nullptr, stream = nullptr;
@@ -192,15 +209,8 @@ struct ftkx_ctx {
   int scalar_mode = -1;             // -1 undecided, 0 vector slices, 1 scalar slices (V = gradient(S) evaluated in flight)
   std::map<int, ftkxh::Slice> slices;
   ftkx_cp_t *d_hits = nullptr;
-  u64 *d_pass = nullptr;            // simplices that passed the integer test, awaiting the record kernel (same capacity)
-  u64 *d_fragile = nullptr;         // 3D records to be re-classified on the host (slot, J[9]): cp_device.hpp, classify3
-  u64 fragile_capacity = 0;
-  u64 capacity = 0;
-  u64 *d_list = nullptr;            // surviving corners of the fast path
-  u64 list_capacity = 0;
-  u64 *d_refine = nullptr;          // words the summary level could not rule out (two-level cull)
-  u64 refine_capacity = 0;
-  u64 *d_counters = nullptr;        // CNT_N counters + 128 words (64 {min, max} slots) for the resolution reduction
+  u64 capacity = 0;                 // of d_hits, and of the pass array of every tail set in use
+  ftkx_tail_set sr_tail[2];         // [0]: the host-driven batch's and every unsplit pass's
   u64 *d_tile_stats = nullptr;      // 512 words: the tile kernels' statistics in 256 slots (TileParams::stats)
   u64 *h_counters = nullptr;        // pinned
   ftkx_cp_t *h_hits = nullptr;      // pinned
@@ -258,20 +268,11 @@ struct ftkx_ctx {
   int sr_place(int k) const { return (sr_head + k) % kPlaces; }      // the k-th oldest open pass's place
   int sr_open = 0, sr_head = 0;       // passes open, and which of sr_pend is the oldest
   bool sr_internal = false;           // the host-driven batch is sweeping for a series pass: its calls are let through while passes are open
-  // which pass the context's counters and survivor lists (d_counters, d_list, d_refine, d_pass) belong to right now: stamped when a pass's
+  // which pass the counters and survivor lists of tail set 0 belong to right now: stamped when a pass's
   // cull is queued, cleared whenever the host-driven batch takes them (series.hip: a pass whose fused tail declined may queue the rest of
   // its chain only while they are still its own)
   unsigned long long sr_pass_uid = 0, sr_lists_owner = 0;
-  hipStream_t sr_copy_stream = nullptr, sr_fetch_stream = nullptr, sr_tail_stream = nullptr, sr_tail_stream2 = nullptr;
-  // what the tail of a split pass works on besides the context's own counters, lists, pass descriptors, fragile list and ordering arrays: a second
-  // set (same capacities) for every other split pass, on the second tail stream, so that the tails of two passes can run at the same time -- a
-  // mask launch shorter than one tail next to it (a single 512^3 slice) then still hides half a tail behind every mask kernel
-  struct tail_set {
-    u64 *counters = nullptr, *list = nullptr, *refine = nullptr, *pass = nullptr, *fragile = nullptr, *bucketed = nullptr, *sorted = nullptr;
-    unsigned *hist = nullptr, *boff = nullptr;
-    u64 capacity = 0, list_capacity = 0, refine_capacity = 0, fragile_capacity = 0;
-    size_t bins_cap = 0;
-  } sr_set1;
+  hipStream_t sr_copy_stream = nullptr;
   ftkxh::split_cal sr_cal;              // the split pass's self-check (split_policy.hpp)
   int sr_split_forced = 0;              // the last plan's FTKX_SERIES_HOOKS split setting: 0 auto, 1 forced on (2, 3, 4), 2 forced off (0)
   double sr_last_complete_s = 0;        // host clock of the last completion (0: the pipeline ran empty since)
@@ -284,19 +285,14 @@ struct ftkx_ctx {
   hipEvent_t sr_ev_fetched = nullptr;  // slab passes: recorded behind the begin kernel, waited for by the copy of the pass before (no spin-wait there)
   unsigned long long mask_epoch = 0;  // source of Slice::mask_gen values
   double sr_last_running = 0;         // the running minimum the host knew when it last collected a pass (hint of a chained pass)
-  unsigned *sr_hist = nullptr, *sr_boff = nullptr;
-  size_t sr_bins_cap = 0;
-  u64 *sr_bucketed = nullptr;
-  size_t sr_bucketed_cap = 0;
-  u64 *sr_sorted = nullptr;
-  size_t sr_sorted_cap = 0;
   int sr_skip_small = 0;             // passes for which the fused tail kernel is not launched (the data was hit-dense a moment ago)
   int sr_late_streak = 0;            // consecutive passes the fused tail declined late
   bool sr_short_chain = false;       // the last pass was finished by the fused tail kernel: the next one is queued without the kernels behind it
   bool sr_sparse = false;            // the last pass had few survivors and records (the fused tail's range): a pass whose mask kernel is long enough is split
   int sr_last_buf = 0;               // the buffers of the pass completed last (ftkx_series_dist_status reads its results block)
   size_t sr_last_gathered_off = 0; int sr_last_nranks = 0;   // where its gathered contributions sit in that block (0 ranks: not a slab pass)
-  int sr_last_path = 0;              // which way the last ftkx_sweep_series went: 1 device-driven, 2 early single-workgroup tail, 0 the host-driven batch
+  int sr_last_path = 0;              // which way the last ftkx_sweep_series went: 0 the host-driven batch, 1 device-driven (the kernel chain), 2 early single-workgroup tail,
+                                     // 4 the one-launch pass, 5 a split pass
   unsigned long long sr_last_status = 0;
   // pass 2 on the device (trace_device.hip): tags up, neighbours / degrees / roots down
   void *tr_dev = nullptr, *tr_host = nullptr, *tr_parent = nullptr, *tr_tables = nullptr;
@@ -336,12 +332,17 @@ int u_pitch(const ftkx_ctx *c);
 size_t u_bytes(const ftkx_ctx *c);
 size_t u_bytes_used(const ftkx_ctx *c, const Mesh &m);
 size_t mask_bytes(const ftkx_ctx *c);
-void free_slice(Slice &s, ftkx_ctx *pool_owner = nullptr);
+void release_slice(Slice &s, ftkx_ctx *pool_owner = nullptr);   // its arrays back to the owner's pools, or (no owner) freed
+void free_slice(Slice &s, ftkx_ctx *c);                         // a slice of a live context is dropped: parked with the newest open split pass, or released
 void release_pools(ftkx_ctx *c);
-int ensure_hit_buffer(ftkx_ctx *c, u64 want);
-int ensure_fragile(ftkx_ctx *c, u64 want);
-int ensure_list(ftkx_ctx *c, u64 want);
-int ensure_refine(ftkx_ctx *c, u64 want);
+int ensure_hit_buffer(ftkx_ctx *c, u64 want);                   // d_hits and set 0's pass array
+int ensure_pass(ftkx_ctx *c, ftkx_tail_set &S, u64 want);
+int ensure_fragile(ftkx_ctx *c, ftkx_tail_set &S, u64 want);
+int ensure_list(ftkx_ctx *c, ftkx_tail_set &S, u64 want);
+int ensure_refine(ftkx_ctx *c, ftkx_tail_set &S, u64 want);
+int ensure_bins(ftkx_ctx *c, ftkx_tail_set &S, u64 want);       // hist + boff
+int ensure_order(ftkx_ctx *c, ftkx_tail_set &S, u64 want);      // bucketed + sorted
+hipError_t sync_tails(ftkx_ctx *c);                             // the host waits for whatever is queued on the tail streams
 int ensure_desc(ftkx_ctx *c, size_t bytes);
 int ensure_host_buffer(ftkx_ctx *c, size_t want);
 void fill_mesh(const ftkx_ctx *c, Mesh &m);

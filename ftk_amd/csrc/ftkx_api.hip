@@ -70,24 +70,15 @@ size_t u_bytes(const ftkx_ctx *c) { return (size_t)u_pitch(c) * (size_t)c->ext_s
 size_t u_bytes_used(const ftkx_ctx *c, const Mesh &m) { return (size_t)u_pitch(c) * (size_t)((c->ext_sz[1] + m.u_rows - 1) / m.u_rows) * (size_t)(c->nd == 3 ? c->ext_sz[2] : 1); }
 size_t mask_bytes(const ftkx_ctx *c) { return (size_t)mask_pitch(c) * (size_t)c->ext_sz[1] * (size_t)(c->nd == 3 ? c->ext_sz[2] : 1); }
 
-void free_slice(Slice &s, ftkx_ctx *pool_owner)
+void release_slice(Slice &s, ftkx_ctx *pool_owner)
 {
-  // The newest open pass is a SPLIT pass: its tail runs on a stream of its own and may still read this slice's arrays, while whatever takes
-  // them out of the pools next -- a push, the mask kernel of the next pass -- runs on the context's stream, in no order with that tail.
-  // The slice is parked with that pass and comes back here when it has been completed (series.hip, release_retired).
-  if (pool_owner && pool_owner->sr_open > 0) {
-    ftkx_series_pending &N = pool_owner->sr_pend[pool_owner->sr_place(pool_owner->sr_open - 1)];
-    if (N.open && N.split) { N.parked.push_back(s); s = Slice(); return; }
-  }
   // owned copies go back to the context's pool: a streaming caller pushes and pops one slice per step, and hipMalloc + hipFree of a
   // slice-sized array cost more than sweeping a 256^3 slice
   auto give_back = [&](double *p, size_t count) {
     if (pool_owner && pool_owner->pool_F.size() < 12) pool_owner->pool_F.push_back({p, count});      // (12: a batch of steps parked with a split pass comes back at once)
     else (void)hipFree(p);
   };
-  size_t nv = 0;
-  if (pool_owner) { nv = 1; for (int d = 0; d < pool_owner->nd; d ++) nv *= (size_t)pool_owner->ext_sz[d]; }
-  const size_t nd_ = pool_owner ? (size_t)pool_owner->nd : 0;
+  const size_t nv = pool_owner ? n_vertices(pool_owner) : 0, nd_ = pool_owner ? (size_t)pool_owner->nd : 0;
   if (s.ownV && s.V) give_back(s.V, nv * nd_);
   if (s.ownJ && s.J) give_back(s.J, nv * nd_ * nd_);
   if (s.ownS && s.S) give_back(s.S, nv);
@@ -95,6 +86,18 @@ void free_slice(Slice &s, ftkx_ctx *pool_owner)
   if (s.M) { if (pool_owner && pool_owner->pool_M.size() < 12) pool_owner->pool_M.push_back(s.M); else (void)hipFree(s.M); }
   if (s.U) { if (pool_owner && pool_owner->pool_U.size() < 12) pool_owner->pool_U.push_back(s.U); else (void)hipFree(s.U); }
   s = Slice();
+}
+
+void free_slice(Slice &s, ftkx_ctx *c)
+{
+  // The newest open pass is a SPLIT pass: its tail runs on a stream of its own and may still read this slice's arrays, while whatever takes
+  // them out of the pools next -- a push, the mask kernel of the next pass -- runs on the context's stream, in no order with that tail.
+  // The slice is parked with that pass and is released when it has been completed (series.hip, release_retired).
+  if (c->sr_open > 0) {
+    ftkx_series_pending &N = c->sr_pend[c->sr_place(c->sr_open - 1)];
+    if (N.open && N.split) { N.parked.push_back(s); s = Slice(); return; }
+  }
+  release_slice(s, c);
 }
 
 void release_pools(ftkx_ctx *c)
@@ -105,42 +108,47 @@ void release_pools(ftkx_ctx *c)
   c->pool_M.clear(); c->pool_U.clear(); c->pool_F.clear();
 }
 
+// ---- the tail sets (ctx.hpp) ---------------------------------------------------------------------------------------------------------
+// An array of a set (or two of one size) replaced by a larger one; contents are not kept.  Nothing of a set is freed while its stream may still read it: the
+// stream is drained first.  (Set 0 grows only where everything has been waited for anyway; the synchronise costs the rare growth path a call.)
+static int regrow(ftkx_ctx *c, ftkx_tail_set &S, u64 *cap, u64 want, size_t elem_bytes, void **p, void **q = nullptr /* a second array of the same size */)
+{
+  if (*cap >= want) return FTKX_OK;
+  *cap = 0;
+  for (void **a : {p, q}) {
+    if (a && *a) {
+      if (S.stream) HIP_TRY(c, hipStreamSynchronize(S.stream));
+      HIP_TRY(c, hipFree(*a));
+      *a = nullptr;
+    }
+    if (a) HIP_TRY(c, hipMalloc(a, want * elem_bytes));
+  }
+  *cap = want;
+  return FTKX_OK;
+}
+
+int ensure_pass(ftkx_ctx *c, ftkx_tail_set &S, u64 want) { return regrow(c, S, &S.capacity, want, sizeof(u64), (void **)&S.pass); }
+int ensure_fragile(ftkx_ctx *c, ftkx_tail_set &S, u64 want) { return regrow(c, S, &S.fragile_capacity, want, 10 * sizeof(u64), (void **)&S.fragile); }
+int ensure_list(ftkx_ctx *c, ftkx_tail_set &S, u64 want) { return regrow(c, S, &S.list_capacity, want, sizeof(u64), (void **)&S.list); }
+int ensure_refine(ftkx_ctx *c, ftkx_tail_set &S, u64 want) { return regrow(c, S, &S.refine_capacity, want, sizeof(u64), (void **)&S.refine); }
+int ensure_bins(ftkx_ctx *c, ftkx_tail_set &S, u64 want) { return regrow(c, S, &S.bins_cap, want, sizeof(unsigned), (void **)&S.hist, (void **)&S.boff); }
+int ensure_order(ftkx_ctx *c, ftkx_tail_set &S, u64 want) { return regrow(c, S, &S.order_capacity, want, sizeof(u64), (void **)&S.bucketed, (void **)&S.sorted); }
+
 int ensure_hit_buffer(ftkx_ctx *c, u64 want)
 {
   if (c->capacity >= want) return FTKX_OK;
   if (c->d_hits) { HIP_TRY(c, hipFree(c->d_hits)); c->d_hits = nullptr; c->capacity = 0; }
-  if (c->d_pass) { HIP_TRY(c, hipFree(c->d_pass)); c->d_pass = nullptr; }
   HIP_TRY(c, hipMalloc((void **)&c->d_hits, want * sizeof(ftkx_cp_t)));
-  HIP_TRY(c, hipMalloc((void **)&c->d_pass, want * sizeof(u64)));
+  if (int rc = ensure_pass(c, c->sr_tail[0], want)) return rc;
   c->capacity = want;
   return FTKX_OK;
 }
 
-int ensure_fragile(ftkx_ctx *c, u64 want)
+hipError_t sync_tails(ftkx_ctx *c)
 {
-  if (c->fragile_capacity >= want) return FTKX_OK;
-  if (c->d_fragile) { HIP_TRY(c, hipFree(c->d_fragile)); c->d_fragile = nullptr; c->fragile_capacity = 0; }
-  HIP_TRY(c, hipMalloc((void **)&c->d_fragile, want * 10 * sizeof(u64)));
-  c->fragile_capacity = want;
-  return FTKX_OK;
-}
-
-int ensure_list(ftkx_ctx *c, u64 want)
-{
-  if (c->list_capacity >= want) return FTKX_OK;
-  if (c->d_list) { HIP_TRY(c, hipFree(c->d_list)); c->d_list = nullptr; c->list_capacity = 0; }
-  HIP_TRY(c, hipMalloc((void **)&c->d_list, want * sizeof(u64)));
-  c->list_capacity = want;
-  return FTKX_OK;
-}
-
-int ensure_refine(ftkx_ctx *c, u64 want)
-{
-  if (c->refine_capacity >= want) return FTKX_OK;
-  if (c->d_refine) { HIP_TRY(c, hipFree(c->d_refine)); c->d_refine = nullptr; c->refine_capacity = 0; }
-  HIP_TRY(c, hipMalloc((void **)&c->d_refine, want * sizeof(u64)));
-  c->refine_capacity = want;
-  return FTKX_OK;
+  for (ftkx_tail_set &S : c->sr_tail)
+    if (S.stream) { const hipError_t e = hipStreamSynchronize(S.stream); if (e != hipSuccess) return e; }
+  return hipSuccess;
 }
 
 int ensure_desc(ftkx_ctx *c, size_t bytes)
@@ -197,15 +205,16 @@ void fill_mesh(const ftkx_ctx *c, Mesh &m)
   for (int i = 0; i < 6; i ++) m.coords_bounds[i] = c->opt.coords_bounds[i];
   for (int d = 0; d < 3; d ++) m.coords_rect[d] = c->d_rect[d];
   m.coords_expl = c->d_expl; m.coords_expl_ncomp = c->expl_ncomp; m.coords_expl_n0 = (int)c->expl_n0;
-  m.hits = c->d_hits; m.pass = c->d_pass; m.counters = c->d_counters; m.capacity = c->capacity;
-  m.fragile = c->d_fragile; m.fragile_capacity = c->fragile_capacity;
+  const ftkx_tail_set &S = c->sr_tail[0];                     // (a series pass on the other set: series.hip, series_mesh)
+  m.hits = c->d_hits; m.pass = S.pass; m.counters = S.counters; m.capacity = c->capacity;
+  m.fragile = S.fragile; m.fragile_capacity = S.fragile_capacity;
   m.u_rows = ftkx::mask_summary_rows(m);
 }
 
 int slice_resolution(ftkx_ctx *c, Slice &s)
 {
   if (s.have_res) return FTKX_OK;
-  u64 *d = c->d_counters + ftkx::CNT_N;
+  u64 *d = c->sr_tail[0].counters + ftkx::CNT_N;
   u64 init[128];
   for (int i = 0; i < 64; i ++) { init[2 * i] = 0x7fefffffffffffffull; init[2 * i + 1] = 0ull; }
   HIP_TRY(c, hipMemcpyAsync(d, init, sizeof(init), hipMemcpyHostToDevice, c->stream));
@@ -389,8 +398,8 @@ int ftkx_create(ftkx_ctx **out, int nd, int device_id)
     HIP_TRY(c, hipStreamCreateWithFlags(&c->own_stream, hipStreamDefault));
     c->stream = c->own_stream;
     // CNT_N counters, 128 words of reduction slots, one word that says "a halo message did not fit this mesh" (halo.hip; survives the sweeps' resets)
-    HIP_TRY(c, hipMalloc((void **)&c->d_counters, (ftkx::CNT_N + 128 + 8) * sizeof(u64)));
-    HIP_TRY(c, hipMemset(c->d_counters, 0, (ftkx::CNT_N + 128 + 8) * sizeof(u64)));
+    HIP_TRY(c, hipMalloc((void **)&c->sr_tail[0].counters, (ftkx::CNT_N + 128 + 8) * sizeof(u64)));
+    HIP_TRY(c, hipMemset(c->sr_tail[0].counters, 0, (ftkx::CNT_N + 128 + 8) * sizeof(u64)));
     HIP_TRY(c, hipHostMalloc((void **)&c->h_counters, ftkx::CNT_N * sizeof(u64), hipHostMallocDefault));
     return FTKX_OK;
   };
@@ -405,9 +414,10 @@ void ftkx_destroy(ftkx_ctx *c)
   if (!c) return;
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
-  for (hipStream_t st : {c->sr_tail_stream, c->sr_tail_stream2, c->sr_copy_stream}) if (st) (void)hipStreamSynchronize(st);      // (passes left open: their tails and copies read what is freed below)
-  for (auto &kv : c->slices) free_slice(kv.second);
-  for (ftkx_series_pending &P : c->sr_pend) { for (Slice &sl : P.parked) free_slice(sl); P.parked.clear(); }
+  (void)sync_tails(c);                                        // (passes left open: their tails and copies read what is freed below)
+  if (c->sr_copy_stream) (void)hipStreamSynchronize(c->sr_copy_stream);
+  for (auto &kv : c->slices) release_slice(kv.second);
+  for (ftkx_series_pending &P : c->sr_pend) { for (Slice &sl : P.parked) release_slice(sl); P.parked.clear(); }
   release_pools(c);
   for (auto &e : c->events) { (void)hipEventDestroy(e.second.first); (void)hipEventDestroy(e.second.second); }
   for (hipEvent_t e : c->event_pool) (void)hipEventDestroy(e);
@@ -417,10 +427,7 @@ void ftkx_destroy(ftkx_ctx *c)
   if (c->d_red) (void)hipFree(c->d_red);
   if (c->d_tile_stats) (void)hipFree(c->d_tile_stats);
   if (c->d_hits) (void)hipFree(c->d_hits);
-  if (c->d_pass) (void)hipFree(c->d_pass);
-  if (c->d_fragile) (void)hipFree(c->d_fragile);
   for (void *p : {(void *)c->d_word_idx, (void *)c->d_words, (void *)c->d_cells, (void *)c->d_patch_cells, (void *)c->d_patches, c->d_packed}) if (p) (void)hipFree(p);
-  for (void *p : {(void *)c->sr_hist, (void *)c->sr_boff, (void *)c->sr_bucketed, (void *)c->sr_sorted}) if (p) (void)hipFree(p);
   for (ftkx_series_buffers &B : c->sr_buf) {
     for (void *p : {(void *)B.results, (void *)B.d_out, B.d_desc, (void *)B.copy_done, (void *)B.dist_block}) if (p) (void)hipFree(p);
     if (B.ev_copied) (void)hipEventDestroy(B.ev_copied);
@@ -430,18 +437,16 @@ void ftkx_destroy(ftkx_ctx *c)
     for (void *p : {(void *)B.h_results, (void *)B.out, B.h_desc}) if (p) (void)hipHostFree(p);
   }
   aux_stream_put(c, false, c->sr_copy_stream);
-  aux_stream_put(c, true, c->sr_tail_stream);
-  aux_stream_put(c, true, c->sr_tail_stream2);
-  for (void *q : {(void *)c->sr_set1.counters, (void *)c->sr_set1.list, (void *)c->sr_set1.refine, (void *)c->sr_set1.pass, (void *)c->sr_set1.fragile,
-                  (void *)c->sr_set1.bucketed, (void *)c->sr_set1.sorted, (void *)c->sr_set1.hist, (void *)c->sr_set1.boff}) if (q) (void)hipFree(q);
+  for (ftkx_tail_set &S : c->sr_tail) {
+    aux_stream_put(c, true, S.stream);
+    for (void *q : {(void *)S.counters, (void *)S.list, (void *)S.refine, (void *)S.pass, (void *)S.fragile, (void *)S.bucketed, (void *)S.sorted, (void *)S.hist, (void *)S.boff})
+      if (q) (void)hipFree(q);
+  }
   if (c->sr_one_scratch) (void)hipFree(c->sr_one_scratch);
   if (c->sr_fetch_flag) (void)hipFree(c->sr_fetch_flag);
   if (c->sr_ev_fetched) (void)hipEventDestroy(c->sr_ev_fetched);
-  if (c->sr_fetch_stream) (void)hipStreamDestroy(c->sr_fetch_stream);
   for (void *p : {c->tr_dev, c->tr_parent, c->tr_tables}) if (p) (void)hipFree(p);
   if (c->tr_host) (void)hipHostFree(c->tr_host);
-  if (c->d_list) (void)hipFree(c->d_list);
-  if (c->d_refine) (void)hipFree(c->d_refine);
   if (c->d_sorted) (void)hipFree(c->d_sorted);
   if (c->d_keys) (void)hipFree(c->d_keys);
   if (c->d_idx) (void)hipFree(c->d_idx);
@@ -450,7 +455,6 @@ void ftkx_destroy(ftkx_ctx *c)
   for (int d = 0; d < 3; d ++) if (c->d_rect[d]) (void)hipFree(c->d_rect[d]);
   if (c->d_expl) (void)hipFree(c->d_expl);
   if (c->h_desc) (void)hipHostFree(c->h_desc);
-  if (c->d_counters) (void)hipFree(c->d_counters);
   if (c->h_counters) (void)hipHostFree(c->h_counters);
   if (c->h_hits) (void)hipHostFree(c->h_hits);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -570,10 +574,10 @@ static int push_common(ftkx_ctx *c, int t, const double *V, const double *J, con
     return FTKX_OK;
   };
   int rc;
-  if ((rc = take(S, n, &s.S, &s.ownS))) { free_slice(s); return rc; }
+  if ((rc = take(S, n, &s.S, &s.ownS))) { release_slice(s); return rc; }
   if (!scalar_only) {
-    if ((rc = take(V, n * nd, &s.V, &s.ownV))) { free_slice(s); return rc; }      // what was already allocated goes back
-    if ((rc = take(J, n * nd * nd, &s.J, &s.ownJ))) { free_slice(s); return rc; }
+    if ((rc = take(V, n * nd, &s.V, &s.ownV))) { release_slice(s); return rc; }      // what was already allocated goes back
+    if ((rc = take(J, n * nd * nd, &s.J, &s.ownJ))) { release_slice(s); return rc; }
   }
   // scalar input: V = gradient2D/3D(S) is never materialised -- every kernel evaluates it where it needs it, with the
   // reference's exact operations (ndarray/grad.hh), so the slice costs 8 bytes per vertex of HBM instead of 8 + 8*nd.
@@ -726,7 +730,7 @@ int ftkx_debug_stream_read(ftkx_ctx *c, const void *device_ptr, size_t bytes)
 {
   if (!c || !device_ptr) return fail(c, FTKX_E_INVALID, "null argument");
   HIP_TRY(c, hipSetDevice(c->device));
-  ftkx::launch_calib_read(device_ptr, bytes, (double *)(c->d_counters + ftkx::CNT_N), c->stream);
+  ftkx::launch_calib_read(device_ptr, bytes, (double *)(c->sr_tail[0].counters + ftkx::CNT_N), c->stream);
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return FTKX_OK;

@@ -27,10 +27,10 @@ int ftkx_export_masks_size(ftkx_ctx *c, int t, size_t *u_bytes_out, size_t *n_wo
   HIP_TRY(c, hipSetDevice(c->device));
   Mesh m; fill_mesh(c, m);
   for (int attempt = 0; attempt < 2; attempt ++) {
-    HIP_TRY(c, hipMemsetAsync(c->d_counters + ftkx::CNT_SPARSE, 0, sizeof(u64), c->stream));
-    ftkx::launch_compact_words(m, s.U, s.M, c->d_word_idx, c->d_words, c->words_cap, c->d_counters + ftkx::CNT_SPARSE, c->stream);
+    HIP_TRY(c, hipMemsetAsync(c->sr_tail[0].counters + ftkx::CNT_SPARSE, 0, sizeof(u64), c->stream));
+    ftkx::launch_compact_words(m, s.U, s.M, c->d_word_idx, c->d_words, c->words_cap, c->sr_tail[0].counters + ftkx::CNT_SPARSE, c->stream);
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(c->h_counters, c->d_counters + ftkx::CNT_SPARSE, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->h_counters, c->sr_tail[0].counters + ftkx::CNT_SPARSE, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     const size_t n = (size_t)c->h_counters[0];
     if (n <= c->words_cap) { c->n_words = n; c->words_t = t; break; }
@@ -66,7 +66,7 @@ int ftkx_export_masks(ftkx_ctx *c, int t, void *U_dst, unsigned *word_index_dst,
 }
 
 namespace {
-u64 *halo_bad_flag(ftkx_ctx *c) { return c->d_counters + ftkx::CNT_N + 128; }
+u64 *halo_bad_flag(ftkx_ctx *c) { return c->sr_tail[0].counters + ftkx::CNT_N + 128; }
 size_t pad8(size_t v) { return (v + 7) / 8 * 8; }
 int factor_log2(unsigned long long f) { int b = 0; while (b < 63 && (1ull << b) < f) b ++; return b; }
 // capacity of the word list in a packed mask message: the mask kernels write a word only where its summary is 0 -- a thin shell around
@@ -215,10 +215,10 @@ int ftkx_export_masks_packed(ftkx_ctx *c, int t, void *dst, int dst_on_device)
   }
   unsigned *idx = (unsigned *)(out + 32 + pad8(ub));
   u64 *words = (u64 *)(out + 32 + pad8(ub) + pad8(cap * sizeof(unsigned)));
-  HIP_TRY(c, hipMemsetAsync(c->d_counters + ftkx::CNT_SPARSE, 0, sizeof(u64), c->stream));
-  ftkx::launch_compact_words(m, s.U, s.M, idx, words, cap, c->d_counters + ftkx::CNT_SPARSE, c->stream);
+  HIP_TRY(c, hipMemsetAsync(c->sr_tail[0].counters + ftkx::CNT_SPARSE, 0, sizeof(u64), c->stream));
+  ftkx::launch_compact_words(m, s.U, s.M, idx, words, cap, c->sr_tail[0].counters + ftkx::CNT_SPARSE, c->stream);
   // (the header says under which factor the masks were built and how many rows a summary byte stands for: the receiver checks both)
-  ftkx::launch_pack_masks((u64 *)out, c->d_counters + ftkx::CNT_SPARSE, s.U, ub, cap, s.u_rows, factor_log2(s.mask_factor), c->stream);
+  ftkx::launch_pack_masks((u64 *)out, c->sr_tail[0].counters + ftkx::CNT_SPARSE, s.U, ub, cap, s.u_rows, factor_log2(s.mask_factor), c->stream);
   HIP_TRY(c, hipGetLastError());
   if (!dst_on_device) { HIP_TRY(c, hipMemcpyAsync(dst, out, total, hipMemcpyDeviceToHost, c->stream)); HIP_TRY(c, hipStreamSynchronize(c->stream)); }
   return FTKX_OK;                                          // (device destination: queued on the context's stream, nothing waited for)
@@ -292,17 +292,17 @@ int ftkx_sweep_cull(ftkx_ctx *c, int t_sparse, size_t *n_cells)
   const double *field = it->second.S ? it->second.S : it->second.V;
   int rc;
   if ((rc = ensure_hit_buffer(c, std::max<u64>(c->capacity, 1u << 16)))) return rc;
-  if ((rc = ensure_list(c, std::max<u64>(c->list_capacity, 1u << 20))) || (rc = ensure_refine(c, std::max<u64>(c->refine_capacity, 1u << 20)))) return rc;
+  if ((rc = ensure_list(c, c->sr_tail[0], std::max<u64>(c->sr_tail[0].list_capacity, 1u << 20))) || (rc = ensure_refine(c, c->sr_tail[0], std::max<u64>(c->sr_tail[0].refine_capacity, 1u << 20)))) return rc;
   for (int attempt = 0; attempt < 4; attempt ++) {
-    if (c->cells_cap < c->list_capacity) {
+    if (c->cells_cap < c->sr_tail[0].list_capacity) {
       if (c->d_cells) (void)hipFree(c->d_cells);
       c->d_cells = nullptr; c->cells_cap = 0;
-      HIP_TRY(c, hipMalloc((void **)&c->d_cells, c->list_capacity * sizeof(u64)));
-      c->cells_cap = c->list_capacity;
+      HIP_TRY(c, hipMalloc((void **)&c->d_cells, c->sr_tail[0].list_capacity * sizeof(u64)));
+      c->cells_cap = c->sr_tail[0].list_capacity;
     }
-    HIP_TRY(c, hipMemsetAsync(c->d_counters, 0, ftkx::CNT_N * sizeof(u64), c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->sr_tail[0].counters, 0, ftkx::CNT_N * sizeof(u64), c->stream));
     if ((rc = run_batch(c, field))) return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->h_counters, c->d_counters, ftkx::CNT_N * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->h_counters, c->sr_tail[0].counters, ftkx::CNT_N * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
     u64 halo_bad = 0;
     HIP_TRY(c, hipMemcpyAsync(&halo_bad, halo_bad_flag(c), sizeof(u64), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -313,9 +313,9 @@ int ftkx_sweep_cull(ftkx_ctx *c, int t_sparse, size_t *n_cells)
     for (auto &e : c->events) { ev_give(c, e.second.first); ev_give(c, e.second.second); }
     c->events.clear();
     const u64 listed = c->h_counters[ftkx::CNT_SURVIVOR_LIST], refined = std::max(c->h_counters[ftkx::CNT_REFINE_LIST], c->h_counters[ftkx::CNT_REFINE_PEAK]);
-    if (listed <= c->list_capacity && refined <= c->refine_capacity) { c->n_cells = (size_t)c->h_counters[ftkx::CNT_SPARSE]; *n_cells = c->n_cells; return FTKX_OK; }
-    if (refined > c->refine_capacity && (rc = ensure_refine(c, refined + refined / 8 + 1024))) return rc;
-    if (listed > c->list_capacity && (rc = ensure_list(c, 2 * listed + 1024))) return rc;
+    if (listed <= c->sr_tail[0].list_capacity && refined <= c->sr_tail[0].refine_capacity) { c->n_cells = (size_t)c->h_counters[ftkx::CNT_SPARSE]; *n_cells = c->n_cells; return FTKX_OK; }
+    if (refined > c->sr_tail[0].refine_capacity && (rc = ensure_refine(c, c->sr_tail[0], refined + refined / 8 + 1024))) return rc;
+    if (listed > c->sr_tail[0].list_capacity && (rc = ensure_list(c, c->sr_tail[0], 2 * listed + 1024))) return rc;
   }
   return fail(c, FTKX_E_DEVICE, "ftkx_sweep_cull: survivor lists kept overflowing");
 }

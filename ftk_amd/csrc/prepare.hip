@@ -94,8 +94,8 @@ bool ahead_steps(ftkx_ctx *c, bool two_level, u64 hint, std::vector<Fields> &ste
 void ahead_launch(ftkx_ctx *c, const Mesh &m, bool two_level, const Fields *d_steps, int nsteps)
 {
   ev_begin(c, K_CULL);
-  if (two_level) ftkx::launch_cull_two_level(m, d_steps, nsteps, c->d_refine, c->refine_capacity, c->d_list, c->list_capacity, c->stream);
-  else ftkx::launch_cull(m, d_steps, nsteps, c->d_list, c->list_capacity, c->stream);
+  if (two_level) ftkx::launch_cull_two_level(m, d_steps, nsteps, c->sr_tail[0].refine, c->sr_tail[0].refine_capacity, c->sr_tail[0].list, c->sr_tail[0].list_capacity, c->stream);
+  else ftkx::launch_cull(m, d_steps, nsteps, c->sr_tail[0].list, c->sr_tail[0].list_capacity, c->stream);
   ev_end(c);
 }
 
@@ -175,14 +175,14 @@ int ftkx_slices_prepare(ftkx_ctx *c, const int *ts, int n, unsigned long long fa
         *reinterpret_cast<volatile unsigned *>(c->h_red + slots) = 0u;
         c->red_seq = 0;
       }
-      if ((rc = ensure_list(c, std::max<u64>(c->list_capacity, 1u << 20))) || (rc = ensure_refine(c, std::max<u64>(c->refine_capacity, 1u << 20)))) return rc;
+      if ((rc = ensure_list(c, c->sr_tail[0], std::max<u64>(c->sr_tail[0].list_capacity, 1u << 20))) || (rc = ensure_refine(c, c->sr_tail[0], std::max<u64>(c->sr_tail[0].refine_capacity, 1u << 20)))) return rc;
     }
     else {                         // (no cull-ahead: the masks are rewritten all the same -- whatever they were valid for is gone)
       marks.armed = true;
       for (Slice *s : todo) s->mask_factor = 0;
     }
     if ((rc = ensure_desc(c, std::max(k * sizeof(MaskJob), k * 128 * sizeof(u64))))) return rc;
-    launch_init_red(c->d_red, k * 64, ahead_ok ? c->d_counters : nullptr, c->stream);
+    launch_init_red(c->d_red, k * 64, ahead_ok ? c->sr_tail[0].counters : nullptr, c->stream);
     MaskJob *jobs = (MaskJob *)c->h_desc;
     for (size_t i = 0; i < k; i ++)
       jobs[i] = with_lean_thresholds(MaskJob{todo[i]->S, todo[i]->V, todo[i]->M, two_level ? todo[i]->U : nullptr, c->d_red + i * 128, cap, HUGE_VAL}, m);   // rule off: validated below

@@ -34,7 +34,7 @@ int series_by_host(ftkx_ctx *c, const int *ts, const int *scopes, int n, const s
   c->sr_lists_owner = 0;                                      // (the batch takes the counters and the survivor lists over)
   // (... from whatever still runs on the tail stream: the tail of a split pass queued behind the one the batch sweeps for shares them in
   // STREAM order only with its own stream -- it must be through before the batch's kernels start on the context's stream)
-  if (c->sr_tail_stream) { HIP_TRY(c, hipStreamSynchronize(c->sr_tail_stream)); if (c->sr_tail_stream2) HIP_TRY(c, hipStreamSynchronize(c->sr_tail_stream2)); }
+  HIP_TRY(c, sync_tails(c));
   struct Through { ftkx_ctx *c; bool was; ~Through() { c->sr_internal = was; } } through{c, c->sr_internal};
   c->sr_internal = true;
   const unsigned long long hint = std::max<unsigned long long>(factor_of(*running), 256ull);
@@ -70,23 +70,8 @@ int series_by_host(ftkx_ctx *c, const int *ts, const int *scopes, int n, const s
   return FTKX_OK;
 }
 
-template <class T> int grow_device(ftkx_ctx *c, T **p, size_t *cap, size_t want)
-{
-  if (*cap >= want) return FTKX_OK;
-  if (*p) { HIP_TRY(c, hipFree(*p)); *p = nullptr; *cap = 0; }
-  HIP_TRY(c, hipMalloc((void **)p, want * sizeof(T)));
-  *cap = want;
-  return FTKX_OK;
-}
-
 size_t align256(size_t v) { return (v + 255) / 256 * 256; }
-
-// buckets of the ordering step: 2^this over the keys a pass can produce (at most kSeriesMaxBins).  2^14: the scan of the counts is a
-// one-workgroup kernel (18 us over 2^16 of them), the ranking inside a bucket costs next to nothing more with four records than with one
-int bins_log2()
-{
-  return 14;
-}
+int factor_log2_of(unsigned long long f) { int b = 0; while (b < 63 && (1ull << b) < f) b ++; return b; }
 
 // ---- the device-driven pass in two halves -------------------------------------------------------------------------------------------
 // what of a pass can be checked without the device: the steps, the slices they read in time order
@@ -128,15 +113,17 @@ bool series_applicable(ftkx_ctx *c, const int *ts, const int *scopes, int n, con
     if ((a.J == nullptr) != (b.J == nullptr) || (a.S == nullptr) != (b.S == nullptr)) ok = false;
   }
   if (ok && (c->opt.coords_mode == 2 || c->opt.coords_mode == 3)) ok = false;     // (their bounds checks live in ftkx_sweep_enqueue)
-  (void)slice_ts;
   return ok;
 }
 
 int ensure_series_buffers(ftkx_ctx *c, ftkx_series_buffers &B, size_t nwords, size_t desc_bytes, bool to_device)
 {
-  int rc;
-  if ((rc = grow_device(c, &B.results, &B.results_cap, std::max<size_t>(nwords, 1024)))) return rc;
-  const size_t h_words = nwords + (size_t)c->fragile_capacity * 10;
+  if (B.results_cap < std::max<size_t>(nwords, 1024)) {
+    if (B.results) { HIP_TRY(c, hipFree(B.results)); B.results = nullptr; B.results_cap = 0; }
+    HIP_TRY(c, hipMalloc((void **)&B.results, std::max<size_t>(nwords, 1024) * sizeof(u64)));
+    B.results_cap = std::max<size_t>(nwords, 1024);
+  }
+  const size_t h_words = nwords + (size_t)c->sr_tail[0].fragile_capacity * 10;
   if (B.h_results_cap < h_words) {
     if (B.h_results) { HIP_TRY(c, hipStreamSynchronize(c->stream)); (void)hipHostFree(B.h_results); B.h_results = nullptr; B.h_results_cap = 0; }
     const size_t cap = h_words + h_words / 4 + 1024;
@@ -180,8 +167,6 @@ int ensure_series_buffers(ftkx_ctx *c, ftkx_series_buffers &B, size_t nwords, si
   return FTKX_OK;
 }
 
-void series_queue_copy(ftkx_ctx *c, ftkx_series_pending &P, const unsigned *wait_flag, unsigned wait_val);
-
 // ---- the tail next to the next mask kernel (round 5) -------------------------------------------------------------------------------------
 // A sparse pass ends in a latency chain -- cull + factors, refine, exact test, ordering, records: ~70 us for a handful of workgroups -- and the
 // mask kernel of the pass queued behind it used to wait for all of it.  A SPLIT pass queues only its begin and mask kernels on the context's
@@ -196,40 +181,24 @@ void series_queue_copy(ftkx_ctx *c, ftkx_series_pending &P, const unsigned *wait
 // What the two sides share is kept apart: the reduction slots are the pass's own (ftkx_series_buffers::red), the counters and the histogram
 // are zeroed on the tail stream, and a slice whose masks the next pass rebuilds while this pass's tail still reads them gets fresh arrays
 // (`retired`: back to the pool when this pass is completed).
-using ftkxh::kSplitMinBytes;
-hipStream_t tail_stream(ftkx_ctx *c, const ftkx_series_pending &P) { return P.split ? (P.tail_set ? c->sr_tail_stream2 : c->sr_tail_stream) : c->stream; }
 
-// the counters, lists and ordering arrays a pass's tail works on: the context's own, or the second set
-struct TailView { u64 *counters, *list, *refine, *pass, *fragile, *bucketed, *sorted; unsigned *hist, *boff; };
-TailView tail_view(ftkx_ctx *c, const ftkx_series_pending &P)
-{
-  if (P.tail_set == 0) return TailView{c->d_counters, c->d_list, c->d_refine, c->d_pass, c->d_fragile, c->sr_bucketed, c->sr_sorted, c->sr_hist, c->sr_boff};
-  const ftkx_ctx::tail_set &S = c->sr_set1;
-  return TailView{S.counters, S.list, S.refine, S.pass, S.fragile, S.bucketed, S.sorted, S.hist, S.boff};
-}
-// the second set at the context's capacities (they change only where everything has been waited for; its stream is drained before anything
-// of it is freed)
+// the counters, lists and ordering arrays a pass's tail works on, and where that tail is queued
+ftkx_tail_set &tail_of(ftkx_ctx *c, const ftkx_series_pending &P) { return c->sr_tail[P.tail_set]; }
+hipStream_t tail_stream(ftkx_ctx *c, const ftkx_series_pending &P) { return P.split ? tail_of(c, P).stream : c->stream; }
+
+// the second set at the first one's capacities (they change only where everything has been waited for), its counters zeroed when they are made
 int ensure_set1(ftkx_ctx *c)
 {
-  ftkx_ctx::tail_set &S = c->sr_set1;
-  if (S.counters && S.capacity == c->capacity && S.list_capacity == c->list_capacity && S.refine_capacity == c->refine_capacity &&
-      S.fragile_capacity == c->fragile_capacity && S.bins_cap == c->sr_bins_cap) return FTKX_OK;
-  if (c->sr_tail_stream2) HIP_TRY(c, hipStreamSynchronize(c->sr_tail_stream2));
-  for (void **q : {(void **)&S.counters, (void **)&S.list, (void **)&S.refine, (void **)&S.pass, (void **)&S.fragile, (void **)&S.bucketed, (void **)&S.sorted, (void **)&S.hist, (void **)&S.boff})
-    if (*q) { HIP_TRY(c, hipFree(*q)); *q = nullptr; }
-  S = ftkx_ctx::tail_set();
-  HIP_TRY(c, hipMalloc((void **)&S.counters, (ftkx::CNT_N + 128 + 8) * sizeof(u64)));
-  HIP_TRY(c, hipMemsetAsync(S.counters, 0, (ftkx::CNT_N + 128 + 8) * sizeof(u64), c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  HIP_TRY(c, hipMalloc((void **)&S.list, (size_t)c->list_capacity * sizeof(u64)));
-  HIP_TRY(c, hipMalloc((void **)&S.refine, (size_t)c->refine_capacity * sizeof(u64)));
-  HIP_TRY(c, hipMalloc((void **)&S.pass, (size_t)c->capacity * sizeof(u64)));
-  HIP_TRY(c, hipMalloc((void **)&S.fragile, (size_t)c->fragile_capacity * 10 * sizeof(u64)));
-  HIP_TRY(c, hipMalloc((void **)&S.bucketed, (size_t)c->capacity * sizeof(u64)));
-  HIP_TRY(c, hipMalloc((void **)&S.sorted, (size_t)c->capacity * sizeof(u64)));
-  HIP_TRY(c, hipMalloc((void **)&S.hist, c->sr_bins_cap * sizeof(unsigned)));
-  HIP_TRY(c, hipMalloc((void **)&S.boff, c->sr_bins_cap * sizeof(unsigned)));
-  S.capacity = c->capacity; S.list_capacity = c->list_capacity; S.refine_capacity = c->refine_capacity; S.fragile_capacity = c->fragile_capacity; S.bins_cap = c->sr_bins_cap;
+  const ftkx_tail_set &S0 = c->sr_tail[0];
+  ftkx_tail_set &S = c->sr_tail[1];
+  if (!S.counters) {
+    HIP_TRY(c, hipMalloc((void **)&S.counters, (ftkx::CNT_N + 128 + 8) * sizeof(u64)));
+    HIP_TRY(c, hipMemsetAsync(S.counters, 0, (ftkx::CNT_N + 128 + 8) * sizeof(u64), c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  int rc;
+  if ((rc = ensure_list(c, S, S0.list_capacity)) || (rc = ensure_refine(c, S, S0.refine_capacity)) || (rc = ensure_pass(c, S, c->capacity)) ||
+      (rc = ensure_fragile(c, S, S0.fragile_capacity)) || (rc = ensure_order(c, S, c->capacity)) || (rc = ensure_bins(c, S, S0.bins_cap))) return rc;
   return FTKX_OK;
 }
 
@@ -237,20 +206,10 @@ void release_retired(ftkx_ctx *c, ftkx_series_pending &P)
 {
   for (auto &mu : P.retired) { if (mu.first) c->pool_M.push_back(mu.first); if (mu.second) c->pool_U.push_back(mu.second); }
   P.retired.clear();
-  // (slices dropped while this pass was the newest one open: called with P.open already false, so that free_slice does not park them again
-  // with THIS pass; a pass queued behind it was planned after the drop and does not know them)
-  std::vector<Slice> parked;
-  parked.swap(P.parked);
-  const bool was_open = P.open;
-  P.open = false;
-  for (Slice &sl : parked) {
-    // (free_slice parks with the newest open split pass: not this one, and a newer one never read these -- straight to the pools)
-    const int open_was = c->sr_open;
-    c->sr_open = 0;
-    free_slice(sl, c);
-    c->sr_open = open_was;
-  }
-  P.open = was_open;
+  // (slices dropped while this pass was the newest one open: its tail is through, and a pass queued behind it was planned after the drop and
+  // never read them -- straight to the pools)
+  for (Slice &sl : P.parked) release_slice(sl, c);
+  P.parked.clear();
 }
 
 bool short_chain_now(const ftkx_ctx *c, bool to_device, bool *small_now)
@@ -270,16 +229,16 @@ void series_queue_rest(ftkx_ctx *c, const ftkx_series_pending &P, const Mesh &m,
   hipStream_t st = tail_stream(c, P);
   // (a split pass: sparse data next to a mask kernel -- every workgroup of these kernels waits for a wavefront slot: few of them)
   const bool few = P.split_sparse;
-  const TailView T = tail_view(c, P);
-  if (P.two_level && !P.refined) ftkx::launch_refine(m, d_steps, T.refine, c->refine_capacity, T.list, c->list_capacity, st, few ? 64 : 0);   // (a slab pass refines before it asks for patches)
-  ftkx::launch_exact(m, d_steps, 0, T.list, c->list_capacity, st, few ? 64 : 0);
+  const ftkx_tail_set &T = tail_of(c, P);
+  if (P.two_level && !P.refined) ftkx::launch_refine(m, d_steps, T.refine, T.refine_capacity, T.list, T.list_capacity, st, few ? 64 : 0);   // (a slab pass refines before it asks for patches)
+  ftkx::launch_exact(m, d_steps, 0, T.list, T.list_capacity, st, few ? 64 : 0);
   ftkx::launch_bucket_scan(T.hist, T.boff, (unsigned)P.nbins, T.counters, st, P.split);
   ftkx::launch_bucket_scatter(m, T.boff, T.bucketed, st, few ? 16 : 0);
   ftkx::launch_bucket_rank(m, T.bucketed, T.boff, T.sorted, B.results, st, few ? 16 : 0);
   if (B.copy_out) { (void)hipStreamWaitEvent(st, B.ev_copied, 0); B.copy_out = false; }   // (the copy of the pass that used these buffers last: long through)
   ftkx::launch_series_records(m, d_steps, T.sorted, P.to_device ? B.d_out : B.out, st, P.split);
   if (!P.split) ev_end(c);
-  ftkx::launch_series_finish(m, B.results, P.nwords, c->list_capacity, c->refine_capacity, B.h_results, flag, seq, st);
+  ftkx::launch_series_finish(m, B.results, P.nwords, T.list_capacity, T.refine_capacity, B.h_results, flag, seq, st);
 }
 
 // the records' way over PCIe: a small kernel on its own stream, behind the finish kernel (the count is final) and next to whatever the
@@ -297,6 +256,27 @@ void series_queue_copy(ftkx_ctx *c, ftkx_series_pending &P, const unsigned *wait
   P.copy_pending = false;
 }
 
+// The pass queued before the one being planned left its records in device memory: which way their copy is ordered behind it.
+//   COPY_BY_FLAG: single-rank passes -- the copy kernel waits on a word of device memory that the new pass's begin kernel stores behind its
+//   descriptor fetch (series_copy_out_kernel).
+//   COPY_BY_TAIL: that pass was split -- its finish kernel is on the tail stream: the copy goes behind that stream's event.
+//   COPY_BY_EVENT: slab passes -- their begin kernel may sit behind the pass before it with its messages from other ranks for as long as a peer
+//   lags: sixteen workgroups would spin for that long, and give up in the end; the copy is ordered behind the begin kernel by an event instead,
+//   5 us on a path that waits for the network anyway.  The one-launch pass, too: the copy needs its launch position, no more.
+enum { COPY_NONE = 0, COPY_BY_FLAG, COPY_BY_TAIL, COPY_BY_EVENT };
+// (by flag: behind the begin kernel that will store `fetch_val`; by event: behind what the context's stream holds now)
+int series_queue_copy_behind(ftkx_ctx *c, ftkx_series_pending &before, int route, unsigned fetch_val)
+{
+  if (route == COPY_BY_TAIL) HIP_TRY(c, hipStreamWaitEvent(c->sr_copy_stream, c->sr_buf[before.buf].ev_tail, 0));
+  if (route == COPY_BY_EVENT) {
+    if (!c->sr_ev_fetched) HIP_TRY(c, hipEventCreateWithFlags(&c->sr_ev_fetched, hipEventDisableTiming));
+    HIP_TRY(c, hipEventRecord(c->sr_ev_fetched, c->stream));
+    HIP_TRY(c, hipStreamWaitEvent(c->sr_copy_stream, c->sr_ev_fetched, 0));
+  }
+  series_queue_copy(c, before, route == COPY_BY_FLAG ? c->sr_fetch_flag : nullptr, route == COPY_BY_FLAG ? fetch_val : 0u);
+  return FTKX_OK;
+}
+
 // A pass that is NOT split works on the context's counters, lists and ordering arrays in the order of the context's stream -- and so does
 // whatever recycles a dropped slice's arrays behind it.  Every split pass still open has its tail on a stream of its own (two of them may
 // be out at once: tail sets 0 and 1): the context's stream waits for ALL of them, not only for the pass queued last -- with two tails
@@ -308,8 +288,16 @@ int wait_for_open_tails(ftkx_ctx *c, const ftkx_series_pending *self)
   return FTKX_OK;
 }
 
+// the slices step (t, scope) reads -- slice1 = -1: no interval sweep -- and the last one its sticky minimum runs over (`last` goes on from the step before)
+ftkx::SeriesStep series_step(const std::vector<int> &slice_ts, int t, int scope, size_t *last)
+{
+  const int j0 = (int)(std::lower_bound(slice_ts.begin(), slice_ts.end(), t) - slice_ts.begin());
+  while (*last + 1 < slice_ts.size() && slice_ts[*last + 1] <= t + 1) ++ *last;
+  return ftkx::SeriesStep{j0, (scope & FTKX_SCOPE_INTERVAL) ? j0 + 1 : -1, (int)*last, 0};
+}
+
 // ---- the one-launch pass for small series (one_kernel.hip) --------------------------------------------------------------------------------
-bool series_one_eligible(ftkx_ctx *c, const ftkx_series_pending &P, int n, size_t k, u64 cells, bool dist)
+bool series_one_eligible(ftkx_ctx *c, int n, size_t k, u64 cells, bool dist)
 {
   const bool one_on = ftkx::env_hook("FTKX_SERIES_HOOKS", "one", 1) != 0;
   if (!one_on || dist || c->sr_one_off > 0) { if (c->sr_one_off > 0 && !dist) c->sr_one_off --; return false; }
@@ -323,7 +311,6 @@ bool series_one_eligible(ftkx_ctx *c, const ftkx_series_pending &P, int n, size_
   // (7 357 records, BASELINE config 1): 92-105 against 91 -- hit-dense series of that size stay with the chain, whose kernels overlap nothing
   // either but whose ten launches cost no more than this kernel's barriers and its one wavefront per SIMD.  The last pass's record count decides.
   if (cells * (u64)n > (1ull << 17) && c->stats.hits > 2048) return false;
-  (void)P;
   return true;
 }
 
@@ -335,8 +322,9 @@ int series_plan_one(ftkx_ctx *c, ftkx_series_pending &P, const int *ts, const in
   P.one = true; P.split = false; P.to_device = false; P.short_chain = false; P.small_now = false;
   P.red_index.assign(k, -1); P.gen.assign(k, 0);               // (no masks are built: nothing to mark when the pass is collected)
   P.ntodo = 0;
+  ftkx_tail_set &T = tail_of(c, P);
   if ((rc = ensure_hit_buffer(c, std::max<u64>(c->capacity, 1u << 16)))) return rc;
-  if ((rc = ensure_fragile(c, std::max<u64>(c->fragile_capacity, 1u << 12)))) return rc;
+  if ((rc = ensure_fragile(c, T, std::max<u64>(T.fragile_capacity, 1u << 12)))) return rc;
   const size_t nwords = (size_t)ftkx::SR_HEAD + (size_t)n + 2 * k;
   P.nwords = nwords;
   P.buf = (int)(&P - c->sr_pend);
@@ -354,10 +342,8 @@ int series_plan_one(ftkx_ctx *c, ftkx_series_pending &P, const int *ts, const in
   for (size_t j = 0; j < k; j ++) { const Slice &s = *sl[j]; a.slice[j] = ftkx::OneSlice{s.S, s.V, s.J, P.slice_ts[j], 0}; }
   size_t last = 0;
   for (int i = 0; i < n; i ++) {
-    const size_t j0 = (size_t)(std::lower_bound(P.slice_ts.begin(), P.slice_ts.end(), ts[i]) - P.slice_ts.begin());
-    const bool interval = (scopes[i] & FTKX_SCOPE_INTERVAL) != 0;
-    while (last + 1 < k && P.slice_ts[last + 1] <= ts[i] + 1) last ++;
-    a.step[i] = ftkx::OneStep{ts[i], scopes[i], (int)j0, interval ? (int)j0 + 1 : -1, (int)last, 0};
+    const ftkx::SeriesStep s = series_step(P.slice_ts, ts[i], scopes[i], &last);
+    a.step[i] = ftkx::OneStep{ts[i], scopes[i], s.slice0, s.slice1, s.last, 0};
   }
   a.running_in = prev ? DBL_MAX : P.running_in;
   a.cap = 1.0 / (double)P.hint;
@@ -368,14 +354,9 @@ int series_plan_one(ftkx_ctx *c, ftkx_series_pending &P, const int *ts, const in
   a.seq = ++ B.seq;
   P.seq = a.seq;
   a.out = B.out; a.capacity = std::min<u64>(c->capacity, (u64)B.out_cap);
-  a.fragile = c->d_fragile; a.fragile_capacity = c->fragile_capacity;
+  a.fragile = T.fragile; a.fragile_capacity = T.fragile_capacity;
   // (the pass before left its records in device memory: their copy needs this pass's launch position, no more)
-  if (before && before->open && before->copy_pending) {
-    if (!c->sr_ev_fetched) HIP_TRY(c, hipEventCreateWithFlags(&c->sr_ev_fetched, hipEventDisableTiming));
-    HIP_TRY(c, hipEventRecord(c->sr_ev_fetched, c->stream));
-    HIP_TRY(c, hipStreamWaitEvent(c->sr_copy_stream, c->sr_ev_fetched, 0));
-    series_queue_copy(c, *before, nullptr, 0);
-  }
+  if (before && before->open && before->copy_pending && (rc = series_queue_copy_behind(c, *before, COPY_BY_EVENT, 0))) return rc;
   if ((rc = wait_for_open_tails(c, &P))) return rc;         // (their tails share the fragile list and the counters)
   if (B.copy_out) { HIP_TRY(c, hipStreamWaitEvent(c->stream, B.ev_copied, 0)); B.copy_out = false; }
   const u64 bs = c->nd == 2 ? 128 : 64, nblocks = (P.cells * (u64)n + bs - 1) / bs;
@@ -385,66 +366,45 @@ int series_plan_one(ftkx_ctx *c, ftkx_series_pending &P, const int *ts, const in
   ev_end(c);
   HIP_TRY(c, hipGetLastError());
   P.uid = ++ c->sr_pass_uid;
-  P.pipelined = true;
   P.open = true;
   return FTKX_OK;
 }
 
-// First half: everything of the pass is queued on the context's stream.  `prev`: the pass queued before this one and not yet collected,
-// whose running minimum this one continues from (on the device), or nullptr: *running_in is the value.
 // what a slab pass (ftkx_series_dist_*) adds to the plan of a pass: the halo slice and where the gathered contributions will be
 struct DistPlan { int t_halo; int rank, nranks, upper; const u64 *gathered; u64 *contrib; void *masks_out; hipStream_t side; };
 
-int series_queue_cull(ftkx_ctx *c, ftkx_series_pending &P);
-int series_queue_tail(ftkx_ctx *c, ftkx_series_pending &P);
-
-// First half, stage 1: the pass is planned -- buffers, descriptors -- and its begin and mask kernels are queued.
-int series_plan(ftkx_ctx *c, ftkx_series_pending &P, const int *ts, const int *scopes, int n, double running_in, const ftkx_series_pending *prev, bool pipelined,
-                ftkx_series_pending *before = nullptr /* the pass queued before this one, if it is still open */, const DistPlan *dist = nullptr)
+void series_mesh(ftkx_ctx *c, const ftkx_series_pending &P, Mesh &m)
 {
-  const int nd = c->nd;
-  release_retired(c, P);                                     // (a slot that was abandoned with arrays still parked in it)
-  P = ftkx_series_pending();
-  if (dist) { P.dist = true; P.t_halo = dist->t_halo; P.dist_rank = dist->rank; P.dist_nranks = dist->nranks; P.dist_upper = dist->upper; P.gathered = dist->gathered; }
-  P.ts.assign(ts, ts + n); P.scopes.assign(scopes, scopes + n); P.n = n;
-  P.running_in = running_in; P.chained = prev != nullptr;
-  int rc;
-  if ((rc = series_steps(c, ts, scopes, n, P.slice_ts))) return rc;
-  const std::vector<int> &slice_ts = P.slice_ts;
-  const size_t k = slice_ts.size();
-  P.k = k;
-  std::vector<Slice *> sl(k);
-  for (size_t j = 0; j < k; j ++) sl[j] = &c->slices.find(slice_ts[j])->second;
+  fill_mesh(c, m);
+  const ftkx_tail_set &T = tail_of(c, P);
+  m.counters = T.counters; m.pass = T.pass; m.fragile = T.fragile;
+  m.hist = T.hist; m.hist_shift = P.shift; m.core_cells = P.cells;
+}
 
-  // ---- is the device-driven form applicable? ---------------------------------------------------------------------------------------
-  Mesh m; fill_mesh(c, m);
-  const bool two_level = ftkx::masks_have_summary(m);
-  u64 cells = 1;
-  for (int d = 0; d < nd; d ++) cells *= (u64)c->core_sz[d];
-  bool ok = series_applicable(c, ts, scopes, n, slice_ts, sl, cells, dist ? dist->t_halo : -1);
-  if (prev && prev->by_host) ok = false;                     // (its running minimum will not be on the device)
-  if (dist && !two_level) ok = false;                        // (the halo's masks travel as summaries + the words they do not describe)
-  const unsigned long long hint = std::max<unsigned long long>(factor_of(running_in), 256ull);
-  P.hint = hint; P.two_level = two_level; P.cells = cells; P.u_rows = m.u_rows;
-  if (!ok) { P.by_host = true; P.open = true; return FTKX_OK; }
-  if (series_one_eligible(c, P, n, k, cells, dist != nullptr)) return series_plan_one(c, P, ts, scopes, n, sl, prev, before);
+// ---- stage 1 of the first half, piece by piece (series_plan) -------------------------------------------------------------------------------
+// Which slices this pass builds masks for (P.red_index[j] >= 0: its mask job; P.ntodo of them), and for the others where the factor job
+// finds their reductions: from_res / from_max non-null = words of a results block on the device, else the slice's own fields.
+void series_slice_readiness(ftkx_ctx *c, ftkx_series_pending &P, const std::vector<Slice *> &sl, const ftkx_series_pending *before, const DistPlan *dist,
+                            std::vector<const u64 *> &from_res, std::vector<const u64 *> &from_max)
+{
+  const size_t k = P.k;
+  const std::vector<int> &slice_ts = P.slice_ts;
   // slices whose masks and reduction stand from an earlier call (a streaming tracker: slice t of this step was slice t + 1 of the last)
   P.red_index.assign(k, -1);
   P.gen.assign(k, 0);
-  std::vector<int> &red_index = P.red_index;
   // ... or are being built by the pass queued before this one, which is still out: their masks will be there in stream order, and what the
   // factor job needs of their reductions it reads from that pass's results block on the device (a streaming caller queues step t + 1
   // before it has collected step t: slice t + 1 is masked ONCE)
-  std::vector<const u64 *> from_res(k, nullptr), from_max(k, nullptr);
+  from_res.assign(k, nullptr); from_max.assign(k, nullptr);
   size_t ntodo = 0;
   for (size_t j = 0; j < k; j ++) {
     const Slice &s = *sl[j];
-    bool ready = s.M && (!two_level || (s.U && s.u_rows == m.u_rows)) && s.mask_factor != 0 && s.mask_factor <= hint && !s.mask_big && (s.have_fused || s.have_res);
-    if (!ready && before && before->open && !before->by_host && before->hint <= hint && before->two_level == two_level && before->u_rows == m.u_rows) {
+    bool ready = s.M && (!P.two_level || (s.U && s.u_rows == P.u_rows)) && s.mask_factor != 0 && s.mask_factor <= P.hint && !s.mask_big && (s.have_fused || s.have_res);
+    if (!ready && before && before->open && !before->by_host && before->hint <= P.hint && before->two_level == P.two_level && before->u_rows == P.u_rows) {
       const auto it = std::lower_bound(before->slice_ts.begin(), before->slice_ts.end(), slice_ts[j]);
       if (it != before->slice_ts.end() && *it == slice_ts[j]) {
         const size_t jj = (size_t)(it - before->slice_ts.begin());
-        if (before->red_index[jj] >= 0 && before->gen[jj] == s.mask_gen && s.M && (!two_level || s.U)) {
+        if (before->red_index[jj] >= 0 && before->gen[jj] == s.mask_gen && s.M && (!P.two_level || s.U)) {
           const u64 *R = c->sr_buf[before->buf].results;
           from_res[j] = R + ftkx::SR_HEAD + (size_t)before->n + jj;
           from_max[j] = R + ftkx::SR_HEAD + (size_t)before->n + before->k + jj;
@@ -459,90 +419,74 @@ int series_plan(ftkx_ctx *c, ftkx_series_pending &P, const int *ts, const int *s
       from_res[j] = dist->gathered + (size_t)ftkx::kDistContrib * (size_t)dist->upper + 2;
       from_max[j] = from_res[j] + 1;
     }
-    if (!ready) red_index[j] = (int)ntodo ++;
+    if (!ready) P.red_index[j] = (int)ntodo ++;
   }
   P.ntodo = ntodo;
+}
 
-  // ---- buffers (persistent; they only ever grow) -----------------------------------------------------------------------------------
-  if ((rc = ensure_hit_buffer(c, std::max<u64>(c->capacity, 1u << 16)))) return rc;
-  if ((rc = ensure_fragile(c, std::max<u64>(c->fragile_capacity, 1u << 12)))) return rc;
-  if ((rc = ensure_list(c, std::max<u64>(c->list_capacity, 1u << 20))) || (rc = ensure_refine(c, std::max<u64>(c->refine_capacity, 1u << 20)))) return rc;
-  // split?  (decided here: the begin kernel of a split pass leaves the counters to the tail stream)
-  P.to_device = false;
-  const unsigned long long mask_bytes_of_pass = (unsigned long long)ntodo * (unsigned long long)n_vertices(c) * 8ull * (c->scalar_mode == 1 ? 1ull : (unsigned long long)nd);
-  {
-    P.to_device = pipelined && c->stats.hits > 4096;
-    // split?  FTKX_SERIES_HOOKS split = 0 never | 1 auto (default): where the size rule below says so AND the self-check found it no slower
-    // | 4 on: the size rule alone, no self-check -- the deterministic setting | 2 whatever the size, no self-check (tests) | 3 = 4.
-    // ftkx_series_split_decision says which way a context went and on what numbers.  (Profiling level 2 times the mask kernel only, with
-    // events on the context's stream: they do not stand between the tail and anything.)
-    const long split_mode = ftkx::env_hook("FTKX_SERIES_HOOKS", "split", 1);
-    const unsigned long long mask_bytes = mask_bytes_of_pass;
-    // hit-dense passes as well, where the mask launch reads 4 GB and more -- their chain at full grids, the records by way of the copy kernel:
-    // double_gyre 2048 x 1024 x 128 0.83 -> 0.77 ms (its mask kernel 692 -> 752 us next to the chain's 550).  Round 5 saw 0.93-0.97 behind other
-    // hit-dense contexts of the same process and kept them in order; round 6 (every open tail waited for by an unsplit pass, the library's
-    // streams kept for the process) measures 0.764-0.774 alone, behind three other configurations and inside the driver's full line
-    // (tools/dense_split.py) -- and auto's self-check keeps a context in order where it is not so.  Smaller hit-dense passes lose: woven
-    // 1024^2 x 64, tail = mask kernel = 100 us, 0.205 -> 0.279 split.
-    const bool sparse_now = c->sr_sparse && !P.to_device;
-    // (a hit-dense chain is ~550 us next to a mask kernel -- double_gyre's 56 766 records --: only mask launches of 4 GB and more hide it.)
-    // The decision, and in "auto" the self-check behind it: split_policy.hpp
-    ftkxh::split_inputs in;
-    in.mode = split_mode; in.pipelined = pipelined; in.dist = dist != nullptr; in.profiling_ok = c->profiling == 0 || c->profiling == 2;
-    in.sparse_now = sparse_now; in.ntodo = ntodo; in.mask_bytes = mask_bytes;
-    in.signature = ((unsigned long long)n << 48) ^ ((unsigned long long)ntodo << 32) ^ (unsigned long long)cells;
-    const ftkxh::split_verdict v = ftkxh::split_decide(c->sr_cal, in);
-    P.split = v.split; P.cal_kind = v.cal_kind; c->sr_split_forced = v.forced;
-    P.split_sparse = P.split && c->sr_sparse && !P.to_device;
+// Split?  (Decided before anything is queued: the begin kernel of a split pass leaves the counters to the tail stream.)  Sets P.to_device, P.split,
+// P.cal_kind, P.split_sparse and the context's sr_split_forced.
+void series_decide_split(ftkx_ctx *c, ftkx_series_pending &P, bool pipelined, bool dist, unsigned long long mask_bytes)
+{
+  P.to_device = pipelined && c->stats.hits > 4096;
+  // split?  FTKX_SERIES_HOOKS split = 0 never | 1 auto (default): where the size rule below says so AND the self-check found it no slower
+  // | 4 on: the size rule alone, no self-check -- the deterministic setting | 2 whatever the size, no self-check (tests) | 3 = 4.
+  // ftkx_series_split_decision says which way a context went and on what numbers.  (Profiling level 2 times the mask kernel only, with
+  // events on the context's stream: they do not stand between the tail and anything.)
+  const long split_mode = ftkx::env_hook("FTKX_SERIES_HOOKS", "split", 1);
+  // hit-dense passes as well, where the mask launch reads 4 GB and more -- their chain at full grids, the records by way of the copy kernel:
+  // double_gyre 2048 x 1024 x 128 0.83 -> 0.77 ms (its mask kernel 692 -> 752 us next to the chain's 550).  Round 5 saw 0.93-0.97 behind other
+  // hit-dense contexts of the same process and kept them in order; round 6 (every open tail waited for by an unsplit pass, the library's
+  // streams kept for the process) measures 0.764-0.774 alone, behind three other configurations and inside the driver's full line
+  // (tools/dense_split.py) -- and auto's self-check keeps a context in order where it is not so.  Smaller hit-dense passes lose: woven
+  // 1024^2 x 64, tail = mask kernel = 100 us, 0.205 -> 0.279 split.
+  const bool sparse_now = c->sr_sparse && !P.to_device;
+  // (a hit-dense chain is ~550 us next to a mask kernel -- double_gyre's 56 766 records --: only mask launches of 4 GB and more hide it.)
+  // The decision, and in "auto" the self-check behind it: split_policy.hpp
+  ftkxh::split_inputs in;
+  in.mode = split_mode; in.pipelined = pipelined; in.dist = dist; in.profiling_ok = c->profiling == 0 || c->profiling == 2;
+  in.sparse_now = sparse_now; in.ntodo = P.ntodo; in.mask_bytes = mask_bytes;
+  in.signature = ((unsigned long long)P.n << 48) ^ ((unsigned long long)P.ntodo << 32) ^ (unsigned long long)P.cells;
+  const ftkxh::split_verdict v = ftkxh::split_decide(c->sr_cal, in);
+  P.split = v.split; P.cal_kind = v.cal_kind; c->sr_split_forced = v.forced;
+  P.split_sparse = P.split && c->sr_sparse && !P.to_device;
+}
+
+// a slice whose masks this pass rebuilds while the tail of the (split) pass before it -- on its own stream -- still reads them: fresh arrays here,
+// the old ones parked with that pass until it is completed
+void series_retire_masks(const ftkx_series_pending &P, const std::vector<Slice *> &sl, ftkx_series_pending &before)
+{
+  for (size_t j = 0; j < P.k; j ++) {
+    if (P.red_index[j] < 0 || !(sl[j]->M || sl[j]->U)) continue;
+    if (!std::binary_search(before.slice_ts.begin(), before.slice_ts.end(), P.slice_ts[j])) continue;
+    before.retired.push_back({sl[j]->M, sl[j]->U});
+    sl[j]->M = nullptr; sl[j]->U = nullptr;
   }
-  const bool before_split = before && before->open && before->split;
-  // a slice whose masks this pass rebuilds while the tail of the pass before it -- on its own stream -- still reads them: fresh arrays here,
-  // the old ones parked with that pass until it is completed
-  if (before_split)
-    for (size_t j = 0; j < k; j ++) {
-      if (red_index[j] < 0 || !(sl[j]->M || sl[j]->U)) continue;
-      if (!std::binary_search(before->slice_ts.begin(), before->slice_ts.end(), slice_ts[j])) continue;
-      before->retired.push_back({sl[j]->M, sl[j]->U});
-      sl[j]->M = nullptr; sl[j]->U = nullptr;
-    }
-  for (size_t j = 0; j < k; j ++) if (red_index[j] >= 0 && (rc = ensure_mask_arrays(c, *sl[j], two_level))) return rc;
-  // order key -> bucket: at most 2^16 buckets over the keys this pass can produce
-  const u64 max_key = (u64)n * cells * 64ull;
+}
+
+// buckets of the ordering step: 2^this over the keys a pass can produce (at most kSeriesMaxBins).  2^14: the scan of the counts is a
+// one-workgroup kernel (18 us over 2^16 of them), the ranking inside a bucket costs next to nothing more with four records than with one
+constexpr int kBinsLog2 = 14;
+
+// order key -> bucket (P.shift), and how many buckets that makes over the keys this pass can produce (P.nbins)
+void series_bucket_geometry(ftkx_series_pending &P)
+{
+  const u64 max_key = (u64)P.n * P.cells * 64ull;
   int key_bits = 1;
   while (key_bits < 63 && (1ull << key_bits) < max_key) key_bits ++;
   // (a split pass: few records, and its scan -- one workgroup of four wavefronts next to a mask kernel -- pays several us per round of loads: 2^10)
-  const int shift = std::max(0, key_bits - (P.split_sparse ? 10 : bins_log2()));
-  const size_t nbins = (size_t)((max_key - 1) >> shift) + 1;
-  P.nbins = nbins;
-  if (c->sr_bins_cap < nbins + 1) {
-    const size_t cap = std::max<size_t>(nbins + 1, (1u << 16) + 1);
-    for (void *p : {(void *)c->sr_hist, (void *)c->sr_boff}) if (p) (void)hipFree(p);
-    c->sr_hist = nullptr; c->sr_boff = nullptr; c->sr_bins_cap = 0;
-    HIP_TRY(c, hipMalloc((void **)&c->sr_hist, cap * sizeof(unsigned)));
-    HIP_TRY(c, hipMalloc((void **)&c->sr_boff, cap * sizeof(unsigned)));
-    c->sr_bins_cap = cap;
-  }
-  if ((rc = grow_device(c, &c->sr_bucketed, &c->sr_bucketed_cap, (size_t)c->capacity))) return rc;
-  if ((rc = grow_device(c, &c->sr_sorted, &c->sr_sorted_cap, (size_t)c->capacity))) return rc;
-  const size_t nwords = (size_t)ftkx::SR_HEAD + (size_t)n + 2 * k + (dist ? (size_t)ftkx::kDistContrib * (size_t)dist->nranks : 0);
-  P.nwords = nwords;
-  // ---- descriptors: mask jobs | steps | slice table | step table, one pinned block fetched by a kernel -------------------------------
-  const size_t off_jobs = 0, off_steps = align256(ntodo * sizeof(MaskJob)), off_slices = off_steps + align256((size_t)n * sizeof(Fields)),
-               off_sinfo = off_slices + align256(k * sizeof(ftkx::SeriesSlice)), total = off_sinfo + align256((size_t)n * sizeof(ftkx::SeriesStep));
-  P.off_steps = off_steps; P.off_slices = off_slices; P.off_sinfo = off_sinfo; P.total_desc = total; P.shift = shift;
-  // A pass with many records, queued while another is still out: the record kernel leaves them in device memory and a small kernel on a
-  // stream of its own takes them over PCIe -- next to the mask kernel of the pass queued behind.  (A record kernel that writes through
-  // PCIe itself holds its stream for the transfer: 106 us of woven 1024^2 x 64's 363.)
-  P.buf = (int)(&P - c->sr_pend);                             // (a pass's buffers go with its place in sr_pend: nothing to undo when a step below fails)
-  ftkx_series_buffers &B = c->sr_buf[P.buf];
-  if ((rc = ensure_series_buffers(c, B, nwords, total, P.to_device))) return rc;
-  if (B.red_cap < std::max<size_t>(ntodo, 1)) {              // (the pass's own reduction slots: a buffer in use by an open pass is never this one -- two buffers, two passes)
-    if (B.red) { HIP_TRY(c, hipFree(B.red)); B.red = nullptr; B.red_cap = 0; }
-    HIP_TRY(c, hipMalloc((void **)&B.red, std::max<size_t>(ntodo, 1) * 128 * sizeof(u64)));
-    B.red_cap = std::max<size_t>(ntodo, 1);
-  }
+  P.shift = std::max(0, key_bits - (P.split_sparse ? 10 : kBinsLog2));
+  P.nbins = (size_t)((max_key - 1) >> P.shift) + 1;
+}
+
+// what a split pass, or a pass behind one, needs beyond its buffers: the tail streams and events, and which tail set it works on (P.tail_set,
+// P.before_buf); a pass that leaves its records on the device: the copy stream
+int series_tail_resources(ftkx_ctx *c, ftkx_series_pending &P, const ftkx_series_pending *before, unsigned long long mask_bytes)
+{
+  int rc;
+  const bool before_split = before && before->open && before->split;
   if (P.split || before_split) {
-    if (!c->sr_tail_stream && (rc = aux_stream_get(c, true, &c->sr_tail_stream))) return rc;    // (high priority: the tail is a latency chain, it goes first wherever a slot frees up)
+    if (!c->sr_tail[0].stream && (rc = aux_stream_get(c, true, &c->sr_tail[0].stream))) return rc;    // (high priority: the tail is a latency chain, it goes first wherever a slot frees up)
     for (ftkx_series_buffers &X : c->sr_buf)
       for (hipEvent_t *e : {&X.ev_masks, &X.ev_factors, &X.ev_tail}) if (!*e) HIP_TRY(c, hipEventCreateWithFlags(e, hipEventDisableTiming));
   }
@@ -550,98 +494,70 @@ int series_plan(ftkx_ctx *c, ftkx_series_pending &P, const int *ts, const int *s
   // time, each hidden behind two mask kernels.  Where one mask kernel hides a whole tail -- 2 GB and more -- the tails stay one behind the
   // other: two of them at once slow each other and the mask kernel down until the tails are what a pass takes: 256^3 x 16 0.41 -> 0.49 ms,
   // double_gyre 0.77 -> 0.97, in some runs and not in others)
-  const bool two_tails = P.split_sparse && mask_bytes_of_pass < 2 * kSplitMinBytes;
+  const bool two_tails = P.split_sparse && mask_bytes < 2 * kSplitMinBytes;
   P.tail_set = two_tails ? (int)(c->sr_split_seq ++ & 1u) : 0;
   // (only where it is used: streams beyond the runtime's hardware queues share them, and a tail that shares its mask kernel's queue runs behind it)
-  if (two_tails && !c->sr_tail_stream2 && (rc = aux_stream_get(c, true, &c->sr_tail_stream2))) return rc;
+  if (two_tails && !c->sr_tail[1].stream && (rc = aux_stream_get(c, true, &c->sr_tail[1].stream))) return rc;
   P.before_buf = before_split ? before->buf : -1;
   if (P.tail_set == 1 && (rc = ensure_set1(c))) return rc;
   if (P.to_device && !c->sr_copy_stream && (rc = aux_stream_get(c, false, &c->sr_copy_stream))) return rc;
-  fill_mesh(c, m);                                           // (the buffers may have moved)
-  m.hist = tail_view(c, P).hist; m.hist_shift = shift; m.core_cells = cells;
-  {
-    MaskJob *jobs = (MaskJob *)((char *)B.h_desc + off_jobs);
-    Fields *steps = (Fields *)((char *)B.h_desc + off_steps);
-    ftkx::SeriesSlice *ss = (ftkx::SeriesSlice *)((char *)B.h_desc + off_slices);
-    ftkx::SeriesStep *si = (ftkx::SeriesStep *)((char *)B.h_desc + off_sinfo);
-    const double cap = 1.0 / (double)hint;
-    for (size_t j = 0; j < k; j ++) {
-      const Slice &s = *sl[j];
-      ss[j].t = slice_ts[j]; ss[j].red_index = red_index[j];
-      ss[j].known_res = DBL_MAX; ss[j].known_max = 0.0;
-      ss[j].from_res = from_res[j]; ss[j].from_max = from_max[j];
-      if (s.have_res) { ss[j].known_res = s.res < cap ? s.res : DBL_MAX; ss[j].known_max = s.maxabs; }
-      else if (red_index[j] < 0 && !from_res[j]) { ss[j].known_res = s.res_below; ss[j].known_max = s.maxabs; }
-      if (from_res[j] && s.sparse) { ss[j].known_res = DBL_MAX; ss[j].known_max = 0.0; }      // (the halo slice: nothing of an earlier pass stands)
-      if (red_index[j] >= 0)
-        jobs[red_index[j]] = with_lean_thresholds(MaskJob{s.S, s.V, s.M, two_level ? s.U : nullptr, B.red + (size_t)red_index[j] * 128, cap, HUGE_VAL}, m);   // rule off: validated by the factor kernel
-    }
-    size_t last = 0;
-    for (int i = 0; i < n; i ++) {
-      const size_t j0 = (size_t)(std::lower_bound(slice_ts.begin(), slice_ts.end(), ts[i]) - slice_ts.begin());
-      const bool interval = (scopes[i] & FTKX_SCOPE_INTERVAL) != 0;
-      const Slice &s0 = *sl[j0];
-      Fields f;
-      memset(&f, 0, sizeof(f));
-      f.S[0] = s0.S; f.V[0] = s0.V; f.J[0] = s0.J; f.M[0] = s0.M; f.U[0] = two_level ? s0.U : nullptr;
-      if (interval) { const Slice &s1 = *sl[j0 + 1]; f.S[1] = s1.S; f.V[1] = s1.V; f.J[1] = s1.J; f.M[1] = s1.M; f.U[1] = two_level ? s1.U : nullptr; }
-      f.factor = 0.0; f.t = ts[i]; f.scope_mask = scopes[i];
-      steps[i] = f;
-      while (last + 1 < k && slice_ts[last + 1] <= ts[i] + 1) last ++;
-      si[i].slice0 = (int)j0; si[i].slice1 = interval ? (int)j0 + 1 : -1; si[i].last = (int)last; si[i].pad = 0;
-    }
-  }
-  const MaskJob *d_jobs = (const MaskJob *)((char *)B.d_desc + off_jobs);
-  Fields *d_steps = (Fields *)((char *)B.d_desc + off_steps);
-  const ftkx::SeriesSlice *d_slices = (const ftkx::SeriesSlice *)((char *)B.d_desc + off_slices);
-  const ftkx::SeriesStep *d_sinfo = (const ftkx::SeriesStep *)((char *)B.d_desc + off_sinfo);
+  return FTKX_OK;
+}
 
-  // ---- the whole pass, queued ------------------------------------------------------------------------------------------------------
-  unsigned *flag = reinterpret_cast<unsigned *>(B.h_results + B.h_results_cap);
-  const unsigned seq = ++ B.seq;
-  P.seq = seq;
-  // (the masks of the slices this pass rebuilds are nobody's until it has been collected; whatever else touches masks meanwhile bumps the
-  // epoch, and the marks of this pass are then not applied)
-  for (size_t j = 0; j < k; j ++) {
-    if (red_index[j] >= 0) { sl[j]->mask_factor = 0; sl[j]->have_fused = false; sl[j]->mask_gen = ++ c->mask_epoch; }
-    if (dist && slice_ts[j] == dist->t_halo && sl[j]->sparse) {
+// the descriptor block (its layout: series_plan) written into the pass's pinned staging buffer
+void series_write_desc(ftkx_ctx *c, const ftkx_series_pending &P, const Mesh &m, const std::vector<Slice *> &sl, const std::vector<const u64 *> &from_res,
+                       const std::vector<const u64 *> &from_max)
+{
+  ftkx_series_buffers &B = c->sr_buf[P.buf];
+  MaskJob *jobs = (MaskJob *)B.h_desc;
+  Fields *steps = (Fields *)((char *)B.h_desc + P.off_steps);
+  ftkx::SeriesSlice *ss = (ftkx::SeriesSlice *)((char *)B.h_desc + P.off_slices);
+  ftkx::SeriesStep *si = (ftkx::SeriesStep *)((char *)B.h_desc + P.off_sinfo);
+  const double cap = 1.0 / (double)P.hint;
+  for (size_t j = 0; j < P.k; j ++) {
+    const Slice &s = *sl[j];
+    const int ri = P.red_index[j];
+    ss[j].t = P.slice_ts[j]; ss[j].red_index = ri;
+    ss[j].known_res = DBL_MAX; ss[j].known_max = 0.0;
+    ss[j].from_res = from_res[j]; ss[j].from_max = from_max[j];
+    if (s.have_res) { ss[j].known_res = s.res < cap ? s.res : DBL_MAX; ss[j].known_max = s.maxabs; }
+    else if (ri < 0 && !from_res[j]) { ss[j].known_res = s.res_below; ss[j].known_max = s.maxabs; }
+    if (from_res[j] && s.sparse) { ss[j].known_res = DBL_MAX; ss[j].known_max = 0.0; }      // (the halo slice: nothing of an earlier pass stands)
+    if (ri >= 0) jobs[ri] = with_lean_thresholds(MaskJob{s.S, s.V, s.M, P.two_level ? s.U : nullptr, B.red + (size_t)ri * 128, cap, HUGE_VAL}, m);   // rule off: validated by the factor kernel
+  }
+  size_t last = 0;
+  for (int i = 0; i < P.n; i ++) {
+    si[i] = series_step(P.slice_ts, P.ts[i], P.scopes[i], &last);
+    const Slice &s0 = *sl[(size_t)si[i].slice0];
+    Fields f;
+    memset(&f, 0, sizeof(f));
+    f.S[0] = s0.S; f.V[0] = s0.V; f.J[0] = s0.J; f.M[0] = s0.M; f.U[0] = P.two_level ? s0.U : nullptr;
+    if (si[i].slice1 >= 0) { const Slice &s1 = *sl[(size_t)si[i].slice1]; f.S[1] = s1.S; f.V[1] = s1.V; f.J[1] = s1.J; f.M[1] = s1.M; f.U[1] = P.two_level ? s1.U : nullptr; }
+    f.factor = 0.0; f.t = P.ts[i]; f.scope_mask = P.scopes[i];
+    steps[i] = f;
+  }
+}
+
+// (the masks of the slices this pass rebuilds are nobody's until it has been collected; whatever else touches masks meanwhile bumps the
+// epoch, and the marks of this pass are then not applied)
+void series_claim_masks(ftkx_ctx *c, ftkx_series_pending &P, const std::vector<Slice *> &sl, const DistPlan *dist)
+{
+  for (size_t j = 0; j < P.k; j ++) {
+    if (P.red_index[j] >= 0) { sl[j]->mask_factor = 0; sl[j]->have_fused = false; sl[j]->mask_gen = ++ c->mask_epoch; }
+    if (dist && P.slice_ts[j] == dist->t_halo && sl[j]->sparse) {
       // (the halo's masks of this pass: built by its owner under the owner's hint, which the import checks against ours on the device)
-      sl[j]->mask_factor = hint; sl[j]->mask_big = false; sl[j]->u_rows = m.u_rows; sl[j]->have_res = false; sl[j]->have_fused = false;
+      sl[j]->mask_factor = P.hint; sl[j]->mask_big = false; sl[j]->u_rows = P.u_rows; sl[j]->have_res = false; sl[j]->have_fused = false;
       sl[j]->mask_gen = ++ c->mask_epoch;
     }
     P.gen[j] = sl[j]->mask_gen;
   }
-  // (the pass queued before this one left its records in device memory: their way over PCIe starts behind this pass's descriptor fetch,
-  // which the begin kernel announces in a word of device memory -- series_copy_out_kernel)
-  const bool copy_behind = before && before->open && before->copy_pending;
-  // (single-rank passes: the copy waits on a word of device memory.  Slab passes: their begin kernel may sit behind the pass before it with
-  // its messages from other ranks for as long as a peer lags -- sixteen workgroups would spin for that long, and give up in the end; the
-  // copy is ordered behind the begin kernel by an event instead, 5 us on a path that waits for the network anyway)
-  const bool copy_by_tail = copy_behind && before->split;      // (its finish kernel is on the tail stream: the copy goes behind that stream's event)
-  const bool copy_by_event = copy_behind && !copy_by_tail && (dist != nullptr || before->dist);
-  const bool copy_by_flag = copy_behind && !copy_by_event && !copy_by_tail;
-  if (copy_by_flag && !c->sr_fetch_flag) { HIP_TRY(c, hipMalloc((void **)&c->sr_fetch_flag, 2 * sizeof(unsigned))); HIP_TRY(c, hipMemsetAsync(c->sr_fetch_flag, 0, 2 * sizeof(unsigned), c->stream)); HIP_TRY(c, hipStreamSynchronize(c->stream)); }   // (once per context; waited for: the copy stream reads it)
-  const unsigned fetch_val = copy_by_flag ? ++ c->sr_fetch_seq : 0u;
-  // (the pass before this one has its tail on the tail stream: a pass that is not split itself shares the counters with it in STREAM order,
-  // so the context's stream waits for that tail; a split pass only needs that pass's cull -- its mask kernel must not start before the fused
-  // tail behind that cull can be placed -- and zeroes the counters on the tail stream, behind it)
-  if (!P.split && (rc = wait_for_open_tails(c, &P))) return rc;
-  // (a split pass: what its TAIL owns -- counters, histogram, the results block, which the tail of the pass before may still be reading as the
-  // block it continues from -- is zeroed on the tail stream)
-  ftkx::launch_series_begin(P.split ? nullptr : c->d_counters, B.red, ntodo * 64, P.split ? nullptr : c->sr_hist, P.split ? 0 : nbins + 1, P.split ? nullptr : B.results, P.split ? 0 : nwords,
-                            c->stream, B.h_desc, B.d_desc, total, copy_by_flag ? c->sr_fetch_flag : nullptr, fetch_val);
-  c->sr_lists_owner = 0;                                      // (the begin kernel zeroes the counters and the histogram: they are nobody's until this pass's cull is queued)
-  if (copy_by_flag) series_queue_copy(c, *before, c->sr_fetch_flag, fetch_val);
-  if (copy_by_tail) {
-    HIP_TRY(c, hipStreamWaitEvent(c->sr_copy_stream, c->sr_buf[before->buf].ev_tail, 0));
-    series_queue_copy(c, *before, nullptr, 0);
-  }
-  if (copy_by_event) {
-    if (!c->sr_ev_fetched) HIP_TRY(c, hipEventCreateWithFlags(&c->sr_ev_fetched, hipEventDisableTiming));
-    HIP_TRY(c, hipEventRecord(c->sr_ev_fetched, c->stream));
-    HIP_TRY(c, hipStreamWaitEvent(c->sr_copy_stream, c->sr_ev_fetched, 0));
-    series_queue_copy(c, *before, nullptr, 0);
-  }
+}
+
+// the mask launches of the pass on the context's stream -- with the slab export between them
+int series_queue_masks(ftkx_ctx *c, ftkx_series_pending &P, const Mesh &m, const std::vector<Slice *> &sl, const DistPlan *dist)
+{
+  ftkx_series_buffers &B = c->sr_buf[P.buf];
+  const MaskJob *d_jobs = (const MaskJob *)B.d_desc;
   if (dist && dist->masks_out) {
     // A slab pass with a lower neighbour: the FIRST slice's masks are that neighbour's halo.  They are built first, by a launch of their
     // own, and packed into the message right behind it -- the message can then cross xGMI (on the caller's side stream, which is made to
@@ -649,39 +565,121 @@ int series_plan(ftkx_ctx *c, ftkx_series_pending &P, const int *ts, const int *s
     if (!B.dist_block) { HIP_TRY(c, hipMalloc((void **)&B.dist_block, (size_t)ftkx::DB_N * sizeof(u64))); HIP_TRY(c, hipMemsetAsync(B.dist_block, 0, (size_t)ftkx::DB_N * sizeof(u64), c->stream)); }
     size_t ub, cap, off_idx, off_words, total_msg;
     if (!packed_layout(c, m, &ub, &cap, &off_idx, &off_words, &total_msg)) return fail(c, FTKX_E_UNSUPPORTED, "slab pass: this mesh has no summarised masks");
-    const bool first_now = red_index[0] == 0;              // (its masks are built in this pass: job 0)
+    const bool first_now = P.red_index[0] == 0;            // (its masks are built in this pass: job 0)
     size_t done = 0;
     if (first_now) { ev_begin(c, K_MASK); ftkx::launch_masks(m, d_jobs, 1, c->stream); ev_end(c); done = 1; }
     char *out = (char *)dist->masks_out;
-    int flog = 0; while (flog < 63 && (1ull << flog) < hint) flog ++;
-    ftkx::launch_dist_export(m, sl[0]->U, sl[0]->M, ub, (u64 *)out, (unsigned *)(out + off_idx), (u64 *)(out + off_words), cap, flog, B.dist_block, c->stream);
+    ftkx::launch_dist_export(m, sl[0]->U, sl[0]->M, ub, (u64 *)out, (unsigned *)(out + off_idx), (u64 *)(out + off_words), cap, factor_log2_of(P.hint), B.dist_block, c->stream);
     if (dist->side) {
       if (!B.ev_export) HIP_TRY(c, hipEventCreateWithFlags(&B.ev_export, hipEventDisableTiming));
       HIP_TRY(c, hipEventRecord(B.ev_export, c->stream));
       HIP_TRY(c, hipStreamWaitEvent(dist->side, B.ev_export, 0));
     }
-    if (ntodo > done) { ev_begin(c, K_MASK); ftkx::launch_masks(m, d_jobs + done, (int)(ntodo - done), c->stream); ev_end(c); }
-  } else if (ntodo) { ev_begin(c, K_MASK); ftkx::launch_masks(m, d_jobs, (int)ntodo, c->stream); ev_end(c); }
-  if (P.split) {
-    // the tail's side: behind the masks (an event), the counters and the histogram zeroed there
-    HIP_TRY(c, hipEventRecord(B.ev_masks, c->stream));
-    const TailView T = tail_view(c, P);
-    HIP_TRY(c, hipStreamWaitEvent(tail_stream(c, P), B.ev_masks, 0));
-    ftkx::launch_series_tail_begin(T.counters, T.hist, nbins + 1, B.results, nwords, tail_stream(c, P));
-  }
-  P.running_from = prev ? c->sr_buf[prev->buf].results : nullptr;
-  P.pipelined = pipelined;
-  HIP_TRY(c, hipGetLastError());
-  (void)d_steps; (void)d_slices; (void)d_sinfo; (void)flag;
+    if (P.ntodo > done) { ev_begin(c, K_MASK); ftkx::launch_masks(m, d_jobs + done, (int)(P.ntodo - done), c->stream); ev_end(c); }
+  } else if (P.ntodo) { ev_begin(c, K_MASK); ftkx::launch_masks(m, d_jobs, (int)P.ntodo, c->stream); ev_end(c); }
   return FTKX_OK;
 }
 
-void series_mesh(ftkx_ctx *c, const ftkx_series_pending &P, Mesh &m)
+// the begin kernel of the pass, and around it the copy of the records the pass before left on the device
+int series_queue_begin(ftkx_ctx *c, ftkx_series_pending &P, ftkx_series_pending *before, bool slab_now, size_t desc_bytes)
 {
-  fill_mesh(c, m);
-  const TailView T = tail_view(c, P);
-  m.counters = T.counters; m.pass = T.pass; m.fragile = T.fragile;
-  m.hist = T.hist; m.hist_shift = P.shift; m.core_cells = P.cells;
+  ftkx_series_buffers &B = c->sr_buf[P.buf];
+  const ftkx_tail_set &T = tail_of(c, P);
+  int rc;
+  const int route = !(before && before->open && before->copy_pending) ? COPY_NONE : before->split ? COPY_BY_TAIL : (slab_now || before->dist) ? COPY_BY_EVENT : COPY_BY_FLAG;
+  if (route == COPY_BY_FLAG && !c->sr_fetch_flag) { HIP_TRY(c, hipMalloc((void **)&c->sr_fetch_flag, 2 * sizeof(unsigned))); HIP_TRY(c, hipMemsetAsync(c->sr_fetch_flag, 0, 2 * sizeof(unsigned), c->stream)); HIP_TRY(c, hipStreamSynchronize(c->stream)); }   // (once per context; waited for: the copy stream reads it)
+  const unsigned fetch_val = route == COPY_BY_FLAG ? ++ c->sr_fetch_seq : 0u;
+  // (the pass before this one has its tail on the tail stream: a pass that is not split itself shares the counters with it in STREAM order,
+  // so the context's stream waits for that tail; a split pass only needs that pass's cull -- its mask kernel must not start before the fused
+  // tail behind that cull can be placed -- and zeroes the counters on the tail stream, behind it)
+  if (!P.split && (rc = wait_for_open_tails(c, &P))) return rc;
+  // (a split pass: what its TAIL owns -- counters, histogram, the results block, which the tail of the pass before may still be reading as the
+  // block it continues from -- is zeroed on the tail stream)
+  // (between choosing the copy's route and queuing the copy: by flag the copy waits for the word this kernel stores, by event for an event recorded behind it)
+  ftkx::launch_series_begin(P.split ? nullptr : T.counters, B.red, P.ntodo * 64, P.split ? nullptr : T.hist, P.split ? 0 : P.nbins + 1, P.split ? nullptr : B.results, P.split ? 0 : P.nwords,
+                            c->stream, B.h_desc, B.d_desc, desc_bytes, route == COPY_BY_FLAG ? c->sr_fetch_flag : nullptr, fetch_val);
+  c->sr_lists_owner = 0;                                      // (the begin kernel zeroes the counters and the histogram: they are nobody's until this pass's cull is queued)
+  return route == COPY_NONE ? FTKX_OK : series_queue_copy_behind(c, *before, route, fetch_val);
+}
+
+// First half, stage 1: the pass is planned -- buffers, descriptors -- and its begin and mask kernels are queued on the context's stream.  `prev`:
+// the pass queued before this one and not yet collected, whose running minimum this one continues from (on the device), or nullptr: running_in
+// is the value.
+int series_plan(ftkx_ctx *c, ftkx_series_pending &P, const int *ts, const int *scopes, int n, double running_in, const ftkx_series_pending *prev, bool pipelined,
+                ftkx_series_pending *before = nullptr /* the pass queued before this one, if it is still open */, const DistPlan *dist = nullptr)
+{
+  const int nd = c->nd;
+  release_retired(c, P);                                     // (a slot that was abandoned with arrays still parked in it)
+  P = ftkx_series_pending();
+  if (dist) { P.dist = true; P.t_halo = dist->t_halo; P.dist_rank = dist->rank; P.dist_nranks = dist->nranks; P.dist_upper = dist->upper; P.gathered = dist->gathered; }
+  P.ts.assign(ts, ts + n); P.scopes.assign(scopes, scopes + n); P.n = n;
+  P.running_in = running_in; P.chained = prev != nullptr;
+  int rc;
+  if ((rc = series_steps(c, ts, scopes, n, P.slice_ts))) return rc;
+  const size_t k = P.slice_ts.size();
+  P.k = k;
+  std::vector<Slice *> sl(k);
+  for (size_t j = 0; j < k; j ++) sl[j] = &c->slices.find(P.slice_ts[j])->second;
+
+  // ---- is the device-driven form applicable? ---------------------------------------------------------------------------------------
+  Mesh m; fill_mesh(c, m);
+  P.two_level = ftkx::masks_have_summary(m);
+  P.cells = 1;
+  for (int d = 0; d < nd; d ++) P.cells *= (u64)c->core_sz[d];
+  bool ok = series_applicable(c, ts, scopes, n, P.slice_ts, sl, P.cells, dist ? dist->t_halo : -1);
+  if (prev && prev->by_host) ok = false;                     // (its running minimum will not be on the device)
+  if (dist && !P.two_level) ok = false;                      // (the halo's masks travel as summaries + the words they do not describe)
+  P.hint = std::max<unsigned long long>(factor_of(running_in), 256ull);
+  P.u_rows = m.u_rows;
+  if (!ok) { P.by_host = true; P.open = true; return FTKX_OK; }
+  if (series_one_eligible(c, n, k, P.cells, dist != nullptr)) return series_plan_one(c, P, ts, scopes, n, sl, prev, before);
+  std::vector<const u64 *> from_res, from_max;
+  series_slice_readiness(c, P, sl, before, dist, from_res, from_max);
+
+  // ---- buffers (persistent; they only ever grow) -----------------------------------------------------------------------------------
+  ftkx_tail_set &S0 = c->sr_tail[0];                           // (grown first whichever set the pass takes: the other one follows it, ensure_set1)
+  if ((rc = ensure_hit_buffer(c, std::max<u64>(c->capacity, 1u << 16)))) return rc;
+  if ((rc = ensure_fragile(c, S0, std::max<u64>(S0.fragile_capacity, 1u << 12)))) return rc;
+  if ((rc = ensure_list(c, S0, std::max<u64>(S0.list_capacity, 1u << 20))) || (rc = ensure_refine(c, S0, std::max<u64>(S0.refine_capacity, 1u << 20)))) return rc;
+  const unsigned long long mask_bytes = (unsigned long long)P.ntodo * (unsigned long long)n_vertices(c) * 8ull * (c->scalar_mode == 1 ? 1ull : (unsigned long long)nd);
+  series_decide_split(c, P, pipelined, dist != nullptr, mask_bytes);
+  if (before && before->open && before->split) series_retire_masks(P, sl, *before);
+  for (size_t j = 0; j < k; j ++) if (P.red_index[j] >= 0 && (rc = ensure_mask_arrays(c, *sl[j], P.two_level))) return rc;
+  series_bucket_geometry(P);
+  if ((rc = ensure_bins(c, S0, std::max<u64>(P.nbins + 1, (1u << 16) + 1))) || (rc = ensure_order(c, S0, c->capacity))) return rc;
+  P.nwords = (size_t)ftkx::SR_HEAD + (size_t)n + 2 * k + (dist ? (size_t)ftkx::kDistContrib * (size_t)dist->nranks : 0);
+  // descriptors: mask jobs | steps | slice table | step table, one pinned block fetched by a kernel
+  P.off_steps = align256(P.ntodo * sizeof(MaskJob)); P.off_slices = P.off_steps + align256((size_t)n * sizeof(Fields)); P.off_sinfo = P.off_slices + align256(k * sizeof(ftkx::SeriesSlice));
+  const size_t desc_bytes = P.off_sinfo + align256((size_t)n * sizeof(ftkx::SeriesStep));
+  // A pass with many records, queued while another is still out: the record kernel leaves them in device memory and a small kernel on a
+  // stream of its own takes them over PCIe -- next to the mask kernel of the pass queued behind.  (A record kernel that writes through
+  // PCIe itself holds its stream for the transfer: 106 us of woven 1024^2 x 64's 363.)
+  P.buf = (int)(&P - c->sr_pend);                             // (a pass's buffers go with its place in sr_pend: nothing to undo when a step below fails)
+  ftkx_series_buffers &B = c->sr_buf[P.buf];
+  if ((rc = ensure_series_buffers(c, B, P.nwords, desc_bytes, P.to_device))) return rc;
+  if (B.red_cap < std::max<size_t>(P.ntodo, 1)) {            // (the pass's own reduction slots: a buffer in use by an open pass is never this one -- two buffers, two passes)
+    if (B.red) { HIP_TRY(c, hipFree(B.red)); B.red = nullptr; B.red_cap = 0; }
+    HIP_TRY(c, hipMalloc((void **)&B.red, std::max<size_t>(P.ntodo, 1) * 128 * sizeof(u64)));
+    B.red_cap = std::max<size_t>(P.ntodo, 1);
+  }
+  if ((rc = series_tail_resources(c, P, before, mask_bytes))) return rc;
+  series_mesh(c, P, m);                                      // (the buffers may have moved)
+  series_write_desc(c, P, m, sl, from_res, from_max);
+
+  // ---- the whole pass, queued ------------------------------------------------------------------------------------------------------
+  P.seq = ++ B.seq;
+  series_claim_masks(c, P, sl, dist);
+  if ((rc = series_queue_begin(c, P, before, dist != nullptr, desc_bytes)) || (rc = series_queue_masks(c, P, m, sl, dist))) return rc;
+  if (P.split) {
+    // the tail's side: behind the masks (an event), the counters and the histogram zeroed there
+    HIP_TRY(c, hipEventRecord(B.ev_masks, c->stream));
+    const ftkx_tail_set &T = tail_of(c, P);
+    HIP_TRY(c, hipStreamWaitEvent(T.stream, B.ev_masks, 0));
+    ftkx::launch_series_tail_begin(T.counters, T.hist, P.nbins + 1, B.results, P.nwords, T.stream);
+  }
+  P.running_from = prev ? c->sr_buf[prev->buf].results : nullptr;
+  HIP_TRY(c, hipGetLastError());
+  return FTKX_OK;
 }
 
 // stage 2: the cull, with the factor job riding in it
@@ -695,7 +693,7 @@ int series_queue_cull(ftkx_ctx *c, ftkx_series_pending &P)
   const ftkx::SeriesSlice *d_slices = (const ftkx::SeriesSlice *)((char *)B.d_desc + P.off_slices);
   const ftkx::SeriesStep *d_sinfo = (const ftkx::SeriesStep *)((char *)B.d_desc + P.off_sinfo);
   hipStream_t st = tail_stream(c, P);
-  const TailView T = tail_view(c, P);
+  const ftkx_tail_set &T = tail_of(c, P);
   if (!P.split) ev_begin(c, K_CULL);
   // (two tails at a time: this pass's factor job continues from the running minimum the factor job of the pass before it leaves -- on the
   // other tail stream)
@@ -713,8 +711,8 @@ int series_queue_cull(ftkx_ctx *c, ftkx_series_pending &P)
     fj.running_in = running_from ? DBL_MAX : P.running_in; fj.safe_m = safe_m; fj.nsteps = n; fj.nslices = (int)k;
     const bool fold_on = ftkx::env_hook("FTKX_SERIES_HOOKS", "fold", 1) != 0;
     fj.enabled = (fold_on && k <= (size_t)ftkx::kFoldMaxSlices) ? 1 : 0;
-    if (P.two_level) ftkx::launch_cull_coarse(m, d_steps, n, T.refine, c->refine_capacity, st, &fj);
-    else ftkx::launch_cull(m, d_steps, n, T.list, c->list_capacity, st, &fj);
+    if (P.two_level) ftkx::launch_cull_coarse(m, d_steps, n, T.refine, T.refine_capacity, st, &fj);
+    else ftkx::launch_cull(m, d_steps, n, T.list, T.list_capacity, st, &fj);
     if (!fj.enabled) ftkx::launch_series_factors(d_steps, n, d_slices, (int)k, d_sinfo, B.red, fj.running_in, running_from, safe_m, B.results, T.counters, st);
   }
   if (P.split) HIP_TRY(c, hipEventRecord(B.ev_factors, st));
@@ -730,9 +728,6 @@ int series_queue_tail(ftkx_ctx *c, ftkx_series_pending &P)
   Mesh m; series_mesh(c, P, m);
   Fields *d_steps = (Fields *)((char *)B.d_desc + P.off_steps);
   unsigned *flag = reinterpret_cast<unsigned *>(B.h_results + B.h_results_cap);
-  const unsigned seq = P.seq;
-  const bool two_level = P.two_level;
-  const size_t nwords = P.nwords;
   hipStream_t st = tail_stream(c, P);
   if (!P.split) ev_begin(c, K_EXACT);
   // sparse data: one kernel does the rest of the pass (and the kernels below leave at once).  (A pass that has just found far more
@@ -745,9 +740,10 @@ int series_queue_tail(ftkx_ctx *c, ftkx_series_pending &P)
   if (P.split) { small_now = false; P.short_chain = false; }      // (the fused tail does not fit next to a mask kernel: the chain)
   if (c->sr_skip_small > 0) c->sr_skip_small --;
   P.small_now = small_now;
-  if (small_now) ftkx::launch_series_small(m, two_level ? ftkx::coarse_view(m) : m, d_steps, two_level, c->d_refine, c->d_list, B.out, B.results, nwords,
-                                          B.h_results, flag, seq, reinterpret_cast<unsigned *>(c->d_counters + ftkx::CNT_SMALL_DONE), P.short_chain, st);
-  if (!P.short_chain) series_queue_rest(c, P, m, seq);
+  const ftkx_tail_set &T = tail_of(c, P);
+  if (small_now) ftkx::launch_series_small(m, P.two_level ? ftkx::coarse_view(m) : m, d_steps, P.two_level, T.refine, T.list, B.out, B.results, P.nwords,
+                                          B.h_results, flag, P.seq, reinterpret_cast<unsigned *>(T.counters + ftkx::CNT_SMALL_DONE), P.short_chain, st);
+  if (!P.short_chain) series_queue_rest(c, P, m, P.seq);
   if (P.split) HIP_TRY(c, hipEventRecord(B.ev_tail, st));
   P.copy_pending = P.to_device;
   HIP_TRY(c, hipGetLastError());
@@ -785,14 +781,12 @@ int series_complete(ftkx_ctx *c, ftkx_series_pending &P, double *running_resolut
   }
   ftkx_series_buffers &B = c->sr_buf[P.buf];
   unsigned *flag = reinterpret_cast<unsigned *>(B.h_results + B.h_results_cap);
-  Mesh m; fill_mesh(c, m);
-  { const TailView T = tail_view(c, P); m.counters = T.counters; m.pass = T.pass; m.fragile = T.fragile; m.hist = T.hist; }
-  m.hist_shift = P.shift; m.core_cells = P.cells;
+  Mesh m; series_mesh(c, P, m);
   if (const char *why = ftkx::wait_flag(flag, P.seq, tail_stream(c, P))) return fail(c, FTKX_E_DEVICE, "ftkx_sweep_series: %s", why);
   release_retired(c, P);                                     // (the tail that read them is through)
   // (with no pass left open the tail stream is at its end: waited for, so that whatever the caller does next on the context's stream --
   // a host-driven batch, a pass that is not split -- finds the counters and lists idle)
-  if (P.split && c->sr_open == 0) { HIP_TRY(c, hipStreamSynchronize(c->sr_tail_stream)); if (c->sr_tail_stream2) HIP_TRY(c, hipStreamSynchronize(c->sr_tail_stream2)); }
+  if (P.split && c->sr_open == 0) HIP_TRY(c, sync_tails(c));
 
   // ---- what came back ----------------------------------------------------------------------------------------------------------------
   // (whoever stored the flag -- the fused tail, finishing or declining, or the finish kernel -- copied the whole results block first: the
@@ -873,12 +867,13 @@ int series_complete(ftkx_ctx *c, ftkx_series_pending &P, double *running_resolut
       const u64 hits = cnt[ftkx::CNT_PASS], listed = cnt[ftkx::CNT_LIST_PEAK], refined = cnt[ftkx::CNT_REFINE_PEAK], fragile = cnt[ftkx::CNT_FRAGILE];
       if (c->sr_open > 0) {                                  // (a pass queued behind this one still uses the buffers)
         HIP_TRY(c, hipStreamSynchronize(c->stream));
-        if (c->sr_tail_stream) { HIP_TRY(c, hipStreamSynchronize(c->sr_tail_stream)); if (c->sr_tail_stream2) HIP_TRY(c, hipStreamSynchronize(c->sr_tail_stream2)); }
+        HIP_TRY(c, sync_tails(c));
       }
       if (hits > c->capacity && (rc = ensure_hit_buffer(c, hits + hits / 8 + 1024))) return rc;
-      if (listed > c->list_capacity && (rc = ensure_list(c, listed + listed / 8 + 1024))) return rc;
-      if (refined > c->refine_capacity && (rc = ensure_refine(c, refined + refined / 8 + 1024))) return rc;
-      if (fragile > c->fragile_capacity && (rc = ensure_fragile(c, fragile + fragile / 8 + 1024))) return rc;
+      ftkx_tail_set &S0 = c->sr_tail[0];                      // (the other set follows when a pass is planned on it)
+      if (listed > S0.list_capacity && (rc = ensure_list(c, S0, listed + listed / 8 + 1024))) return rc;
+      if (refined > S0.refine_capacity && (rc = ensure_refine(c, S0, refined + refined / 8 + 1024))) return rc;
+      if (fragile > S0.fragile_capacity && (rc = ensure_fragile(c, S0, fragile + fragile / 8 + 1024))) return rc;
     }
     rc = series_by_host(c, P.ts.data(), P.scopes.data(), n, P.slice_ts, &running, factors, out, n_out);
     if (rc == FTKX_OK) *running_resolution = running;
@@ -1018,7 +1013,6 @@ int ftkx_sweep_series_complete(ftkx_ctx *c, double *running_resolution, unsigned
 
 // ---- the slab pass: one rank's part of a series cut into timestep slabs, queued in stages -----------------------------------------------
 namespace {
-int factor_log2_of(unsigned long long f) { int b = 0; while (b < 63 && (1ull << b) < f) b ++; return b; }
 size_t dist_cells_cap(const ftkx_ctx *c)
 {
   // cells a request carries: the reply has a FIXED size (the owner never sees the count on the host) -- at most 1 MiB of patches
@@ -1113,11 +1107,12 @@ int ftkx_series_dist_cull(ftkx_ctx *c, const void *masks_in, void *request_out)
     // the cells whose exact test reads the halo slice: refine now (the rest of the chain will not refine again), list them, write the request
     Fields *d_steps = (Fields *)((char *)B.d_desc + P.off_steps);
     const Slice &h = c->slices.find(P.t_halo)->second;          // (checked above)
-    ftkx::launch_refine(m, d_steps, c->d_refine, c->refine_capacity, c->d_list, c->list_capacity, c->stream);
+    const ftkx_tail_set &T = tail_of(c, P);
+    ftkx::launch_refine(m, d_steps, T.refine, T.refine_capacity, T.list, T.list_capacity, c->stream);
     P.refined = true;
     u64 *req = (u64 *)request_out;
     const size_t cap = dist_cells_cap(c);
-    ftkx::launch_dist_cells(m, d_steps, c->d_list, c->list_capacity, c->refine_capacity, h.S ? h.S : h.V, req, cap, B.dist_block, B.results, c->stream);
+    ftkx::launch_dist_cells(m, d_steps, T.list, T.list_capacity, T.refine_capacity, h.S ? h.S : h.V, req, cap, B.dist_block, B.results, c->stream);
     P.request_out = req;
   }
   HIP_TRY(c, hipGetLastError());
@@ -1194,8 +1189,7 @@ int ftkx_sweep_series_abort(ftkx_ctx *c)
   // whatever the open passes queued runs to its end (their kernels write buffers that stay allocated); nothing of it is read
   hipError_t e = hipStreamSynchronize(c->stream);
   if (c->sr_copy_stream && e == hipSuccess) e = hipStreamSynchronize(c->sr_copy_stream);
-  if (c->sr_tail_stream && e == hipSuccess) e = hipStreamSynchronize(c->sr_tail_stream);
-  if (c->sr_tail_stream2 && e == hipSuccess) e = hipStreamSynchronize(c->sr_tail_stream2);
+  if (e == hipSuccess) e = sync_tails(c);
   for (ftkx_series_pending &P : c->sr_pend) {
     if (P.dist && P.dist_stage > 0 && P.dist_stage < 4) { P.open = true; }      // (a slab pass that was never finished: its masks are nobody's either)
     if (!P.open) continue;
