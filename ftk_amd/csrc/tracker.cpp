@@ -5,7 +5,6 @@
 #include "host_sort.hpp"
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <condition_variable>
 #include <cstring>
@@ -17,16 +16,55 @@
 
 namespace ftkx {
 
-critical_point_tracker_regular::critical_point_tracker_regular(int nd_, int device_id) : nd(nd_)
+namespace {
+// the writer of what ftkx_cp_ordinal / ftkx_cp_timestep (include/ftkx.h) read: bit 0 = ordinal, bits 1..31 = the timestep
+void set_cp_aux(ftkx_cp_t &r, int timestep, bool ordinal) { reinterpret_cast<unsigned int *>(&r)[15] = ((unsigned)timestep << 1) | (ordinal ? 1u : 0u); }
+ftkx_cp_t record_of(const feature_point_t &cp)
 {
-  std::memset(&last_stats, 0, sizeof(last_stats));
-  int rc = ftkx_create(&ctx, nd, device_id);
-  if (rc != FTKX_OK) {
-    char buf[512];
-    ftkx_last_error(nullptr, buf, sizeof(buf));
-    throw ftkx_error(rc, buf);   // no device, no tracker: there is no CPU path behind this class
-  }
+  ftkx_cp_t r;
+  std::memset(&r, 0, sizeof(r));
+  for (int k = 0; k < 3; k ++) { r.x[k] = cp.x[k]; r.scalar[k] = cp.scalar[k]; }
+  r.t = cp.t; r.type = cp.type; r.tag = cp.tag;
+  set_cp_aux(r, cp.timestep, cp.ordinal);
+  return r;
 }
+feature_point_t point_of(const ftkx_cp_t &r)
+{
+  feature_point_t cp;
+  for (int k = 0; k < 3; k ++) { cp.x[k] = r.x[k]; cp.scalar[k] = r.scalar[k]; }
+  cp.t = r.t; cp.type = r.type; cp.tag = r.tag;
+  cp.ordinal = ftkx_cp_ordinal(&r) != 0; cp.timestep = ftkx_cp_timestep(&r);
+  return cp;
+}
+
+// a failed call of the C ABI -> ftkx_error with the context's message (c == nullptr: the calling thread's last error)
+ftkx_error last_error_of(const ftkx_ctx *c, int rc) { char buf[512] = ""; ftkx_last_error(c, buf, sizeof(buf)); return ftkx_error(rc, buf); }
+[[noreturn]] void throw_last(const ftkx_ctx *c, int rc) { throw last_error_of(c, rc); }
+void check_on(const ftkx_ctx *c, int rc) { if (rc != FTKX_OK) throw_last(c, rc); }
+void check_slab(const ftkx_slab *s, int rc) { if (rc != FTKX_OK) throw ftkx_error(rc, ftkx_slab_last_error(s)); }
+
+ftkx_ctx *create_context(int nd, int device_id)
+{
+  ftkx_ctx *c = nullptr;
+  check_on(nullptr, ftkx_create(&c, nd, device_id));   // no device, no tracker: there is no CPU path behind this class
+  return c;
+}
+
+// critical_point_tracker.hh:857-863: the quantisation factor that belongs to a running minimum of ndarray::resolution()
+unsigned long long factor_of(double resolution, int minbits, int maxbits)
+{
+  const int nbits = (int)std::ceil(std::log2(1.0 / resolution));
+  return 1ull << std::max(minbits, std::min(nbits, maxbits));
+}
+
+// one snapshot -> one context.  kind: 0 scalar (V derived), 1 vector, 2 all three given
+int push_to(ftkx_ctx *c, int kind, int t, const double *s, const double *v, const double *j, int on_device)
+{
+  if (kind == 0) return ftkx_push_scalar_slice(c, t, s, on_device);
+  if (kind == 1) return ftkx_push_slice(c, t, v, nullptr, nullptr, on_device);
+  return ftkx_push_slice(c, t, v, j, s, on_device);
+}
+}  // namespace
 
 // ---- several devices behind one tracker ---------------------------------------------------------------------------------------
 struct critical_point_tracker_regular::multi_engine {
@@ -38,6 +76,15 @@ struct critical_point_tracker_regular::multi_engine {
     std::deque<std::function<void()>> q;
     bool stop = false, busy = false;
     unsigned long long posted = 0, done = 0;     // jobs handed in / finished (FIFO: `done >= ticket` says a particular job is through)
+    ~worker() { ftkx_destroy(ctx); }
+  };
+  // what one step hands back to the tracker (the records are the context's: valid while `deliver` runs)
+  struct step_result {
+    int t = 0;
+    double resolution = 0;                     // the running minimum at this step, and the factor it gives
+    unsigned long long factor = 0;
+    const ftkx_cp_t *recs = nullptr; size_t n = 0;
+    ftkx_stats stats;
   };
   std::vector<std::unique_ptr<worker>> w;
   int block = 2, t_first = -1;
@@ -51,7 +98,13 @@ struct critical_point_tracker_regular::multi_engine {
   std::mutex emu;
   int error_code = 0;
   std::string error;
-  std::mutex rmu;                              // guards the tracker's result members while jobs write them
+  std::mutex rmu;                              // held while a step's result is delivered: the jobs of several devices finish at the same time
+
+  multi_engine(int nd, const std::vector<int> &device_ids, int block_) : block(block_)
+  {
+    for (int dev : device_ids) { w.emplace_back(new worker()); w.back()->ctx = create_context(nd, dev); }
+    for (auto &W : w) { worker *wp = W.get(); W->th = std::thread([this, wp] { run(wp); }); }
+  }
 
   int dev_of(int t) const { return ((t - t_first) / block) % (int)w.size(); }
 
@@ -94,12 +147,10 @@ struct critical_point_tracker_regular::multi_engine {
     std::unique_lock<std::mutex> lk(w[d]->mu);
     w[d]->cv.wait(lk, [&] { return w[d]->done >= ticket; });
   }
-  void wait(int d)
+  void wait_all()
   {
-    std::unique_lock<std::mutex> lk(w[d]->mu);
-    w[d]->cv.wait(lk, [&] { return w[d]->q.empty() && !w[d]->busy; });
+    for (auto &W : w) { std::unique_lock<std::mutex> lk(W->mu); W->cv.wait(lk, [&] { return W->q.empty() && !W->busy; }); }
   }
-  void wait_all() { for (size_t d = 0; d < w.size(); d ++) wait((int)d); }
   bool failed() { std::lock_guard<std::mutex> g(emu); return error_code != 0; }
   void rethrow()
   {
@@ -138,32 +189,79 @@ struct critical_point_tracker_regular::multi_engine {
     for (int s = t_first; s <= t_last; s ++) { auto it = res_below.find(s); if (it != res_below.end()) r = std::min(r, it->second); }
     return r;
   }
-  ~multi_engine()
+
+  // one snapshot -> the devices whose steps read it; returns when the caller's buffer is free again
+  void push(int kind, int t, const double *s, const double *v, const double *j, bool device)
+  {
+    if (t_first < 0) t_first = t;
+    std::set<int> targets;
+    targets.insert(dev_of(t));
+    if (t > t_first) targets.insert(dev_of(t - 1));        // the interval sweep [t-1, t] of the previous block reads it too
+    // Device memory is COPIED into each context (a peer copy where the devices differ; the contexts recycle their slice buffers, so
+    // no allocation per step): the steps run later than the calls that queue them, and the caller's buffer is free again on return
+    // -- adopting the pointer would tie its lifetime to a queue the caller cannot see.
+    std::vector<std::pair<int, unsigned long long>> tickets;
+    for (int d : targets) {
+      ftkx_ctx *c = w[d]->ctx;
+      tickets.push_back({d, post(d, [=] { check_on(c, push_to(c, kind, t, s, v, j, device ? 2 : 0)); })});
+    }
+    for (const auto &tk : tickets) wait_job(tk.first, tk.second);     // (the caller's buffer is free again once these copies are through)
+    rethrow();
+    resident[t] = targets;
+  }
+  // the slice of timestep t leaves every device that holds it: queued behind the steps that still read it
+  void drop(int t)
+  {
+    for (int d : resident[t]) {
+      ftkx_ctx *c = w[d]->ctx;
+      post(d, [=] { check_on(c, ftkx_drop_slice(c, t)); });
+    }
+    resident.erase(t);
+  }
+  // The step of timestep t over the slices `ts` is queued on the device that owns t, and this call returns.  Inside the job: reduce
+  // (and mask) the step's slices under the factor known so far, publish their contribution, wait for the contributions of ALL
+  // earlier slices -- other devices publish theirs before they sweep, so this is a wait for reductions only -- and sweep under
+  // the factor the reference would have at this step.  `deliver(const step_result &)` runs on the device's thread, under rmu.
+  template <class Deliver>
+  void step(int t, int scope, const std::vector<int> &ts, int minbits, int maxbits, Deliver deliver)
+  {
+    rethrow();
+    ftkx_ctx *c = w[dev_of(t)]->ctx;
+    post(dev_of(t), [this, c, t, scope, ts, minbits, maxbits, deliver] {
+      std::vector<double> below(ts.size());
+      check_on(c, ftkx_sweep_announce(c, &t, &scope, 1));
+      check_on(c, ftkx_slices_prepare(c, ts.data(), (int)ts.size(), factor_of(known_before(t), minbits, maxbits), below.data(), nullptr));
+      publish(ts, below);
+      step_result r;
+      r.t = t;
+      r.resolution = wait_running_min(ts.back());
+      if (failed()) return;                     // another step failed: do not sweep with a partial minimum
+      r.factor = factor_of(r.resolution, minbits, maxbits);
+      check_on(c, ftkx_sweep(c, t, scope, r.factor, &r.recs, &r.n));
+      check_on(c, ftkx_get_stats(c, &r.stats));
+      std::lock_guard<std::mutex> g(rmu);
+      deliver(r);
+    });
+  }
+  void settle() { wait_all(); rethrow(); }
+  // a new series: the board is empty again, and what the last series reduced stays in force (the running minimum is sticky)
+  void restart(double resolution) { base_resolution = resolution; res_below.clear(); t_first = -1; }
+
+  ~multi_engine()      // (the workers' destructors then destroy the contexts)
   {
     for (auto &W : w) { { std::lock_guard<std::mutex> lk(W->mu); W->stop = true; } W->cv.notify_all(); }
     for (auto &W : w) if (W->th.joinable()) W->th.join();
-    for (auto &W : w) ftkx_destroy(W->ctx);
   }
 };
+
+critical_point_tracker_regular::critical_point_tracker_regular(int nd_, int device_id) : critical_point_tracker_regular(nd_, std::vector<int>(1, device_id)) {}
 
 critical_point_tracker_regular::critical_point_tracker_regular(int nd_, const std::vector<int> &device_ids, int block) : nd(nd_)
 {
   std::memset(&last_stats, 0, sizeof(last_stats));
   if (device_ids.empty() || block < 1) throw ftkx_error(FTKX_E_INVALID, "critical_point_tracker_regular: need at least one device and block >= 1");
-  if (device_ids.size() == 1) {
-    const int rc = ftkx_create(&ctx, nd, device_ids[0]);
-    if (rc != FTKX_OK) { char buf[512]; ftkx_last_error(nullptr, buf, sizeof(buf)); throw ftkx_error(rc, buf); }
-    return;
-  }
-  multi.reset(new multi_engine());
-  multi->block = block;
-  for (int dev : device_ids) {
-    std::unique_ptr<multi_engine::worker> W(new multi_engine::worker());
-    const int rc = ftkx_create(&W->ctx, nd, dev);
-    if (rc != FTKX_OK) { char buf[512]; ftkx_last_error(nullptr, buf, sizeof(buf)); multi.reset(); throw ftkx_error(rc, buf); }
-    multi->w.push_back(std::move(W));
-  }
-  for (auto &W : multi->w) { multi_engine *e = multi.get(); multi_engine::worker *wp = W.get(); W->th = std::thread([e, wp] { e->run(wp); }); }
+  if (device_ids.size() == 1) { ctx = create_context(nd, device_ids[0]); return; }
+  multi.reset(new multi_engine(nd, device_ids, block));
   ctx = multi->w[0]->ctx;     // (context() of a multi-device tracker: its first device's)
 }
 
@@ -182,11 +280,13 @@ void critical_point_tracker_regular::enter_slab_mode(int rank, int nranks, int n
   if (slab || !field_data_snapshots.empty()) throw ftkx_error(FTKX_E_INVALID, "slab mode: set it once, before the first snapshot is pushed");
   if (enable_streaming_trajectories) throw ftkx_error(FTKX_E_UNSUPPORTED, "slab mode: not with streaming trajectories");
   if (nt <= 0 || nranks <= 0 || rank < 0 || rank >= nranks) throw ftkx_error(FTKX_E_INVALID, "slab mode: bad rank / nranks / nt");
-  slab_nt = nt; slab_rank = rank; slab_nranks = nranks;
+  slab_rank = rank;
   ftkx_slab_range(nt, nranks, rank, &slab_t0, &slab_t1);
-  current_timestep = next_push_timestep = slab_t0;          // the first snapshot this rank pushes is its slab's first timestep
-  slab_steps.clear(); slab_swept = false;
+  restart_slab();
 }
+
+// the first snapshot this rank pushes is its slab's first timestep; nothing recorded, nothing swept
+void critical_point_tracker_regular::restart_slab() { current_timestep = next_push_timestep = slab_t0; slab_steps.clear(); slab_swept = false; }
 
 void critical_point_tracker_regular::set_communicator(void *comm, int rank, int nranks, int nt)
 {
@@ -212,46 +312,53 @@ void critical_point_tracker_regular::set_slab_hub(ftkx_slab_hub *hub, int rank, 
   slab = probe;
 }
 
-// the slab's pass: every step recorded so far must be the slab's -- t0 .. t1 - 1 in order -- and every snapshot still resident
-void critical_point_tracker_regular::run_slab() const
+// slab mode: the step is recorded; the slab is swept as one pass (run_slab)
+void critical_point_tracker_regular::step_slab()
 {
-  critical_point_tracker_regular *self = const_cast<critical_point_tracker_regular *>(this);
+  if (slab_swept) throw ftkx_error(FTKX_E_INVALID, "slab mode: the slab has been swept (reset() starts a new series)");
+  if (slab_steps.empty() || slab_steps.back() != current_timestep) slab_steps.push_back(current_timestep);
+}
+
+// the slab's pass: every step recorded so far must be the slab's -- t0 .. t1 - 1 in order -- and every snapshot still resident
+void critical_point_tracker_regular::run_slab()
+{
   const int nown = slab_t1 - slab_t0;
   if ((int)slab_steps.size() != nown || (int)field_data_snapshots.size() != nown)
     throw ftkx_error(FTKX_E_INVALID, "slab mode: " + std::to_string(slab_steps.size()) + " steps recorded and " + std::to_string(field_data_snapshots.size()) +
                      " snapshots pushed of this rank's " + std::to_string(nown) + " (push the slab's snapshots, advance_timestep() between them, update_timestep() after the last)");
   for (int i = 0; i < nown; i ++) if (slab_steps[(size_t)i] != slab_t0 + i) throw ftkx_error(FTKX_E_INVALID, "slab mode: the steps must be the slab's timesteps in order");
-  auto slab_check = [&](int rc) { if (rc != FTKX_OK) throw ftkx_error(rc, ftkx_slab_last_error(slab)); };
-  slab_check(ftkx_slab_submit(slab, &vector_field_resolution));
+  check_slab(slab, ftkx_slab_submit(slab, &vector_field_resolution));
   std::vector<unsigned long long> f((size_t)std::max(nown, 1), 0ull);
   const ftkx_cp_t *recs = nullptr;
   size_t n = 0;
   double run = vector_field_resolution;
-  slab_check(ftkx_slab_complete(slab, &run, f.data(), &recs, &n));
-  self->slab_swept = true;
+  check_slab(slab, ftkx_slab_complete(slab, &run, f.data(), &recs, &n));
+  slab_swept = true;
   if (nown > 0) {
-    self->vector_field_resolution = std::min(vector_field_resolution, run);
-    self->vector_field_scaling_factor = f[(size_t)nown - 1];
-    for (size_t i = 0; i < n; i ++) self->take_records(recs + i, 1, ftkx_cp_timestep(recs + i));
-    check(ftkx_get_stats(ctx, &self->last_stats));
+    vector_field_resolution = std::min(vector_field_resolution, run);
+    vector_field_scaling_factor = f[(size_t)nown - 1];
+    take_records_by_step(recs, n);
+    check(ftkx_get_stats(ctx, &last_stats));
   }
 }
 
-void critical_point_tracker_regular::wait_devices() const
+// what is still out comes in: the slab's pass, the queues of several devices, the deferred sweeps
+void critical_point_tracker_regular::wait_devices()
 {
   if (slab) { if (!slab_swept) run_slab(); return; }
-  if (multi) {
-    multi->wait_all();
-    multi->rethrow();
-  }
+  if (multi) multi->settle();
+  collect_deferred();
+}
+
+void critical_point_tracker_regular::collect_deferred()
+{
   if (!batch_ts.empty()) submit_batch();                       // deferred collection in batches: the steps recorded since the last full batch
   while (!open_steps.empty()) collect_open_step();             // deferred collection: what is still out
 }
 
 // deferred collection: the oldest queued sweep -> its records, factor, running minimum and statistics, as update_timestep leaves them
-void critical_point_tracker_regular::collect_open_step() const
+void critical_point_tracker_regular::collect_open_step()
 {
-  critical_point_tracker_regular *self = const_cast<critical_point_tracker_regular *>(this);
   const int t = open_steps.front();
   open_steps.erase(open_steps.begin());
   const ftkx_cp_t *recs = nullptr;
@@ -262,36 +369,29 @@ void critical_point_tracker_regular::collect_open_step() const
   if (rc != FTKX_OK) {
     // the other open pass (if any) is discarded with it: the context is left as if nothing had been queued, so that the tracker's later
     // calls do not fail with "passes open" or chain from a stale running minimum
-    char why[512] = "";
-    ftkx_last_error(ctx, why, sizeof(why));
+    const ftkx_error why = last_error_of(ctx, rc);
     open_steps.clear();
     (void)ftkx_sweep_series_abort(ctx);
     batch_ts.clear(); batch_scopes.clear();
     for (int d : batch_drops) (void)ftkx_drop_slice(ctx, d);
     batch_drops.clear();
-    throw ftkx_error(rc, why);
+    throw why;
   }
-  self->vector_field_resolution = res;
-  self->vector_field_scaling_factor = f;
-  if (t >= 0) self->take_records(recs, n, t);
-  else for (size_t i = 0; i < n;) {                             // a batch: runs of one timestep (the records are ordered by tag, not by step)
-    size_t j = i + 1;
-    while (j < n && ftkx_cp_timestep(&recs[j]) == ftkx_cp_timestep(&recs[i])) j ++;
-    self->take_records(recs + i, j - i, ftkx_cp_timestep(&recs[i]));
-    i = j;
-  }
-  check(ftkx_get_stats(ctx, &self->last_stats));
+  vector_field_resolution = res;
+  vector_field_scaling_factor = f;
+  if (t >= 0) take_records(recs, n, t);
+  else take_records_by_step(recs, n);                            // a batch: its steps' records, ordered by tag, not by step
+  check(ftkx_get_stats(ctx, &last_stats));
 }
 
 // deferred collection in batches: the recorded steps as one pass (continuing, on the device, from the pass queued before it if that one is
 // still out); the snapshots popped since the batch began are dropped behind it -- their buffers are reused in stream order
-void critical_point_tracker_regular::submit_batch() const
+void critical_point_tracker_regular::submit_batch()
 {
-  critical_point_tracker_regular *self = const_cast<critical_point_tracker_regular *>(this);
   const bool chained = !open_steps.empty();
   std::vector<int> ts, scopes, drops;
   ts.swap(batch_ts); scopes.swap(batch_scopes); drops.swap(batch_drops);
-  int rc = ftkx_sweep_series_submit(ctx, ts.data(), scopes.data(), (int)ts.size(), chained ? nullptr : &self->vector_field_resolution);
+  int rc = ftkx_sweep_series_submit(ctx, ts.data(), scopes.data(), (int)ts.size(), chained ? nullptr : &vector_field_resolution);
   if (rc == FTKX_OK) open_steps.push_back(-1);
   for (int t : drops) { const int rc2 = ftkx_drop_slice(ctx, t); if (rc == FTKX_OK) rc = rc2; }
   check(rc);
@@ -300,7 +400,7 @@ void critical_point_tracker_regular::submit_batch() const
 
 void critical_point_tracker_regular::sync() const
 {
-  wait_devices();
+  const_cast<critical_point_tracker_regular *>(this)->wait_devices();   // (a getter is const; bringing in what is still out is not)
   flush_points();
 }
 
@@ -345,13 +445,7 @@ const discrete_map_t &critical_point_tracker_regular::get_discrete_critical_poin
 
 int critical_point_tracker_regular::num_devices() const { return multi ? (int)multi->w.size() : 1; }
 
-void critical_point_tracker_regular::check(int rc) const
-{
-  if (rc == FTKX_OK) return;
-  char buf[512];
-  ftkx_last_error(ctx, buf, sizeof(buf));
-  throw ftkx_error(rc, buf);
-}
+void critical_point_tracker_regular::check(int rc) const { check_on(ctx, rc); }
 
 void critical_point_tracker_regular::set_stream(void *s)
 {
@@ -359,14 +453,19 @@ void critical_point_tracker_regular::set_stream(void *s)
   check(ftkx_set_stream(ctx, s));
 }
 
+void critical_point_tracker_regular::domain_arrays(long long dst[3], long long dsz[3]) const
+{
+  for (int d = 0; d < 3; d ++) { dst[d] = d < nd ? domain.start(d) : 0; dsz[d] = d < nd ? domain.size(d) : 1; }
+}
+
 // regular_tracker::initialize, regular_tracker.hh:105-149.  Single process per GPU: the partitioner returns the whole domain
 // (local_domain == domain) and, with is_input_array_partial == false, local_array_domain == array_domain.
 void critical_point_tracker_regular::apply_configuration(ftkx_ctx *c)
 {
-  auto ck = [&](int rc) { if (rc != FTKX_OK) { char buf[512]; ftkx_last_error(c, buf, sizeof(buf)); throw ftkx_error(rc, buf); } };
-  long long dst[3] = {0, 0, 0}, dsz[3] = {1, 1, 1}, est[3] = {0, 0, 0}, esz[3] = {1, 1, 1};
-  for (int d = 0; d < nd; d ++) { dst[d] = domain.start(d); dsz[d] = domain.size(d); est[d] = array_domain.start(d); esz[d] = array_domain.size(d); }
-  ck(ftkx_set_mesh(c, dst, dsz, dst, dsz, est, esz));
+  long long dst[3], dsz[3], est[3] = {0, 0, 0}, esz[3] = {1, 1, 1};
+  domain_arrays(dst, dsz);
+  for (int d = 0; d < nd; d ++) { est[d] = array_domain.start(d); esz[d] = array_domain.size(d); }
+  check_on(c, ftkx_set_mesh(c, dst, dsz, dst, dsz, est, esz));
   ftkx_options o;
   ftkx_default_options(&o);
   o.jacobian_symmetric = is_jacobian_field_symmetric;
@@ -381,20 +480,18 @@ void critical_point_tracker_regular::apply_configuration(ftkx_ctx *c)
     if ((int)rectilinear_coords.size() < nd) throw ftkx_error(FTKX_E_INVALID, "initialize: set_coords_rectilinear needs one array per axis");
     const std::vector<double> none;
     const std::vector<double> &z = nd == 3 ? rectilinear_coords[2] : none;
-    ck(ftkx_set_coords_rectilinear(c, rectilinear_coords[0].data(), rectilinear_coords[0].size(), rectilinear_coords[1].data(), rectilinear_coords[1].size(),
-                                   z.empty() ? nullptr : z.data(), z.size()));
+    check_on(c, ftkx_set_coords_rectilinear(c, rectilinear_coords[0].data(), rectilinear_coords[0].size(), rectilinear_coords[1].data(), rectilinear_coords[1].size(),
+                                            z.empty() ? nullptr : z.data(), z.size()));
   } else if (mode_phys_coords == 3)
-    ck(ftkx_set_coords_explicit(c, explicit_coords.data(), explicit_ncomp, explicit_n0, explicit_n1));
+    check_on(c, ftkx_set_coords_explicit(c, explicit_coords.data(), explicit_ncomp, explicit_n0, explicit_n1));
   o.coords_mode = mode_phys_coords;
   for (size_t i = 0; i < 6 && i < bounds_coords.size(); i ++) o.coords_bounds[i] = bounds_coords[i];
-  ck(ftkx_set_options(c, &o));
+  check_on(c, ftkx_set_options(c, &o));
 }
 
 void critical_point_tracker_regular::initialize()
 {
   if ((int)domain.nd() != nd || (int)array_domain.nd() != nd) throw ftkx_error(FTKX_E_INVALID, "initialize: set_domain / set_array_domain first");
-  local_domain = domain;
-  local_array_domain = array_domain;
   sync();
   if (multi) { for (auto &W : multi->w) apply_configuration(W->ctx); }
   else apply_configuration(ctx);
@@ -419,85 +516,52 @@ void critical_point_tracker_regular::reset()
 {
   if (!slab) sync();                            // (slab mode: sync() is the slab's pass, a collective -- a reset does not sweep)
   ftkx_online_tracer_destroy(online); online = nullptr;
-  if (multi) { multi->base_resolution = vector_field_resolution; multi->res_below.clear(); multi->t_first = -1; }
+  if (multi) multi->restart(vector_field_resolution);
   current_timestep = 0;
   while (pop_field_data_snapshot()) {}
   next_push_timestep = 0;
-  if (slab) { current_timestep = next_push_timestep = slab_t0; slab_steps.clear(); slab_swept = false; }
+  if (slab) restart_slab();
   pending_points.clear(); pending_ascending = true;
   points.clear(); point_keys.clear();
   discrete_critical_points.clear(); map_valid = true;
 }
 
-// one snapshot -> the context(s) whose steps read it.  kind: 0 scalar (V derived), 1 vector, 2 all three given
-static int push_to(ftkx_ctx *c, int kind, int t, const double *s, const double *v, const double *j, int on_device)
+// one snapshot -> the context(s) whose steps read it (kind: see push_to)
+void critical_point_tracker_regular::push_snapshot(int kind, const double *s, const double *v, const double *j, bool device)
 {
-  if (kind == 0) return ftkx_push_scalar_slice(c, t, s, on_device);
-  if (kind == 1) return ftkx_push_slice(c, t, v, nullptr, nullptr, on_device);
-  return ftkx_push_slice(c, t, v, j, s, on_device);
-}
-
-void critical_point_tracker_regular::push_everywhere(int kind, int t, const double *s, const double *v, const double *j, bool device)
-{
-  auto fail = [](ftkx_ctx *c, int rc) { char buf[512]; ftkx_last_error(c, buf, sizeof(buf)); throw ftkx_error(rc, buf); };
+  const int t = next_push_timestep;
   if (slab && (t < slab_t0 || t >= slab_t1)) throw ftkx_error(FTKX_E_INVALID, "slab mode: timestep " + std::to_string(t) + " is not in this rank's slab [" + std::to_string(slab_t0) + ", " + std::to_string(slab_t1) + ")");
-  if (!multi) { const int rc = push_to(ctx, kind, t, s, v, j, device ? 1 : 0); if (rc) fail(ctx, rc); return; }
-  if (multi->t_first < 0) multi->t_first = t;
-  std::set<int> targets;
-  targets.insert(multi->dev_of(t));
-  if (t > multi->t_first) targets.insert(multi->dev_of(t - 1));        // the interval sweep [t-1, t] of the previous block reads it too
-  // Device memory is COPIED into each context (a peer copy where the devices differ; the contexts recycle their slice buffers, so
-  // no allocation per step): the steps run later than the calls that queue them, and the caller's buffer is free again on return
-  // -- adopting the pointer would tie its lifetime to a queue the caller cannot see.
-  std::vector<std::pair<int, unsigned long long>> tickets;
-  for (int d : targets) {
-    ftkx_ctx *c = multi->w[d]->ctx;
-    tickets.push_back({d, multi->post(d, [=] { const int rc = push_to(c, kind, t, s, v, j, device ? 2 : 0); if (rc) { char buf[512]; ftkx_last_error(c, buf, sizeof(buf)); throw ftkx_error(rc, buf); } })});
-  }
-  for (const auto &tk : tickets) multi->wait_job(tk.first, tk.second);     // (the caller's buffer is free again once these copies are through)
-  multi->rethrow();
-  multi->resident[t] = targets;
+  if (multi) multi->push(kind, t, s, v, j, device);
+  else check(push_to(ctx, kind, t, s, v, j, device ? 1 : 0));
+  field_data_snapshots.push_back(t);
+  next_push_timestep ++;
 }
 
 void critical_point_tracker_regular::push_scalar_field_snapshot(const double *s, bool device)
 {
   if (!initialized) throw ftkx_error(FTKX_E_INVALID, "push: initialize() first");
   if (vector_field_source != SOURCE_DERIVED) throw ftkx_error(FTKX_E_INVALID, "push_scalar_field_snapshot: vector_field_source must be SOURCE_DERIVED");
-  const int t = next_push_timestep;
-  push_everywhere(0, t, s, nullptr, nullptr, device);       // V = gradientND(s) on the device
-  field_data_snapshots.push_back(t);
-  next_push_timestep ++;
+  push_snapshot(0, s, nullptr, nullptr, device);            // V = gradientND(s) on the device
 }
 
 void critical_point_tracker_regular::push_vector_field_snapshot(const double *v, bool device)
 {
   if (!initialized) throw ftkx_error(FTKX_E_INVALID, "push: initialize() first");
-  const int t = next_push_timestep;
-  push_everywhere(1, t, nullptr, v, nullptr, device);       // J derived at hits when jacobian_field_source == SOURCE_DERIVED
-  field_data_snapshots.push_back(t);
-  next_push_timestep ++;
+  push_snapshot(1, nullptr, v, nullptr, device);            // J derived at hits when jacobian_field_source == SOURCE_DERIVED
 }
 
 void critical_point_tracker_regular::push_field_data_snapshot(const double *s, const double *v, const double *j, bool device)
 {
   if (!initialized) throw ftkx_error(FTKX_E_INVALID, "push: initialize() first");
-  const int t = next_push_timestep;
-  push_everywhere(2, t, s, v, j, device);
-  field_data_snapshots.push_back(t);
-  next_push_timestep ++;
+  push_snapshot(2, s, v, j, device);
 }
 
 bool critical_point_tracker_regular::pop_field_data_snapshot()
 {
   if (field_data_snapshots.empty()) return false;
   const int t = field_data_snapshots.front();
-  if (multi) {
-    for (int d : multi->resident[t]) {           // queued behind the steps that still read the slice
-      ftkx_ctx *c = multi->w[d]->ctx;
-      multi->post(d, [=] { const int rc = ftkx_drop_slice(c, t); if (rc) { char buf[512]; ftkx_last_error(c, buf, sizeof(buf)); throw ftkx_error(rc, buf); } });
-    }
-    multi->resident.erase(t);
-  } else if (!batch_ts.empty() && t >= batch_ts.front()) batch_drops.push_back(t);      // (a recorded step still reads it: dropped behind its batch)
+  if (multi) multi->drop(t);
+  else if (!batch_ts.empty() && t >= batch_ts.front()) batch_drops.push_back(t);      // (a recorded step still reads it: dropped behind its batch)
   else check(ftkx_drop_slice(ctx, t));
   field_data_snapshots.erase(field_data_snapshots.begin());
   return true;
@@ -516,22 +580,14 @@ void critical_point_tracker_regular::update_vector_field_scaling_factor(int minb
   if (!field_data_snapshots.empty())
     check(ftkx_slices_prepare(ctx, field_data_snapshots.data(), (int)field_data_snapshots.size(), hint, below.data(), nullptr));
   for (double r : below) vector_field_resolution = std::min(vector_field_resolution, r);
-  int nbits = (int)std::ceil(std::log2(1.0 / vector_field_resolution));
-  nbits = std::max(minbits, std::min(nbits, maxbits));
-  vector_field_scaling_factor = 1ull << nbits;
+  vector_field_scaling_factor = factor_of(vector_field_resolution, minbits, maxbits);
 }
 
-// critical_point_tracker_{2d,3d}_regular::update_timestep (2d:263-433, 3d:150-308): ordinal sweep at current_timestep and,
-// when two snapshots are queued, the interval sweep [current, current+1] -- here one launch, one download.
+// the records of one sweep -> pending points of timestep `timestep`
 void critical_point_tracker_regular::take_records(const ftkx_cp_t *recs, size_t n, int timestep)
 {
   for (size_t i = 0; i < n; i ++) {
-    feature_point_t cp;
-    for (int k = 0; k < 3; k ++) { cp.x[k] = recs[i].x[k]; cp.scalar[k] = recs[i].scalar[k]; }
-    cp.t = recs[i].t;
-    cp.type = recs[i].type;
-    cp.tag = recs[i].tag;
-    cp.ordinal = ftkx_cp_ordinal(&recs[i]) != 0;
+    feature_point_t cp = point_of(recs[i]);
     cp.timestep = timestep;
     if (scalar_field_source == SOURCE_NONE) cp.scalar[0] = 0.0;   // 2d:642-646: scalar only when a scalar field exists
     if (!pending_points.empty() && pending_points.back().tag >= cp.tag) pending_ascending = false;
@@ -539,83 +595,73 @@ void critical_point_tracker_regular::take_records(const ftkx_cp_t *recs, size_t 
   }
 }
 
+// records of several steps, each under the timestep it carries
+void critical_point_tracker_regular::take_records_by_step(const ftkx_cp_t *recs, size_t n)
+{
+  for (size_t i = 0; i < n; i ++) take_records(recs + i, 1, ftkx_cp_timestep(recs + i));
+}
+
+// critical_point_tracker_{2d,3d}_regular::update_timestep (2d:263-433, 3d:150-308): ordinal sweep at current_timestep and,
+// when two snapshots are queued, the interval sweep [current, current+1] -- here one launch, one download.
 void critical_point_tracker_regular::update_timestep()
 {
   if (field_data_snapshots.empty()) return;
-  if (slab) {                                   // slab mode: the step is recorded; the slab is swept as one pass (run_slab)
-    if (slab_swept) throw ftkx_error(FTKX_E_INVALID, "slab mode: the slab has been swept (reset() starts a new series)");
-    if (slab_steps.empty() || slab_steps.back() != current_timestep) slab_steps.push_back(current_timestep);
-    return;
-  }
+  if (slab) return step_slab();
   const int scope = field_data_snapshots.size() >= 2 ? FTKX_SCOPE_BOTH : FTKX_SCOPE_ORDINAL;
-  if (!multi) {
-    // (the step that follows is known before its factor is: announced, its cull is queued right behind the mask kernel of the
-    // newly arrived snapshot and runs while the host waits for the reduction)
-    const ftkx_cp_t *recs = nullptr;
-    size_t n = 0;
-    if (deferred_collection && !enable_streaming_trajectories && field_data_snapshots.size() <= 2 && field_data_snapshots.front() == current_timestep) {
-      // queue this step (continuing, on the device, from the running minimum of the step queued before it if that one is still out),
-      // then collect the step before it
-      if (deferred_depth > 1) {                 // batches: recorded; queued with the batch's last step (submit_batch)
-        batch_ts.push_back(current_timestep); batch_scopes.push_back(scope);
-        if ((int)batch_ts.size() >= deferred_depth) submit_batch();
-        return;
-      }
-      const bool chained = !open_steps.empty();
-      check(ftkx_sweep_series_submit(ctx, &current_timestep, &scope, 1, chained ? nullptr : &vector_field_resolution));
-      open_steps.push_back(current_timestep);
-      if (open_steps.size() >= 3) collect_open_step();      // (three in flight: the host runs one pass ahead of a split pass's tail)
-      return;
-    }
-    if (!batch_ts.empty()) submit_batch();
-    while (!open_steps.empty()) collect_open_step();
-    if (field_data_snapshots.size() <= 2 && field_data_snapshots.front() == current_timestep) {
-      // The device-driven pass (ftkx_sweep_series): the newly arrived snapshot's masks and reduction, the sticky factor (formed on the
-      // device from the running minimum handed in), cull, exact test and records are queued at once and waited for once.
-      unsigned long long f = 0;
-      check(ftkx_sweep_series(ctx, &current_timestep, &scope, 1, &vector_field_resolution, &f, &recs, &n));
-      vector_field_scaling_factor = f;
-    } else {
-      // (more than two snapshots queued: the reference's factor takes every queued snapshot into account, critical_point_tracker.hh:853)
-      check(ftkx_sweep_announce(ctx, &current_timestep, &scope, 1));
-      update_vector_field_scaling_factor();
-      check(ftkx_sweep(ctx, current_timestep, scope, vector_field_scaling_factor, &recs, &n));
-    }
-    take_records(recs, n, current_timestep);
-    check(ftkx_get_stats(ctx, &last_stats));
-    if (enable_streaming_trajectories && scope == FTKX_SCOPE_BOTH) grow();      // 2d:326-330, 3d:197-201: only after an interval sweep
+  if (multi) return step_multi(scope);
+  if (deferred_collection && !enable_streaming_trajectories && window_is_the_step()) return step_deferred(scope);
+  step_now(scope);
+}
+
+// deferred collection: queue this step (continuing, on the device, from the running minimum of the step queued before it if that one is
+// still out), then collect the step before it
+void critical_point_tracker_regular::step_deferred(int scope)
+{
+  if (deferred_depth > 1) {                 // batches: recorded; queued with the batch's last step (submit_batch)
+    batch_ts.push_back(current_timestep); batch_scopes.push_back(scope);
+    if ((int)batch_ts.size() >= deferred_depth) submit_batch();
     return;
   }
+  const bool chained = !open_steps.empty();
+  check(ftkx_sweep_series_submit(ctx, &current_timestep, &scope, 1, chained ? nullptr : &vector_field_resolution));
+  open_steps.push_back(current_timestep);
+  if (open_steps.size() >= 3) collect_open_step();      // (three in flight: the host runs one pass ahead of a split pass's tail)
+}
+
+// one device, the step swept and collected in this call
+void critical_point_tracker_regular::step_now(int scope)
+{
+  // (the step that follows is known before its factor is: announced, its cull is queued right behind the mask kernel of the
+  // newly arrived snapshot and runs while the host waits for the reduction)
+  const ftkx_cp_t *recs = nullptr;
+  size_t n = 0;
+  collect_deferred();
+  if (window_is_the_step()) {
+    // The device-driven pass (ftkx_sweep_series): the newly arrived snapshot's masks and reduction, the sticky factor (formed on the
+    // device from the running minimum handed in), cull, exact test and records are queued at once and waited for once.
+    unsigned long long f = 0;
+    check(ftkx_sweep_series(ctx, &current_timestep, &scope, 1, &vector_field_resolution, &f, &recs, &n));
+    vector_field_scaling_factor = f;
+  } else {
+    // (more than two snapshots queued: the reference's factor takes every queued snapshot into account, critical_point_tracker.hh:853)
+    check(ftkx_sweep_announce(ctx, &current_timestep, &scope, 1));
+    update_vector_field_scaling_factor();
+    check(ftkx_sweep(ctx, current_timestep, scope, vector_field_scaling_factor, &recs, &n));
+  }
+  take_records(recs, n, current_timestep);
+  check(ftkx_get_stats(ctx, &last_stats));
+  if (enable_streaming_trajectories && scope == FTKX_SCOPE_BOTH) grow();      // 2d:326-330, 3d:197-201: only after an interval sweep
+}
+
+// Several devices: the step is queued on the device that owns its timestep and this call returns (multi_engine::step).
+void critical_point_tracker_regular::step_multi(int scope)
+{
   if (enable_streaming_trajectories) throw ftkx_error(FTKX_E_UNSUPPORTED, "enable_streaming_trajectories: single-device trackers only");
-  // Several devices: the step is queued on the device that owns its timestep and this call returns.  Inside the job: reduce
-  // (and mask) the step's slices under the factor known so far, publish their contribution, wait for the contributions of ALL
-  // earlier slices -- other devices publish theirs before they sweep, so this is a wait for reductions only -- and sweep under
-  // the factor the reference would have at this step.
-  multi->rethrow();
-  const int t = current_timestep, d = multi->dev_of(t);
-  multi_engine *e = multi.get();
-  ftkx_ctx *c = e->w[d]->ctx;
-  std::vector<int> ts(field_data_snapshots.begin(), field_data_snapshots.begin() + (scope == FTKX_SCOPE_BOTH ? 2 : 1));
-  e->post(d, [this, e, c, t, scope, ts] {
-    auto ck = [&](int rc) { if (rc != FTKX_OK) { char buf[512]; ftkx_last_error(c, buf, sizeof(buf)); throw ftkx_error(rc, buf); } };
-    const int minbits = 8, maxbits = 21;
-    auto factor_of = [&](double res) { int nb = (int)std::ceil(std::log2(1.0 / res)); nb = std::max(minbits, std::min(nb, maxbits)); return 1ull << nb; };
-    std::vector<double> below(ts.size());
-    ck(ftkx_sweep_announce(c, &t, &scope, 1));
-    ck(ftkx_slices_prepare(c, ts.data(), (int)ts.size(), factor_of(e->known_before(t)), below.data(), nullptr));
-    e->publish(ts, below);
-    const double res = e->wait_running_min(ts.back());
-    if (e->failed()) return;                    // another step failed: do not sweep with a partial minimum
-    const unsigned long long factor = factor_of(res);
-    const ftkx_cp_t *recs = nullptr;
-    size_t n = 0;
-    ck(ftkx_sweep(c, t, scope, factor, &recs, &n));
-    ftkx_stats st;
-    ck(ftkx_get_stats(c, &st));
-    std::lock_guard<std::mutex> g(e->rmu);
-    take_records(recs, n, t);
+  const std::vector<int> ts(field_data_snapshots.begin(), field_data_snapshots.begin() + (scope == FTKX_SCOPE_BOTH ? 2 : 1));
+  multi->step(current_timestep, scope, ts, default_minbits, default_maxbits, [this](const multi_engine::step_result &r) {
+    take_records(r.recs, r.n, r.t);
     // steps finish out of order: the members keep the values of the LATEST timestep, as a sequential run would leave them
-    if (t >= result_timestep) { result_timestep = t; last_stats = st; vector_field_scaling_factor = factor; vector_field_resolution = res; }
+    if (r.t >= result_timestep) { result_timestep = r.t; last_stats = r.stats; vector_field_scaling_factor = r.factor; vector_field_resolution = r.resolution; }
   });
 }
 
@@ -629,92 +675,80 @@ bool critical_point_tracker_regular::advance_timestep()
   return field_data_snapshots.size() > 0;
 }
 
-// critical_point_tracker_{2d,3d}_regular::finalize (2d:143-225, 3d:86-117) without streaming trajectories:
-// traced_critical_points = trace_critical_points_offline(discrete_critical_points, neighbours-sharing-a-cell)
 // trace_critical_points_online (critical_point_tracker.hh:523-639) on everything in discrete_critical_points, which it consumes
 void critical_point_tracker_regular::grow()
 {
   flush_points();
-  long long dst[3] = {0, 0, 0}, dsz[3] = {1, 1, 1};
-  for (int d = 0; d < nd; d ++) { dst[d] = domain.start(d); dsz[d] = domain.size(d); }
-  if (!online) { const int rc = ftkx_online_tracer_create(&online, nd, dst, dsz); if (rc != FTKX_OK) throw ftkx_error(rc, "online tracer"); }
+  if (!online) {
+    long long dst[3], dsz[3];
+    domain_arrays(dst, dsz);
+    const int rc = ftkx_online_tracer_create(&online, nd, dst, dsz);
+    if (rc != FTKX_OK) throw ftkx_error(rc, "online tracer");
+  }
   std::vector<ftkx_cp_t> recs;
   recs.reserve(points.size());
-  for (const feature_point_t &cp : points) {
-    ftkx_cp_t r;
-    std::memset(&r, 0, sizeof(r));
-    for (int k = 0; k < 3; k ++) { r.x[k] = cp.x[k]; r.scalar[k] = cp.scalar[k]; }
-    r.t = cp.t; r.type = cp.type; r.tag = cp.tag;
-    reinterpret_cast<unsigned int *>(&r)[15] = ((unsigned)cp.timestep << 1) | (cp.ordinal ? 1u : 0u);
-    recs.push_back(r);
-  }
+  for (const feature_point_t &cp : points) recs.push_back(record_of(cp));
   const int rc = ftkx_online_tracer_grow(online, recs.data(), recs.size());
   if (rc != FTKX_OK) throw ftkx_error(rc, "grow: ftkx_online_tracer_grow failed (element tags needed: FTKX_TAG_EXACT64, or REFERENCE where it does not wrap)");
   points.clear(); point_keys.clear();
   discrete_critical_points.clear(); map_valid = true;
 }
 
+void critical_point_tracker_regular::clear_traced() { traced_points.clear(); traced_offsets.assign(1, 0); traced_nested_valid = false; traced_loop.clear(); traced_id.clear(); }
+
+// critical_point_tracker_{2d,3d}_regular::finalize (2d:143-225, 3d:86-117)
 void critical_point_tracker_regular::finalize()
 {
   wait_devices();
-  if (slab) {
-    // critical_point_tracker.hh:689: the ranks' discrete points gathered on the root, which traces them -- curves cross slab boundaries like
-    // any other cell boundary.  The other ranks keep their own points and end without trajectories.
-    flush_points();
-    std::vector<ftkx_cp_t> mine(points.size());
-    for (size_t i = 0; i < points.size(); i ++) {
-      const feature_point_t &cp = points[i];
-      ftkx_cp_t r;
-      std::memset(&r, 0, sizeof(r));
-      for (int k = 0; k < 3; k ++) { r.x[k] = cp.x[k]; r.scalar[k] = cp.scalar[k]; }
-      r.t = cp.t; r.type = cp.type; r.tag = cp.tag;
-      reinterpret_cast<unsigned int *>(&r)[15] = ((unsigned)cp.timestep << 1) | (cp.ordinal ? 1u : 0u);
-      mine[i] = r;
-    }
-    ftkx_cp_t *merged = nullptr;
-    size_t nm = 0;
-    const int rc = ftkx_slab_gather_records(slab, mine.data(), mine.size(), 0, &merged, &nm);
-    if (rc != FTKX_OK) throw ftkx_error(rc, ftkx_slab_last_error(slab));
-    if (slab_rank != 0) {
-      traced_points.clear(); traced_offsets.assign(1, 0); traced_nested_valid = false; traced_loop.clear(); traced_id.clear();
-      return;
-    }
-    points.clear(); point_keys.clear(); pending_points.clear(); pending_ascending = true;
-    discrete_critical_points.clear(); map_valid = false;
-    for (size_t i = 0; i < nm; i ++) take_records(merged + i, 1, ftkx_cp_timestep(merged + i));
-    ftkx_free(merged);
+  if (slab && !gather_slab_points()) { clear_traced(); return; }
+  if (enable_streaming_trajectories) finish_streaming();
+  else trace_offline();
+}
+
+// critical_point_tracker.hh:689: the ranks' discrete points gathered on the root, which traces them -- curves cross slab boundaries like
+// any other cell boundary.  The other ranks keep their own points and end without trajectories.  True on the rank that traces.
+bool critical_point_tracker_regular::gather_slab_points()
+{
+  flush_points();
+  std::vector<ftkx_cp_t> mine(points.size());
+  for (size_t i = 0; i < points.size(); i ++) mine[i] = record_of(points[i]);
+  ftkx_cp_t *merged = nullptr;
+  size_t nm = 0;
+  check_slab(slab, ftkx_slab_gather_records(slab, mine.data(), mine.size(), 0, &merged, &nm));
+  if (slab_rank != 0) return false;
+  points.clear(); point_keys.clear(); pending_points.clear(); pending_ascending = true;
+  discrete_critical_points.clear(); map_valid = false;
+  take_records_by_step(merged, nm);
+  ftkx_free(merged);
+  return true;
+}
+
+// 2d:150-151: "done" -- the trajectories are what grow() built
+void critical_point_tracker_regular::finish_streaming()
+{
+  flush_points();
+  clear_traced();
+  if (!online) return;
+  ftkx_cp_t *pts = nullptr;
+  ftkx_curves c{};
+  const int rc = ftkx_online_tracer_curves(online, &pts, &c);
+  if (rc != FTKX_OK) { ftkx_free(pts); ftkx_free_curves(&c); throw ftkx_error(rc, "finalize: ftkx_online_tracer_curves failed"); }
+  for (size_t i = 0; i < c.n_curves; i ++) {
+    for (long long k = c.offsets[i]; k < c.offsets[i + 1]; k ++) traced_points.push_back(point_of(pts[k]));
+    traced_offsets.push_back((long long)traced_points.size());
+    traced_loop.push_back(c.loop[i]);
+    traced_id.push_back((int)i);
   }
-  if (enable_streaming_trajectories) {
-    flush_points();             // 2d:150-151: "done" -- the trajectories are what grow() built
-    traced_points.clear(); traced_offsets.assign(1, 0); traced_nested_valid = false; traced_loop.clear(); traced_id.clear();
-    if (!online) return;
-    ftkx_cp_t *pts = nullptr;
-    ftkx_curves c{};
-    const int rc = ftkx_online_tracer_curves(online, &pts, &c);
-    if (rc != FTKX_OK) { ftkx_free(pts); ftkx_free_curves(&c); throw ftkx_error(rc, "finalize: ftkx_online_tracer_curves failed"); }
-    for (size_t i = 0; i < c.n_curves; i ++) {
-      for (long long k = c.offsets[i]; k < c.offsets[i + 1]; k ++) {
-        const ftkx_cp_t &r = pts[k];
-        feature_point_t cp;
-        for (int q = 0; q < 3; q ++) { cp.x[q] = r.x[q]; cp.scalar[q] = r.scalar[q]; }
-        cp.t = r.t; cp.type = r.type; cp.tag = r.tag;
-        cp.ordinal = ftkx_cp_ordinal(&r) != 0; cp.timestep = ftkx_cp_timestep(&r);
-        traced_points.push_back(cp);
-      }
-      traced_offsets.push_back((long long)traced_points.size());
-      traced_loop.push_back(c.loop[i]);
-      traced_id.push_back((int)i);
-    }
-    ftkx_free(pts); ftkx_free_curves(&c);
-    return;
-  }
+  ftkx_free(pts); ftkx_free_curves(&c);
+}
+
+// Without streaming trajectories:
+// traced_critical_points = trace_critical_points_offline(discrete_critical_points, neighbours-sharing-a-cell)
+void critical_point_tracker_regular::trace_offline()
+{
   // Nothing has to be ordered for this: ftkx_trace_curves takes the points in any order (it indexes them by tag) and returns the curves
   // in the reference's order.  Sweeps in time order with 64-bit tags deliver ascending tags: the pending points are traced as they are.
-  constexpr bool timing = false;      // (phase timing to stderr: a debugging aid, compiled out)
-  typedef std::chrono::steady_clock clk;
-  const clk::time_point tq0 = clk::now();
   if (!(points.empty() && pending_ascending)) flush_points();
-  const clk::time_point tq1 = clk::now();
   const std::vector<feature_point_t> &src = points.empty() ? pending_points : points;
   // (the flat store is in the reference's element order; the trace's device phases want ascending tags: an index sorted on a few
   // threads, and the curves' indices mapped back through it)
@@ -726,13 +760,11 @@ void critical_point_tracker_regular::finalize()
   }
   std::vector<unsigned long long> tags(src.size());           // (the trace reads nothing but the tags)
   for (size_t i = 0; i < src.size(); i ++) tags[i] = by_tag.empty() ? src[i].tag : by_tag[i].first;
-  long long dst[3] = {0, 0, 0}, dsz[3] = {1, 1, 1};
-  for (int d = 0; d < nd; d ++) { dst[d] = domain.start(d); dsz[d] = domain.size(d); }
+  long long dst[3], dsz[3];
+  domain_arrays(dst, dsz);
   ftkx_curves c{};
-  const clk::time_point tq2 = clk::now();
   // (neighbour search and component labelling on the tracker's GPU where the record set is large enough to pay for the round trip)
   const int rc = ftkx_trace_curves_tags_ctx(ctx, nd, dst, dsz, tags.data(), tags.size(), &c);
-  const clk::time_point tq3 = clk::now();
   if (rc != FTKX_OK) { ftkx_free_curves(&c); throw ftkx_error(rc, "finalize: ftkx_trace_curves failed (tags must not have overflowed int32: use FTKX_TAG_EXACT64 on very large meshes)"); }
   // the curves stay flat -- the points of all curves one after the other; one vector per curve is built only if somebody asks for it
   traced_points.resize(c.n_points); traced_offsets.assign(c.offsets, c.offsets + c.n_curves + 1);
@@ -743,30 +775,9 @@ void critical_point_tracker_regular::finalize()
   for (size_t i = 0; i < c.n_curves; i ++) traced_id[i] = (int)i;
   traced_nested_valid = false;
   ftkx_free_curves(&c);
-  if (timing) {
-    auto us = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
-    fprintf(stderr, "tracker finalize: flush %.0f us, tag index + records %.0f us, trace %.0f us, curves -> points %.0f us\n", us(tq0, tq1), us(tq1, tq2), us(tq2, tq3), us(tq3, clk::now()));
-  }
 }
 
 namespace {
-ftkx_cp_t record_of(const feature_point_t &cp)
-{
-  ftkx_cp_t r;
-  std::memset(&r, 0, sizeof(r));
-  for (int k = 0; k < 3; k ++) { r.x[k] = cp.x[k]; r.scalar[k] = cp.scalar[k]; }
-  r.t = cp.t; r.type = cp.type; r.tag = cp.tag;
-  reinterpret_cast<unsigned int *>(&r)[15] = ((unsigned)cp.timestep << 1) | (cp.ordinal ? 1u : 0u);
-  return r;
-}
-feature_point_t point_of(const ftkx_cp_t &r)
-{
-  feature_point_t cp;
-  for (int k = 0; k < 3; k ++) { cp.x[k] = r.x[k]; cp.scalar[k] = r.scalar[k]; }
-  cp.t = r.t; cp.type = r.type; cp.tag = r.tag;
-  cp.ordinal = ftkx_cp_ordinal(&r) != 0; cp.timestep = ftkx_cp_timestep(&r);
-  return cp;
-}
 struct flat_curves {   // traced curves as one record array (points in curve order) + the identity as index list
   std::vector<ftkx_cp_t> recs;
   std::vector<long long> indices;
@@ -775,14 +786,7 @@ struct flat_curves {   // traced curves as one record array (points in curve ord
     ftkx::for_ranges_on_threads(pts.size(), [&](size_t b, size_t e) { for (size_t i = b; i < e; i ++) { recs[i] = record_of(pts[i]); indices[i] = (long long)i; } });
   }
 };
-std::string io_error()
-{
-  char msg[512] = {0};
-  ftkx_last_error(nullptr, msg, sizeof msg);
-  return msg;
-}
 }  // namespace
-
 // json_interface::post_process (filters/json_interface.hh:758-800) with the options it defaults to
 void critical_point_tracker_regular::post_process()
 {
@@ -828,8 +832,7 @@ void critical_point_tracker_regular::write_discrete(const std::string &filename,
   recs.reserve(points.size());
   for (const feature_point_t &cp : points) recs.push_back(record_of(cp));
   // text labels: the reference's scalar_components default to {"scalar"} whether or not a scalar field exists
-  const int rc = ftkx_write_critical_points(filename.c_str(), format, recs.data(), recs.size(), nullptr, nullptr, nullptr, -1);
-  if (rc != FTKX_OK) throw ftkx_error(rc, io_error());
+  check_on(nullptr, ftkx_write_critical_points(filename.c_str(), format, recs.data(), recs.size(), nullptr, nullptr, nullptr, -1));     // (the i/o calls leave their message with the calling thread)
 }
 void critical_point_tracker_regular::write_critical_points_json(const std::string &f) const { write_discrete(f, FTKX_FORMAT_JSON); }
 void critical_point_tracker_regular::write_critical_points_binary(const std::string &f) const { write_discrete(f, FTKX_FORMAT_BINARY); }
@@ -848,8 +851,7 @@ void critical_point_tracker_regular::read_discrete(const std::string &filename, 
 {
   ftkx_cp_t *recs = nullptr;
   size_t n = 0;
-  const int rc = ftkx_read_critical_points(filename.c_str(), format, &recs, &n, nullptr, nullptr);
-  if (rc != FTKX_OK) throw ftkx_error(rc, io_error());
+  check_on(nullptr, ftkx_read_critical_points(filename.c_str(), format, &recs, &n, nullptr, nullptr));     // (the i/o calls leave their message with the calling thread)
   std::vector<feature_point_t> cps;
   cps.reserve(n);
   for (size_t i = 0; i < n; i ++) cps.push_back(point_of(recs[i]));
@@ -872,8 +874,7 @@ void critical_point_tracker_regular::write_traced(const std::string &filename, i
   std::memset(&tr, 0, sizeof(tr));
   tr.n_curves = num_traced_curves(); tr.n_points = f.recs.size();
   tr.offsets = offsets.data(); tr.indices = f.indices.data(); tr.loop = loop.data(); tr.type = type.data(); tr.t = t.data(); tr.id = ids.data();
-  const int rc = ftkx_write_traced_critical_points(filename.c_str(), format, f.recs.data(), f.recs.size(), &tr, nullptr, -1);
-  if (rc != FTKX_OK) throw ftkx_error(rc, io_error());
+  check_on(nullptr, ftkx_write_traced_critical_points(filename.c_str(), format, f.recs.data(), f.recs.size(), &tr, nullptr, -1));     // (the i/o calls leave their message with the calling thread)
 }
 void critical_point_tracker_regular::write_traced_critical_points_json(const std::string &f) const { write_traced(f, FTKX_FORMAT_JSON); }
 void critical_point_tracker_regular::write_traced_critical_points_binary(const std::string &f) const { write_traced(f, FTKX_FORMAT_BINARY); }
@@ -891,19 +892,29 @@ std::vector<feature_point_t> critical_point_tracker_regular::get_critical_points
 struct ftkx_tracker {
   ftkx::critical_point_tracker_regular *t = nullptr;
   int nd = 0;
-  std::string err;
+  mutable std::string err;     // (the last error is the handle's own note: a failing getter of a const handle leaves it too)
 };
 
 namespace {
 thread_local std::string g_tracker_error;
 
 template <class F>
-int guarded(ftkx_tracker *h, F f)
+int guarded(const ftkx_tracker *h, F f)
 {
   if (!h || !h->t) { g_tracker_error = "null tracker"; return FTKX_E_INVALID; }
   try { f(); return FTKX_OK; }
   catch (const ftkx::ftkx_error &e) { h->err = e.what(); g_tracker_error = e.what(); return e.code; }
   catch (const std::exception &e) { h->err = e.what(); g_tracker_error = e.what(); return FTKX_E_INVALID; }
+}
+
+// a handle around the tracker that `make` constructs; a constructor's error is the calling thread's
+template <class Make>
+int create_handle(ftkx_tracker **out, int nd, Make make)
+{
+  std::unique_ptr<ftkx_tracker> h(new ftkx_tracker());
+  try { h->nd = nd; h->t = make(); *out = h.release(); return FTKX_OK; }
+  catch (const ftkx::ftkx_error &e) { g_tracker_error = e.what(); return e.code; }
+  catch (const std::exception &e) { g_tracker_error = e.what(); return FTKX_E_INVALID; }
 }
 }  // namespace
 
@@ -912,27 +923,13 @@ extern "C" {
 int ftkx_tracker_create(ftkx_tracker **out, int nd, int device_id)
 {
   if (!out || (nd != 2 && nd != 3)) { g_tracker_error = "ftkx_tracker_create: nd must be 2 or 3"; return FTKX_E_INVALID; }
-  ftkx_tracker *h = new ftkx_tracker();
-  try {
-    h->nd = nd;
-    h->t = new ftkx::critical_point_tracker_regular(nd, device_id);
-    *out = h;
-    return FTKX_OK;
-  } catch (const ftkx::ftkx_error &e) { delete h; g_tracker_error = e.what(); return e.code; }
-  catch (const std::exception &e) { delete h; g_tracker_error = e.what(); return FTKX_E_INVALID; }
+  return create_handle(out, nd, [&] { return new ftkx::critical_point_tracker_regular(nd, device_id); });
 }
 
 int ftkx_tracker_create_multi(ftkx_tracker **out, int nd, const int *device_ids, int ndev, int block)
 {
   if (!out || (nd != 2 && nd != 3) || !device_ids || ndev < 1) { g_tracker_error = "ftkx_tracker_create_multi: bad arguments"; return FTKX_E_INVALID; }
-  ftkx_tracker *h = new ftkx_tracker();
-  try {
-    h->nd = nd;
-    h->t = new ftkx::critical_point_tracker_regular(nd, std::vector<int>(device_ids, device_ids + ndev), block);
-    *out = h;
-    return FTKX_OK;
-  } catch (const ftkx::ftkx_error &e) { delete h; g_tracker_error = e.what(); return e.code; }
-  catch (const std::exception &e) { delete h; g_tracker_error = e.what(); return FTKX_E_INVALID; }
+  return create_handle(out, nd, [&] { return new ftkx::critical_point_tracker_regular(nd, std::vector<int>(device_ids, device_ids + ndev), block); });
 }
 
 int ftkx_tracker_sync(ftkx_tracker *h) { return guarded(h, [&] { h->t->sync(); }); }
@@ -994,7 +991,7 @@ int ftkx_tracker_update_timestep(ftkx_tracker *h) { return guarded(h, [&] { h->t
 int ftkx_tracker_num_critical_points(const ftkx_tracker *h, size_t *n)
 {
   if (!n) return FTKX_E_INVALID;
-  return guarded(const_cast<ftkx_tracker *>(h), [&] { *n = h->t->num_discrete_critical_points(); });
+  return guarded(h, [&] { *n = h->t->num_discrete_critical_points(); });
 }
 
 int ftkx_tracker_get_critical_points(const ftkx_tracker *h, ftkx_cp_t *out, int *ordinal, int *timestep, size_t cap)
@@ -1002,7 +999,7 @@ int ftkx_tracker_get_critical_points(const ftkx_tracker *h, ftkx_cp_t *out, int 
   if (!h || !h->t || !out) return FTKX_E_INVALID;
   size_t i = 0;
   std::vector<ftkx::feature_point_t> pts;
-  const int rc = guarded(const_cast<ftkx_tracker *>(h), [&] { pts = h->t->get_critical_points(); });
+  const int rc = guarded(h, [&] { pts = h->t->get_critical_points(); });
   if (rc) return rc;
   for (const ftkx::feature_point_t &cp : pts) {
     if (i >= cap) break;
@@ -1019,7 +1016,7 @@ int ftkx_tracker_get_critical_points(const ftkx_tracker *h, ftkx_cp_t *out, int 
 int ftkx_tracker_get_scaling(const ftkx_tracker *h, unsigned long long *factor, double *resolution)
 {
   // (a getter waits for what is still out -- a several-device tracker's queues, a slab's pass: whatever that raises is the call's error)
-  return guarded(const_cast<ftkx_tracker *>(h), [&] {
+  return guarded(h, [&] {
     if (factor) *factor = h->t->get_vector_field_scaling_factor();
     if (resolution) *resolution = h->t->get_vector_field_resolution();
   });
@@ -1060,7 +1057,7 @@ int ftkx_tracker_get_curve_points(const ftkx_tracker *h, unsigned int *type, dou
 int ftkx_tracker_write(const ftkx_tracker *h, const char *path, int format, int traced)
 {
   if (!path) return FTKX_E_INVALID;
-  return guarded(const_cast<ftkx_tracker *>(h), [&] {
+  return guarded(h, [&] {
     const std::string f(path);
     const ftkx::critical_point_tracker_regular &t = *h->t;
     if (format == FTKX_FORMAT_JSON) { if (traced) t.write_traced_critical_points_json(f); else t.write_critical_points_json(f); }
@@ -1083,7 +1080,7 @@ int ftkx_tracker_read_critical_points(ftkx_tracker *h, const char *path, int for
 int ftkx_tracker_get_stats(const ftkx_tracker *h, ftkx_stats *st)
 {
   if (!st) return FTKX_E_INVALID;
-  return guarded(const_cast<ftkx_tracker *>(h), [&] { *st = h->t->get_last_stats(); });
+  return guarded(h, [&] { *st = h->t->get_last_stats(); });
 }
 
 }  // extern "C"

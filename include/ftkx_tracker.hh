@@ -214,23 +214,17 @@ public:
   ftkx_ctx *context() { return ctx; }
 
 protected:
-  void update_vector_field_scaling_factor(int minbits = 8, int maxbits = 21);   // critical_point_tracker.hh:850-864
-  void check(int rc) const;
+  static constexpr int default_minbits = 8, default_maxbits = 21;             // the reference's bounds of the factor's bit count
+  void update_vector_field_scaling_factor(int minbits = default_minbits, int maxbits = default_maxbits);   // critical_point_tracker.hh:850-864
+  void check(int rc) const;                                 // a failed call on `ctx` -> ftkx_error with the context's message
 
   int nd;
   ftkx_ctx *ctx = nullptr;
-  lattice domain, array_domain, local_domain, local_array_domain;
+  lattice domain, array_domain;
+  void domain_arrays(long long dst[3], long long dsz[3]) const;             // `domain` as the C ABI takes it (unused axes: start 0, size 1)
   int scalar_field_source = SOURCE_NONE, vector_field_source = SOURCE_NONE, jacobian_field_source = SOURCE_NONE;
   bool is_jacobian_field_symmetric = false;
   bool enable_robust_detection = true, enable_computing_degrees = false, enable_streaming_trajectories = false;
-  bool deferred_collection = false;
-  mutable std::vector<int> open_steps;                      // deferred collection: the timesteps of the sweeps that are queued and not yet collected (at most three)
-  void collect_open_step() const;
-  int deferred_depth = 1;
-  mutable std::vector<int> batch_ts, batch_scopes, batch_drops;    // deferred collection in batches: the steps recorded and not yet queued; the snapshots popped meanwhile
-  void submit_batch() const;
-  ftkx_online_tracer *online = nullptr;
-  void grow();                                                 // 2d:288-322: trace_critical_points_online on the points found since the last call
   bool use_type_filter = false;
   unsigned int type_filter = 0;
   bool exact_only = false;
@@ -242,13 +236,54 @@ protected:
   int explicit_ncomp = 0;
   size_t explicit_n0 = 0, explicit_n1 = 0;
   bool initialized = false;
+  void apply_configuration(ftkx_ctx *c);                      // mesh, options, coordinates of initialize() on one context
 
   int current_timestep = 0;
-  int result_timestep = -1;                                 // multi-device: the timestep last_stats / the scaling factor belong to
   std::vector<int> field_data_snapshots;                    // timesteps resident on the device (<= 2, a deque in the reference)
   int next_push_timestep = 0;
+  void push_snapshot(int kind, const double *s, const double *v, const double *j, bool device);   // behind the three push_* methods: one snapshot -> the context(s) that read it
   double vector_field_resolution = std::numeric_limits<double>::max();   // sticky running minimum (never reset)
   unsigned long long vector_field_scaling_factor = 1;
+  ftkx_stats last_stats;
+
+  // update_timestep() is one of these.  Whatever a mode leaves out -- a recorded slab, queued devices, deferred sweeps -- wait_devices() brings in.
+  void step_slab();                                         // slab mode: the step is recorded
+  void step_deferred(int scope);                            // deferred collection: queued (alone or with its batch), an earlier step collected
+  void step_now(int scope);                                 // one device: swept and collected in this call
+  void step_multi(int scope);                               // several devices: queued on the device that owns the timestep
+  void wait_devices();
+  // the queued snapshots are this step's and nothing else: the device-driven pass (ftkx_sweep_series) takes the step
+  bool window_is_the_step() const { return field_data_snapshots.size() <= 2 && field_data_snapshots.front() == current_timestep; }
+  void take_records(const ftkx_cp_t *recs, size_t n, int timestep);
+  void take_records_by_step(const ftkx_cp_t *recs, size_t n);               // records of several steps, each under the timestep it carries
+
+  // deferred collection
+  bool deferred_collection = false;
+  int deferred_depth = 1;
+  std::vector<int> open_steps;                              // the timesteps of the sweeps that are queued and not yet collected (at most three; -1: a batch)
+  std::vector<int> batch_ts, batch_scopes, batch_drops;     // in batches: the steps recorded and not yet queued; the snapshots popped meanwhile
+  void collect_open_step();
+  void submit_batch();
+  void collect_deferred();                                  // a partial batch submitted, everything collected
+
+  // streaming trajectories
+  ftkx_online_tracer *online = nullptr;
+  void grow();                                                 // 2d:288-322: trace_critical_points_online on the points found since the last call
+
+  // slab mode (set_communicator / set_slab_transport / set_slab_hub): the C++ host of this rank's slab, the steps recorded so far
+  ftkx_slab *slab = nullptr;
+  int slab_rank = 0, slab_t0 = 0, slab_t1 = 0;
+  std::vector<int> slab_steps;
+  bool slab_swept = false;
+  void enter_slab_mode(int rank, int nranks, int nt);
+  void restart_slab();
+  void run_slab();
+
+  // several devices
+  struct multi_engine;                                        // per-device contexts + worker threads (tracker.cpp); null with one device
+  std::unique_ptr<multi_engine> multi;
+  int result_timestep = -1;                                 // the timestep last_stats / the scaling factor belong to
+
   // The discrete points (the reference keeps a std::map<element_t, feature_point_t>): a flat array in the reference's element order with
   // unique tags (`points`, its order keys beside it), what the sweeps have delivered since it was last brought up to date
   // (`pending_points`: a streaming run delivers ~10^3 points per step), and -- only when somebody asks for it -- the std::map view.
@@ -261,27 +296,19 @@ protected:
   mutable discrete_map_t discrete_critical_points;
   mutable bool map_valid = true;
   element_order order_;
-  void wait_devices() const;
   void flush_points() const;
+
+  // finalize(): one of three, after wait_devices()
+  bool gather_slab_points();                                // slab mode: every rank's points -> rank 0; true on the rank that goes on to trace
+  void finish_streaming();                                  // streaming trajectories: what grow() built
+  void trace_offline();                                     // trace_critical_points_offline on the discrete points
+  void clear_traced();
   std::vector<feature_point_t> traced_points;
   std::vector<long long> traced_offsets = std::vector<long long>(1, 0);
   mutable std::vector<std::vector<feature_point_t>> traced_critical_points;
   mutable bool traced_nested_valid = true;
   std::vector<int> traced_loop, traced_id;
-  ftkx_stats last_stats;
 
-  // slab mode (set_communicator / set_slab_transport / set_slab_hub): the C++ host of this rank's slab, the steps recorded so far
-  ftkx_slab *slab = nullptr;
-  int slab_nt = 0, slab_rank = 0, slab_nranks = 1, slab_t0 = 0, slab_t1 = 0;
-  mutable std::vector<int> slab_steps;
-  mutable bool slab_swept = false;
-  void enter_slab_mode(int rank, int nranks, int nt);
-  void run_slab() const;
-  struct multi_engine;                                        // per-device contexts + worker threads (tracker.cpp); null with one device
-  std::unique_ptr<multi_engine> multi;
-  void apply_configuration(ftkx_ctx *c);                      // mesh, options, coordinates of initialize() on one context
-  void take_records(const ftkx_cp_t *recs, size_t n, int timestep);
-  void push_everywhere(int kind, int t, const double *s, const double *v, const double *j, bool device);   // one snapshot -> the context(s) that read it
   void write_discrete(const std::string &filename, int format) const;
   void read_discrete(const std::string &filename, int format);
   void write_traced(const std::string &filename, int format) const;

@@ -37,6 +37,73 @@ def test_tracker_matches_reference_fixture(gpu, name, exact_only):
         assert all(s["cull_enabled"] == 0 for s in stats)
 
 
+@pytest.fixture(scope="module")
+def reset_run(gpu, tmp_path_factory):
+    """tests/tracker/reset_run.cpp: the C++ tracker driven twice with a reset() in between (reset() has no C handle)"""
+    import os
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lib_dir = os.path.join(root, "ftk_amd")
+    exe = tmp_path_factory.mktemp("reset_run") / "reset_run"
+    r = subprocess.run(["g++", "-std=c++17", "-O1", "-I" + os.path.join(root, "include"), os.path.join(root, "tests", "tracker", "reset_run.cpp"), "-o", str(exe),
+                        "-L" + lib_dir, "-lftkx", "-Wl,-rpath," + lib_dir, "-Wl,-rpath-link,/opt/rocm/lib", "-lpthread"], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    return str(exe)
+
+
+# the smallest 2D and the smallest 3D record fixture of test_tracker_matches_reference_fixture (1 326 and 2 187 values, 6 and 3 timesteps)
+@pytest.mark.parametrize("mode", ["plain", "deferred3", "multi"])
+@pytest.mark.parametrize("name", ["adversarial_2d_scalar_17x13x6", "adversarial_3d_scalar_9x9x9x3_b"])
+def test_tracker_runs_again_after_reset(gpu, reset_run, tmp_path, name, mode):
+    """run a series, reset(), run it again: both runs hold the reference's records bit for bit -- on a plain tracker, with
+    set_deferred_collection(true, 3), and on the multi-device tracker (2 devices, block 1).  The running resolution is sticky across reset()
+    by design, so the second run is held to the fixture, not to a fresh tracker; only the first run's factor is the reference's for certain."""
+    import subprocess
+    g = load_golden(name)
+    assert g["robust"] and not g["type_filter"] and not g["degrees"] and g["bounds"] is None and g["rectilinear"] is None and g["explicit"] is None and not g["t0"]
+    D = g["dims"] + [1] * (3 - g["nd"])
+    inp, out = tmp_path / "in.bin", tmp_path / "out.bin"
+    with open(inp, "wb") as f:
+        f.write(np.array([g["nd"], g["nv"], D[0], D[1], D[2], g["DT"]], dtype=np.int32).tobytes())
+        for a in g["steps"]:
+            f.write(np.ascontiguousarray(a, dtype=np.float64).tobytes())
+    r = subprocess.run([reset_run, str(inp), str(out), mode], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    raw, at = open(out, "rb").read(), 0
+    for run in (0, 1):
+        factor, n = (int(v) for v in np.frombuffer(raw, dtype=np.uint64, count=2, offset=at))
+        recs = np.frombuffer(raw, dtype=gpu.CP_DTYPE, count=n, offset=at + 16)
+        at += 16 + 72 * n
+        got = np.zeros(n, dtype=[("tag", "<u8"), ("type", "<u4"), ("ordinal", "<i4"), ("timestep", "<i4"), ("x", "<f8", (3,)), ("t", "<f8"), ("scalar", "<f8", (3,))])
+        for fld in ("tag", "type", "x", "t", "scalar"):
+            got[fld] = recs[fld]
+        got["ordinal"] = recs["aux"] & 1; got["timestep"] = recs["aux"] >> 1
+        print(f"{name} {mode} run {run}: {n} records, last factor {factor} (reference {int(g['factors'][-1])})")
+        if run == 0:
+            assert factor == int(g["factors"][-1])
+        assert_records_equal(got, g["records"], coord_tol=0.0, what=f"{name} {mode}, run {run} (bit-exact)")
+    assert at == len(raw)
+
+
+def test_push_outside_the_slab_is_refused(gpu):
+    """slab mode: a snapshot whose timestep is not in this rank's slab is refused on the host, before anything is uploaded or launched"""
+    from ftk_amd import _lib
+    L = _lib.load()
+    hub = L.ftkx_slab_hub_create(2)
+    tr = gpu.CriticalPointTracker2DRegular()
+    tr.set_scalar_field_source(gpu.SOURCE_GIVEN); tr.set_vector_field_source(gpu.SOURCE_DERIVED)
+    tr.set_jacobian_field_source(gpu.SOURCE_DERIVED); tr.set_jacobian_symmetric(True)
+    tr.set_domain([2, 2], [14, 10]); tr.set_array_domain([0, 0], [17, 13])
+    tr.initialize()
+    tr.set_slab_hub(hub, 0, 4)              # rank 0 of 2 over 4 timesteps: the slab [0, 2)
+    tr.set_current_timestep(3)
+    with pytest.raises(_lib.FtkxError) as e:
+        tr.push_scalar_field_snapshot(np.zeros((13, 17)))
+    assert e.value.code == _lib.E_INVALID and "slab mode: timestep 3 is not in this rank's slab [0, 2)" in str(e.value)
+    tr.close()
+    L.ftkx_slab_hub_destroy(hub)
+
+
 @pytest.mark.parametrize("exact_only", [False, True], ids=["cull", "exact_only"])
 @pytest.mark.parametrize("name", wrap_golden_names())
 def test_reference_tags_and_vertex_ids_where_int32_wraps(gpu, name, exact_only):
