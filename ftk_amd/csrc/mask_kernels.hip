@@ -1021,10 +1021,9 @@ __device__ __forceinline__ void march6_body(const Mesh &m, const MaskJob *__rest
   const int DW = m.ext_sz[0], DH = m.ext_sz[1], DD = m.ext_sz[2], P = m.mask_pitch;
   unsigned bx, by, bz;
   remap_block(swizzle, bx, by, bz);
-  // (njobs < 0: slice-major -- blockIdx.z = slice * npieces + piece, the pieces of a slice back to back)
-  const unsigned nj = (unsigned)(njobs < 0 ? -njobs : njobs);
-  const unsigned piece = njobs < 0 ? bz % plan.npieces : bz / nj;
-  const MaskJob job = jobs[njobs < 0 ? bz / plan.npieces : bz - piece * nj];
+  const ZWhere at = zplan_decode(plan, njobs, bz);      // (the three orders of the workgroups: mask_plan.hpp)
+  const unsigned piece = at.piece;
+  const MaskJob job = jobs[at.job];
   const int z0 = (int)plan.z0[piece];
   const int z1 = z0 + (int)plan.len[piece];
   const int lane = threadIdx.x & 63;

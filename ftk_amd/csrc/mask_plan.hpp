@@ -10,25 +10,59 @@
 
 namespace ftkx {
 
-// The z extent of a slice in PIECES of unequal length, the same for every tile column: blockIdx.z = piece * njobs + slice, pieces in
-// order of decreasing length.  The hardware hands workgroups out in order of their index as slots free up -- a queue --, so the long
-// pieces (up to half a column) go out first and the launch ends on pieces of a few planes: the device stays full until a few
-// microseconds before the end whatever the size of the series (equal chunks of 32 planes: 256^3 x 16 is 5.3 rounds of workgroups, a
-// 512^3 slice on its own 2.7), and the two start-up planes of a march are paid per piece -- 7 pieces per 512 planes on 512^3 x 32
-// instead of 16 chunks.  (Persistent workgroups pulling such pieces from a queue of their own were built and measured: the loop state
-// costs the kernel 36 more SGPR spills and 12 VGPRs of scratch at three wavefronts per SIMD -- 7.6 ms against 5.7 on 512^3 x 32.)
-// Equal chunks (launches of a dozen rounds and more) go out slice by slice instead: neighbouring chunks of a slice then run at the same
-// time and find each other's start-up planes in the caches.
+// The z extent of a slice in PIECES of unequal length, the same for every tile column, pieces in order of decreasing length.  The
+// hardware hands workgroups out in order of their index as slots free up -- a queue --, so the long pieces (up to half a column) go out
+// first and the launch ends on pieces of a few planes: the device stays full until a few microseconds before the end whatever the size
+// of the series (equal chunks of 32 planes: 256^3 x 16 is 5.3 rounds of workgroups, a 512^3 slice on its own 2.7).  (Persistent
+// workgroups pulling such pieces from a queue of their own were built and measured: the loop state costs the kernel 36 more SGPR spills
+// and 12 VGPRs of scratch at three wavefronts per SIMD -- 7.6 ms against 5.7 on 512^3 x 32.)
+// Every piece starts by fetching two planes that its predecessor in z fetches as well (its last plane and that plane's halo): 46 of 512
+// planes on a 512^3 slice.  Whether the second fetch is served by a cache is a matter of WHERE and WHEN the two pieces run, that is of
+// the order in which blockIdx.z enumerates (slice, piece) -- zplan_decode below, three orders:
+//   piece by piece over all slices (njobs > 0): bz = piece * njobs + slice.  A column's next piece follows one round of njobs x columns
+//     workgroups behind; where that round is a whole number of rounds of 8 placement groups (remap_block), on the same XCD;
+//   slice by slice (njobs < 0, sgroup == 0): bz = slice * npieces + piece, the pieces of a slice back to back: neighbouring pieces of
+//     a slice run at the same time;
+//   slices in groups of about `sgroup`, piece by piece inside a group (njobs < 0, sgroup >= 1): bz enumerates (group, piece, slice
+//     in the group), the slice fastest.  A column's next piece follows its predecessor by one round of (slices of the group) x columns
+//     workgroups.  Groups are as even as possible (32 slices at a cap of 6: 6, 6, 5, 5, 5, 5 -- a short last group would put its
+//     columns' pieces several rounds apart).  sgroup == 1 is slice by slice, sgroup >= |njobs| piece by piece.
+// What was measured, and which order a launch gets: plan_masks, "Order of the workgroups".
 struct ZPlan {
   unsigned npieces;
   unsigned z0[47], len[47];
+  unsigned sgroup;      // slices per group of the third order; 0: one of the first two
 };
+
+#if defined(__HIPCC__)
+#define FTKX_PLAN_HD __host__ __device__
+#else
+#define FTKX_PLAN_HD
+#endif
+
+// blockIdx.z (after remap_block) -> the job and the piece of a tile column, for all three orders: the one place that knows them (the
+// kernel and tests/test_mask_order.py both call it).  njobs as MaskPlan::njobs carries it: negative unless piece by piece over all slices.
+struct ZWhere { unsigned job, piece; };
+FTKX_PLAN_HD inline ZWhere zplan_decode(const ZPlan &plan, int njobs, unsigned bz)
+{
+  ZWhere w;
+  if (njobs >= 0) { w.piece = bz / (unsigned)njobs; w.job = bz - w.piece * (unsigned)njobs; return w; }
+  const unsigned nj = (unsigned)-njobs, t = bz / plan.npieces;       // t: whole slices' worth of workgroups in front of this one
+  if (plan.sgroup == 0) { w.piece = bz - t * plan.npieces; w.job = t; return w; }
+  // ngroups groups, the first `extra` of them of small + 1 slices, the others of small
+  const unsigned ngroups = (nj + plan.sgroup - 1) / plan.sgroup, small = nj / ngroups, extra = nj - small * ngroups, head = extra * (small + 1);
+  const unsigned size = t < head ? small + 1 : small;
+  const unsigned first = t < head ? t / size * size : head + (t - head) / size * size;      // the group's first slice
+  const unsigned r = bz - first * plan.npieces;
+  w.piece = r / size; w.job = first + (r - w.piece * size);
+  return w;
+}
 
 // The test hooks of the mask kernels, parsed once per plan -- still at every use: tests switch them inside one process.
 // FTKX_MASK_PLAN="name=value,...": launch geometry; FTKX_U_ROWS: rows per summary byte (1 / 4 / 16; -1: no summaries, the one-level cull).
 constexpr long kHookUnset = -0x7fffffffL;
 struct MaskHooks {
-  long swizzle = kHookUnset, yg = kHookUnset, zchunk = kHookUnset, lmin = kHookUnset, lcap = kHookUnset, order = kHookUnset, rows = kHookUnset, lean = kHookUnset;
+  long swizzle = kHookUnset, yg = kHookUnset, zchunk = kHookUnset, lmin = kHookUnset, lcap = kHookUnset, order = kHookUnset, sgroup = kHookUnset, rows = kHookUnset, lean = kHookUnset;
   long u_rows = 0;                    // (0: unset)
 };
 inline long hook_or(long v, long dflt) { return v == kHookUnset ? dflt : v; }
@@ -37,7 +71,7 @@ inline MaskHooks parse_mask_hooks(const char *plan, const char *u_rows)
 {
   MaskHooks h;
   const struct { const char *name; long MaskHooks::*knob; } knobs[] = {{"swizzle", &MaskHooks::swizzle}, {"yg", &MaskHooks::yg}, {"zchunk", &MaskHooks::zchunk},
-    {"lmin", &MaskHooks::lmin}, {"lcap", &MaskHooks::lcap}, {"order", &MaskHooks::order}, {"rows", &MaskHooks::rows}, {"lean", &MaskHooks::lean}};
+    {"lmin", &MaskHooks::lmin}, {"lcap", &MaskHooks::lcap}, {"order", &MaskHooks::order}, {"sgroup", &MaskHooks::sgroup}, {"rows", &MaskHooks::rows}, {"lean", &MaskHooks::lean}};
   for (const char *p = plan ? plan : ""; *p;) {
     while (*p == ',' || *p == ' ') p ++;
     for (const auto &k : knobs) {
@@ -68,7 +102,7 @@ struct MaskPlan {
   int u_rows;                 // rows a summary byte stands for (Mesh::u_rows)
   unsigned grid[3], block, lds_bytes;
   // kernel arguments (0 where the family's kernel takes no such argument): the packed placement word (remap_block), planes per chunk (mask_march4_kernel),
-  // groups of 8 rows a wavefront marches (mask_rows2_kernel), the job count -- negative: slice-major (mask_march6_kernel) --, the pieces of a column
+  // groups of 8 rows a wavefront marches (mask_rows2_kernel), the job count -- negative: slice by slice, or in groups of z.sgroup slices (mask_march6_kernel) --, the pieces of a column
   int swizzle, zchunk, groups, njobs;
   ZPlan z;
 };
@@ -121,10 +155,19 @@ inline MaskPlan plan_masks(const MaskShape &s, const MaskHooks &h, int njobs, bo
       // 0.756 -> 0.748, 512^3 x 32 5.72 -> 5.69.  LONGER marches are slower although they pay fewer start-up planes (caps of 28 / 32 / 48:
       // +9 / +5 / +1..2 % on 512^3 x 32; half columns +3.7 %: the tiles of a group drift apart and stop sharing their halo rows in the L2),
       // equal chunks swing by +-3 % with their length (24: 5.89, 27: 5.68, 30: 5.98, 32: 5.72, 33: 5.84 ms -- what is left over at a
-      // column's top decides).  Order of the workgroups: slice by slice where a slice alone fills the device (neighbouring pieces of a
-      // slice then run together and find each other's start-up planes in the caches: 512^3 x 32 5.59 against 5.85 ms piece by piece),
-      // piece by piece over all slices otherwise (256^3 x 16: 0.379 against 0.399).
-      // FTKX_MASK_PLAN (test hooks): zchunk=n: equal chunks of n planes; lcap / lmin: the two bounds; order=0 / 1
+      // column's top decides).
+      // Order of the workgroups (ZPlan).  Where a slice alone does not fill the device: piece by piece over all slices (256^3 x 16: 0.374
+      // against 0.388 ms slice by slice; a round is 512 workgroups = 8 placement groups, a column's next piece runs one round behind
+      // its predecessor on the same XCD and finds the two start-up planes in that L2: 1.062 x the algorithmic bytes at the fabric).
+      // Where a slice alone fills the device (768 workgroups, three per CU): piece by piece over all 32 slices of 512^3 x 32 is a round of
+      // 4 096 workgroups -- 1.5 GB between a plane's two fetches, 5.75 ms --, slice by slice six neighbouring pieces start together and
+      // the later one of a pair wants the planes ~45 us before the earlier one fetches them (5.45 ms, 1.119 x).  In between: slices in
+      // groups of S, piece by piece inside a group.  Interleaved in one process, 15 rounds, 512^3 x 32 (tools/ab_mask.py; slice by slice
+      // twice: 5.449 / 5.443): S = 2 5.403, S = 4 5.309, S = 6 5.352, S = 8 5.361 ms.  S = 4 is the 256^3 x 16 geometry -- 512 workgroups a
+      // round, a whole number of rounds of 8 placement groups, the device's 768 not exceeded -- and that is the rule below; four 512^3
+      // slices (one group: piece by piece) 0.704 against 0.709 / 0.703, inside that run's noise.  One slice per launch stays as it was.
+      // FTKX_MASK_PLAN (test hooks): zchunk=n: equal chunks of n planes; lcap / lmin: the two bounds; order=0: slice by slice, order=1: piece
+      // by piece over all slices, order=2: groups of slices at any shape; sgroup=n: the slices of a group, clamped to [1, njobs]
       int lmin = 6, lcap = 24;
       if (hook_or(h.lmin, 0) >= 1) lmin = (int)h.lmin;
       if (hook_or(h.lcap, 0) >= 1) lcap = (int)h.lcap;
@@ -154,8 +197,20 @@ inline MaskPlan plan_masks(const MaskShape &s, const MaskHooks &h, int njobs, bo
       if (swizzle & 8) { int yg = yg_want; if (yg > (int)p.grid[1]) yg = (int)p.grid[1]; p.grid[1] = (p.grid[1] + (unsigned)yg - 1) / (unsigned)yg * (unsigned)yg; p.swizzle = grouped(swizzle, yg); }
       p.lds_bytes = (unsigned)NS6 * (unsigned)(rows + 2) * 1024u + (unsigned)(NS6 + 1) * 256u + 128u;   // row slots, edge ring, the summaries' exchange
       bool slice_major = (size_t)p.grid[0] * ((DH + rows - 1) / rows) * p.z.npieces >= 768;      // a slice alone fills the device (three workgroups per CU)
-      if (h.order != kHookUnset) slice_major = h.order == 0;
+      bool grouped_slices = slice_major && njobs > 1;
+      if (h.order != kHookUnset) { slice_major = h.order == 0 || h.order == 2; grouped_slices = h.order == 2; }
       if (slice_major) p.njobs = -njobs;
+      if (grouped_slices) {
+        // the largest group whose round the device holds (768 workgroups) and, with grouped placement, is whole rounds of 8 placement
+        // groups -- a column's next piece then lands on its predecessor's XCD; where there is none, the largest the device holds
+        const unsigned per_piece = p.grid[0] * p.grid[1], pgroups = (p.swizzle & 8) ? p.grid[1] / (((unsigned)p.swizzle >> 8) & 0xffu) : 0;
+        unsigned fits = 768 / per_piece, sg = 0;
+        if (fits > (unsigned)njobs) fits = (unsigned)njobs;
+        for (unsigned c = fits; c >= 1 && !sg; c --) if (pgroups && (c * pgroups) % 8 == 0) sg = c;
+        if (!sg) sg = fits >= 1 ? fits : 1;
+        if (h.sgroup != kHookUnset) sg = (unsigned)(h.sgroup < 1 ? 1 : h.sgroup > njobs ? njobs : h.sgroup);
+        p.z.sgroup = sg;
+      }
       return p;
     }
     // 2D, and the exact stand-alone reduction (ftkx_slice_resolution) of either dimension: mask_march4_kernel -- every wavefront loads

@@ -42,7 +42,7 @@ for rnd in range(rounds + 1):
                 old[k] = os.environ.get(k)
                 os.environ[k] = val
             else:
-                plan.append("%s=%s" % (k.lower(), val))                 # FTKX_MASK_PLAN: "swizzle=..,yg=..,zchunk=..,lmin=..,lcap=..,order=..,lean=.."
+                plan.append("%s=%s" % (k.lower(), val))                 # FTKX_MASK_PLAN: "swizzle=..,yg=..,zchunk=..,lmin=..,lcap=..,order=..,sgroup=..,lean=.."
         old["FTKX_MASK_PLAN"] = os.environ.get("FTKX_MASK_PLAN")
         os.environ["FTKX_MASK_PLAN"] = ",".join(plan)
         ctx.invalidate_masks()
