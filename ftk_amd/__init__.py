@@ -280,6 +280,11 @@ class Context:
         st = C.c_ulonglong()
         return int(self._L.ftkx_series_last_path(self._h, C.byref(st))), int(st.value)
 
+    def trace_last_path(self):
+        """which way the last trace on this context went: 0 host, 1 device phases + host walks (ftkx_trace_curves_ctx), 2 all on the
+        device (ftkx_trace_curves_device)"""
+        return int(self._L.ftkx_trace_last_path(self._h))
+
     def series_split_decision(self):
         """how this context decides on the split pass: {"state": "auto: measuring" | "auto: split" | "auto: in order" | "forced on" | "forced off",
         "median_in_order_ms", "median_split_ms"} (ftkx_series_split_decision)"""
@@ -394,13 +399,33 @@ def extract_cp3dt(scope, current_timestep, domain, core, ext, Vc, Vn, Jc, Jn, Sc
     return _extract(3, scope, current_timestep, domain, core, ext, Vc, Vn, Jc, Jn, Sc, Sn, factor, options, device_id)
 
 
-def trace_curves(nd, domain, records, ctx=None):
+def _trace_on_device(L, ctx, nd, domain, recs, out, tags=None):
+    """ftkx_trace_curves_device on the records' tags, or on `tags`: a torch tensor (int64 / uint64 bit patterns) on the context's device"""
+    if ctx is None:
+        raise ValueError("device=True needs a Context: ftkx_trace_curves_device runs on its GPU")
+    if tags is not None:
+        if not tags.is_cuda or tags.dim() != 1 or not tags.is_contiguous() or tags.element_size() != 8:
+            raise ValueError("tags: a contiguous 1-d tensor of 64-bit tags on the context's device")
+        ptr, n, on_device = tags.data_ptr(), tags.numel(), 1
+    else:
+        host = np.ascontiguousarray(recs["tag"], dtype=np.uint64)
+        ptr, n, on_device = host.ctypes.data, len(host), 0
+    _lib.check(L.ftkx_trace_curves_device(ctx._h, nd, _lib.ll(domain[0]), _lib.ll(domain[1], fill=1), ptr, n, on_device, C.byref(out)), ctx._h)
+
+
+def trace_curves(nd, domain, records, ctx=None, device=False, tags=None):
     """Pass 2 (ftkx_trace_curves): records (CP_DTYPE, element tags) -> (list of index arrays into `records`, loop flags, n_special).
-    ctx: a Context whose GPU does the neighbour search and the component labelling (ftkx_trace_curves_ctx); same curves."""
+    ctx: a Context whose GPU does the neighbour search and the component labelling (ftkx_trace_curves_ctx); same curves.
+    device=True (needs ctx): seeds, walks and compaction on that GPU as well (ftkx_trace_curves_device); same curves.  With it,
+    tags: the records' tags as a torch tensor already on the context's device (`records` may then be None)."""
     L = _lib.load()
-    recs = np.ascontiguousarray(records, dtype=CP_DTYPE)
+    recs = None if records is None else np.ascontiguousarray(records, dtype=CP_DTYPE)
     out = _lib.Curves()
-    if ctx is not None:
+    if device:
+        _trace_on_device(L, ctx, nd, domain, recs, out, tags)
+    elif tags is not None:
+        raise ValueError("tags: only with device=True")
+    elif ctx is not None:
         _lib.check(L.ftkx_trace_curves_ctx(ctx._h, nd, _lib.ll(domain[0]), _lib.ll(domain[1], fill=1), recs.ctypes.data, len(recs), C.byref(out)), ctx._h)
     else:
         _lib.check(L.ftkx_trace_curves(nd, _lib.ll(domain[0]), _lib.ll(domain[1], fill=1), recs.ctypes.data, len(recs), C.byref(out)))
@@ -497,16 +522,22 @@ def post_process(nd, domain, records):
     return ts
 
 
-def pass2(nd, domain, records, ctx=None):
-    """ftkx_trace_curves (ctx given: ftkx_trace_curves_ctx, its data-parallel half on that context's GPU), then ftkx_post_process_curves
+def pass2(nd, domain, records, ctx=None, device=False):
+    """ftkx_trace_curves (ctx given: ftkx_trace_curves_ctx, its data-parallel half on that context's GPU; device=True, which needs
+    ctx: ftkx_trace_curves_device, all of it on that GPU), then ftkx_post_process_curves
     on its result, each timed by itself (the C calls only)
     -> (curves as index arrays, loop flags, n_special, TrajectorySet, ms_trace, ms_post_process)"""
     import time
     L = _lib.load()
     recs = np.ascontiguousarray(records, dtype=CP_DTYPE)
     cur = _lib.Curves()
+    if device and ctx is None:
+        raise ValueError("device=True needs a Context: ftkx_trace_curves_device runs on its GPU")
+    tags = np.ascontiguousarray(recs["tag"], dtype=np.uint64) if device else None
     t0 = time.perf_counter()
-    if ctx is not None:
+    if device:
+        _lib.check(L.ftkx_trace_curves_device(ctx._h, nd, _lib.ll(domain[0]), _lib.ll(domain[1], fill=1), tags.ctypes.data, len(tags), 0, C.byref(cur)), ctx._h)
+    elif ctx is not None:
         _lib.check(L.ftkx_trace_curves_ctx(ctx._h, nd, _lib.ll(domain[0]), _lib.ll(domain[1], fill=1), recs.ctypes.data, len(recs), C.byref(cur)), ctx._h)
     else:
         _lib.check(L.ftkx_trace_curves(nd, _lib.ll(domain[0]), _lib.ll(domain[1], fill=1), recs.ctypes.data, len(recs), C.byref(cur)))
@@ -638,6 +669,14 @@ class _TrackerRegular:
         self._deferred = bool(b)
         self._deferred_depth = max(1, int(depth)) if b else 1
         self._ck(self._L.ftkx_tracker_set_deferred_collection(self._h, self._deferred_depth if b else 0))
+
+    def set_trace_on_device(self, b):
+        """finalize() traces the curves entirely on the tracker's GPU (ftkx_trace_curves_device); same curves; off by default"""
+        self._ck(self._L.ftkx_tracker_set_trace_on_device(self._h, int(bool(b))))
+
+    def trace_last_path(self):
+        """Context.trace_last_path() of the tracker's (first) context"""
+        return int(self._L.ftkx_tracker_trace_last_path(self._h))
 
     # several ranks behind the tracker (include/ftkx_tracker.hh: slab mode): this rank's tracker takes the snapshots of its timestep slab
     # (tslab.slab_range), sweeps it as one device-driven pass, finalize() gathers the points on rank 0.  Pushed device tensors are kept alive.

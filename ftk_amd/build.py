@@ -4,12 +4,13 @@
 
 -ffp-contract=off is part of the contract, not a tuning flag: the FP64 hit path and the derived-field kernels must not fuse
 a*b+c (the x86-64 reference build has no FMA contraction; the one fused op, std::fma in eigen_solver2.hh:32, is explicit)."""
+import hashlib
 import os
 import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = [os.path.join(HERE, "csrc", f) for f in ("tile_kernels.hip", "mask_kernels.hip", "cull_exact_kernels.hip", "halo_kernels.hip", "derive_kernels.hip", "ftkx_api.hip", "prepare.hip", "collect.hip", "halo.hip", "series.hip", "series_kernels.hip", "one_kernel.hip", "dist_kernels.hip", "trace_device.hip", "tracker.cpp", "trace.cpp", "io.cpp", "slab.cpp", "slab_rccl.cpp", "upload.cpp")]
+SRC = [os.path.join(HERE, "csrc", f) for f in ("tile_kernels.hip", "mask_kernels.hip", "cull_exact_kernels.hip", "halo_kernels.hip", "derive_kernels.hip", "ftkx_api.hip", "prepare.hip", "collect.hip", "halo.hip", "series.hip", "series_kernels.hip", "one_kernel.hip", "dist_kernels.hip", "trace_device.hip", "trace_order_kernels.hip", "tracker.cpp", "trace.cpp", "io.cpp", "slab.cpp", "slab_rccl.cpp", "upload.cpp")]
 OUT = os.path.join(HERE, "libftkx.so")
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math",
          "-Wall", "-Wno-unused-function", "-Wno-unused-variable"]
@@ -33,9 +34,31 @@ def up_to_date():
     return os.path.exists(OUT) and all(os.path.getmtime(OUT) >= os.path.getmtime(p) for p in deps())
 
 
+def refresh_shim_driver():
+    """oracle/_ref/ftk_shim_driver -- the patched reference's trackers on this library (tests/test_shim.py, bench.py) -- is compiled from
+    include/ftkx.h and include/ftkx_shim.hh.  Where it exists and oracle/Makefile's record of the sources it was made from
+    (ftk_shim_driver.sha256) no longer matches the tree, it is made again, so that a header that changed cannot leave an older driver
+    next to a newer library.  Nothing happens where it was never built; where the reference tree is absent make leaves it as it is."""
+    oracle = os.path.join(os.path.dirname(HERE), "oracle")
+    record = os.path.join(oracle, "_ref", "ftk_shim_driver.sha256")
+    if not os.path.exists(record) or not os.path.exists(OUT):
+        return
+    try:
+        for line in open(record):
+            digest, name = line.split(None, 1)
+            if hashlib.sha256(open(os.path.join(oracle, name.strip()), "rb").read()).hexdigest() != digest:
+                break
+        else:
+            return
+    except (OSError, ValueError):
+        pass
+    subprocess.call(["make", "-s", "-C", oracle, "ref"], stdout=subprocess.DEVNULL)
+
+
 def build(force=False, verbose=False):
     """one object per source under ftk_amd/csrc/build/ (rebuilt when the source or any header is newer), then one link"""
     if not force and up_to_date():
+        refresh_shim_driver()
         return OUT
     objdir = os.path.join(HERE, "csrc", "build")
     os.makedirs(objdir, exist_ok=True)
@@ -66,6 +89,7 @@ def build(force=False, verbose=False):
                 sys.stderr.write(open(err.name).read()[-4000:])
             raise subprocess.CalledProcessError(rc, cmd)
     subprocess.check_call([hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", OUT] + objs + ["-lrccl"])     # (slab_rccl.cpp: the slab pass's messages over RCCL)
+    refresh_shim_driver()
     return OUT
 
 

@@ -74,6 +74,24 @@ void launch_dist_import(const u64 *gathered, int rank, int nranks, double runnin
                         u64 capacity, int u_rows, int max_factor_log2, unsigned char *U, unsigned char *M, u64 mask_words, hipStream_t st);
 void launch_dist_cells(const Mesh &m, const Fields *d_steps, const u64 *d_list, u64 list_capacity, u64 refine_capacity, const double *halo_field, u64 *request, u64 cap, u64 *block, u64 *results, hipStream_t st);
 void launch_dist_patches(const Mesh &m, bool scatter, const u64 *request, u64 cap, int ncomp, double *field, double *patches, u64 *served, hipStream_t st);
+// trace_order_kernels.hip: pass 2 from neighbours, degrees and roots to ordered curves (trace_device.hip: ftkx_trace_curves_device)
+struct TraceOrder {
+  int n, nd, ntypes, maxnb;
+  long long sz[3];
+  u64 prod[4];
+  const u64 *tags; const int *nbr; const unsigned char *deg; const int *root;      // what the three kernels of trace_device.hip left
+  u64 *key, *best, *link, *info;     // per record: order key; per root: smallest key; per arc: (link << 32) | distance; per seed: key, record | length << 32
+  int *on, *cnt;                     // per record: first / last ordinary neighbour (-1: none); per root: points behind / in front of the seed
+  int *cyc, *seedpos, *seedlist;     // per root: the curve is closed, where its seed lies in `indices`; the seeds in no order
+  int *indices, *loop, *off, *sorted;   // the curves: points, loop flags; from the host: offsets, the seeds in key order
+  unsigned *counters;                // TRO_* words, then one "not done" flag per jump launch
+};
+enum { TRO_SEEDS = 0, TRO_SPECIAL = 1, TRO_ERROR = 2, TRO_CHECK = 3, TRO_FLAGS = 8, TRO_WORDS = 128 };
+void launch_trace_check(const u64 *tags, int n, u64 per_step, unsigned *counters, hipStream_t st);
+void launch_trace_order_begin(const TraceOrder &o, hipStream_t st);                // keys, ordinary neighbours, seeds, arcs
+void launch_trace_order_jump(const TraceOrder &o, int round, hipStream_t st);      // one round of pointer jumping over the arcs
+void launch_trace_order_ends(const TraceOrder &o, unsigned nseeds, hipStream_t st);   // chain lengths, closed curves, the seeds' (key, record, length)
+void launch_trace_order_scatter(const TraceOrder &o, int ncurves, int npoints, hipStream_t st);   // points to their places, loop flags
 }  // namespace ftkx
 
 using ftkx::Fields;
@@ -298,6 +316,9 @@ struct ftkx_ctx {
   void *tr_dev = nullptr, *tr_host = nullptr, *tr_parent = nullptr, *tr_tables = nullptr;
   size_t tr_cap = 0;
   int tr_tables_nd = 0;
+  void *tr_ord = nullptr, *tr_ord_host = nullptr;      // ... and the ordering on the device (trace_order_kernels.hip): its arrays, its pinned staging
+  size_t tr_ord_cap = 0;                               // records both hold
+  int tr_last_path = 0;            // which way the last trace went: 0 host, 1 device phases + host walks, 2 all on the device
   ftkx_stats stats;
   // optional kernel timing (hipEvents on the context's stream)
   int profiling = 0;               // 0 off, 1 every kernel family, 2 the mask kernel only

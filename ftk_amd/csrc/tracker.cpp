@@ -764,7 +764,8 @@ void critical_point_tracker_regular::trace_offline()
   domain_arrays(dst, dsz);
   ftkx_curves c{};
   // (neighbour search and component labelling on the tracker's GPU where the record set is large enough to pay for the round trip)
-  const int rc = ftkx_trace_curves_tags_ctx(ctx, nd, dst, dsz, tags.data(), tags.size(), &c);
+  const int rc = trace_on_device && ctx ? ftkx_trace_curves_device(ctx, nd, dst, dsz, tags.data(), tags.size(), 0, &c)
+                                 : ftkx_trace_curves_tags_ctx(ctx, nd, dst, dsz, tags.data(), tags.size(), &c);
   if (rc != FTKX_OK) { ftkx_free_curves(&c); throw ftkx_error(rc, "finalize: ftkx_trace_curves failed (tags must not have overflowed int32: use FTKX_TAG_EXACT64 on very large meshes)"); }
   // the curves stay flat -- the points of all curves one after the other; one vector per curve is built only if somebody asks for it
   traced_points.resize(c.n_points); traced_offsets.assign(c.offsets, c.offsets + c.n_curves + 1);
@@ -960,6 +961,7 @@ int ftkx_tracker_set_flags(ftkx_tracker *h, int robust, int use_tf, unsigned tf,
   });
 }
 int ftkx_tracker_set_stream(ftkx_tracker *h, void *s) { return guarded(h, [&] { h->t->set_stream(s); }); }
+int ftkx_tracker_set_trace_on_device(ftkx_tracker *h, int on) { return guarded(h, [&] { h->t->set_trace_on_device(on != 0); }); }
 int ftkx_tracker_set_deferred_collection(ftkx_tracker *h, int on) { return guarded(h, [&] { h->t->set_deferred_collection(on != 0, on); }); }
 int ftkx_tracker_set_communicator(ftkx_tracker *h, void *comm, int rank, int nranks, int nt) { return guarded(h, [&] { h->t->set_communicator(comm, rank, nranks, nt); }); }
 int ftkx_tracker_set_slab_transport(ftkx_tracker *h, const ftkx_slab_transport *tr, int rank, int nranks, int nt)
@@ -1082,5 +1084,7 @@ int ftkx_tracker_get_stats(const ftkx_tracker *h, ftkx_stats *st)
   if (!st) return FTKX_E_INVALID;
   return guarded(h, [&] { *st = h->t->get_last_stats(); });
 }
+
+int ftkx_tracker_trace_last_path(const ftkx_tracker *h) { return h && h->t ? ftkx_trace_last_path(h->t->context()) : 0; }
 
 }  // extern "C"

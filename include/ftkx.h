@@ -341,6 +341,15 @@ void ftkx_free_curves(ftkx_curves *c);
 int  ftkx_trace_curves_ctx(ftkx_ctx *ctx, int nd, const long long domain_st[3], const long long domain_sz[3], const ftkx_cp_t *recs, size_t n, ftkx_curves *out);
 /* the same on the tags alone (8 bytes per record): a caller that holds its points in another form need not build records around them */
 int  ftkx_trace_curves_tags_ctx(ftkx_ctx *ctx, int nd, const long long domain_st[3], const long long domain_sz[3], const unsigned long long *tags, size_t n, ftkx_curves *out);
+/* pass 2 with nothing but the result crossing back: neighbour search, component labelling, seeds, walks and compaction on the
+ * context's GPU.  tags: n strictly ascending element tags; tags_on_device = 1: a device pointer of this context's device.
+ * Curves identical to ftkx_trace_curves.  Any n >= 0 (no size floor).  Sets that the device form does not cover (tags not strictly
+ * ascending, n >= 2^30, a timestep >= 2^24 or a mesh whose order key does not fit 64 bits) are traced by ftkx_trace_curves_tags_ctx
+ * inside this call, with the same result. */
+int  ftkx_trace_curves_device(ftkx_ctx *ctx, int nd, const long long domain_st[3], const long long domain_sz[3],
+                              const unsigned long long *tags, size_t n, int tags_on_device, ftkx_curves *out);
+/* which way the last trace on this context went: 0 host, 1 device phases + host walks (ftkx_trace_curves_ctx), 2 all on the device */
+int  ftkx_trace_last_path(const ftkx_ctx *ctx);
 
 /* enable_streaming_trajectories (critical_point_tracker.hh:38; update_timestep 2d:326-330, 3d:197-201): trajectories that grow while
  * the sweep streams -- trace_critical_points_online (critical_point_tracker.hh:523-639).  After every interval sweep the caller hands
