@@ -11,7 +11,7 @@ from . import _lib
 from ._lib import (CP_DTYPE, FORMAT_BINARY, FORMAT_JSON, FORMAT_TEXT, SCOPE_BOTH, SCOPE_INTERVAL, SCOPE_ORDINAL, SOURCE_DERIVED, SOURCE_GIVEN, SOURCE_NONE,  # noqa: F401
                    TAG_EXACT64, TAG_REFERENCE, TAG_WORK_INDEX, FtkxError, Options, Stats)
 
-__all__ = ["trace_curves", "pass2", "trace_and_post_process", "post_process", "TrajectorySet", "write_critical_points", "read_critical_points",
+__all__ = ["trace_curves", "pass2", "trace_and_post_process", "post_process", "post_process_curves", "TrajectorySet", "write_critical_points", "read_critical_points",
            "write_traced_critical_points", "read_traced_critical_points", "Context", "CriticalPointTracker2DRegular", "CriticalPointTracker3DRegular", "extract_cp2dt", "extract_cp3dt",
            "scaling_factor", "CP_DTYPE", "FtkxError"]
 
@@ -285,6 +285,11 @@ class Context:
         device (ftkx_trace_curves_device)"""
         return int(self._L.ftkx_trace_last_path(self._h))
 
+    def post_process_last_path(self):
+        """which way the last post-processing on this context went: 0 host, 2 all on the device (ftkx_post_process_curves_device,
+        ftkx_pass2_device)"""
+        return int(self._L.ftkx_post_process_last_path(self._h))
+
     def series_split_decision(self):
         """how this context decides on the split pass: {"state": "auto: measuring" | "auto: split" | "auto: in order" | "forced on" | "forced off",
         "median_in_order_ms", "median_split_ms"} (ftkx_series_split_decision)"""
@@ -507,50 +512,102 @@ class TrajectorySet:
         return out
 
 
-def post_process(nd, domain, records):
-    """ftkx_trace_curves followed by ftkx_post_process_curves (json_interface::post_process defaults) -> TrajectorySet."""
-    L = _lib.load()
-    recs = np.ascontiguousarray(records, dtype=CP_DTYPE)
+def _curves_to_c(offsets, indices, loop):
+    """(Curves, the arrays it points into) from numpy arrays"""
+    offs = np.ascontiguousarray(offsets, dtype=np.int64)
+    idx = np.ascontiguousarray(indices, dtype=np.int64)
+    lp = np.ascontiguousarray(loop, dtype=np.int32)
     cur = _lib.Curves()
-    _lib.check(L.ftkx_trace_curves(nd, _lib.ll(domain[0]), _lib.ll(domain[1], fill=1), recs.ctypes.data, len(recs), C.byref(cur)))
+    cur.n_curves, cur.n_points, cur.n_special = len(lp), len(idx), 0
+    cur.offsets = offs.ctypes.data_as(C.POINTER(C.c_longlong)); cur.indices = idx.ctypes.data_as(C.POINTER(C.c_longlong))
+    cur.loop = lp.ctypes.data_as(C.POINTER(C.c_int))
+    return cur, (offs, idx, lp)
+
+
+def _post_process_c(L, recs, cur, ctx, device):
+    if device and ctx is None:
+        raise ValueError("device=True needs a Context: ftkx_post_process_curves_device runs on its GPU")
     out = _lib.Trajectories()
-    rc = L.ftkx_post_process_curves(recs.ctypes.data, len(recs), C.byref(cur), C.byref(out))
-    L.ftkx_free_curves(C.byref(cur))
-    _lib.check(rc)
+    if device:
+        rc = L.ftkx_post_process_curves_device(ctx._h, recs.ctypes.data, len(recs), C.byref(cur), C.byref(out))
+    else:
+        rc = L.ftkx_post_process_curves(recs.ctypes.data, len(recs), C.byref(cur), C.byref(out))
+    if rc != _lib.OK:
+        L.ftkx_free_trajectories(C.byref(out))
+    return rc, out
+
+
+def post_process_curves(records, offsets, indices, loop, ctx=None, device=False):
+    """ftkx_post_process_curves on curves given as arrays (curve c = indices[offsets[c]:offsets[c + 1]] into `records`, loop[c])
+    -> TrajectorySet.  device=True (needs ctx): ftkx_post_process_curves_device on that context's GPU; same trajectories."""
+    L = _lib.load()
+    if device and ctx is None:
+        raise ValueError("device=True needs a Context: ftkx_post_process_curves_device runs on its GPU")
+    recs = np.ascontiguousarray(records, dtype=CP_DTYPE)
+    cur, _keep = _curves_to_c(offsets, indices, loop)
+    rc, out = _post_process_c(L, recs, cur, ctx, device)
+    _lib.check(rc, ctx._h if device else None)
     ts = TrajectorySet._from_c(out)
     L.ftkx_free_trajectories(C.byref(out))
     return ts
 
 
-def pass2(nd, domain, records, ctx=None, device=False):
+def post_process(nd, domain, records, ctx=None, device=False):
+    """ftkx_trace_curves followed by ftkx_post_process_curves (json_interface::post_process defaults) -> TrajectorySet.
+    device=True (needs ctx): the post-processing on that context's GPU (ftkx_post_process_curves_device); same trajectories."""
+    L = _lib.load()
+    if device and ctx is None:
+        raise ValueError("device=True needs a Context: ftkx_post_process_curves_device runs on its GPU")
+    recs = np.ascontiguousarray(records, dtype=CP_DTYPE)
+    cur = _lib.Curves()
+    _lib.check(L.ftkx_trace_curves(nd, _lib.ll(domain[0]), _lib.ll(domain[1], fill=1), recs.ctypes.data, len(recs), C.byref(cur)))
+    rc, out = _post_process_c(L, recs, cur, ctx, device)
+    L.ftkx_free_curves(C.byref(cur))
+    _lib.check(rc, ctx._h if device else None)
+    ts = TrajectorySet._from_c(out)
+    L.ftkx_free_trajectories(C.byref(out))
+    return ts
+
+
+def pass2(nd, domain, records, ctx=None, device=False, *, post_device=False):
     """ftkx_trace_curves (ctx given: ftkx_trace_curves_ctx, its data-parallel half on that context's GPU; device=True, which needs
     ctx: ftkx_trace_curves_device, all of it on that GPU), then ftkx_post_process_curves
     on its result, each timed by itself (the C calls only)
-    -> (curves as index arrays, loop flags, n_special, TrajectorySet, ms_trace, ms_post_process)"""
+    -> (curves as index arrays, loop flags, n_special, TrajectorySet, ms_trace, ms_post_process)
+    post_device=True (needs ctx): the post-processing on that GPU too.  With device=True it is ONE call, ftkx_pass2_device -- the curves
+    stay on the device in between -- and ms_trace is the time of that call, ms_post_process 0; otherwise ftkx_post_process_curves_device
+    on the curves the trace returned."""
     import time
     L = _lib.load()
     recs = np.ascontiguousarray(records, dtype=CP_DTYPE)
     cur = _lib.Curves()
     if device and ctx is None:
         raise ValueError("device=True needs a Context: ftkx_trace_curves_device runs on its GPU")
-    tags = np.ascontiguousarray(recs["tag"], dtype=np.uint64) if device else None
-    t0 = time.perf_counter()
-    if device:
-        _lib.check(L.ftkx_trace_curves_device(ctx._h, nd, _lib.ll(domain[0]), _lib.ll(domain[1], fill=1), tags.ctypes.data, len(tags), 0, C.byref(cur)), ctx._h)
-    elif ctx is not None:
-        _lib.check(L.ftkx_trace_curves_ctx(ctx._h, nd, _lib.ll(domain[0]), _lib.ll(domain[1], fill=1), recs.ctypes.data, len(recs), C.byref(cur)), ctx._h)
-    else:
-        _lib.check(L.ftkx_trace_curves(nd, _lib.ll(domain[0]), _lib.ll(domain[1], fill=1), recs.ctypes.data, len(recs), C.byref(cur)))
-    t1 = time.perf_counter()
+    if post_device and ctx is None:
+        raise ValueError("post_device=True needs a Context: ftkx_post_process_curves_device runs on its GPU")
+    tags = np.ascontiguousarray(recs["tag"], dtype=np.uint64) if device and not post_device else None
     out = _lib.Trajectories()
-    rc = L.ftkx_post_process_curves(recs.ctypes.data, len(recs), C.byref(cur), C.byref(out))
-    t2 = time.perf_counter()
+    t0 = time.perf_counter()
+    if device and post_device:
+        _lib.check(L.ftkx_pass2_device(ctx._h, nd, _lib.ll(domain[0]), _lib.ll(domain[1], fill=1), recs.ctypes.data, len(recs), C.byref(cur), C.byref(out)), ctx._h)
+        rc = _lib.OK
+        t1 = t2 = time.perf_counter()
+    else:
+        if device:
+            _lib.check(L.ftkx_trace_curves_device(ctx._h, nd, _lib.ll(domain[0]), _lib.ll(domain[1], fill=1), tags.ctypes.data, len(tags), 0, C.byref(cur)), ctx._h)
+        elif ctx is not None:
+            _lib.check(L.ftkx_trace_curves_ctx(ctx._h, nd, _lib.ll(domain[0]), _lib.ll(domain[1], fill=1), recs.ctypes.data, len(recs), C.byref(cur)), ctx._h)
+        else:
+            _lib.check(L.ftkx_trace_curves(nd, _lib.ll(domain[0]), _lib.ll(domain[1], fill=1), recs.ctypes.data, len(recs), C.byref(cur)))
+        t1 = time.perf_counter()
+        rc, out = _post_process_c(L, recs, cur, ctx, post_device)
+        t2 = time.perf_counter()
     offs = np.ctypeslib.as_array(cur.offsets, shape=(cur.n_curves + 1,)).copy()
     idx = np.ctypeslib.as_array(cur.indices, shape=(max(1, cur.n_points),))[:cur.n_points].copy()
     loop = np.ctypeslib.as_array(cur.loop, shape=(max(1, cur.n_curves),))[:cur.n_curves].copy()
     nspecial = cur.n_special
     L.ftkx_free_curves(C.byref(cur))
-    _lib.check(rc)
+    _lib.check(rc, ctx._h if post_device else None)
     ts = TrajectorySet._from_c(out)
     L.ftkx_free_trajectories(C.byref(out))
     return [idx[offs[i]:offs[i + 1]] for i in range(len(offs) - 1)], loop, nspecial, ts, (t1 - t0) * 1e3, (t2 - t1) * 1e3
@@ -677,6 +734,14 @@ class _TrackerRegular:
     def trace_last_path(self):
         """Context.trace_last_path() of the tracker's (first) context"""
         return int(self._L.ftkx_tracker_trace_last_path(self._h))
+
+    def set_post_process_on_device(self, b):
+        """with set_trace_on_device(True): post_process() on the tracker's GPU as well (ftkx_post_process_curves_device); same trajectories"""
+        self._ck(self._L.ftkx_tracker_set_post_process_on_device(self._h, int(bool(b))))
+
+    def post_process_last_path(self):
+        """Context.post_process_last_path() of the tracker's (first) context"""
+        return int(self._L.ftkx_tracker_post_process_last_path(self._h))
 
     # several ranks behind the tracker (include/ftkx_tracker.hh: slab mode): this rank's tracker takes the snapshots of its timestep slab
     # (tslab.slab_range), sweeps it as one device-driven pass, finalize() gathers the points on rank 0.  Pushed device tensors are kept alive.

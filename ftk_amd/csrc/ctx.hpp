@@ -92,6 +92,11 @@ void launch_trace_order_begin(const TraceOrder &o, hipStream_t st);             
 void launch_trace_order_jump(const TraceOrder &o, int round, hipStream_t st);      // one round of pointer jumping over the arcs
 void launch_trace_order_ends(const TraceOrder &o, unsigned nseeds, hipStream_t st);   // chain lengths, closed curves, the seeds' (key, record, length)
 void launch_trace_order_scatter(const TraceOrder &o, int ncurves, int npoints, hipStream_t st);   // points to their places, loop flags
+// post_process_kernels.hip: the maps and scans of post_process_steps.hpp, queued in order (post_process_device.hip)
+struct PostProc;
+constexpr size_t kPostProcAggBytes = 16;                   // per tile of a scan: its total
+size_t post_process_tiles(size_t np);                      // how many totals `agg` must hold
+hipError_t launch_post_process(const PostProc &p, void *agg, hipStream_t st, bool timed);   // timed: the host waits after every phase and prints its time
 }  // namespace ftkx
 
 using ftkx::Fields;
@@ -319,6 +324,10 @@ struct ftkx_ctx {
   void *tr_ord = nullptr, *tr_ord_host = nullptr;      // ... and the ordering on the device (trace_order_kernels.hip): its arrays, its pinned staging
   size_t tr_ord_cap = 0;                               // records both hold
   int tr_last_path = 0;            // which way the last trace went: 0 host, 1 device phases + host walks, 2 all on the device
+  // post-processing on the device (post_process_device.hip): one device block (input, work arrays, results), one pinned block (input, results)
+  void *pp_dev = nullptr, *pp_host = nullptr;
+  size_t pp_dev_cap = 0, pp_host_cap = 0;              // bytes
+  int pp_last_path = 0;            // which way the last post-processing went: 0 host, 2 all on the device
   ftkx_stats stats;
   // optional kernel timing (hipEvents on the context's stream)
   int profiling = 0;               // 0 off, 1 every kernel family, 2 the mask kernel only
@@ -377,6 +386,8 @@ int ensure_mask_arrays(ftkx_ctx *c, Slice &s, bool two_level);
 int upload_from_host(ftkx_ctx *c, void *dst, const void *src, size_t bytes);       // upload.cpp
 int aux_stream_get(ftkx_ctx *c, bool high_priority, hipStream_t *out);       // the library's own streams, kept for the process (ftkx_api.hip)
 void aux_stream_put(ftkx_ctx *c, bool high_priority, hipStream_t st);
+// trace_device.hip: where the last ftkx_trace_curves_device left its curves on the device (while tr_last_path == 2, until the next trace)
+void trace_device_curves(const ftkx_ctx *c, const int **indices, const int **off, const int **loop);
 // halo.hip
 bool packed_layout(const ftkx_ctx *c, const Mesh &m, size_t *ub, size_t *cap, size_t *off_idx, size_t *off_words, size_t *total);
 int ensure_sparse_slice(ftkx_ctx *c, int t, int scalar_input);

@@ -445,8 +445,8 @@ void ftkx_destroy(ftkx_ctx *c)
   if (c->sr_one_scratch) (void)hipFree(c->sr_one_scratch);
   if (c->sr_fetch_flag) (void)hipFree(c->sr_fetch_flag);
   if (c->sr_ev_fetched) (void)hipEventDestroy(c->sr_ev_fetched);
-  for (void *p : {c->tr_dev, c->tr_parent, c->tr_tables, c->tr_ord}) if (p) (void)hipFree(p);
-  for (void *p : {c->tr_host, c->tr_ord_host}) if (p) (void)hipHostFree(p);
+  for (void *p : {c->tr_dev, c->tr_parent, c->tr_tables, c->tr_ord, c->pp_dev}) if (p) (void)hipFree(p);
+  for (void *p : {c->tr_host, c->tr_ord_host, c->pp_host}) if (p) (void)hipHostFree(p);
   if (c->d_sorted) (void)hipFree(c->d_sorted);
   if (c->d_keys) (void)hipFree(c->d_keys);
   if (c->d_idx) (void)hipFree(c->d_idx);

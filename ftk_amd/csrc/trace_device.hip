@@ -144,6 +144,25 @@ static TraceGeom trace_geom(int nd, const long long domain_st[3], const long lon
   return g;
 }
 
+// the ordering's arrays inside the context's block
+static void order_arrays(const ftkx_ctx *c, ftkx::TraceOrder &o)
+{
+  const size_t cap = c->tr_ord_cap;
+  u64 *q = (u64 *)c->tr_ord;
+  o.key = q; q += cap; o.best = q; q += cap; o.info = q; q += 2 * cap; o.link = q; q += 2 * cap;
+  int *r = (int *)q;
+  o.on = r; r += 2 * cap; o.cnt = r; r += 2 * cap; o.cyc = r; r += cap; o.seedpos = r; r += cap; o.seedlist = r; r += cap;
+  o.indices = r; r += cap; o.loop = r; r += cap; o.off = r; r += cap; o.sorted = r; r += cap;
+  o.counters = (unsigned *)r;
+}
+
+void ftkxh::trace_device_curves(const ftkx_ctx *c, const int **indices, const int **off, const int **loop)
+{
+  ftkx::TraceOrder o;
+  order_arrays(c, o);
+  *indices = o.indices; *off = o.off; *loop = o.loop;
+}
+
 extern "C" {
 
 static int trace_curves_ctx_impl(ftkx_ctx *c, int nd, const long long domain_st[3], const long long domain_sz[3], const ftkx_cp_t *recs, const unsigned long long *tags, size_t n, ftkx_curves *out)
@@ -290,14 +309,7 @@ int ftkx_trace_curves_device(ftkx_ctx *c, int nd, const long long domain_st[3], 
   o.n = (int)n; o.nd = nd; o.ntypes = ntypes; o.maxnb = maxnb;
   o.prod[0] = 1;
   for (int a = 0; a < nd; a ++) { o.sz[a] = domain_sz[a]; o.prod[a + 1] = o.prod[a] * (u64)domain_sz[a]; }
-  {
-    u64 *q = (u64 *)c->tr_ord;
-    o.key = q; q += cap; o.best = q; q += cap; o.info = q; q += 2 * cap; o.link = q; q += 2 * cap;
-    int *r = (int *)q;
-    o.on = r; r += 2 * cap; o.cnt = r; r += 2 * cap; o.cyc = r; r += cap; o.seedpos = r; r += cap; o.seedlist = r; r += cap;
-    o.indices = r; r += cap; o.loop = r; r += cap; o.off = r; r += cap; o.sorted = r; r += cap;
-    o.counters = (unsigned *)r;
-  }
+  order_arrays(c, o);
   // pinned: info u64[2 cap] | off int[cap] | sorted int[cap] | indices int[cap] | loop int[cap] | counters
   u64 *h_info = (u64 *)c->tr_ord_host;
   int *h_off = (int *)(h_info + 2 * cap), *h_sorted = h_off + cap, *h_indices = h_sorted + cap, *h_loop = h_indices + cap;

@@ -797,7 +797,8 @@ void critical_point_tracker_regular::post_process()
   in.n_curves = num_traced_curves(); in.n_points = f.recs.size();
   in.offsets = traced_offsets.data(); in.indices = f.indices.data(); in.loop = traced_loop.data();
   ftkx_trajectories out{};
-  const int rc = ftkx_post_process_curves(f.recs.data(), f.recs.size(), &in, &out);
+  const int rc = post_process_on_device && trace_on_device && ctx ? ftkx_post_process_curves_device(ctx, f.recs.data(), f.recs.size(), &in, &out)
+                                                                  : ftkx_post_process_curves(f.recs.data(), f.recs.size(), &in, &out);
   if (rc != FTKX_OK) { ftkx_free_trajectories(&out); throw ftkx_error(rc, "post_process failed"); }
   std::vector<feature_point_t> pts(out.n_points);
   std::vector<int> loop(out.n_curves), ids(out.n_curves);
@@ -962,6 +963,7 @@ int ftkx_tracker_set_flags(ftkx_tracker *h, int robust, int use_tf, unsigned tf,
 }
 int ftkx_tracker_set_stream(ftkx_tracker *h, void *s) { return guarded(h, [&] { h->t->set_stream(s); }); }
 int ftkx_tracker_set_trace_on_device(ftkx_tracker *h, int on) { return guarded(h, [&] { h->t->set_trace_on_device(on != 0); }); }
+int ftkx_tracker_set_post_process_on_device(ftkx_tracker *h, int on) { return guarded(h, [&] { h->t->set_post_process_on_device(on != 0); }); }
 int ftkx_tracker_set_deferred_collection(ftkx_tracker *h, int on) { return guarded(h, [&] { h->t->set_deferred_collection(on != 0, on); }); }
 int ftkx_tracker_set_communicator(ftkx_tracker *h, void *comm, int rank, int nranks, int nt) { return guarded(h, [&] { h->t->set_communicator(comm, rank, nranks, nt); }); }
 int ftkx_tracker_set_slab_transport(ftkx_tracker *h, const ftkx_slab_transport *tr, int rank, int nranks, int nt)
@@ -1086,5 +1088,6 @@ int ftkx_tracker_get_stats(const ftkx_tracker *h, ftkx_stats *st)
 }
 
 int ftkx_tracker_trace_last_path(const ftkx_tracker *h) { return h && h->t ? ftkx_trace_last_path(h->t->context()) : 0; }
+int ftkx_tracker_post_process_last_path(const ftkx_tracker *h) { return h && h->t ? ftkx_post_process_last_path(h->t->context()) : 0; }
 
 }  // extern "C"

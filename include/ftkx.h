@@ -378,6 +378,20 @@ typedef struct ftkx_trajectories {
 } ftkx_trajectories;
 int  ftkx_post_process_curves(const ftkx_cp_t *recs, size_t n, const ftkx_curves *in, ftkx_trajectories *out);
 void ftkx_free_trajectories(ftkx_trajectories *c);
+/* ftkx_post_process_curves on the context's GPU: the same trajectories, field for field (t bit for bit: the only floating-point
+ * operations are max and min).  Every step is a map or a scan over the flat array of points, whatever the curves' lengths.  Per record
+ * 16 bytes go up (type, aux word, t), per point 4 and per curve 8; offsets, indices, loop, type, t and id come down once.  What the
+ * device form does not cover -- n_points >= 2^30, or a point whose t is not finite (max and min as the host code calls them are not
+ * associative with NaN) -- is done by ftkx_post_process_curves inside this call, with the same result.  Argument errors as the host
+ * function's (an index outside recs[], offsets that do not ascend or run past n_points: FTKX_E_INVALID); ctx == NULL: FTKX_E_INVALID. */
+int  ftkx_post_process_curves_device(ftkx_ctx *ctx, const ftkx_cp_t *recs, size_t n, const ftkx_curves *in, ftkx_trajectories *out);
+/* pass 2 in one call: ftkx_trace_curves_device on the records' tags, then the above on the curves where they lie on the device (indices,
+ * offsets and loop flags are not sent up again); curves (nullable): the traced curves as well, released with ftkx_free_curves.  A trace
+ * that did not go all the way on the device is post-processed by ftkx_post_process_curves, with the same result. */
+int  ftkx_pass2_device(ftkx_ctx *ctx, int nd, const long long domain_st[3], const long long domain_sz[3],
+                       const ftkx_cp_t *recs, size_t n, ftkx_curves *curves, ftkx_trajectories *out);
+/* which way the last post-processing on this context went: 0 host, 2 all on the device */
+int  ftkx_post_process_last_path(const ftkx_ctx *ctx);
 
 /* ---- record-stream formats: what `ftk --output-type discrete|traced` writes and reads -------- */
 /* binary = diy::serializeToFile, byte-identical to the reference's files; json = nlohmann's compact dump (parses to the

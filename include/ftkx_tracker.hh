@@ -151,6 +151,9 @@ public:
   void set_deferred_collection(bool b, int depth = 1) { sync(); deferred_collection = b; deferred_depth = depth > 1 ? depth : 1; }
   // not in the reference: finalize() traces the curves entirely on the tracker's GPU (ftkx_trace_curves_device) -- same curves; off by default
   void set_trace_on_device(bool b) { trace_on_device = b; }
+  // not in the reference: with set_trace_on_device(true), post_process() runs on the tracker's GPU as well (ftkx_post_process_curves_device)
+  // -- same trajectories; off by default
+  void set_post_process_on_device(bool b) { post_process_on_device = b; }
   // Several RANKS behind the tracker -- one process per GPU, or one tracker per device and thread in one process.  The reference keeps an
   // MPI communicator on the filter and distributes inside the tracker (regular_tracker.hh:127-149), gathering the discrete points on the
   // root in front of pass 2 (critical_point_tracker.hh:689).  Here the series of `nt` timesteps is cut in TIME (include/ftkx_slab.h): this
@@ -262,6 +265,7 @@ protected:
   // deferred collection
   bool deferred_collection = false;
   bool trace_on_device = false;
+  bool post_process_on_device = false;
   int deferred_depth = 1;
   std::vector<int> open_steps;                              // the timesteps of the sweeps that are queued and not yet collected (at most three; -1: a batch)
   std::vector<int> batch_ts, batch_scopes, batch_drops;     // in batches: the steps recorded and not yet queued; the snapshots popped meanwhile
@@ -342,6 +346,7 @@ int  ftkx_tracker_set_flags(ftkx_tracker *, int robust, int use_type_filter, uns
 int  ftkx_tracker_set_stream(ftkx_tracker *, void *hip_stream);
 int  ftkx_tracker_set_current_timestep(ftkx_tracker *, int t);
 int  ftkx_tracker_set_trace_on_device(ftkx_tracker *, int on);       /* not in the reference: see critical_point_tracker_regular::set_trace_on_device */
+int  ftkx_tracker_set_post_process_on_device(ftkx_tracker *, int on);   /* not in the reference: see critical_point_tracker_regular::set_post_process_on_device */
 int  ftkx_tracker_set_deferred_collection(ftkx_tracker *, int on);   /* not in the reference: see critical_point_tracker_regular::set_deferred_collection; on > 1: batches of `on` steps */
 /* several ranks behind the tracker (critical_point_tracker_regular::set_communicator / set_slab_transport / set_slab_hub): this rank's
  * tracker takes the snapshots of its timestep slab, sweeps it as one device-driven pass, and ftkx_tracker_finalize gathers the points on rank 0 */
@@ -364,6 +369,7 @@ int  ftkx_tracker_get_critical_points(const ftkx_tracker *, ftkx_cp_t *out, int 
 int  ftkx_tracker_get_scaling(const ftkx_tracker *, unsigned long long *factor, double *resolution);
 int  ftkx_tracker_get_stats(const ftkx_tracker *, ftkx_stats *st);
 int  ftkx_tracker_trace_last_path(const ftkx_tracker *);             /* ftkx_trace_last_path of the tracker's (first) context */
+int  ftkx_tracker_post_process_last_path(const ftkx_tracker *);      /* ftkx_post_process_last_path of the tracker's (first) context */
 int  ftkx_tracker_finalize(ftkx_tracker *);
 /* after finalize: number of curves / total points; then offsets[n_curves+1], tags[n_points] (element tags in curve order), loop[n_curves] */
 int  ftkx_tracker_num_curves(const ftkx_tracker *, size_t *n_curves, size_t *n_points);
