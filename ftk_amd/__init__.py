@@ -13,7 +13,7 @@ from ._lib import (CP_DTYPE, FORMAT_BINARY, FORMAT_JSON, FORMAT_TEXT, SCOPE_BOTH
 
 __all__ = ["trace_curves", "pass2", "trace_and_post_process", "post_process", "post_process_curves", "TrajectorySet", "write_critical_points", "read_critical_points",
            "write_traced_critical_points", "read_traced_critical_points", "Context", "CriticalPointTracker2DRegular", "CriticalPointTracker3DRegular", "extract_cp2dt", "extract_cp3dt",
-           "scaling_factor", "CP_DTYPE", "FtkxError"]
+           "scaling_factor", "gaussian_kernel", "CP_DTYPE", "FtkxError"]
 
 
 def _ptr(a):
@@ -50,6 +50,13 @@ def scaling_factor(resolution):
     return int(f), nb.value
 
 
+def gaussian_kernel(nd, sigma, ksize):
+    """ftkx_gaussian_kernel: the reference's gaussian_kernel2D / 3D weights (host), shape (ksize,) * nd with x last"""
+    w = np.zeros(max(1, int(ksize)) ** nd if nd in (2, 3) else 1, dtype=np.float64)
+    _lib.check(_lib.load().ftkx_gaussian_kernel(int(nd), float(sigma), int(ksize), w.ctypes.data))
+    return w.reshape((int(ksize),) * nd)
+
+
 class Context:
     """ftkx_ctx: slices resident in HBM + sweeps (include/ftkx.h)."""
 
@@ -59,6 +66,7 @@ class Context:
         self._h = C.c_void_p()
         _lib.check(self._L.ftkx_create(C.byref(self._h), nd, device_id))
         self._keep = {}
+        self._smoothing = False
 
     def close(self):
         if self._h:
@@ -99,6 +107,12 @@ class Context:
             args += [_lib.ll(st), _lib.ll(sz, fill=1)]
         self._ck(self._L.ftkx_set_mesh(self._h, *args))
 
+    def set_spatial_smoothing(self, sigma, ksize=3):
+        """ftkx_set_spatial_smoothing: scalar slices pushed from now on are conv_gaussian(S, sigma, ksize, ksize // 2); ksize 0: off"""
+        rc = self._L.ftkx_set_spatial_smoothing(self._h, float(sigma), int(ksize))
+        self._ck(rc)                                   # (raises: a refused setting leaves the context, and this flag, as they were)
+        self._smoothing = int(ksize) != 0
+
     def push_slice(self, t, V, J=None, S=None):
         pv, kv, dv = _ptr(V); pj, kj, dj = _ptr(J); ps, ks, ds = _ptr(S)
         devs = {d for p, d in ((pv, dv), (pj, dj), (ps, ds)) if p is not None}
@@ -108,10 +122,15 @@ class Context:
         self._ck(self._L.ftkx_push_slice(self._h, t, pv, pj, ps, on_dev))
         self._keep[t] = (kv, kj, ks) if on_dev else None
 
-    def push_scalar_slice(self, t, S):
+    def push_scalar_slice(self, t, S, on_device=None):
+        """on_device: None = 0 for a host array, 1 (borrowed) for a device tensor; 2: a device tensor, copied"""
         ps, ks, ds = _ptr(S)
+        if on_device is not None:
+            if int(on_device) not in (0, 1, 2) or (int(on_device) != 0) != bool(ds):
+                raise ValueError("on_device: 0 for a host array, 1 or 2 for a device tensor")
+            ds = int(on_device)
         self._ck(self._L.ftkx_push_scalar_slice(self._h, t, ps, ds))
-        self._keep[t] = ks if ds else None
+        self._keep[t] = ks if ds == 1 and not self._smoothing else None     # (2, and smoothing: the context owns a copy)
 
     def drop_slice(self, t):
         self._ck(self._L.ftkx_drop_slice(self._h, t))
@@ -366,6 +385,27 @@ class Context:
     def jacobian2D(self, V_ptr, DW, DH, symmetric, J_ptr): self._ck(self._L.ftkx_jacobian2D(self._h, V_ptr, DW, DH, int(symmetric), J_ptr))
     def gradient3D(self, S_ptr, DW, DH, DD, V_ptr): self._ck(self._L.ftkx_gradient3D(self._h, S_ptr, DW, DH, DD, V_ptr))
     def jacobian3D(self, V_ptr, DW, DH, DD, J_ptr): self._ck(self._L.ftkx_jacobian3D(self._h, V_ptr, DW, DH, DD, J_ptr))
+
+    # spatial smoothing on device tensors (ndarray/conv.hh); weights: a host array of ksize ** nd doubles, x fastest
+    def conv2D(self, S_ptr, DW, DH, weights, ksize, out_ptr):
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        if w.size != int(ksize) ** 2:
+            raise ValueError("conv2D: ksize ** 2 weights")
+        self._ck(self._L.ftkx_conv2D(self._h, S_ptr, DW, DH, w.ctypes.data, int(ksize), out_ptr))
+
+    def conv3D(self, S_ptr, DW, DH, DD, weights, ksize, out_ptr):
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        if w.size != int(ksize) ** 3:
+            raise ValueError("conv3D: ksize ** 3 weights")
+        self._ck(self._L.ftkx_conv3D(self._h, S_ptr, DW, DH, DD, w.ctypes.data, int(ksize), out_ptr))
+
+    def debug_conv_relaunch(self, S_ptr, dims, weights, ksize, out_ptr, reps):
+        """profiling aid: the convolution kernel `reps` times back to back -> device ms per launch (HIP events)"""
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        d = [int(x) for x in dims] + [1] * (3 - len(dims))
+        ms = (C.c_double * int(reps))()
+        self._ck(self._L.ftkx_debug_conv_relaunch(self._h, len(dims), S_ptr, d[0], d[1], d[2], w.ctypes.data, int(ksize), out_ptr, int(reps), ms))
+        return list(ms)
 
 
 def _extract(nd, scope, current_timestep, domain, core, ext, Vc, Vn, Jc, Jn, Sc, Sn, factor, options, device_id, coords=None):
@@ -730,6 +770,11 @@ class _TrackerRegular:
     def set_trace_on_device(self, b):
         """finalize() traces the curves entirely on the tracker's GPU (ftkx_trace_curves_device); same curves; off by default"""
         self._ck(self._L.ftkx_tracker_set_trace_on_device(self._h, int(bool(b))))
+
+    def set_spatial_smoothing(self, sigma, ksize=3):
+        """before initialize(): every scalar snapshot is smoothed on the device like the reference stream's --spatial-smoothing-kernel
+        (conv_gaussian(snapshot, sigma, ksize, ksize // 2)); ksize 0: off"""
+        self._ck(self._L.ftkx_tracker_set_spatial_smoothing(self._h, float(sigma), int(ksize)))
 
     def trace_last_path(self):
         """Context.trace_last_path() of the tracker's (first) context"""

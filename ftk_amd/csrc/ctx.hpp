@@ -47,6 +47,7 @@ void launch_jacobian2d(const double *V, int DW, int DH, int symmetric, double *J
 void launch_gradient3d(const double *S, int DW, int DH, int DD, double *V, hipStream_t st);
 void launch_jacobian3d(const double *V, int DW, int DH, int DD, double *J, hipStream_t st);
 void launch_resolution(const double *p, size_t n, u64 *out2, hipStream_t st);
+void launch_conv(int nd, const double *S, int DW, int DH, int DD, const double *d_weights, int ksize, double *out, hipStream_t st);   // conv_kernels.hip
 void launch_calib_read(const void *p, size_t bytes, double *scratch, hipStream_t stream);
 const char *last_mask_kernel();
 void launch_cull_coarse(const Mesh &m, const Fields *d_steps, int nsteps, u64 *d_refine, u64 refine_cap, hipStream_t stream, const FactorJob *job = nullptr);
@@ -259,6 +260,11 @@ struct ftkx_ctx {
   double *d_expl = nullptr;
   int expl_ncomp = 0;
   size_t expl_n0 = 0, expl_n1 = 0;
+  // spatial smoothing (ftkx_set_spatial_smoothing): ksize 0 = off; d_conv_w holds two sets of 9^3 weights -- [0] those of the ftkx_conv2D /
+  // ftkx_conv3D call in hand (the call waits for its kernel), [1] the smoothing's, written when it is set and only read afterwards
+  int smooth_ksize = 0;
+  double smooth_sigma = 0;
+  double *d_conv_w = nullptr;
   std::vector<ftkxh::Request> pending;
   // Cull-ahead: the sweeps the caller announced (ftkx_sweep_announce) for the slices of the next ftkx_slices_prepare, and -- once that
   // call has queued their cull right behind the mask kernel -- the survivor list it left on the device.  The cull needs the masks

@@ -452,6 +452,7 @@ void ftkx_destroy(ftkx_ctx *c)
   if (c->d_idx) (void)hipFree(c->d_idx);
   if (c->d_sort_tmp) (void)hipFree(c->d_sort_tmp);
   if (c->d_desc) (void)hipFree(c->d_desc);
+  if (c->d_conv_w) (void)hipFree(c->d_conv_w);
   for (int d = 0; d < 3; d ++) if (c->d_rect[d]) (void)hipFree(c->d_rect[d]);
   if (c->d_expl) (void)hipFree(c->d_expl);
   if (c->h_desc) (void)hipHostFree(c->h_desc);
@@ -542,6 +543,8 @@ int ftkx_set_mesh(ftkx_ctx *c, const long long dst[3], const long long dsz[3], c
   return FTKX_OK;
 }
 
+constexpr size_t kSmoothWeights = 729;      // ftkx_ctx::d_conv_w: where the smoothing's weights start
+
 static int push_common(ftkx_ctx *c, int t, const double *V, const double *J, const double *S, int on_device, bool scalar_only)
 {
   if (c) c->ahead.clear();
@@ -554,19 +557,50 @@ static int push_common(ftkx_ctx *c, int t, const double *V, const double *J, con
   if (c->slices.empty()) c->scalar_mode = -1;
   if (c->scalar_mode >= 0 && c->scalar_mode != (scalar_only ? 1 : 0))
     return fail(c, FTKX_E_INVALID, "push: scalar and vector slices cannot be mixed in one context");
+  // conv_gaussian dispatches on the array's nd(): a vector field would be convolved across its components (conv.hh:213-221) -- not reproduced
+  if (c->smooth_ksize && !scalar_only) return fail(c, FTKX_E_UNSUPPORTED, "push: spatial smoothing is set and takes scalar slices only (ftkx_push_scalar_slice)");
   HIP_TRY(c, hipSetDevice(c->device));
   auto it = c->slices.find(t);
   if (it != c->slices.end()) { free_slice(it->second, c); c->slices.erase(it); }
   Slice s;
   const size_t n = n_vertices(c);
   const int nd = c->nd;
-  auto take = [&](const double *src, size_t count, double **dst, bool *own) -> int {
-    if (!src) { *dst = nullptr; *own = false; return FTKX_OK; }
-    if (on_device == 1) { *dst = const_cast<double *>(src); *own = false; return FTKX_OK; }
+  auto pooled = [&](size_t count, double **dst) -> int {
     *dst = nullptr;
     for (size_t i = 0; i < c->pool_F.size(); i ++)
       if (c->pool_F[i].second == count) { *dst = c->pool_F[i].first; c->pool_F.erase(c->pool_F.begin() + (long)i); break; }
     if (!*dst) HIP_TRY(c, hipMalloc((void **)dst, count * sizeof(double)));
+    return FTKX_OK;
+  };
+  // spatial smoothing: the slice is conv(src), in a buffer of the context's own whatever on_device says.  A host source, and a device source
+  // that lives on another device, goes through a pooled buffer first (the kernel reads this device's memory only); that buffer goes back
+  // to the pool at once: whatever takes it out next is ordered behind the kernel by the context's stream (upload.cpp waits for it too).
+  auto take_smoothed = [&](const double *src, size_t count, double **dst, bool *own) -> int {
+    if (int rc = pooled(count, dst)) return rc;
+    *own = true;
+    const double *from = src;
+    double *tmp = nullptr;
+    if (on_device == 0 || ftkx_pointer_device(src) != c->device) {
+      if (int rc = pooled(count, &tmp)) return rc;
+      int rc = FTKX_OK;
+      if (on_device == 0) rc = upload_from_host(c, tmp, src, count * sizeof(double));
+      else if (hipMemcpyAsync(tmp, src, count * sizeof(double), hipMemcpyDefault, c->stream) != hipSuccess) rc = fail(c, FTKX_E_DEVICE, "push: copy of the source failed");
+      // (a failed copy: nothing of it is in flight any more -- upload.cpp drains its DMA streams before it reports an error, and a
+      // hipMemcpyAsync that was refused was never queued -- but what the buffer holds is unknown and the device may be in an error state:
+      // it is freed, not pooled)
+      if (rc) { (void)hipFree(tmp); return rc; }
+      from = tmp;
+    }
+    ftkx::launch_conv(nd, from, (int)c->ext_sz[0], (int)c->ext_sz[1], (int)c->ext_sz[2], c->d_conv_w + kSmoothWeights, c->smooth_ksize, *dst, c->stream);
+    const hipError_t e = hipGetLastError();
+    if (tmp) { if (c->pool_F.size() < 12) c->pool_F.push_back({tmp, count}); else { (void)hipStreamSynchronize(c->stream); (void)hipFree(tmp); } }
+    HIP_TRY(c, e);
+    return FTKX_OK;
+  };
+  auto take = [&](const double *src, size_t count, double **dst, bool *own) -> int {
+    if (!src) { *dst = nullptr; *own = false; return FTKX_OK; }
+    if (on_device == 1) { *dst = const_cast<double *>(src); *own = false; return FTKX_OK; }
+    if (int rc = pooled(count, dst)) return rc;
     *own = true;
     // 0: host memory; 2: device memory of ANY device (a multi-device tracker hands one snapshot to two contexts), copied
     if (on_device == 0) return upload_from_host(c, *dst, src, count * sizeof(double));
@@ -574,7 +608,7 @@ static int push_common(ftkx_ctx *c, int t, const double *V, const double *J, con
     return FTKX_OK;
   };
   int rc;
-  if ((rc = take(S, n, &s.S, &s.ownS))) { release_slice(s); return rc; }
+  if ((rc = c->smooth_ksize ? take_smoothed(S, n, &s.S, &s.ownS) : take(S, n, &s.S, &s.ownS))) { release_slice(s); return rc; }
   if (!scalar_only) {
     if ((rc = take(V, n * nd, &s.V, &s.ownV))) { release_slice(s); return rc; }      // what was already allocated goes back
     if ((rc = take(J, n * nd * nd, &s.J, &s.ownJ))) { release_slice(s); return rc; }
@@ -583,7 +617,8 @@ static int push_common(ftkx_ctx *c, int t, const double *V, const double *J, con
   // reference's exact operations (ndarray/grad.hh), so the slice costs 8 bytes per vertex of HBM instead of 8 + 8*nd.
   // the source buffers may be reused by the caller on return: a device source (2) has to be read first; a host source has been staged
   // completely by upload_from_host (nothing to wait for: the DMAs run on while the caller produces its next snapshot)
-  if (on_device == 2) HIP_TRY(c, hipStreamSynchronize(c->stream));
+  // (smoothing: a borrowed array (1) is read by the kernel and never adopted -- the call returns once it has been read, like 2)
+  if (on_device == 2 || (on_device == 1 && c->smooth_ksize)) HIP_TRY(c, hipStreamSynchronize(c->stream));
   s.mask_gen = ++ c->mask_epoch;
   c->slices[t] = s;
   c->scalar_mode = scalar_only ? 1 : 0;
@@ -822,5 +857,106 @@ int ftkx_gradient3D(ftkx_ctx *c, const double *S, int DW, int DH, int DD, double
 { DERIVE_PROLOGUE(c); ftkx::launch_gradient3d(S, DW, DH, DD, V, c->stream); HIP_TRY(c, hipGetLastError()); HIP_TRY(c, hipStreamSynchronize(c->stream)); return FTKX_OK; }
 int ftkx_jacobian3D(ftkx_ctx *c, const double *V, int DW, int DH, int DD, double *J)
 { DERIVE_PROLOGUE(c); ftkx::launch_jacobian3d(V, DW, DH, DD, J, c->stream); HIP_TRY(c, hipGetLastError()); HIP_TRY(c, hipStreamSynchronize(c->stream)); return FTKX_OK; }
+
+
+// ---- spatial Gaussian smoothing (ndarray/conv.hh) ----------------------------------------------------------------------------------------
+static bool conv_ksize_ok(int ksize) { return ksize >= 1 && ksize <= 9 && (ksize & 1) == 1; }
+
+// gaussian_kernel2D (conv.hh:74-100) / gaussian_kernel3D (165-196) with the host's exp.  The order in which `sum` grows is the reference's
+// loop order -- 2D: y outer, x inner; 3D: y outer, then x, then z innermost -- not memory order.
+int ftkx_gaussian_kernel(int nd, double sigma, int ksize, double *weights)
+{
+  if (nd != 2 && nd != 3) return fail(nullptr, FTKX_E_INVALID, "ftkx_gaussian_kernel: nd must be 2 or 3");
+  if (!conv_ksize_ok(ksize)) return fail(nullptr, FTKX_E_INVALID, "ftkx_gaussian_kernel: ksize must be odd and in [1, 9] (got %d)", ksize);
+  if (!std::isfinite(sigma) || !(sigma > 0)) return fail(nullptr, FTKX_E_INVALID, "ftkx_gaussian_kernel: sigma must be finite and positive");
+  if (!weights) return fail(nullptr, FTKX_E_INVALID, "ftkx_gaussian_kernel: null output");
+  const double center = static_cast<double>(ksize - 1) * .5;
+  const double s = 2. * sigma * sigma;
+  double sum = 0.;
+  const int nz = nd == 3 ? ksize : 1;
+  for (int j = 0; j < ksize; ++ j)
+    for (int i = 0; i < ksize; ++ i)
+      for (int k = 0; k < nz; ++ k) {
+        const double x = static_cast<double>(i) - center, y = static_cast<double>(j) - center, z = static_cast<double>(k) - center;
+        const double r = nd == 3 ? x * x + y * y + z * z : x * x + y * y;
+        double &w = weights[((size_t)k * ksize + j) * ksize + i];
+        w = std::exp(-r / s);
+        sum += w;
+      }
+  const int n = ksize * ksize * nz;
+  for (int i = 0; i < n; ++ i) weights[i] /= sum;
+  return FTKX_OK;
+}
+
+static int conv_weights(ftkx_ctx *c, const double *weights, int n, size_t at)
+{
+  if (!c->d_conv_w) HIP_TRY(c, hipMalloc((void **)&c->d_conv_w, 2 * kSmoothWeights * sizeof(double)));
+  HIP_TRY(c, hipMemcpyAsync(c->d_conv_w + at, weights, (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  return FTKX_OK;
+}
+
+static int conv_common(ftkx_ctx *c, int nd, const double *S, int DW, int DH, int DD, const double *weights, int ksize, double *out)
+{
+  DERIVE_PROLOGUE(c);
+  if (!S || !out || !weights) return fail(c, FTKX_E_INVALID, "ftkx_conv%dD: null argument", nd);
+  if (DW < 1 || DH < 1 || DD < 1) return fail(c, FTKX_E_INVALID, "ftkx_conv%dD: extents must be positive", nd);
+  if (!conv_ksize_ok(ksize)) return fail(c, FTKX_E_INVALID, "ftkx_conv%dD: ksize must be odd and in [1, 9] (got %d)", nd, ksize);
+  const size_t n = (size_t)DW * (size_t)DH * (size_t)DD;
+  if (S < out + n && out < S + n) return fail(c, FTKX_E_INVALID, "ftkx_conv%dD: input and output overlap", nd);
+  int taps = ksize * ksize * (nd == 3 ? ksize : 1);
+  if (int rc = conv_weights(c, weights, taps, 0)) return rc;
+  ftkx::launch_conv(nd, S, DW, DH, DD, c->d_conv_w, ksize, out, c->stream);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipStreamSynchronize(c->stream));      // (the next call may overwrite the weights; the caller may read `out`)
+  return FTKX_OK;
+}
+
+int ftkx_conv2D(ftkx_ctx *c, const double *S, int DW, int DH, const double *weights, int ksize, double *out)
+{ return conv_common(c, 2, S, DW, DH, 1, weights, ksize, out); }
+int ftkx_conv3D(ftkx_ctx *c, const double *S, int DW, int DH, int DD, const double *weights, int ksize, double *out)
+{ return conv_common(c, 3, S, DW, DH, DD, weights, ksize, out); }
+
+// profiling aid (tools/conv_time.py): the convolution kernel `reps` times back to back, a pair of events around every launch
+int ftkx_debug_conv_relaunch(ftkx_ctx *c, int nd, const double *S, int DW, int DH, int DD, const double *weights, int ksize, double *out, int reps, double *ms)
+{
+  DERIVE_PROLOGUE(c);
+  if ((nd != 2 && nd != 3) || !S || !out || !weights || !ms || reps < 1 || DW < 1 || DH < 1 || DD < 1 || !conv_ksize_ok(ksize)) return fail(c, FTKX_E_INVALID, "ftkx_debug_conv_relaunch: bad argument");
+  if (int rc = conv_weights(c, weights, ksize * ksize * (nd == 3 ? ksize : 1), 0)) return rc;
+  std::vector<hipEvent_t> ev(2 * (size_t)reps, nullptr);
+  int rc = FTKX_OK;
+  auto run = [&]() -> int {
+    for (hipEvent_t &e : ev) HIP_TRY(c, hipEventCreate(&e));
+    for (int i = 0; i < reps; i ++) {
+      HIP_TRY(c, hipEventRecord(ev[2 * (size_t)i], c->stream));
+      ftkx::launch_conv(nd, S, DW, DH, nd == 3 ? DD : 1, c->d_conv_w, ksize, out, c->stream);
+      HIP_TRY(c, hipEventRecord(ev[2 * (size_t)i + 1], c->stream));
+    }
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (int i = 0; i < reps; i ++) { float t = 0; HIP_TRY(c, hipEventElapsedTime(&t, ev[2 * (size_t)i], ev[2 * (size_t)i + 1])); ms[i] = t; }
+    return FTKX_OK;
+  };
+  rc = run();
+  if (rc) (void)hipStreamSynchronize(c->stream);
+  for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+  return rc;
+}
+
+int ftkx_set_spatial_smoothing(ftkx_ctx *c, double sigma, int ksize)
+{
+  if (c) c->ahead.clear();
+  if (!c) return fail(nullptr, FTKX_E_INVALID, "null context");
+  if (!c->pending.empty()) return fail(c, FTKX_E_INVALID, "ftkx_set_spatial_smoothing: sweeps pending, collect first");
+  if (c->sr_open && !c->sr_internal) return fail(c, FTKX_E_INVALID, "ftkx_set_spatial_smoothing: series passes open (ftkx_sweep_series_submit), complete them first");
+  if (ksize == 0) { c->smooth_ksize = 0; c->smooth_sigma = 0; return FTKX_OK; }
+  double w[kSmoothWeights];
+  if (int rc = ftkx_gaussian_kernel(c->nd, sigma, ksize, w)) { c->err = g_last_error; return rc; }
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));      // (a push queued under the old weights still reads them)
+  if (int rc = conv_weights(c, w, ksize * ksize * (c->nd == 3 ? ksize : 1), kSmoothWeights)) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));      // (`w` is this call's)
+  c->smooth_ksize = ksize; c->smooth_sigma = sigma;
+  return FTKX_OK;
+}
 
 }  // extern "C"

@@ -487,6 +487,7 @@ void critical_point_tracker_regular::apply_configuration(ftkx_ctx *c)
   o.coords_mode = mode_phys_coords;
   for (size_t i = 0; i < 6 && i < bounds_coords.size(); i ++) o.coords_bounds[i] = bounds_coords[i];
   check_on(c, ftkx_set_options(c, &o));
+  check_on(c, ftkx_set_spatial_smoothing(c, spatial_smoothing_sigma, spatial_smoothing_ksize));
 }
 
 void critical_point_tracker_regular::initialize()
@@ -547,12 +548,14 @@ void critical_point_tracker_regular::push_scalar_field_snapshot(const double *s,
 void critical_point_tracker_regular::push_vector_field_snapshot(const double *v, bool device)
 {
   if (!initialized) throw ftkx_error(FTKX_E_INVALID, "push: initialize() first");
+  if (spatial_smoothing_ksize) throw ftkx_error(FTKX_E_UNSUPPORTED, "push_vector_field_snapshot: spatial smoothing takes scalar snapshots only");
   push_snapshot(1, nullptr, v, nullptr, device);            // J derived at hits when jacobian_field_source == SOURCE_DERIVED
 }
 
 void critical_point_tracker_regular::push_field_data_snapshot(const double *s, const double *v, const double *j, bool device)
 {
   if (!initialized) throw ftkx_error(FTKX_E_INVALID, "push: initialize() first");
+  if (spatial_smoothing_ksize) throw ftkx_error(FTKX_E_UNSUPPORTED, "push_field_data_snapshot: spatial smoothing takes scalar snapshots only");
   push_snapshot(2, s, v, j, device);
 }
 
@@ -962,6 +965,7 @@ int ftkx_tracker_set_flags(ftkx_tracker *h, int robust, int use_tf, unsigned tf,
   });
 }
 int ftkx_tracker_set_stream(ftkx_tracker *h, void *s) { return guarded(h, [&] { h->t->set_stream(s); }); }
+int ftkx_tracker_set_spatial_smoothing(ftkx_tracker *h, double sigma, int ksize) { return guarded(h, [&] { h->t->set_spatial_smoothing(sigma, ksize); }); }
 int ftkx_tracker_set_trace_on_device(ftkx_tracker *h, int on) { return guarded(h, [&] { h->t->set_trace_on_device(on != 0); }); }
 int ftkx_tracker_set_post_process_on_device(ftkx_tracker *h, int on) { return guarded(h, [&] { h->t->set_post_process_on_device(on != 0); }); }
 int ftkx_tracker_set_deferred_collection(ftkx_tracker *h, int on) { return guarded(h, [&] { h->t->set_deferred_collection(on != 0, on); }); }

@@ -423,6 +423,32 @@ int ftkx_jacobian2D(ftkx_ctx *ctx, const double *V, int DW, int DH, int symmetri
 int ftkx_gradient3D(ftkx_ctx *ctx, const double *S, int DW, int DH, int DD, double *V);            /* grad.hh:130-149 */
 int ftkx_jacobian3D(ftkx_ctx *ctx, const double *V, int DW, int DH, int DD, double *J);            /* grad.hh:175-212 */
 
+/* ---- spatial Gaussian smoothing of scalar snapshots (ndarray/conv.hh; the stream's --spatial-smoothing-kernel[-size]) ---- */
+/* What ndarray_stream::modified_callback does to every snapshot in front of the tracker (stream.hh:1597-1603):
+ * conv_gaussian(array, sigma, ksize, ksize / 2), bit for bit -- weights normalised by their sum AND the result divided by ksize^nd, taps
+ * outside the array skipped, every product rounded before it is added, kz outer / ky / kx innermost.
+ * ftkx_gaussian_kernel: host only.  gaussian_kernel2D / 3D (conv.hh:74-100, 165-196) with the host's exp; `weights` takes ksize^nd
+ * doubles, x fastest.  FTKX_E_INVALID: nd not 2 or 3, ksize even or outside [1, 9], sigma not finite or not positive.  (An even ksize
+ * makes the reference's output one larger than its input on every axis, which no tracker can consume.) */
+int ftkx_gaussian_kernel(int nd, double sigma, int ksize, double *weights);
+/* S and out: DEVICE pointers of DW * DH (* DD) doubles that do not overlap; weights: a HOST array of ksize^nd finite doubles, x fastest
+ * (ftkx_gaussian_kernel's, or any other).  Queued on the context's stream; the call returns when `out` is complete. */
+int ftkx_conv2D(ftkx_ctx *ctx, const double *S, int DW, int DH, const double *weights, int ksize, double *out);
+int ftkx_conv3D(ftkx_ctx *ctx, const double *S, int DW, int DH, int DD, const double *weights, int ksize, double *out);
+/* ksize 0 (the default): off.  While on, ftkx_push_scalar_slice makes conv(S) the resident slice -- masks, resolution, halo export and
+ * patches see the smoothed array.  A host source is staged into a pooled buffer and convolved into the slice's; with on_device = 1 the
+ * caller's array is read, never written and NOT adopted: the context owns the smoothed copy and the call returns once the source has been
+ * read, as with 2.  ftkx_push_slice (vector input) fails with FTKX_E_UNSUPPORTED while smoothing is on: conv_gaussian dispatches on nd()
+ * and would convolve a vector field across its components.
+ * Every push is taken for a RAW snapshot.  An array that is smoothed already -- the resident slice of another context, handed over whole
+ * where a slab pass asks for its halo slice as a whole (ftkx_series_dist_status: asked < 0) -- must be pushed with smoothing switched off
+ * around that push, or it is convolved twice.  ftkx_slab_* (include/ftkx_slab.h) and the tracker's slab mode do that themselves; the compact
+ * halo (masks, request, patches) is built from resident slices and needs nothing. */
+int ftkx_set_spatial_smoothing(ftkx_ctx *ctx, double sigma, int ksize);
+/* profiling aid (tools/conv_time.py): the kernel of ftkx_conv2D / 3D (nd 2: DD ignored) launched `reps` times back to back on the context's
+ * stream, a pair of events around every launch; ms: reps device times. */
+int ftkx_debug_conv_relaunch(ftkx_ctx *ctx, int nd, const double *S, int DW, int DH, int DD, const double *weights, int ksize, double *out, int reps, double *ms);
+
 /* profiling aid: streams `bytes` of device memory with the mask kernel's load shape (16 B per lane) and nothing else, so that
  * rocprofv3's FETCH_SIZE can be calibrated on a known byte count (tools/calibrate_fetch.py) */
 int ftkx_debug_stream_read(ftkx_ctx *ctx, const void *device_ptr, size_t bytes);

@@ -154,6 +154,11 @@ public:
   // not in the reference: with set_trace_on_device(true), post_process() runs on the tracker's GPU as well (ftkx_post_process_curves_device)
   // -- same trajectories; off by default
   void set_post_process_on_device(bool b) { post_process_on_device = b; }
+  // The stream's --spatial-smoothing-kernel / --spatial-smoothing-kernel-size (ndarray_stream::modified_callback, stream.hh:1597-1603; 3 is
+  // the stream's default size, stream.hh:961): every scalar snapshot pushed after initialize() is replaced by conv_gaussian(snapshot, sigma,
+  // ksize, ksize / 2) on the device (ftkx_set_spatial_smoothing).  Set before initialize(); ksize 0: off (the default).  Scalar input only:
+  // a push that hands over a vector field while this is set throws FTKX_E_UNSUPPORTED.
+  void set_spatial_smoothing(double sigma, int ksize = 3) { spatial_smoothing_sigma = sigma; spatial_smoothing_ksize = ksize; }
   // Several RANKS behind the tracker -- one process per GPU, or one tracker per device and thread in one process.  The reference keeps an
   // MPI communicator on the filter and distributes inside the tracker (regular_tracker.hh:127-149), gathering the discrete points on the
   // root in front of pass 2 (critical_point_tracker.hh:689).  Here the series of `nt` timesteps is cut in TIME (include/ftkx_slab.h): this
@@ -265,6 +270,8 @@ protected:
   // deferred collection
   bool deferred_collection = false;
   bool trace_on_device = false;
+  double spatial_smoothing_sigma = 0;
+  int spatial_smoothing_ksize = 0;
   bool post_process_on_device = false;
   int deferred_depth = 1;
   std::vector<int> open_steps;                              // the timesteps of the sweeps that are queued and not yet collected (at most three; -1: a batch)
@@ -345,6 +352,7 @@ int  ftkx_tracker_set_sources(ftkx_tracker *, int scalar, int vector, int jacobi
 int  ftkx_tracker_set_flags(ftkx_tracker *, int robust, int use_type_filter, unsigned type_filter, int compute_degrees, int exact_only, int tag_mode);
 int  ftkx_tracker_set_stream(ftkx_tracker *, void *hip_stream);
 int  ftkx_tracker_set_current_timestep(ftkx_tracker *, int t);
+int  ftkx_tracker_set_spatial_smoothing(ftkx_tracker *, double sigma, int ksize);   /* the stream's spatial smoothing in front of the tracker; ksize 0: off */
 int  ftkx_tracker_set_trace_on_device(ftkx_tracker *, int on);       /* not in the reference: see critical_point_tracker_regular::set_trace_on_device */
 int  ftkx_tracker_set_post_process_on_device(ftkx_tracker *, int on);   /* not in the reference: see critical_point_tracker_regular::set_post_process_on_device */
 int  ftkx_tracker_set_deferred_collection(ftkx_tracker *, int on);   /* not in the reference: see critical_point_tracker_regular::set_deferred_collection; on > 1: batches of `on` steps */
