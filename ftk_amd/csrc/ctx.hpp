@@ -19,6 +19,9 @@
 #include "sweep_params.hpp"
 #include "split_policy.hpp"
 #include "internal.hpp"
+#include "pass2_layout.hpp"
+
+struct ftkx_phase_clock;
 
 namespace ftkx {
 void mask_kernel_launches(unsigned long long *out, const char **names);
@@ -85,20 +88,38 @@ struct TraceOrder {
   int *on, *cnt;                     // per record: first / last ordinary neighbour (-1: none); per root: points behind / in front of the seed
   int *cyc, *seedpos, *seedlist;     // per root: the curve is closed, where its seed lies in `indices`; the seeds in no order
   int *indices, *loop, *off, *sorted;   // the curves: points, loop flags; from the host: offsets, the seeds in key order
-  unsigned *counters;                // TRO_* words, then one "not done" flag per jump launch
+  unsigned *counters;                // TRO_* words (pass2_layout.hpp), then one "not done" flag per jump launch
 };
-enum { TRO_SEEDS = 0, TRO_SPECIAL = 1, TRO_ERROR = 2, TRO_CHECK = 3, TRO_FLAGS = 8, TRO_WORDS = 128 };
 void launch_trace_check(const u64 *tags, int n, u64 per_step, unsigned *counters, hipStream_t st);
 void launch_trace_order_begin(const TraceOrder &o, hipStream_t st);                // keys, ordinary neighbours, seeds, arcs
 void launch_trace_order_jump(const TraceOrder &o, int round, hipStream_t st);      // one round of pointer jumping over the arcs
 void launch_trace_order_ends(const TraceOrder &o, unsigned nseeds, hipStream_t st);   // chain lengths, closed curves, the seeds' (key, record, length)
 void launch_trace_order_scatter(const TraceOrder &o, int ncurves, int npoints, hipStream_t st);   // points to their places, loop flags
 // post_process_kernels.hip: the maps and scans of post_process_steps.hpp, queued in order (post_process_device.hip)
-struct PostProc;
 constexpr size_t kPostProcAggBytes = 16;                   // per tile of a scan: its total
 size_t post_process_tiles(size_t np);                      // how many totals `agg` must hold
-hipError_t launch_post_process(const PostProc &p, void *agg, hipStream_t st, bool timed);   // timed: the host waits after every phase and prints its time
+hipError_t launch_post_process(const PostProc &p, void *agg, ftkx_phase_clock &clock);   // on the clock's stream, one lap per group of steps
 }  // namespace ftkx
+
+// Phase timing of pass 2 on the device (FTKX_TRACE_PHASES, FTKX_POST_PROCESS_PHASES): where it is on, the host waits for the stream after
+// every phase and prints "prefix: name, microseconds since the lap before" to stderr.  A measuring aid: the waits cost time of their own.
+struct ftkx_phase_clock {
+  bool on;
+  hipStream_t stream;
+  const char *prefix;
+  std::chrono::steady_clock::time_point first, last;
+  void start() { if (on) first = last = std::chrono::steady_clock::now(); }
+  hipError_t lap(const char *what, size_t count)
+  {
+    if (!on) return hipSuccess;
+    const hipError_t e = hipStreamSynchronize(stream);
+    const auto now = std::chrono::steady_clock::now();
+    fprintf(stderr, "%s: %-32s %8.1f us  (%zu)\n", prefix, what, std::chrono::duration<double, std::micro>(now - last).count(), count);
+    last = now;
+    return e;
+  }
+  double us_in_all() const { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - first).count(); }   // since start()
+};
 
 using ftkx::Fields;
 using ftkx::MaskJob;
@@ -224,6 +245,29 @@ struct ftkx_tail_set {
   hipStream_t stream = nullptr;     // the tail of a split pass on this set; created where the first such pass is planned
 };
 
+// Pass 2 on the device (trace_device.hip, post_process_device.hip): every block it keeps with the context.  A call lays its arrays out
+// (pass2_layout.hpp), reserves the blocks for the layout's totals and works on the context's stream, which it waits for before it returns:
+// what a block held does not outlive the call, but for the curves of the last trace that went all the way on the device (`order`).
+struct ftkx_ctx;
+struct pass2_block {
+  void *p = nullptr;
+  size_t bytes = 0;
+  bool pinned = false;
+  int reserve(ftkx_ctx *c, size_t want, bool pinned_);   // (ftkx_api.hip) at least `want` bytes; grows by a quarter more; contents are not kept
+  void release();
+};
+struct ftkx_pass2_state {
+  pass2_block trace_dev, trace_host;   // TraceLayout
+  pass2_block tables;                  // the neighbour search's candidate tables of dimension `tables_nd`
+  pass2_block order_dev, order_host;   // OrderLayout
+  pass2_block pp_dev, pp_host;         // PpPlan
+  int tables_nd = 0;
+  ftkx::OrderLayout order;             // of the last trace that ended with path 2: where its curves lie in order_dev
+  int trace_last_path = 0;             // which way the last trace went: 0 host, 1 device phases + host walks, 2 all on the device
+  int pp_last_path = 0;                // which way the last post-processing went: 0 host, 2 all on the device
+  void release() { for (pass2_block *b : {&trace_dev, &trace_host, &tables, &order_dev, &order_host, &pp_dev, &pp_host}) b->release(); tables_nd = 0; }
+};
+
 struct ftkx_ctx {
   int nd = 0, device = 0;
   hipStream_t own_stream = nullptr, stream = nullptr;
@@ -323,17 +367,7 @@ struct ftkx_ctx {
   int sr_last_path = 0;              // which way the last ftkx_sweep_series went: 0 the host-driven batch, 1 device-driven (the kernel chain), 2 early single-workgroup tail,
                                      // 4 the one-launch pass, 5 a split pass
   unsigned long long sr_last_status = 0;
-  // pass 2 on the device (trace_device.hip): tags up, neighbours / degrees / roots down
-  void *tr_dev = nullptr, *tr_host = nullptr, *tr_parent = nullptr, *tr_tables = nullptr;
-  size_t tr_cap = 0;
-  int tr_tables_nd = 0;
-  void *tr_ord = nullptr, *tr_ord_host = nullptr;      // ... and the ordering on the device (trace_order_kernels.hip): its arrays, its pinned staging
-  size_t tr_ord_cap = 0;                               // records both hold
-  int tr_last_path = 0;            // which way the last trace went: 0 host, 1 device phases + host walks, 2 all on the device
-  // post-processing on the device (post_process_device.hip): one device block (input, work arrays, results), one pinned block (input, results)
-  void *pp_dev = nullptr, *pp_host = nullptr;
-  size_t pp_dev_cap = 0, pp_host_cap = 0;              // bytes
-  int pp_last_path = 0;            // which way the last post-processing went: 0 host, 2 all on the device
+  ftkx_pass2_state p2;
   ftkx_stats stats;
   // optional kernel timing (hipEvents on the context's stream)
   int profiling = 0;               // 0 off, 1 every kernel family, 2 the mask kernel only
@@ -392,7 +426,7 @@ int ensure_mask_arrays(ftkx_ctx *c, Slice &s, bool two_level);
 int upload_from_host(ftkx_ctx *c, void *dst, const void *src, size_t bytes);       // upload.cpp
 int aux_stream_get(ftkx_ctx *c, bool high_priority, hipStream_t *out);       // the library's own streams, kept for the process (ftkx_api.hip)
 void aux_stream_put(ftkx_ctx *c, bool high_priority, hipStream_t st);
-// trace_device.hip: where the last ftkx_trace_curves_device left its curves on the device (while tr_last_path == 2, until the next trace)
+// trace_device.hip: where the last ftkx_trace_curves_device left its curves on the device (while p2.trace_last_path == 2, until the next trace)
 void trace_device_curves(const ftkx_ctx *c, const int **indices, const int **off, const int **loop);
 // halo.hip
 bool packed_layout(const ftkx_ctx *c, const Mesh &m, size_t *ub, size_t *cap, size_t *off_idx, size_t *off_words, size_t *total);

@@ -409,6 +409,23 @@ int ftkx_create(ftkx_ctx **out, int nd, int device_id)
   return FTKX_OK;
 }
 
+void pass2_block::release()
+{
+  if (p) (void)(pinned ? hipHostFree(p) : hipFree(p));
+  p = nullptr; bytes = 0;
+}
+
+int pass2_block::reserve(ftkx_ctx *c, size_t want, bool pinned_)
+{
+  if (bytes >= want) return FTKX_OK;
+  release();
+  pinned = pinned_;
+  const size_t cap = want + want / 4;
+  if (pinned) HIP_TRY(c, hipHostMalloc(&p, cap, hipHostMallocNonCoherent)); else HIP_TRY(c, hipMalloc(&p, cap));
+  bytes = cap;
+  return FTKX_OK;
+}
+
 void ftkx_destroy(ftkx_ctx *c)
 {
   if (!c) return;
@@ -445,8 +462,7 @@ void ftkx_destroy(ftkx_ctx *c)
   if (c->sr_one_scratch) (void)hipFree(c->sr_one_scratch);
   if (c->sr_fetch_flag) (void)hipFree(c->sr_fetch_flag);
   if (c->sr_ev_fetched) (void)hipEventDestroy(c->sr_ev_fetched);
-  for (void *p : {c->tr_dev, c->tr_parent, c->tr_tables, c->tr_ord, c->pp_dev}) if (p) (void)hipFree(p);
-  for (void *p : {c->tr_host, c->tr_ord_host, c->pp_host}) if (p) (void)hipHostFree(p);
+  c->p2.release();
   if (c->d_sorted) (void)hipFree(c->d_sorted);
   if (c->d_keys) (void)hipFree(c->d_keys);
   if (c->d_idx) (void)hipFree(c->d_idx);

@@ -34,5 +34,9 @@ int trace_candidates(int nd, std::vector<int> &cand_off, std::vector<int> &cand_
 int trace_curves_with(int nd, const long long *dst, const long long *dsz, const unsigned long long *tags, size_t n, ftkx_curves *out,
                       const int *nbr, const unsigned char *deg, const int *root, int maxnb);
 int trace_curves_tags(int nd, const long long *dst, const long long *dsz, const unsigned long long *tags, size_t n, ftkx_curves *out);   // host only
+// Result arrays as ftkx_free_curves / ftkx_free_trajectories release them (trace.cpp): the struct zeroed, every array malloc'ed for
+// max(count, 1) elements (offsets: n_curves + 1, offsets[0] = 0), the counts set.  FTKX_E_NOMEM: nothing is left allocated.
+int alloc_curves(ftkx_curves *out, size_t n_curves, size_t n_points);
+int alloc_trajectories(ftkx_trajectories *out, size_t n_curves, size_t n_points);
 }
 #endif

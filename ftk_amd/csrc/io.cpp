@@ -413,26 +413,18 @@ int trajectories_of(const std::vector<Curve> &curves, ftkx_cp_t **recs, size_t *
   size_t np = 0;
   for (const Curve &c : curves) np += c.pts.size();
   const size_t nc = curves.size();
+  if (ftkx::alloc_trajectories(tr, nc, np) != FTKX_OK) return io_fail(FTKX_E_NOMEM, "out of memory");
   ftkx_cp_t *r = (ftkx_cp_t *)malloc((np ? np : 1) * sizeof(ftkx_cp_t));
-  memset(tr, 0, sizeof(*tr));
-  tr->offsets = (long long *)malloc((nc + 1) * sizeof(long long));
-  tr->indices = (long long *)malloc((np ? np : 1) * sizeof(long long));
-  tr->loop = (int *)malloc((nc ? nc : 1) * sizeof(int));
-  tr->id = (int *)malloc((nc ? nc : 1) * sizeof(int));
-  tr->type = (unsigned *)malloc((np ? np : 1) * sizeof(unsigned));
-  tr->t = (double *)malloc((np ? np : 1) * sizeof(double));
-  if (!r || !tr->offsets || !tr->indices || !tr->loop || !tr->id || !tr->type || !tr->t) {
-    free(r); ftkx_free_trajectories(tr);
+  if (!r) {
+    ftkx_free_trajectories(tr);
     return io_fail(FTKX_E_NOMEM, "out of memory");
   }
   size_t k = 0;
-  tr->offsets[0] = 0;
   for (size_t c = 0; c < nc; c ++) {
     for (const Point &p : curves[c].pts) { record_of(p, &r[k]); tr->indices[k] = (long long)k; tr->type[k] = p.type; tr->t[k] = p.t; k ++; }
     tr->offsets[c + 1] = (long long)k;
     tr->loop[c] = curves[c].loop; tr->id[c] = curves[c].id;
   }
-  tr->n_curves = nc; tr->n_points = np;
   *recs = r; *n = np;
   return FTKX_OK;
 }

@@ -8,7 +8,6 @@
 // of the totals by one workgroup, the tiles again with their prefix.  Segments (curves, gaps between ordinal points, pieces) are part of
 // the operators, not of the building block: a flag in the element (ScanTime*), or "the last flagged point so far" compared with the
 // segment's head (ScanLast) -- the scans run over the flat point array whatever the curves' lengths.
-#include <chrono>
 #include "ctx.hpp"
 #include "post_process_steps.hpp"
 
@@ -125,9 +124,8 @@ struct DeviceRun {
   int np;
   void *agg;
   hipStream_t st;
-  bool timed;
+  ftkx_phase_clock &clock;
   hipError_t err = hipSuccess;
-  std::chrono::steady_clock::time_point mark;
   template <class F> void map(const F &f) { hipLaunchKernelGGL(pp_map_kernel<F>, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, f); }
   template <class S> void scan(const S &s)
   {
@@ -139,24 +137,16 @@ struct DeviceRun {
     hipLaunchKernelGGL(pp_scan_spine_kernel<S>, dim3(1), dim3(256), 0, st, a, ntiles);
     hipLaunchKernelGGL(pp_scan_tiles_kernel<S>, dim3((unsigned)ntiles), dim3(256), 0, st, s, (const typename S::T *)a);
   }
-  void phase(const char *what)
-  {
-    if (!timed || err != hipSuccess) return;
-    err = hipStreamSynchronize(st);
-    const auto now = std::chrono::steady_clock::now();
-    fprintf(stderr, "ftkx_post_process_curves_device: %-32s %8.1f us\n", what, std::chrono::duration<double, std::micro>(now - mark).count());
-    mark = now;
-  }
+  void phase(const char *what) { if (err == hipSuccess) err = clock.lap(what, (size_t)np); }
 };
 
 }  // namespace
 
 size_t post_process_tiles(size_t np) { return (np + kTile - 1) / kTile + 1; }
 
-hipError_t launch_post_process(const PostProc &p, void *agg, hipStream_t st, bool timed)
+hipError_t launch_post_process(const PostProc &p, void *agg, ftkx_phase_clock &clock)
 {
-  DeviceRun run{p.np, agg, st, timed};
-  run.mark = std::chrono::steady_clock::now();
+  DeviceRun run{p.np, agg, clock.stream, clock};
   post_process_steps(p, run);
   return run.err != hipSuccess ? run.err : hipGetLastError();
 }

@@ -29,7 +29,7 @@
 #include <unistd.h>
 #include <vector>
 
-#include "../../include/ftkx.h"
+#include "internal.hpp"
 #include "fan_tables.hpp"
 
 namespace {
@@ -561,12 +561,7 @@ int trace_impl(const long long *dst, const long long *dsz, const TagView tags, s
 
   tp[np_ ++] = now();
   if (prof) fprintf(stderr, "trace: n %zu  index %.3f  neighbours %.3f  components+order %.3f  walk %.3f ms\n", n, tp[1] - tp[0], tp[2] - tp[1], tp[3] - tp[2], tp[4] - tp[3]);
-  out->n_curves = loops.size();
-  out->n_points = seq.size();
-  out->offsets = (long long *)malloc(offsets.size() * sizeof(long long));
-  out->indices = (long long *)malloc((seq.size() ? seq.size() : 1) * sizeof(long long));
-  out->loop = (int *)malloc((loops.size() ? loops.size() : 1) * sizeof(int));
-  if (!out->offsets || !out->indices || !out->loop) return FTKX_E_NOMEM;
+  if (const int rc = ftkx::alloc_curves(out, loops.size(), seq.size())) return rc;
   memcpy(out->offsets, offsets.data(), offsets.size() * sizeof(long long));
   for (size_t i = 0; i < seq.size(); i ++) out->indices[i] = seq[i];
   for (size_t i = 0; i < loops.size(); i ++) out->loop[i] = loops[i];
@@ -715,6 +710,34 @@ int trace_curves_tags(int nd, const long long *dst, const long long *dsz, const 
 }
 }  // namespace ftkx
 
+// result arrays for every producer of curves and trajectories (internal.hpp)
+namespace ftkx {
+
+template <class T> static bool alloc_array(T **p, size_t count) { return (*p = (T *)malloc((count ? count : 1) * sizeof(T))) != nullptr; }
+
+int alloc_curves(ftkx_curves *out, size_t n_curves, size_t n_points)
+{
+  memset(out, 0, sizeof(*out));
+  const bool ok = alloc_array(&out->offsets, n_curves + 1) && alloc_array(&out->indices, n_points) && alloc_array(&out->loop, n_curves);
+  if (!ok) { ftkx_free_curves(out); return FTKX_E_NOMEM; }
+  out->offsets[0] = 0;
+  out->n_curves = n_curves; out->n_points = n_points;
+  return FTKX_OK;
+}
+
+int alloc_trajectories(ftkx_trajectories *out, size_t n_curves, size_t n_points)
+{
+  memset(out, 0, sizeof(*out));
+  const bool ok = alloc_array(&out->offsets, n_curves + 1) && alloc_array(&out->indices, n_points) && alloc_array(&out->loop, n_curves)
+                && alloc_array(&out->type, n_points) && alloc_array(&out->t, n_points) && alloc_array(&out->id, n_curves);
+  if (!ok) { ftkx_free_trajectories(out); return FTKX_E_NOMEM; }
+  out->offsets[0] = 0;
+  out->n_curves = n_curves; out->n_points = n_points;
+  return FTKX_OK;
+}
+
+}  // namespace ftkx
+
 extern "C" {
 
 int ftkx_online_tracer_create(ftkx_online_tracer **out, int nd, const long long domain_st[3], const long long domain_sz[3])
@@ -740,22 +763,17 @@ int ftkx_online_tracer_grow(ftkx_online_tracer *t, const ftkx_cp_t *recs, size_t
 int ftkx_online_tracer_curves(const ftkx_online_tracer *t, ftkx_cp_t **points, ftkx_curves *out)
 {
   if (!t || !points || !out) return FTKX_E_INVALID;
-  memset(out, 0, sizeof(*out));
   size_t np = 0;
   for (const auto &c : t->curves) np += c.size();
+  if (const int rc = ftkx::alloc_curves(out, t->curves.size(), np)) return rc;
   *points = (ftkx_cp_t *)malloc((np ? np : 1) * sizeof(ftkx_cp_t));
-  out->offsets = (long long *)malloc((t->curves.size() + 1) * sizeof(long long));
-  out->indices = (long long *)malloc((np ? np : 1) * sizeof(long long));
-  out->loop = (int *)malloc((t->curves.size() ? t->curves.size() : 1) * sizeof(int));
-  if (!*points || !out->offsets || !out->indices || !out->loop) return FTKX_E_NOMEM;
+  if (!*points) { ftkx_free_curves(out); return FTKX_E_NOMEM; }
   size_t k = 0;
-  out->offsets[0] = 0;
   for (size_t c = 0; c < t->curves.size(); c ++) {
     for (const ftkx_cp_t &p : t->curves[c]) { (*points)[k] = p; out->indices[k] = (long long)k; k ++; }
     out->offsets[c + 1] = (long long)k;
     out->loop[c] = t->loop[c];
   }
-  out->n_curves = t->curves.size(); out->n_points = np;
   return FTKX_OK;
 }
 
@@ -892,15 +910,7 @@ int ftkx_post_process_curves(const ftkx_cp_t *recs, size_t n, const ftkx_curves 
   const size_t nres = first[nc];
   size_t np = 0;
   for (const auto &pc : pieces) for (const Piece &q : pc) np += q.e - q.b;
-  out->n_curves = nres; out->n_points = np;
-  out->offsets = (long long *)malloc((nres + 1) * sizeof(long long));
-  out->indices = (long long *)malloc((np ? np : 1) * sizeof(long long));
-  out->loop = (int *)malloc((nres ? nres : 1) * sizeof(int));
-  out->type = (unsigned *)malloc((np ? np : 1) * sizeof(unsigned));
-  out->t = (double *)malloc((np ? np : 1) * sizeof(double));
-  out->id = (int *)malloc((nres ? nres : 1) * sizeof(int));
-  if (!out->offsets || !out->indices || !out->loop || !out->type || !out->t || !out->id) return FTKX_E_NOMEM;
-  out->offsets[0] = 0;
+  if (const int rc = ftkx::alloc_trajectories(out, nres, np)) return rc;
   for (size_t c = 0; c < nc; c ++)
     for (size_t j = 0; j < pieces[c].size(); j ++) out->offsets[first[c] + j + 1] = out->offsets[first[c] + j] + (long long)(pieces[c][j].e - pieces[c][j].b);
   std::atomic<size_t> next_out{0};

@@ -14,7 +14,6 @@
 // for every record's side of its seed and hop count, the chain ends for the lengths -- with two small exchanges in between (the jump
 // rounds' "done" flag; 16 bytes per curve down, sorted by key on the host, 8 bytes per curve up) and one download of the finished
 // curves: 4 bytes per point and per curve.  No size floor; tags may already be on the device.
-#include <chrono>
 #include "ctx.hpp"
 
 using namespace ftkxh;
@@ -96,33 +95,6 @@ __global__ __launch_bounds__(256) void trace_roots_kernel(int n, int *parent, in
 
 }  // namespace
 
-// device / pinned buffers, kept with the context: tags | nbr | root | deg on both sides, parent and the candidate tables on the device
-static int ensure_trace_buffers(ftkx_ctx *c, int nd, size_t n, int maxnb, const std::vector<int> &cand_off, const std::vector<int> &cand_flat)
-{
-  const size_t per = 8 + (size_t)maxnb * 4 + 4 + 1;
-  const size_t bytes = n * per + 64, tbytes = (cand_off.size() + cand_flat.size()) * sizeof(int);
-  if (c->tr_cap < bytes) {
-    if (c->tr_dev) (void)hipFree(c->tr_dev);
-    if (c->tr_host) (void)hipHostFree(c->tr_host);
-    if (c->tr_parent) (void)hipFree(c->tr_parent);
-    c->tr_dev = nullptr; c->tr_host = nullptr; c->tr_parent = nullptr; c->tr_cap = 0;
-    const size_t cap = bytes + bytes / 4;
-    HIP_TRY(c, hipMalloc(&c->tr_dev, cap));
-    HIP_TRY(c, hipHostMalloc(&c->tr_host, cap, hipHostMallocNonCoherent));
-    HIP_TRY(c, hipMalloc(&c->tr_parent, (cap / per + 1) * sizeof(int)));
-    c->tr_cap = cap;
-  }
-  if (c->tr_tables_nd != nd) {
-    if (c->tr_tables) (void)hipFree(c->tr_tables);
-    c->tr_tables = nullptr; c->tr_tables_nd = 0;
-    HIP_TRY(c, hipMalloc(&c->tr_tables, tbytes));
-    HIP_TRY(c, hipMemcpy(c->tr_tables, cand_off.data(), cand_off.size() * sizeof(int), hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy((int *)c->tr_tables + cand_off.size(), cand_flat.data(), cand_flat.size() * sizeof(int), hipMemcpyHostToDevice));
-    c->tr_tables_nd = nd;
-  }
-  return FTKX_OK;
-}
-
 // the candidate tables of the neighbour search (trace.cpp), built once per thread and dimension; returns the slots per record
 static int trace_tables(int nd, const std::vector<int> **off, const std::vector<int> **flat)
 {
@@ -134,33 +106,56 @@ static int trace_tables(int nd, const std::vector<int> **off, const std::vector<
   return maxnb_of[w];
 }
 
-static TraceGeom trace_geom(int nd, const long long domain_st[3], const long long domain_sz[3], int maxnb)
+// the blocks of one call's layout, and the candidate tables of its dimension on the device
+static int reserve_trace(ftkx_ctx *c, int nd, const TraceLayout &L, const std::vector<int> &cand_off, const std::vector<int> &cand_flat)
+{
+  ftkx_pass2_state &s = c->p2;
+  if (const int rc = s.trace_dev.reserve(c, L.dev_bytes, false)) return rc;
+  if (const int rc = s.trace_host.reserve(c, L.host_bytes, true)) return rc;
+  if (s.tables_nd != nd) {
+    s.tables_nd = 0;
+    if (const int rc = s.tables.reserve(c, (cand_off.size() + cand_flat.size()) * sizeof(int), false)) return rc;
+    HIP_TRY(c, hipMemcpy(s.tables.p, cand_off.data(), cand_off.size() * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy((int *)s.tables.p + cand_off.size(), cand_flat.data(), cand_flat.size() * sizeof(int), hipMemcpyHostToDevice));
+    s.tables_nd = nd;
+  }
+  return FTKX_OK;
+}
+
+// the geometry of the neighbour search and (o given) the ordering's copy of it
+static TraceGeom trace_geom(int nd, const long long domain_st[3], const long long domain_sz[3], int maxnb, ftkx::TraceOrder *o = nullptr)
 {
   TraceGeom g;
   memset(&g, 0, sizeof(g));
   g.nd = nd; g.ntypes = nd == 2 ? 12 : 60; g.maxnb = maxnb;
   g.prod[0] = 1;
   for (int a = 0; a < nd; a ++) { g.lb[a] = domain_st[a]; g.sz[a] = domain_sz[a]; g.prod[a + 1] = g.prod[a] * (unsigned long long)domain_sz[a]; }
+  if (o) {
+    o->nd = nd; o->ntypes = g.ntypes; o->maxnb = maxnb;
+    for (int a = 0; a < 3; a ++) o->sz[a] = g.sz[a];
+    for (int a = 0; a < 4; a ++) o->prod[a] = g.prod[a];
+  }
   return g;
 }
 
-// the ordering's arrays inside the context's block
-static void order_arrays(const ftkx_ctx *c, ftkx::TraceOrder &o)
+// neighbours, unite, roots: queued on the layout's arrays in the context's device block
+static void launch_trace_front(ftkx_ctx *c, const TraceGeom &g, const TraceLayout &L, const u64 *d_tags, size_t n, size_t n_cand_off)
 {
-  const size_t cap = c->tr_ord_cap;
-  u64 *q = (u64 *)c->tr_ord;
-  o.key = q; q += cap; o.best = q; q += cap; o.info = q; q += 2 * cap; o.link = q; q += 2 * cap;
-  int *r = (int *)q;
-  o.on = r; r += 2 * cap; o.cnt = r; r += 2 * cap; o.cyc = r; r += cap; o.seedpos = r; r += cap; o.seedlist = r; r += cap;
-  o.indices = r; r += cap; o.loop = r; r += cap; o.off = r; r += cap; o.sorted = r; r += cap;
-  o.counters = (unsigned *)r;
+  void *d = c->p2.trace_dev.p;
+  int *nbr = L.nbr.in<int>(d), *root = L.root.in<int>(d), *parent = L.parent.in<int>(d);
+  unsigned char *deg = L.deg.in<unsigned char>(d);
+  const int *d_off = (const int *)c->p2.tables.p, *d_cand = d_off + n_cand_off;
+  const unsigned grid = (unsigned)((n + 255) / 256);
+  hipLaunchKernelGGL(trace_neighbours_kernel, dim3(grid), dim3(256), 0, c->stream, g, d_tags, (int)n, d_off, d_cand, nbr, deg, parent);
+  hipLaunchKernelGGL(trace_unite_kernel, dim3(grid), dim3(256), 0, c->stream, (int)n, g.maxnb, (const int *)nbr, (const unsigned char *)deg, parent);
+  hipLaunchKernelGGL(trace_roots_kernel, dim3(grid), dim3(256), 0, c->stream, (int)n, parent, root);
 }
 
 void ftkxh::trace_device_curves(const ftkx_ctx *c, const int **indices, const int **off, const int **loop)
 {
-  ftkx::TraceOrder o;
-  order_arrays(c, o);
-  *indices = o.indices; *off = o.off; *loop = o.loop;
+  const OrderLayout &L = c->p2.order;
+  void *d = c->p2.order_dev.p;
+  *indices = L.indices.in<int>(d); *off = L.off.in<int>(d); *loop = L.loop.in<int>(d);
 }
 
 extern "C" {
@@ -170,45 +165,27 @@ static int trace_curves_ctx_impl(ftkx_ctx *c, int nd, const long long domain_st[
   auto tag_of = [&](size_t i) { return tags ? tags[i] : recs[i].tag; };
   auto on_host = [&]() { return tags ? ftkx::trace_curves_tags(nd, domain_st, domain_sz, tags, n, out) : ftkx_trace_curves(nd, domain_st, domain_sz, recs, n, out); };
   if (!c) return on_host();
-  c->tr_last_path = 0;
-  constexpr bool timing = false;      // (phase timing to stderr: a debugging aid, compiled out)
-  const auto tp0 = std::chrono::steady_clock::now();
+  c->p2.trace_last_path = 0;
   if ((nd != 2 && nd != 3) || !domain_st || !domain_sz || (!recs && !tags && n) || !out) return fail(c, FTKX_E_INVALID, "ftkx_trace_curves_ctx: bad arguments");
   // few records, or tags that do not come strictly ascending (the sweep delivers them so): the host does it all
   bool ascending = n < (1u << 30);
   for (size_t i = 1; i < n && ascending; i ++) ascending = tag_of(i - 1) < tag_of(i);
   if (n < 4096 || !ascending) return on_host();
   HIP_TRY(c, hipSetDevice(c->device));
-  c->tr_last_path = 1;
+  c->p2.trace_last_path = 1;
   const std::vector<int> *p_off, *p_flat;
   const int maxnb = trace_tables(nd, &p_off, &p_flat);
-  const std::vector<int> &cand_off = *p_off, &cand_flat = *p_flat;
-  if (const int rc = ensure_trace_buffers(c, nd, n, maxnb, cand_off, cand_flat)) return rc;
-  // layout (8-byte aligned pieces): tags u64[n] | nbr int[n * maxnb] | root int[n] | deg u8[n]
-  const size_t off_nbr = n * 8, off_root = off_nbr + n * (size_t)maxnb * 4, off_deg = off_root + n * 4;
-  u64 *h_tags = (u64 *)c->tr_host;
+  const TraceLayout L(maxnb, n);
+  if (const int rc = reserve_trace(c, nd, L, *p_off, *p_flat)) return rc;
+  char *h = (char *)c->p2.trace_host.p, *d = (char *)c->p2.trace_dev.p;
+  u64 *h_tags = L.tags.in<u64>(h);
   if (tags) memcpy(h_tags, tags, n * sizeof(u64)); else for (size_t i = 0; i < n; i ++) h_tags[i] = recs[i].tag;
-  char *d = (char *)c->tr_dev;
-  const auto tp1 = std::chrono::steady_clock::now();
-  HIP_TRY(c, hipMemcpyAsync(d, c->tr_host, n * 8, hipMemcpyHostToDevice, c->stream));
-  const TraceGeom g = trace_geom(nd, domain_st, domain_sz, maxnb);
-  const unsigned grid = (unsigned)((n + 255) / 256);
-  const int *d_off = (const int *)c->tr_tables, *d_cand = d_off + cand_off.size();
-  hipLaunchKernelGGL(trace_neighbours_kernel, dim3(grid), dim3(256), 0, c->stream, g, (const u64 *)d, (int)n, d_off, d_cand, (int *)(d + off_nbr), (unsigned char *)(d + off_deg), (int *)c->tr_parent);
-  hipLaunchKernelGGL(trace_unite_kernel, dim3(grid), dim3(256), 0, c->stream, (int)n, maxnb, (const int *)(d + off_nbr), (const unsigned char *)(d + off_deg), (int *)c->tr_parent);
-  hipLaunchKernelGGL(trace_roots_kernel, dim3(grid), dim3(256), 0, c->stream, (int)n, (int *)c->tr_parent, (int *)(d + off_root));
+  HIP_TRY(c, hipMemcpyAsync(d + L.tags.at, h_tags, n * 8, hipMemcpyHostToDevice, c->stream));
+  launch_trace_front(c, trace_geom(nd, domain_st, domain_sz, maxnb), L, L.tags.in<const u64>(d), n, p_off->size());
   HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipMemcpyAsync((char *)c->tr_host + off_nbr, d + off_nbr, off_deg + n - off_nbr, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(h + L.nbr.at, d + L.nbr.at, L.down_bytes(), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  const auto tp2 = std::chrono::steady_clock::now();
-  const char *h = (const char *)c->tr_host;
-  const int rc = ftkx::trace_curves_with(nd, domain_st, domain_sz, h_tags, n, out, (const int *)(h + off_nbr), (const unsigned char *)(h + off_deg), (const int *)(h + off_root), maxnb);
-  if (timing) {
-    const auto tp3 = std::chrono::steady_clock::now();
-    auto us = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
-    fprintf(stderr, "ftkx_trace_curves_ctx: %zu records, maxnb %d: checks + tags %.0f us, device (up, 3 kernels, down %zu bytes) %.0f us, host (seeds, walks, curves) %.0f us\n",
-            n, maxnb, us(tp0, tp1), off_deg + n - off_nbr, us(tp1, tp2), us(tp2, tp3));
-  }
+  const int rc = ftkx::trace_curves_with(nd, domain_st, domain_sz, h_tags, n, out, L.nbr.in<const int>(h), L.deg.in<const unsigned char>(h), L.root.in<const int>(h), maxnb);
   if (rc != FTKX_OK) return fail(c, rc, "ftkx_trace_curves_ctx: tracing failed (%d)", rc);
   return FTKX_OK;
 }
@@ -220,33 +197,6 @@ int ftkx_trace_curves_ctx(ftkx_ctx *c, int nd, const long long domain_st[3], con
 int ftkx_trace_curves_tags_ctx(ftkx_ctx *c, int nd, const long long domain_st[3], const long long domain_sz[3], const unsigned long long *tags, size_t n, ftkx_curves *out)
 { return trace_curves_ctx_impl(c, nd, domain_st, domain_sz, nullptr, tags, n, out); }
 
-// the ordering's device arrays (TraceOrder) and pinned staging for `cap` records
-static constexpr size_t kOrdDevPer = 6 * 8 + 11 * 4;                     // key, best, info[2], link[2] | on[2], cnt[2], cyc, seedpos, seedlist, indices, loop, off, sorted
-static constexpr size_t kOrdHostPer = 16 + 8 + 8;                        // info | off, sorted | indices, loop
-static int ensure_order_buffers(ftkx_ctx *c, size_t n)
-{
-  if (c->tr_ord_cap >= n + 2) return FTKX_OK;
-  if (c->tr_ord) (void)hipFree(c->tr_ord);
-  if (c->tr_ord_host) (void)hipHostFree(c->tr_ord_host);
-  c->tr_ord = nullptr; c->tr_ord_host = nullptr; c->tr_ord_cap = 0;
-  const size_t cap = n + n / 4 + 64;
-  HIP_TRY(c, hipMalloc(&c->tr_ord, cap * kOrdDevPer + TRO_WORDS * sizeof(unsigned)));
-  HIP_TRY(c, hipHostMalloc(&c->tr_ord_host, cap * kOrdHostPer + TRO_WORDS * sizeof(unsigned), hipHostMallocNonCoherent));
-  c->tr_ord_cap = cap;
-  return FTKX_OK;
-}
-
-static int empty_curves(ftkx_curves *out)
-{
-  memset(out, 0, sizeof(*out));
-  out->offsets = (long long *)malloc(sizeof(long long));
-  out->indices = (long long *)malloc(sizeof(long long));
-  out->loop = (int *)malloc(sizeof(int));
-  if (!out->offsets || !out->indices || !out->loop) return FTKX_E_NOMEM;
-  out->offsets[0] = 0;
-  return FTKX_OK;
-}
-
 int ftkx_trace_curves_device(ftkx_ctx *c, int nd, const long long domain_st[3], const long long domain_sz[3], const unsigned long long *tags, size_t n, int tags_on_device, ftkx_curves *out)
 {
   if (!c) return FTKX_E_INVALID;
@@ -255,8 +205,8 @@ int ftkx_trace_curves_device(ftkx_ctx *c, int nd, const long long domain_st[3], 
   // FTKX_TRACE_PHASES=1: the host waits after every phase and prints its time (a measuring aid: the waits cost time of their own)
   static const bool phases = [] { const char *e = getenv("FTKX_TRACE_PHASES"); return e && atoi(e) > 0; }();
   if (n == 0) {
-    c->tr_last_path = 2;
-    const int rc = empty_curves(out);
+    c->p2.trace_last_path = 2;
+    const int rc = ftkx::alloc_curves(out, 0, 0);
     return rc == FTKX_OK ? rc : fail(c, rc, "ftkx_trace_curves_device: out of memory");
   }
   HIP_TRY(c, hipSetDevice(c->device));
@@ -286,37 +236,29 @@ int ftkx_trace_curves_device(ftkx_ctx *c, int nd, const long long domain_st[3], 
   }
   if (!covered) return other_way();
 
-  const auto tp0 = std::chrono::steady_clock::now();
-  auto lap = [&](const char *what, size_t count) -> int {
-    static thread_local std::chrono::steady_clock::time_point last;
-    if (!phases) return FTKX_OK;
-    if (!what) { last = std::chrono::steady_clock::now(); return FTKX_OK; }
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    const auto now = std::chrono::steady_clock::now();
-    fprintf(stderr, "ftkx_trace_curves_device: %-28s %8.1f us  (%zu)\n", what, std::chrono::duration<double, std::micro>(now - last).count(), count);
-    last = now;
-    return FTKX_OK;
-  };
+  ftkx_phase_clock clock{phases, c->stream, "ftkx_trace_curves_device"};
   const std::vector<int> *p_off, *p_flat;
   const int maxnb = trace_tables(nd, &p_off, &p_flat);
-  if (const int rc = ensure_trace_buffers(c, nd, n, maxnb, *p_off, *p_flat)) return rc;
-  if (const int rc = ensure_order_buffers(c, n)) return rc;
-  const size_t off_nbr = n * 8, off_root = off_nbr + n * (size_t)maxnb * 4, off_deg = off_root + n * 4;
-  char *d = (char *)c->tr_dev;
-  const size_t cap = c->tr_ord_cap;
+  const TraceLayout L(maxnb, n);
+  const OrderLayout O(n);
+  if (const int rc = reserve_trace(c, nd, L, *p_off, *p_flat)) return rc;
+  if (const int rc = c->p2.order_dev.reserve(c, O.dev_bytes, false)) return rc;
+  if (const int rc = c->p2.order_host.reserve(c, O.host_bytes, true)) return rc;
+  void *d = c->p2.trace_dev.p, *od = c->p2.order_dev.p, *oh = c->p2.order_host.p;
   ftkx::TraceOrder o;
   memset(&o, 0, sizeof(o));
-  o.n = (int)n; o.nd = nd; o.ntypes = ntypes; o.maxnb = maxnb;
-  o.prod[0] = 1;
-  for (int a = 0; a < nd; a ++) { o.sz[a] = domain_sz[a]; o.prod[a + 1] = o.prod[a] * (u64)domain_sz[a]; }
-  order_arrays(c, o);
-  // pinned: info u64[2 cap] | off int[cap] | sorted int[cap] | indices int[cap] | loop int[cap] | counters
-  u64 *h_info = (u64 *)c->tr_ord_host;
-  int *h_off = (int *)(h_info + 2 * cap), *h_sorted = h_off + cap, *h_indices = h_sorted + cap, *h_loop = h_indices + cap;
-  unsigned *h_counters = (unsigned *)(h_loop + cap);
+  o.n = (int)n;
+  const TraceGeom g = trace_geom(nd, domain_st, domain_sz, maxnb, &o);
+  o.key = O.key.in<u64>(od); o.best = O.best.in<u64>(od); o.info = O.info.in<u64>(od); o.link = O.link.in<u64>(od);
+  o.on = O.on.in<int>(od); o.cnt = O.cnt.in<int>(od); o.cyc = O.cyc.in<int>(od); o.seedpos = O.seedpos.in<int>(od); o.seedlist = O.seedlist.in<int>(od);
+  o.indices = O.indices.in<int>(od); o.loop = O.loop.in<int>(od); o.off = O.off.in<int>(od); o.sorted = O.sorted.in<int>(od);
+  o.counters = O.counters.in<unsigned>(od);
+  u64 *h_info = O.h_info.in<u64>(oh);
+  int *h_off = O.h_off.in<int>(oh), *h_sorted = O.h_sorted.in<int>(oh), *h_indices = O.h_indices.in<int>(oh), *h_loop = O.h_loop.in<int>(oh);
+  unsigned *h_counters = O.h_counters.in<unsigned>(oh);
 
-  lap(nullptr, 0);
-  const u64 *d_tags = (const u64 *)d;
+  clock.start();
+  const u64 *d_tags = L.tags.in<const u64>(d);
   if (tags_on_device) {
     // one check kernel and its flag: strictly ascending, no timestep beyond the key's 24 bits
     d_tags = (const u64 *)tags;
@@ -327,22 +269,17 @@ int ftkx_trace_curves_device(ftkx_ctx *c, int nd, const long long domain_st[3], 
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (h_counters[TRO_CHECK]) return other_way();
   } else {
-    memcpy(c->tr_host, tags, n * sizeof(u64));
-    HIP_TRY(c, hipMemcpyAsync(d, c->tr_host, n * 8, hipMemcpyHostToDevice, c->stream));
+    memcpy(c->p2.trace_host.p, tags, n * sizeof(u64));
+    HIP_TRY(c, hipMemcpyAsync(L.tags.in<u64>(d), c->p2.trace_host.p, n * 8, hipMemcpyHostToDevice, c->stream));
   }
-  if (const int rc = lap(tags_on_device ? "check" : "upload", n)) return rc;
-  o.tags = d_tags; o.nbr = (const int *)(d + off_nbr); o.deg = (const unsigned char *)(d + off_deg); o.root = (const int *)(d + off_root);
-  const TraceGeom g = trace_geom(nd, domain_st, domain_sz, maxnb);
-  const unsigned grid = (unsigned)((n + 255) / 256);
-  const int *d_off = (const int *)c->tr_tables, *d_cand = d_off + p_off->size();
-  hipLaunchKernelGGL(trace_neighbours_kernel, dim3(grid), dim3(256), 0, c->stream, g, d_tags, (int)n, d_off, d_cand, (int *)(d + off_nbr), (unsigned char *)(d + off_deg), (int *)c->tr_parent);
-  hipLaunchKernelGGL(trace_unite_kernel, dim3(grid), dim3(256), 0, c->stream, (int)n, maxnb, o.nbr, o.deg, (int *)c->tr_parent);
-  hipLaunchKernelGGL(trace_roots_kernel, dim3(grid), dim3(256), 0, c->stream, (int)n, (int *)c->tr_parent, (int *)(d + off_root));
+  HIP_TRY(c, clock.lap(tags_on_device ? "check" : "upload", n));
+  o.tags = d_tags; o.nbr = L.nbr.in<const int>(d); o.deg = L.deg.in<const unsigned char>(d); o.root = L.root.in<const int>(d);
+  launch_trace_front(c, g, L, d_tags, n, p_off->size());
   HIP_TRY(c, hipGetLastError());
-  if (const int rc = lap("neighbours, unite, roots", n)) return rc;
+  HIP_TRY(c, clock.lap("neighbours, unite, roots", n));
   ftkx::launch_trace_order_begin(o, c->stream);
   HIP_TRY(c, hipGetLastError());
-  if (const int rc = lap("keys, seeds, arcs", n)) return rc;
+  HIP_TRY(c, clock.lap("keys, seeds, arcs", n));
   // pointer jumping: a launch doubles what every arc knows at least; the flag of the last launch is read every third one
   int max_rounds = 2;
   while (max_rounds < 40 && (1ull << (max_rounds - 1)) < 2 * (u64)n) max_rounds ++;
@@ -356,14 +293,14 @@ int ftkx_trace_curves_device(ftkx_ctx *c, int nd, const long long domain_st[3], 
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     done = h_counters[TRO_FLAGS + rounds - 1] == 0;
   }
-  if (const int rc = lap("ordering rounds", (size_t)rounds)) return rc;
+  HIP_TRY(c, clock.lap("ordering rounds", (size_t)rounds));
   const size_t nseeds = h_counters[TRO_SEEDS], nspecial = h_counters[TRO_SPECIAL];
   if (!done || nseeds > n || nspecial > n) return other_way();        // (links that do not end: not a set of paths and cycles)
   ftkx::launch_trace_order_ends(o, (unsigned)nseeds, c->stream);
   HIP_TRY(c, hipGetLastError());
   if (nseeds) HIP_TRY(c, hipMemcpyAsync(h_info, o.info, nseeds * 16, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (const int rc = lap("ends, seeds down", nseeds)) return rc;
+  HIP_TRY(c, clock.lap("ends, seeds down", nseeds));
   // the curves in the order of their seeds' keys (the host path sorts the same pairs)
   struct SeedInfo { u64 key, rec_len; };
   SeedInfo *si = (SeedInfo *)h_info;
@@ -378,7 +315,7 @@ int ftkx_trace_curves_device(ftkx_ctx *c, int nd, const long long domain_st[3], 
   }
   h_off[nseeds] = (int)npoints;
   if (!sane || npoints + nspecial != n) return other_way();
-  if (const int rc = lap("seed sort (host)", nseeds)) return rc;
+  HIP_TRY(c, clock.lap("seed sort (host)", nseeds));
   if (nseeds) {
     HIP_TRY(c, hipMemcpyAsync(o.off, h_off, (nseeds + 1) * sizeof(int), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(o.sorted, h_sorted, nseeds * sizeof(int), hipMemcpyHostToDevice, c->stream));
@@ -390,24 +327,21 @@ int ftkx_trace_curves_device(ftkx_ctx *c, int nd, const long long domain_st[3], 
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (h_counters[TRO_ERROR]) return other_way();
   }
-  if (const int rc = lap("scatter, curves down", npoints)) return rc;
-  memset(out, 0, sizeof(*out));
-  out->n_curves = nseeds; out->n_points = npoints; out->n_special = nspecial;
-  out->offsets = (long long *)malloc((nseeds + 1) * sizeof(long long));
-  out->indices = (long long *)malloc((npoints ? npoints : 1) * sizeof(long long));
-  out->loop = (int *)malloc((nseeds ? nseeds : 1) * sizeof(int));
-  if (!out->offsets || !out->indices || !out->loop) { ftkx_free_curves(out); return fail(c, FTKX_E_NOMEM, "ftkx_trace_curves_device: out of memory"); }
+  HIP_TRY(c, clock.lap("scatter, curves down", npoints));
+  if (const int rc = ftkx::alloc_curves(out, nseeds, npoints)) return fail(c, rc, "ftkx_trace_curves_device: out of memory");
+  out->n_special = nspecial;
   for (size_t k = 0; k <= nseeds; k ++) out->offsets[k] = h_off[k];
   bool filled = true;
   for (size_t k = 0; k < npoints; k ++) { out->indices[k] = h_indices[k]; filled = filled && h_indices[k] >= 0; }
   if (nseeds) memcpy(out->loop, h_loop, nseeds * sizeof(int));
   if (!filled) { ftkx_free_curves(out); return other_way(); }
-  c->tr_last_path = 2;
+  c->p2.trace_last_path = 2;
+  c->p2.order = O;
   if (phases) fprintf(stderr, "ftkx_trace_curves_device: %zu records, %zu curves, %zu special, %d rounds: %.1f us in all (with the waits of the phase timing)\n", n, nseeds, nspecial, rounds,
-                      std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tp0).count());
+                      clock.us_in_all());
   return FTKX_OK;
 }
 
-int ftkx_trace_last_path(const ftkx_ctx *c) { return c ? c->tr_last_path : 0; }
+int ftkx_trace_last_path(const ftkx_ctx *c) { return c ? c->p2.trace_last_path : 0; }
 
 }  // extern "C"

@@ -135,6 +135,35 @@ def test_pass2_on_device(ctxs):
         assert np.array_equal(getattr(ts2, f), getattr(ts1, f)), f
 
 
+def test_buffers_grow_shrink_and_change_dimension():
+    """one context through calls of changing size and dimension: its pass-2 blocks are sized by bytes and shared by 2D (6 neighbour slots per
+    record) and 3D (8) traces, so a block that a 3D call of 100 records sized is next addressed by a 2D call of 150; then calls that grow
+    them, within the quarter of headroom and past it, small calls in large blocks, post-processing, and the trace with host walks"""
+    import ftk_amd
+    g3, dom3, recs3 = fixture_records("moving_extremum_3d_21x21x21x4_overflow")
+    g2, dom2, recs2 = fixture_records("woven_31x37x32")
+    gw, domw, recsw = fixture_records("woven_128x128x10")
+    assert (g3["nd"], g2["nd"], gw["nd"]) == (3, 2, 2) and len(recs2) == 4491 and len(recsw) == 7357
+    ctx = ftk_amd.Context(2)
+    try:
+        steps = [(3, dom3, recs3[:100]), (2, dom2, recs2[:150]), (2, dom2, recs2), (2, domw, recsw), (2, dom2, recs2[:150])]
+        for k, (nd, dom, recs) in enumerate(steps):
+            dev = ftk_amd.trace_curves(nd, dom, recs, ctx=ctx, device=True)
+            assert ctx.trace_last_path() == 2, k
+            assert_same_curves(dev, ftk_amd.trace_curves(nd, dom, recs), "step %d" % (k + 1))
+        c1, l1, n1, ts1, _a, _b = ftk_amd.pass2(2, dom2, recs2)
+        c2, l2, n2, ts2, _a, _b = ftk_amd.pass2(2, dom2, recs2, ctx=ctx, device=True, post_device=True)
+        assert ctx.trace_last_path() == 2 and ctx.post_process_last_path() == 2
+        assert_same_curves((c2, l2, n2), (c1, l1, n1), "step 6")
+        for f in ("offsets", "indices", "type", "t", "loop", "id"):
+            assert np.array_equal(getattr(ts2, f), getattr(ts1, f)), f
+        got = ftk_amd.trace_curves(2, dom2, recs2, ctx=ctx)       # device phases, host walks: the same trace block
+        assert ctx.trace_last_path() == 1
+        assert_same_curves(got, (c1, l1, n1), "step 7")
+    finally:
+        ctx.close()
+
+
 def test_tracker_traces_on_device():
     """a tracker over a small woven series, finalize() + post_process() with set_trace_on_device(True) and without: the same curves and
     trajectories; the first run's trace went all the way on the device"""
