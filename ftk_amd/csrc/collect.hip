@@ -113,33 +113,27 @@ int sort_hits_on_device(ftkx_ctx *c, size_t n, int key_bits)
 {
   if (n == 0) return FTKX_OK;                                // (no tiles: nothing to launch)
   if (n >= (size_t)1 << 31) return fail(c, FTKX_E_UNSUPPORTED, "sort_hits_on_device: %zu records (indices are 32-bit)", n);
-  if (c->sort_cap < n) {
-    for (void *p : {(void *)c->d_sorted, (void *)c->d_keys, (void *)c->d_idx, c->d_sort_tmp}) if (p) (void)hipFree(p);
-    c->d_sorted = nullptr; c->d_keys = nullptr; c->d_idx = nullptr; c->d_sort_tmp = nullptr; c->sort_cap = 0;
-    const size_t cap = n + n / 4 + 1024;
-    HIP_TRY(c, hipMalloc((void **)&c->d_sorted, cap * sizeof(ftkx_cp_t)));
-    HIP_TRY(c, hipMalloc((void **)&c->d_keys, 2 * cap * sizeof(u64)));
-    HIP_TRY(c, hipMalloc((void **)&c->d_idx, 2 * cap * sizeof(unsigned)));
-    c->sort_tmp_bytes = 16 * ((cap + kRsTile - 1) / kRsTile) * sizeof(unsigned);      // digit counts per tile
-    HIP_TRY(c, hipMalloc(&c->d_sort_tmp, c->sort_tmp_bytes));
-    c->sort_cap = cap;
-  }
-  const size_t cap = c->sort_cap;
-  hipLaunchKernelGGL(sort_keys_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->d_hits, n, c->d_keys, c->d_idx);
+  const size_t room = n + n / 4 + 1024;
+  auto tile_counts = [](size_t records) { return 16 * ((records + kRsTile - 1) / kRsTile) * sizeof(unsigned); };      // digit counts per tile
+  int rc;
+  if ((rc = c->d_sorted.reserve(c, n * sizeof(ftkx_cp_t), room * sizeof(ftkx_cp_t))) || (rc = c->d_keys.reserve(c, 2 * n * sizeof(u64), 2 * room * sizeof(u64))) ||
+      (rc = c->d_idx.reserve(c, 2 * n * sizeof(unsigned), 2 * room * sizeof(unsigned))) || (rc = c->d_sort_tmp.reserve(c, tile_counts(n), tile_counts(room)))) return rc;
+  const size_t cap = std::min(c->d_keys.count<u64>(), c->d_idx.count<unsigned>()) / 2;      // where the second half of the ping-pong buffers starts: n or more
+  hipLaunchKernelGGL(sort_keys_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->d_hits.as<ftkx_cp_t>(), n, c->d_keys.as<u64>(), c->d_idx.as<unsigned>());
   const unsigned ntiles = (unsigned)((n + kRsTile - 1) / kRsTile);
-  unsigned *counts = (unsigned *)c->d_sort_tmp;
+  unsigned *counts = (unsigned *)c->d_sort_tmp.p;
   int from = 0;                                              // which half of the ping-pong buffers holds the pairs
   for (int shift = 0; shift < key_bits; shift += 4) {
-    const u64 *kin = c->d_keys + (from ? cap : 0);
-    const unsigned *iin = c->d_idx + (from ? cap : 0);
-    u64 *kout = c->d_keys + (from ? 0 : cap);
-    unsigned *iout = c->d_idx + (from ? 0 : cap);
+    const u64 *kin = c->d_keys.as<u64>() + (from ? cap : 0);
+    const unsigned *iin = c->d_idx.as<unsigned>() + (from ? cap : 0);
+    u64 *kout = c->d_keys.as<u64>() + (from ? 0 : cap);
+    unsigned *iout = c->d_idx.as<unsigned>() + (from ? 0 : cap);
     hipLaunchKernelGGL(rs_count_kernel, dim3(ntiles), dim3(kRsThreads), 0, c->stream, kin, n, shift, counts, ntiles);
     hipLaunchKernelGGL(rs_scan_kernel, dim3(1), dim3(1024), 0, c->stream, counts, 16u * ntiles);
     hipLaunchKernelGGL(rs_scatter_kernel, dim3(ntiles), dim3(kRsThreads), 0, c->stream, kin, iin, n, shift, counts, ntiles, kout, iout);
     from ^= 1;
   }
-  hipLaunchKernelGGL(sort_gather_kernel, dim3((unsigned)((n * 9 + 255) / 256)), dim3(256), 0, c->stream, c->d_hits, c->d_idx + (from ? cap : 0), n, c->d_sorted);
+  hipLaunchKernelGGL(sort_gather_kernel, dim3((unsigned)((n * 9 + 255) / 256)), dim3(256), 0, c->stream, c->d_hits.as<ftkx_cp_t>(), c->d_idx.as<unsigned>() + (from ? cap : 0), n, c->d_sorted.as<ftkx_cp_t>());
   HIP_TRY(c, hipGetLastError());
   return FTKX_OK;
 }
@@ -264,53 +258,52 @@ int run_batch(ftkx_ctx *c, const double *sparse_field, bool cull_done)
   if (total) {
     int rc = ensure_desc(c, total);
     if (rc) return rc;
-    Fields *hf = (Fields *)((char *)c->h_desc + fields_off);
+    Fields *hf = (Fields *)((char *)c->h_desc.p + fields_off);
     for (size_t i = 0; i < subs.size(); i ++) {
-      if (!subs[i].jobs.empty()) memcpy((char *)c->h_desc + job_off[i], subs[i].jobs.data(), subs[i].jobs.size() * sizeof(MaskJob));
+      if (!subs[i].jobs.empty()) memcpy((char *)c->h_desc.p + job_off[i], subs[i].jobs.data(), subs[i].jobs.size() * sizeof(MaskJob));
       if (!subs[i].steps.empty()) memcpy(hf + step_base[i], subs[i].steps.data(), subs[i].steps.size() * sizeof(Fields));
     }
     for (size_t i = 0; i < tile_fields.size(); i ++) hf[tile_base + i] = tile_fields[i];
-    HIP_TRY(c, hipMemcpyAsync(c->d_desc, c->h_desc, total, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->d_desc.p, c->h_desc.p, total, hipMemcpyHostToDevice, c->stream));
   }
-  const Fields *d_fields = (const Fields *)((char *)c->d_desc + fields_off);
+  const Fields *d_fields = (const Fields *)((char *)c->d_desc.p + fields_off);
   for (TileParams &p : tiles) { p.step += (int)tile_base; p.steps = d_fields + p.step; }
   if (cull_only && (subs.size() > 1 || !tiles.empty()))
     return fail(c, FTKX_E_UNSUPPORTED, "ftkx_sweep_cull: the batch needs masks under two factors or the tile path (send the slice itself)");
   for (size_t i = 0; i < subs.size(); i ++) {
     const Sub &sb = subs[i];
     if (sb.steps.empty()) continue;
-    const MaskJob *d_jobs = (const MaskJob *)((char *)c->d_desc + job_off[i]);
+    const MaskJob *d_jobs = (const MaskJob *)((char *)c->d_desc.p + job_off[i]);
     const Fields *d_steps = d_fields + step_base[i];
     if (!sb.jobs.empty()) { ev_begin(c, K_MASK); ftkx::launch_masks(m, d_jobs, (int)sb.jobs.size(), c->stream); ev_end(c); }
     // the survivor list is shared by the sub-batches of one collect: the exact kernel of sub-batch i must not re-test the
     // survivors of sub-batch i-1, so each sub-batch gets its own list segment by resetting the list counter in between
     if (i > 0) {
-      HIP_TRY(c, hipMemsetAsync(c->sr_tail[0].counters + ftkx::CNT_SURVIVOR_LIST, 0, sizeof(u64), c->stream));
-      HIP_TRY(c, hipMemsetAsync(c->sr_tail[0].counters + ftkx::CNT_REFINE_LIST, 0, sizeof(u64), c->stream));
+      HIP_TRY(c, hipMemsetAsync(c->sr_tail[0].counters.as<u64>() + ftkx::CNT_SURVIVOR_LIST, 0, sizeof(u64), c->stream));
+      HIP_TRY(c, hipMemsetAsync(c->sr_tail[0].counters.as<u64>() + ftkx::CNT_REFINE_LIST, 0, sizeof(u64), c->stream));
     }
     if (cull_done) {    // the survivor list of exactly these steps is on the device already (cull-ahead, see ftkx_ctx::ahead)
       if (subs.size() != 1 || !sb.jobs.empty()) return fail(c, FTKX_E_DEVICE, "internal: cull-ahead taken over by a batch that rebuilds masks");
     } else {
       ev_begin(c, K_CULL);
-      if (two_level) ftkx::launch_cull_two_level(m, d_steps, (int)sb.steps.size(), c->sr_tail[0].refine, c->sr_tail[0].refine_capacity, c->sr_tail[0].list, c->sr_tail[0].list_capacity, c->stream);
-      else ftkx::launch_cull(m, d_steps, (int)sb.steps.size(), c->sr_tail[0].list, c->sr_tail[0].list_capacity, c->stream);
+      if (two_level) ftkx::launch_cull_two_level(m, d_steps, (int)sb.steps.size(), c->sr_tail[0].refine.as<u64>(), c->sr_tail[0].refine_capacity, c->sr_tail[0].list.as<u64>(), c->sr_tail[0].list_capacity, c->stream);
+      else ftkx::launch_cull(m, d_steps, (int)sb.steps.size(), c->sr_tail[0].list.as<u64>(), c->sr_tail[0].list_capacity, c->stream);
       ev_end(c);
     }
     if (cull_only) {
       // (the exact kernel is what publishes the list peak; without it the host reads the list counter itself)
-      ftkx::launch_sparse_cells(m, d_steps, c->sr_tail[0].list, c->sr_tail[0].list_capacity, sparse_field, c->d_cells, c->cells_cap, c->stream);
+      ftkx::launch_sparse_cells(m, d_steps, c->sr_tail[0].list.as<u64>(), c->sr_tail[0].list_capacity, sparse_field, c->d_cells.as<u64>(), c->d_cells.count<u64>(), c->stream);
       continue;
     }
-    ev_begin(c, K_EXACT); ftkx::launch_exact(m, d_steps, (int)step_base[i], c->sr_tail[0].list, c->sr_tail[0].list_capacity, c->stream); ev_end(c);
+    ev_begin(c, K_EXACT); ftkx::launch_exact(m, d_steps, (int)step_base[i], c->sr_tail[0].list.as<u64>(), c->sr_tail[0].list_capacity, c->stream); ev_end(c);
   }
   if (cull_only) { HIP_TRY(c, hipGetLastError()); return FTKX_OK; }
   if (!tiles.empty()) {
-    if (!c->d_tile_stats) {
-      HIP_TRY(c, hipMalloc((void **)&c->d_tile_stats, 512 * sizeof(u64)));
-      HIP_TRY(c, hipMemsetAsync(c->d_tile_stats, 0, 512 * sizeof(u64), c->stream));
-    }
-    for (TileParams &p : tiles) { p.stats = c->d_tile_stats; ev_begin(c, K_TILE); ftkx::launch_tile(p, c->stream); ev_end(c); }
-    ftkx::launch_tile_stats_fold(c->d_tile_stats, m.counters, c->stream);
+    bool fresh = false;
+    if (const int rc = c->d_tile_stats.reserve(c, 512 * sizeof(u64), 0, nullptr, &fresh)) return rc;
+    if (fresh) HIP_TRY(c, hipMemsetAsync(c->d_tile_stats.p, 0, 512 * sizeof(u64), c->stream));
+    for (TileParams &p : tiles) { p.stats = c->d_tile_stats.as<u64>(); ev_begin(c, K_TILE); ftkx::launch_tile(p, c->stream); ev_end(c); }
+    ftkx::launch_tile_stats_fold(c->d_tile_stats.as<u64>(), m.counters, c->stream);
   }
   // the FP64 half, once for the whole batch: records of every simplex that passed (timed with the kernel family that fed it)
   // (K_EXACT also behind tile requests: K_TILE is the integer test of every simplex and nothing else -- bench.py's int-VALU figure)
@@ -430,18 +423,19 @@ int ftkx_sweep_collect(ftkx_ctx *c, const ftkx_cp_t **out, size_t *n_out)
     use_ahead = ahead_serves_pending(c, m, ftkx::masks_have_summary(m));
     c->ahead.clear();                                        // one use; and a replay below culls afresh
   }
+  const u64 *hc = c->h_counters.as<u64>();
   for (int attempt = 0; ; attempt ++) {
     // (cull-ahead: the counters were zeroed before that cull and hold its list counts)
-    if (!use_ahead) HIP_TRY(c, hipMemsetAsync(c->sr_tail[0].counters, 0, ftkx::CNT_N * sizeof(u64), c->stream));
+    if (!use_ahead) HIP_TRY(c, hipMemsetAsync(c->sr_tail[0].counters.as<u64>(), 0, ftkx::CNT_N * sizeof(u64), c->stream));
     if ((rc = run_batch(c, nullptr, use_ahead))) { c->pending.clear(); return rc; }
     use_ahead = false;
-    HIP_TRY(c, hipMemcpyAsync(c->h_counters, c->sr_tail[0].counters, ftkx::CNT_N * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->h_counters.p, c->sr_tail[0].counters.as<u64>(), ftkx::CNT_N * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     c->ahead_staged = false;
     // (records <= simplices that passed: the 2D type filter may drop some; the pass list shares the hit buffer's capacity)
-    const u64 hits = std::max(c->h_counters[ftkx::CNT_HITS], c->h_counters[ftkx::CNT_PASS]);
-    const u64 listed = c->h_counters[ftkx::CNT_LIST_PEAK], refined = c->h_counters[ftkx::CNT_REFINE_PEAK];
-    const u64 fragile = c->h_counters[ftkx::CNT_FRAGILE];
+    const u64 hits = std::max(hc[ftkx::CNT_HITS], hc[ftkx::CNT_PASS]);
+    const u64 listed = hc[ftkx::CNT_LIST_PEAK], refined = hc[ftkx::CNT_REFINE_PEAK];
+    const u64 fragile = hc[ftkx::CNT_FRAGILE];
     if (hits <= c->capacity && listed <= c->sr_tail[0].list_capacity && refined <= c->sr_tail[0].refine_capacity && fragile <= c->sr_tail[0].fragile_capacity) { ev_harvest(c); break; }
     // a buffer was too small (records / survivors beyond capacity were only counted): grow to what this batch needs, replay it
     for (auto &e : c->events) { ev_give(c, e.second.first); ev_give(c, e.second.second); }
@@ -472,17 +466,17 @@ int ftkx_sweep_collect(ftkx_ctx *c, const ftkx_cp_t **out, size_t *n_out)
     if (want_hits > c->capacity && (rc = ensure_hit_buffer(c, want_hits))) { c->pending.clear(); return rc; }
   }
   c->pending.clear();
-  const size_t n = (size_t)c->h_counters[ftkx::CNT_HITS];
+  const size_t n = (size_t)hc[ftkx::CNT_HITS];
   c->stats.hits = n;
-  c->stats.cells_survived = c->h_counters[ftkx::CNT_CELLS_SURVIVED];
-  c->stats.simplices_tested = c->h_counters[ftkx::CNT_SIMPLICES_TESTED];
+  c->stats.cells_survived = hc[ftkx::CNT_CELLS_SURVIVED];
+  c->stats.simplices_tested = hc[ftkx::CNT_SIMPLICES_TESTED];
   if ((rc = ensure_host_buffer(c, n))) return rc;
   // 3D records whose class hangs on the last bits of pow / acos / cos (an eigenvalue of the Hessian that is zero up to rounding):
   // classified again here, with the libm the reference itself runs on, and written back before the records are sorted.  Rare -- an
   // exactly singular Hessian takes plateaus or lattice-aligned data -- and then one small round trip.
-  if (const u64 nf = c->h_counters[ftkx::CNT_FRAGILE]) {
+  if (const u64 nf = hc[ftkx::CNT_FRAGILE]) {
     std::vector<u64> frag((size_t)nf * 10), pairs((size_t)nf * 2);
-    HIP_TRY(c, hipMemcpyAsync(frag.data(), c->sr_tail[0].fragile, frag.size() * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(frag.data(), c->sr_tail[0].fragile.as<u64>(), frag.size() * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     for (size_t i = 0; i < (size_t)nf; i ++) {
       double A[3][3];
@@ -491,22 +485,22 @@ int ftkx_sweep_collect(ftkx_ctx *c, const ftkx_cp_t **out, size_t *n_out)
       pairs[2 * i + 1] = (u64)ftkx::classify3(A, c->opt.jacobian_symmetric != 0);
     }
     if ((rc = ensure_desc(c, pairs.size() * sizeof(u64)))) return rc;
-    memcpy(c->h_desc, pairs.data(), pairs.size() * sizeof(u64));
-    HIP_TRY(c, hipMemcpyAsync(c->d_desc, c->h_desc, pairs.size() * sizeof(u64), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(patch_types_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, c->stream, c->d_hits, (const u64 *)c->d_desc, (size_t)nf);
+    memcpy(c->h_desc.p, pairs.data(), pairs.size() * sizeof(u64));
+    HIP_TRY(c, hipMemcpyAsync(c->d_desc.p, c->h_desc.p, pairs.size() * sizeof(u64), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(patch_types_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, c->stream, c->d_hits.as<ftkx_cp_t>(), (const u64 *)c->d_desc.p, (size_t)nf);
     HIP_TRY(c, hipGetLastError());
     c->stats.reclassified = nf;
   }
   if (n >= 4096 && n < (1ull << 31)) {
     if ((rc = sort_hits_on_device(c, n, key_bits))) return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->h_hits, c->d_sorted, n * sizeof(ftkx_cp_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->h_hits.as<ftkx_cp_t>(), c->d_sorted.as<ftkx_cp_t>(), n * sizeof(ftkx_cp_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
   } else if (n) {
-    HIP_TRY(c, hipMemcpyAsync(c->h_hits, c->d_hits, n * sizeof(ftkx_cp_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->h_hits.as<ftkx_cp_t>(), c->d_hits.as<ftkx_cp_t>(), n * sizeof(ftkx_cp_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    std::sort(c->h_hits, c->h_hits + n, [](const ftkx_cp_t &a, const ftkx_cp_t &b) { return a.tag < b.tag; });
+    std::sort(c->h_hits.as<ftkx_cp_t>(), c->h_hits.as<ftkx_cp_t>() + n, [](const ftkx_cp_t &a, const ftkx_cp_t &b) { return a.tag < b.tag; });
   }
-  if (out) *out = c->h_hits;
+  if (out) *out = c->h_hits.as<ftkx_cp_t>();
   if (n_out) *n_out = n;
   return FTKX_OK;
 }

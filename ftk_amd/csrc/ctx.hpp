@@ -20,6 +20,7 @@
 #include "split_policy.hpp"
 #include "internal.hpp"
 #include "pass2_layout.hpp"
+#include "ctx_block.hpp"
 
 struct ftkx_phase_clock;
 
@@ -213,18 +214,18 @@ struct ftkx_series_pending {
 
 // what one of the passes in flight writes that the host reads, or that a copy engine reads after the pass
 struct ftkx_series_buffers {
-  u64 *results = nullptr, *h_results = nullptr;       // device block; coherent pinned copy with the flag word behind it
-  size_t results_cap = 0, h_results_cap = 0;
+  ftkx_block results;                                  // u64: the device block
+  ftkx_block h_results{FTKX_BLOCK_PINNED_COHERENT};    // u64: its pinned copy; the last 8 words are the flag words (series.hip: series_flag)
   unsigned seq = 0;
-  ftkx_cp_t *out = nullptr; size_t out_cap = 0;       // pinned: the records as the caller reads them
-  ftkx_cp_t *d_out = nullptr; size_t d_out_cap = 0;   // device: the records of a pass whose way over PCIe is left to the copy kernel on its own stream
-  unsigned *copy_done = nullptr;                       // that kernel's workgroup counter
+  ftkx_block out{FTKX_BLOCK_PINNED_COHERENT};          // ftkx_cp_t: the records as the caller reads them (kind: series.hip, ensure_series_buffers)
+  ftkx_block d_out;                                    // ftkx_cp_t: the records of a pass whose way over PCIe is left to the copy kernel on its own stream
+  ftkx_block copy_done;                                // unsigned: that kernel's workgroup counter
   hipEvent_t ev_copied = nullptr, ev_export = nullptr;
   hipEvent_t ev_masks = nullptr, ev_factors = nullptr, ev_tail = nullptr;   // split pass: masks done (stream), cull + factor job / tail done (tail stream)
-  u64 *red = nullptr; size_t red_cap = 0;             // the reduction slots of this pass's mask jobs (128 words per slice): its own, the next pass's begin kernel must not wipe them
+  ftkx_block red;                                      // u64: the reduction slots of this pass's mask jobs (128 words per slice): its own, the next pass's begin kernel must not wipe them
   bool copy_out = false;                               // a copy has been queued since the buffers were last used: the next record kernel waits for it
-  void *h_desc = nullptr, *d_desc = nullptr; size_t desc_cap = 0;
-  u64 *dist_block = nullptr;                           // slab pass: DB_N words (sweep_params.hpp)
+  ftkx_block h_desc{FTKX_BLOCK_PINNED}, d_desc;
+  ftkx_block dist_block;                               // u64: slab pass, DB_N words (sweep_params.hpp)
 };
 
 // What the tail of a sweep works on, and the stream a SPLIT pass's tail runs on.  The context has two (ftkx_ctx::sr_tail).  Set 0 is what the
@@ -232,40 +233,33 @@ struct ftkx_series_buffers {
 // (same capacities: ensure_set1) is for every other split pass of a short mask launch, so that the tails of two passes can run at the same time --
 // a mask launch shorter than one tail next to it (a single 512^3 slice) then still hides half a tail behind every mask kernel.
 struct ftkx_tail_set {
-  u64 *counters = nullptr;          // CNT_N counters + 128 words (64 {min, max} slots) for the resolution reduction + 8
-  u64 *list = nullptr;              // surviving corners of the fast path
-  u64 *refine = nullptr;            // words the summary level could not rule out (two-level cull)
-  u64 *pass = nullptr;              // simplices that passed the integer test, awaiting the record kernel
-  u64 *fragile = nullptr;           // 3D records to be re-classified on the host (slot, J[9]): cp_device.hpp, classify3
-  u64 *bucketed = nullptr, *sorted = nullptr;   // series pass: the order keys by bucket, and ranked
-  unsigned *hist = nullptr, *boff = nullptr;    // series pass: bucket counts and offsets
-  // `capacity` is the set's own copy of ftkx_ctx::capacity (which stays the capacity of d_hits / h_hits and of Mesh::capacity): how far THIS
-  // set's pass array has followed it
-  u64 capacity = 0, list_capacity = 0, refine_capacity = 0, fragile_capacity = 0, order_capacity = 0, bins_cap = 0;
+  ftkx_block counters;              // u64: CNT_N counters + 128 words (64 {min, max} slots) for the resolution reduction + 8
+  ftkx_block list;                  // u64: surviving corners of the fast path
+  ftkx_block refine;                // u64: words the summary level could not rule out (two-level cull)
+  ftkx_block pass;                  // u64: simplices that passed the integer test, awaiting the record kernel
+  ftkx_block fragile;               // u64: 3D records to be re-classified on the host (slot, J[9]): cp_device.hpp, classify3
+  ftkx_block bucketed, sorted;      // u64: series pass, the order keys by bucket, and ranked
+  ftkx_block hist, boff;            // unsigned: series pass, bucket counts and offsets
+  // what the kernels are handed: the element counts of pass, list, refine and fragile (10 words each), set by their ensure_* (ftkx_api.hip)
+  // on the line behind the reserve and nowhere else.  `capacity` is how far THIS set's pass array has followed ftkx_ctx::capacity.
+  u64 capacity = 0, list_capacity = 0, refine_capacity = 0, fragile_capacity = 0;
   hipStream_t stream = nullptr;     // the tail of a split pass on this set; created where the first such pass is planned
 };
 
 // Pass 2 on the device (trace_device.hip, post_process_device.hip): every block it keeps with the context.  A call lays its arrays out
 // (pass2_layout.hpp), reserves the blocks for the layout's totals and works on the context's stream, which it waits for before it returns:
 // what a block held does not outlive the call, but for the curves of the last trace that went all the way on the device (`order`).
-struct ftkx_ctx;
-struct pass2_block {
-  void *p = nullptr;
-  size_t bytes = 0;
-  bool pinned = false;
-  int reserve(ftkx_ctx *c, size_t want, bool pinned_);   // (ftkx_api.hip) at least `want` bytes; grows by a quarter more; contents are not kept
-  void release();
-};
+// Every block grows by a quarter more than it is asked for (pass2_room).
+inline size_t pass2_room(size_t want) { return want + want / 4; }
 struct ftkx_pass2_state {
-  pass2_block trace_dev, trace_host;   // TraceLayout
-  pass2_block tables;                  // the neighbour search's candidate tables of dimension `tables_nd`
-  pass2_block order_dev, order_host;   // OrderLayout
-  pass2_block pp_dev, pp_host;         // PpPlan
+  ftkx_block trace_dev, trace_host{FTKX_BLOCK_PINNED_NONCOHERENT};   // TraceLayout
+  ftkx_block tables;                                                 // the neighbour search's candidate tables of dimension `tables_nd`
+  ftkx_block order_dev, order_host{FTKX_BLOCK_PINNED_NONCOHERENT};   // OrderLayout
+  ftkx_block pp_dev, pp_host{FTKX_BLOCK_PINNED_NONCOHERENT};         // PpPlan
   int tables_nd = 0;
   ftkx::OrderLayout order;             // of the last trace that ended with path 2: where its curves lie in order_dev
   int trace_last_path = 0;             // which way the last trace went: 0 host, 1 device phases + host walks, 2 all on the device
   int pp_last_path = 0;                // which way the last post-processing went: 0 host, 2 all on the device
-  void release() { for (pass2_block *b : {&trace_dev, &trace_host, &tables, &order_dev, &order_host, &pp_dev, &pp_host}) b->release(); tables_nd = 0; }
 };
 
 struct ftkx_ctx {
@@ -276,39 +270,34 @@ struct ftkx_ctx {
   bool mesh_set = false;
   int scalar_mode = -1;             // -1 undecided, 0 vector slices, 1 scalar slices (V = gradient(S) evaluated in flight)
   std::map<int, ftkxh::Slice> slices;
-  ftkx_cp_t *d_hits = nullptr;
-  u64 capacity = 0;                 // of d_hits, and of the pass array of every tail set in use
+  ftkx_block d_hits;                // ftkx_cp_t
+  u64 capacity = 0;                 // records d_hits holds (set in ensure_hit_buffer), and the pass array of every tail set in use
   ftkx_tail_set sr_tail[2];         // [0]: the host-driven batch's and every unsplit pass's
-  u64 *d_tile_stats = nullptr;      // 512 words: the tile kernels' statistics in 256 slots (TileParams::stats)
-  u64 *h_counters = nullptr;        // pinned
-  ftkx_cp_t *h_hits = nullptr;      // pinned
-  size_t h_cap = 0;
-  // device-side ordering of the hit records by tag (radix sort of (tag, index) pairs + one gather)
-  ftkx_cp_t *d_sorted = nullptr;
-  u64 *d_keys = nullptr;            // 2 * sort_cap
-  unsigned *d_idx = nullptr;        // 2 * sort_cap
-  void *d_sort_tmp = nullptr;
-  size_t sort_cap = 0, sort_tmp_bytes = 0;
+  ftkx_block d_tile_stats;          // u64, 512 words: the tile kernels' statistics in 256 slots (TileParams::stats)
+  ftkx_block h_counters{FTKX_BLOCK_PINNED};              // u64, CNT_N words
+  ftkx_block h_hits{FTKX_BLOCK_PINNED_NONCOHERENT};      // ftkx_cp_t
+  // device-side ordering of the hit records by tag (radix sort of (tag, index) pairs + one gather): collect.hip, sort_hits_on_device
+  ftkx_block d_sorted;              // ftkx_cp_t, sort_cap of them
+  ftkx_block d_keys, d_idx;         // u64 / unsigned, 2 * sort_cap each
+  ftkx_block d_sort_tmp;            // unsigned: digit counts per tile
   // per-batch descriptors: pinned staging + device copies
-  void *h_desc = nullptr, *d_desc = nullptr;
-  size_t desc_cap = 0;
+  ftkx_block h_desc{FTKX_BLOCK_PINNED}, d_desc;
   // mask / summary arrays of dropped slices, kept for the next slice (a streaming tracker pushes and pops one slice per step:
   // hipMalloc + hipFree per step cost more than the sweep itself).  Their padding bytes stay valid: kernels never write them.
   std::vector<unsigned char *> pool_M, pool_U;
   std::vector<std::pair<double *, size_t>> pool_F;   // owned field arrays (S / V / J copies) of dropped slices, by size in doubles
-  u64 *d_red = nullptr;             // {min, max} slots of a batched resolution reduction: 128 words per slice
-  size_t red_cap = 0;
+  ftkx_block d_red;                 // u64: {min, max} slots of a batched resolution reduction, 128 words per slice (ensure_red)
   // physical coordinates (REGULAR_COORDS_RECTILINEAR / _EXPLICIT): device copies
-  double *d_rect[3] = {nullptr, nullptr, nullptr};
+  ftkx_block d_rect[3];             // double
   size_t rect_n[3] = {0, 0, 0};
-  double *d_expl = nullptr;
+  ftkx_block d_expl;                // double
   int expl_ncomp = 0;
   size_t expl_n0 = 0, expl_n1 = 0;
   // spatial smoothing (ftkx_set_spatial_smoothing): ksize 0 = off; d_conv_w holds two sets of 9^3 weights -- [0] those of the ftkx_conv2D /
   // ftkx_conv3D call in hand (the call waits for its kernel), [1] the smoothing's, written when it is set and only read afterwards
   int smooth_ksize = 0;
   double smooth_sigma = 0;
-  double *d_conv_w = nullptr;
+  ftkx_block d_conv_w;              // double
   std::vector<ftkxh::Request> pending;
   // Cull-ahead: the sweeps the caller announced (ftkx_sweep_announce) for the slices of the next ftkx_slices_prepare, and -- once that
   // call has queued their cull right behind the mask kernel -- the survivor list it left on the device.  The cull needs the masks
@@ -318,20 +307,18 @@ struct ftkx_ctx {
   std::vector<std::pair<int, int>> announced;
   struct AheadStep { int t, scope; const unsigned char *M[2], *U[2]; };
   std::vector<AheadStep> ahead;     // non-empty: survivor list + counters on the device belong to these steps
-  void *h_ahead = nullptr, *d_ahead = nullptr;   // the cull-ahead's own descriptors: pinned staging (read by fetch_desc_kernel) + device copy
-  size_t ahead_cap = 0;
+  ftkx_block h_ahead{FTKX_BLOCK_PINNED_COHERENT}, d_ahead;   // the cull-ahead's own descriptors: pinned staging (read by fetch_desc_kernel) + device copy
   bool ahead_staged = false;        // a fetch out of h_ahead may still be queued (cleared by every full stream synchronise of collect)
-  u64 *h_red = nullptr;             // coherent pinned copy of the reduction slots + one flag word, written by readback_kernel
-  size_t h_red_cap = 0;             //   (slots it can hold; the flag lives behind them)
+  ftkx_block h_red{FTKX_BLOCK_PINNED_COHERENT};   // u64: copy of the reduction slots, written by readback_kernel; its last 8 words hold the flag
   unsigned red_seq = 0;
   int dense_collects = 0;           // > 0: the last fast collect found most cells surviving; fast requests run MODE_TILE_CULL for a while
   unsigned long long uploads_staged = 0, uploads_direct = 0;   // ftkx_debug_upload_counts (upload.cpp)
   int tile_repeat = 1;              // ftkx_debug_tile_repeat: the tile kernel's fan phase that many times per tile (the int-VALU yardstick of bench.py)
   // compact halo: the compacted mask words of the last ftkx_export_masks_size, the surviving cells of the last ftkx_sweep_cull
-  unsigned *d_word_idx = nullptr; u64 *d_words = nullptr; size_t words_cap = 0, n_words = 0; int words_t = -1;
-  u64 *d_cells = nullptr; size_t cells_cap = 0, n_cells = 0;
-  u64 *d_patch_cells = nullptr; double *d_patches = nullptr; size_t patch_cap = 0;   // staging for host-side callers
-  void *d_packed = nullptr; size_t packed_cap = 0;                                   // staging of a packed mask message for host-side callers
+  ftkx_block d_word_idx, d_words; size_t n_words = 0; int words_t = -1;     // unsigned / u64
+  ftkx_block d_cells; size_t n_cells = 0;                                    // u64
+  ftkx_block d_patch_cells, d_patches;                                       // u64 / double: staging for host-side callers
+  ftkx_block d_packed;                                                       // staging of a packed mask message for host-side callers
   // series pass (series.hip): per pass in flight the results block (device + coherent pinned copy: it also holds the fragile list, the flag
   // lives behind it), the record buffers and the descriptors; shared, in stream order: the ordering buffers
   static constexpr int kPlaces = 3;   // passes in flight at most: two keep the stream fed; the third lets the host run one pass ahead of a split pass's
@@ -352,8 +339,8 @@ struct ftkx_ctx {
   int sr_last_complete_kind = 0;        // 1 in order / 2 split, of a calibration pass; 0 otherwise
   unsigned sr_split_seq = 0;          // split passes queued so far: their parity picks the set
   int sr_one_off = 0;                  // passes for which the one-launch form is not tried (it declined a moment ago)
-  u64 *sr_one_scratch = nullptr;       // the one-launch pass's barrier counters, partial reductions and per-workgroup counts (ONE_WORDS)
-  unsigned *sr_fetch_flag = nullptr;   // device: [0] the number of the last pass whose descriptors have been fetched (series_begin_kernel), [1] its arrival counter
+  ftkx_block sr_one_scratch;           // u64: the one-launch pass's barrier counters, partial reductions and per-workgroup counts (ONE_WORDS)
+  ftkx_block sr_fetch_flag;            // unsigned, device: [0] the number of the last pass whose descriptors have been fetched (series_begin_kernel), [1] its arrival counter
   unsigned sr_fetch_seq = 0;
   hipEvent_t sr_ev_fetched = nullptr;  // slab passes: recorded behind the begin kernel, waited for by the copy of the pass before (no spin-wait there)
   unsigned long long mask_epoch = 0;  // source of Slice::mask_gen values
@@ -414,6 +401,7 @@ int ensure_bins(ftkx_ctx *c, ftkx_tail_set &S, u64 want);       // hist + boff
 int ensure_order(ftkx_ctx *c, ftkx_tail_set &S, u64 want);      // bucketed + sorted
 hipError_t sync_tails(ftkx_ctx *c);                             // the host waits for whatever is queued on the tail streams
 int ensure_desc(ftkx_ctx *c, size_t bytes);
+int ensure_red(ftkx_ctx *c, size_t nslices);                    // d_red: 128 words per slice
 int ensure_host_buffer(ftkx_ctx *c, size_t want);
 void fill_mesh(const ftkx_ctx *c, Mesh &m);
 int slice_resolution(ftkx_ctx *c, Slice &s);

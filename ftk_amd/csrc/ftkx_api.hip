@@ -109,39 +109,31 @@ void release_pools(ftkx_ctx *c)
 }
 
 // ---- the tail sets (ctx.hpp) ---------------------------------------------------------------------------------------------------------
-// An array of a set (or two of one size) replaced by a larger one; contents are not kept.  Nothing of a set is freed while its stream may still read it: the
-// stream is drained first.  (Set 0 grows only where everything has been waited for anyway; the synchronise costs the rare growth path a call.)
-static int regrow(ftkx_ctx *c, ftkx_tail_set &S, u64 *cap, u64 want, size_t elem_bytes, void **p, void **q = nullptr /* a second array of the same size */)
+// An array of a set replaced by a larger one; contents are not kept.  Nothing of a set is freed while its stream may still read it: the stream is
+// drained first.  (Set 0 grows only where everything has been waited for anyway; the synchronise costs the rare growth path a call.)
+// The element counts the kernels are handed are read off the blocks here, on the line behind the reserve.
+constexpr size_t kFragileBytes = 10 * sizeof(u64);      // (slot, J[9])
+int ensure_pass(ftkx_ctx *c, ftkx_tail_set &S, u64 want) { const int rc = S.pass.reserve(c, want * sizeof(u64), 0, S.stream); S.capacity = S.pass.count<u64>(); return rc; }
+int ensure_fragile(ftkx_ctx *c, ftkx_tail_set &S, u64 want) { const int rc = S.fragile.reserve(c, want * kFragileBytes, 0, S.stream); S.fragile_capacity = S.fragile.bytes / kFragileBytes; return rc; }
+int ensure_list(ftkx_ctx *c, ftkx_tail_set &S, u64 want) { const int rc = S.list.reserve(c, want * sizeof(u64), 0, S.stream); S.list_capacity = S.list.count<u64>(); return rc; }
+int ensure_refine(ftkx_ctx *c, ftkx_tail_set &S, u64 want) { const int rc = S.refine.reserve(c, want * sizeof(u64), 0, S.stream); S.refine_capacity = S.refine.count<u64>(); return rc; }
+int ensure_bins(ftkx_ctx *c, ftkx_tail_set &S, u64 want)
 {
-  if (*cap >= want) return FTKX_OK;
-  *cap = 0;
-  for (void **a : {p, q}) {
-    if (a && *a) {
-      if (S.stream) HIP_TRY(c, hipStreamSynchronize(S.stream));
-      HIP_TRY(c, hipFree(*a));
-      *a = nullptr;
-    }
-    if (a) HIP_TRY(c, hipMalloc(a, want * elem_bytes));
-  }
-  *cap = want;
-  return FTKX_OK;
+  if (const int rc = S.hist.reserve(c, want * sizeof(unsigned), 0, S.stream)) return rc;
+  return S.boff.reserve(c, want * sizeof(unsigned), 0, S.stream);
 }
-
-int ensure_pass(ftkx_ctx *c, ftkx_tail_set &S, u64 want) { return regrow(c, S, &S.capacity, want, sizeof(u64), (void **)&S.pass); }
-int ensure_fragile(ftkx_ctx *c, ftkx_tail_set &S, u64 want) { return regrow(c, S, &S.fragile_capacity, want, 10 * sizeof(u64), (void **)&S.fragile); }
-int ensure_list(ftkx_ctx *c, ftkx_tail_set &S, u64 want) { return regrow(c, S, &S.list_capacity, want, sizeof(u64), (void **)&S.list); }
-int ensure_refine(ftkx_ctx *c, ftkx_tail_set &S, u64 want) { return regrow(c, S, &S.refine_capacity, want, sizeof(u64), (void **)&S.refine); }
-int ensure_bins(ftkx_ctx *c, ftkx_tail_set &S, u64 want) { return regrow(c, S, &S.bins_cap, want, sizeof(unsigned), (void **)&S.hist, (void **)&S.boff); }
-int ensure_order(ftkx_ctx *c, ftkx_tail_set &S, u64 want) { return regrow(c, S, &S.order_capacity, want, sizeof(u64), (void **)&S.bucketed, (void **)&S.sorted); }
+int ensure_order(ftkx_ctx *c, ftkx_tail_set &S, u64 want)
+{
+  if (const int rc = S.bucketed.reserve(c, want * sizeof(u64), 0, S.stream)) return rc;
+  return S.sorted.reserve(c, want * sizeof(u64), 0, S.stream);
+}
 
 int ensure_hit_buffer(ftkx_ctx *c, u64 want)
 {
-  if (c->capacity >= want) return FTKX_OK;
-  if (c->d_hits) { HIP_TRY(c, hipFree(c->d_hits)); c->d_hits = nullptr; c->capacity = 0; }
-  HIP_TRY(c, hipMalloc((void **)&c->d_hits, want * sizeof(ftkx_cp_t)));
-  if (int rc = ensure_pass(c, c->sr_tail[0], want)) return rc;
-  c->capacity = want;
-  return FTKX_OK;
+  int rc = c->d_hits.reserve(c, want * sizeof(ftkx_cp_t));
+  if (rc == FTKX_OK) rc = ensure_pass(c, c->sr_tail[0], want);
+  c->capacity = rc == FTKX_OK ? c->d_hits.count<ftkx_cp_t>() : 0;
+  return rc;
 }
 
 hipError_t sync_tails(ftkx_ctx *c)
@@ -153,27 +145,16 @@ hipError_t sync_tails(ftkx_ctx *c)
 
 int ensure_desc(ftkx_ctx *c, size_t bytes)
 {
-  if (c->desc_cap >= bytes) return FTKX_OK;
-  if (c->h_desc) { HIP_TRY(c, hipHostFree(c->h_desc)); c->h_desc = nullptr; }
-  if (c->d_desc) { HIP_TRY(c, hipFree(c->d_desc)); c->d_desc = nullptr; }
   const size_t cap = std::max<size_t>(bytes, 1 << 16);
-  HIP_TRY(c, hipHostMalloc(&c->h_desc, cap, hipHostMallocDefault));
-  HIP_TRY(c, hipMalloc(&c->d_desc, cap));
-  c->desc_cap = cap;
-  return FTKX_OK;
+  if (const int rc = c->h_desc.reserve(c, bytes, cap)) return rc;
+  return c->d_desc.reserve(c, bytes, cap);
 }
 
-int ensure_host_buffer(ftkx_ctx *c, size_t want)
-{
-  if (c->h_cap >= want) return FTKX_OK;
-  if (c->h_hits) { HIP_TRY(c, hipHostFree(c->h_hits)); c->h_hits = nullptr; c->h_cap = 0; }
-  const size_t cap = std::max<size_t>(want, 4096);
-  // non-coherent = ordinary cached host memory for the CPU (it only reads the records after a stream synchronise);
-  // the default coherent mapping is uncached on this platform and made every consumer crawl (5 GB/s)
-  HIP_TRY(c, hipHostMalloc((void **)&c->h_hits, cap * sizeof(ftkx_cp_t), hipHostMallocNonCoherent));
-  c->h_cap = cap;
-  return FTKX_OK;
-}
+int ensure_red(ftkx_ctx *c, size_t nslices) { return c->d_red.reserve(c, nslices * 128 * sizeof(u64)); }
+
+// h_hits is non-coherent = ordinary cached host memory for the CPU (it only reads the records after a stream synchronise);
+// the default coherent mapping is uncached on this platform and made every consumer crawl (5 GB/s)
+int ensure_host_buffer(ftkx_ctx *c, size_t want) { return c->h_hits.reserve(c, want * sizeof(ftkx_cp_t), std::max<size_t>(want, 4096) * sizeof(ftkx_cp_t)); }
 
 void fill_mesh(const ftkx_ctx *c, Mesh &m)
 {
@@ -203,18 +184,18 @@ void fill_mesh(const ftkx_ctx *c, Mesh &m)
   { const char *e = getenv("FTKX_RECORD_GENERAL"); m.record_general = (e && atoi(e) != 0) ? 1 : 0; }
   m.coords_mode = c->opt.coords_mode;
   for (int i = 0; i < 6; i ++) m.coords_bounds[i] = c->opt.coords_bounds[i];
-  for (int d = 0; d < 3; d ++) m.coords_rect[d] = c->d_rect[d];
-  m.coords_expl = c->d_expl; m.coords_expl_ncomp = c->expl_ncomp; m.coords_expl_n0 = (int)c->expl_n0;
+  for (int d = 0; d < 3; d ++) m.coords_rect[d] = c->d_rect[d].as<double>();
+  m.coords_expl = c->d_expl.as<double>(); m.coords_expl_ncomp = c->expl_ncomp; m.coords_expl_n0 = (int)c->expl_n0;
   const ftkx_tail_set &S = c->sr_tail[0];                     // (a series pass on the other set: series.hip, series_mesh)
-  m.hits = c->d_hits; m.pass = S.pass; m.counters = S.counters; m.capacity = c->capacity;
-  m.fragile = S.fragile; m.fragile_capacity = S.fragile_capacity;
+  m.hits = c->d_hits.as<ftkx_cp_t>(); m.pass = S.pass.as<u64>(); m.counters = S.counters.as<u64>(); m.capacity = c->capacity;
+  m.fragile = S.fragile.as<u64>(); m.fragile_capacity = S.fragile_capacity;
   m.u_rows = ftkx::mask_summary_rows(m);
 }
 
 int slice_resolution(ftkx_ctx *c, Slice &s)
 {
   if (s.have_res) return FTKX_OK;
-  u64 *d = c->sr_tail[0].counters + ftkx::CNT_N;
+  u64 *d = c->sr_tail[0].counters.as<u64>() + ftkx::CNT_N;
   u64 init[128];
   for (int i = 0; i < 64; i ++) { init[2 * i] = 0x7fefffffffffffffull; init[2 * i + 1] = 0ull; }
   HIP_TRY(c, hipMemcpyAsync(d, init, sizeof(init), hipMemcpyHostToDevice, c->stream));
@@ -225,8 +206,8 @@ int slice_resolution(ftkx_ctx *c, Slice &s)
       int rc = ensure_desc(c, sizeof(MaskJob));
       if (rc) return rc;
       const MaskJob job{s.S, nullptr, nullptr, nullptr, d, 1.0};
-      HIP_TRY(c, hipMemcpyAsync(c->d_desc, &job, sizeof(job), hipMemcpyHostToDevice, c->stream));
-      ftkx::launch_reduce_march(m, (const MaskJob *)c->d_desc, 1, c->stream);
+      HIP_TRY(c, hipMemcpyAsync(c->d_desc.p, &job, sizeof(job), hipMemcpyHostToDevice, c->stream));
+      ftkx::launch_reduce_march(m, (const MaskJob *)c->d_desc.p, 1, c->stream);
     } else ftkx::launch_resolution_scalar(m, s.S, d, c->stream);
   }
   else ftkx::launch_resolution(s.V, n_vertices(c) * (size_t)c->nd, d, c->stream);
@@ -334,6 +315,21 @@ int ensure_mask_arrays(ftkx_ctx *c, Slice &s, bool two_level)
 
 }  // namespace ftkxh
 
+// ---- the three raw functions behind ftkx_block (ctx_block.hpp) -----------------------------------------------------------------------
+int ftkx_block_alloc(ftkx_ctx *c, ftkx_block_kind kind, size_t bytes, void **p)
+{
+  *p = nullptr;
+  switch (kind) {
+    case FTKX_BLOCK_DEVICE: HIP_TRY(c, hipMalloc(p, bytes)); break;
+    case FTKX_BLOCK_PINNED: HIP_TRY(c, hipHostMalloc(p, bytes, hipHostMallocDefault)); break;
+    case FTKX_BLOCK_PINNED_COHERENT: HIP_TRY(c, hipHostMalloc(p, bytes, hipHostMallocCoherent)); break;
+    case FTKX_BLOCK_PINNED_NONCOHERENT: HIP_TRY(c, hipHostMalloc(p, bytes, hipHostMallocNonCoherent)); break;
+  }
+  return FTKX_OK;
+}
+void ftkx_block_free(ftkx_block_kind kind, void *p) { (void)(kind == FTKX_BLOCK_DEVICE ? hipFree(p) : hipHostFree(p)); }
+int ftkx_block_drain(ftkx_ctx *c, void *stream) { HIP_TRY(c, hipStreamSynchronize((hipStream_t)stream)); return FTKX_OK; }
+
 extern "C" {
 
 const char *ftkx_last_mask_kernel(void) { return ftkx::last_mask_kernel(); }
@@ -398,31 +394,13 @@ int ftkx_create(ftkx_ctx **out, int nd, int device_id)
     HIP_TRY(c, hipStreamCreateWithFlags(&c->own_stream, hipStreamDefault));
     c->stream = c->own_stream;
     // CNT_N counters, 128 words of reduction slots, one word that says "a halo message did not fit this mesh" (halo.hip; survives the sweeps' resets)
-    HIP_TRY(c, hipMalloc((void **)&c->sr_tail[0].counters, (ftkx::CNT_N + 128 + 8) * sizeof(u64)));
-    HIP_TRY(c, hipMemset(c->sr_tail[0].counters, 0, (ftkx::CNT_N + 128 + 8) * sizeof(u64)));
-    HIP_TRY(c, hipHostMalloc((void **)&c->h_counters, ftkx::CNT_N * sizeof(u64), hipHostMallocDefault));
-    return FTKX_OK;
+    if (const int rc = c->sr_tail[0].counters.reserve(c, (ftkx::CNT_N + 128 + 8) * sizeof(u64))) return rc;
+    HIP_TRY(c, hipMemset(c->sr_tail[0].counters.p, 0, (ftkx::CNT_N + 128 + 8) * sizeof(u64)));
+    return c->h_counters.reserve(c, ftkx::CNT_N * sizeof(u64));
   };
   const int rc = init();
   if (rc != FTKX_OK) { ftkx_destroy(c); return rc; }     // nothing half-built is left behind
   *out = c;
-  return FTKX_OK;
-}
-
-void pass2_block::release()
-{
-  if (p) (void)(pinned ? hipHostFree(p) : hipFree(p));
-  p = nullptr; bytes = 0;
-}
-
-int pass2_block::reserve(ftkx_ctx *c, size_t want, bool pinned_)
-{
-  if (bytes >= want) return FTKX_OK;
-  release();
-  pinned = pinned_;
-  const size_t cap = want + want / 4;
-  if (pinned) HIP_TRY(c, hipHostMalloc(&p, cap, hipHostMallocNonCoherent)); else HIP_TRY(c, hipMalloc(&p, cap));
-  bytes = cap;
   return FTKX_OK;
 }
 
@@ -438,44 +416,13 @@ void ftkx_destroy(ftkx_ctx *c)
   release_pools(c);
   for (auto &e : c->events) { (void)hipEventDestroy(e.second.first); (void)hipEventDestroy(e.second.second); }
   for (hipEvent_t e : c->event_pool) (void)hipEventDestroy(e);
-  if (c->h_red) (void)hipHostFree(c->h_red);
-  if (c->h_ahead) (void)hipHostFree(c->h_ahead);
-  if (c->d_ahead) (void)hipFree(c->d_ahead);
-  if (c->d_red) (void)hipFree(c->d_red);
-  if (c->d_tile_stats) (void)hipFree(c->d_tile_stats);
-  if (c->d_hits) (void)hipFree(c->d_hits);
-  for (void *p : {(void *)c->d_word_idx, (void *)c->d_words, (void *)c->d_cells, (void *)c->d_patch_cells, (void *)c->d_patches, c->d_packed}) if (p) (void)hipFree(p);
-  for (ftkx_series_buffers &B : c->sr_buf) {
-    for (void *p : {(void *)B.results, (void *)B.d_out, B.d_desc, (void *)B.copy_done, (void *)B.dist_block}) if (p) (void)hipFree(p);
-    if (B.ev_copied) (void)hipEventDestroy(B.ev_copied);
-    if (B.ev_export) (void)hipEventDestroy(B.ev_export);
-    for (hipEvent_t e : {B.ev_masks, B.ev_factors, B.ev_tail}) if (e) (void)hipEventDestroy(e);
-    if (B.red) (void)hipFree(B.red);
-    for (void *p : {(void *)B.h_results, (void *)B.out, B.h_desc}) if (p) (void)hipHostFree(p);
-  }
-  aux_stream_put(c, false, c->sr_copy_stream);
-  for (ftkx_tail_set &S : c->sr_tail) {
-    aux_stream_put(c, true, S.stream);
-    for (void *q : {(void *)S.counters, (void *)S.list, (void *)S.refine, (void *)S.pass, (void *)S.fragile, (void *)S.bucketed, (void *)S.sorted, (void *)S.hist, (void *)S.boff})
-      if (q) (void)hipFree(q);
-  }
-  if (c->sr_one_scratch) (void)hipFree(c->sr_one_scratch);
-  if (c->sr_fetch_flag) (void)hipFree(c->sr_fetch_flag);
+  for (ftkx_series_buffers &B : c->sr_buf)
+    for (hipEvent_t e : {B.ev_copied, B.ev_export, B.ev_masks, B.ev_factors, B.ev_tail}) if (e) (void)hipEventDestroy(e);
   if (c->sr_ev_fetched) (void)hipEventDestroy(c->sr_ev_fetched);
-  c->p2.release();
-  if (c->d_sorted) (void)hipFree(c->d_sorted);
-  if (c->d_keys) (void)hipFree(c->d_keys);
-  if (c->d_idx) (void)hipFree(c->d_idx);
-  if (c->d_sort_tmp) (void)hipFree(c->d_sort_tmp);
-  if (c->d_desc) (void)hipFree(c->d_desc);
-  if (c->d_conv_w) (void)hipFree(c->d_conv_w);
-  for (int d = 0; d < 3; d ++) if (c->d_rect[d]) (void)hipFree(c->d_rect[d]);
-  if (c->d_expl) (void)hipFree(c->d_expl);
-  if (c->h_desc) (void)hipHostFree(c->h_desc);
-  if (c->h_counters) (void)hipHostFree(c->h_counters);
-  if (c->h_hits) (void)hipHostFree(c->h_hits);
+  aux_stream_put(c, false, c->sr_copy_stream);
+  for (ftkx_tail_set &S : c->sr_tail) aux_stream_put(c, true, S.stream);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-  delete c;
+  delete c;                                                   // every block (ctx_block.hpp) goes with it
 }
 
 int ftkx_set_stream(ftkx_ctx *c, void *s)
@@ -496,8 +443,8 @@ int ftkx_set_options(ftkx_ctx *c, const ftkx_options *o)
   if (c->sr_open && !c->sr_internal) return fail(c, FTKX_E_INVALID, "ftkx_set_options: series passes open (ftkx_sweep_series_submit), complete them first");
   if (o->tag_mode < FTKX_TAG_WORK_INDEX || o->tag_mode > FTKX_TAG_EXACT64) return fail(c, FTKX_E_INVALID, "bad tag_mode %d", o->tag_mode);
   if (o->coords_mode < 0 || o->coords_mode > 3) return fail(c, FTKX_E_INVALID, "bad coords_mode %d", o->coords_mode);
-  if (o->coords_mode == 2 && !c->d_rect[0]) return fail(c, FTKX_E_INVALID, "coords_mode RECTILINEAR: call ftkx_set_coords_rectilinear");
-  if (o->coords_mode == 3 && !c->d_expl) return fail(c, FTKX_E_INVALID, "coords_mode EXPLICIT: call ftkx_set_coords_explicit");
+  if (o->coords_mode == 2 && !c->d_rect[0].as<double>()) return fail(c, FTKX_E_INVALID, "coords_mode RECTILINEAR: call ftkx_set_coords_rectilinear");
+  if (o->coords_mode == 3 && !c->d_expl.as<double>()) return fail(c, FTKX_E_INVALID, "coords_mode EXPLICIT: call ftkx_set_coords_explicit");
   c->opt = *o;
   return FTKX_OK;
 }
@@ -511,9 +458,9 @@ int ftkx_set_coords_rectilinear(ftkx_ctx *c, const double *x, size_t nx, const d
   for (int d = 0; d < c->nd; d ++) if (!src[d] || !n[d]) return fail(c, FTKX_E_INVALID, "ftkx_set_coords_rectilinear: axis %d missing", d);
   HIP_TRY(c, hipSetDevice(c->device));
   for (int d = 0; d < c->nd; d ++) {
-    if (c->d_rect[d]) { (void)hipFree(c->d_rect[d]); c->d_rect[d] = nullptr; }
-    HIP_TRY(c, hipMalloc((void **)&c->d_rect[d], n[d] * sizeof(double)));
-    HIP_TRY(c, hipMemcpy(c->d_rect[d], src[d], n[d] * sizeof(double), hipMemcpyHostToDevice));
+    c->d_rect[d] = ftkx_block();                             // (a new array every time, of exactly this size)
+    if (const int rc = c->d_rect[d].reserve(c, n[d] * sizeof(double))) return rc;
+    HIP_TRY(c, hipMemcpy(c->d_rect[d].p, src[d], n[d] * sizeof(double), hipMemcpyHostToDevice));
     c->rect_n[d] = n[d];
   }
   c->opt.coords_mode = 2;
@@ -526,10 +473,10 @@ int ftkx_set_coords_explicit(ftkx_ctx *c, const double *coords, int ncomp, size_
   if (!c->pending.empty()) return fail(c, FTKX_E_INVALID, "ftkx_set_coords_explicit: sweeps pending, collect first");
   if (ncomp < 2 || (c->nd == 3 && ncomp < 3) || !n0 || !n1) return fail(c, FTKX_E_INVALID, "ftkx_set_coords_explicit: need %d components and a non-empty array", c->nd == 3 ? 3 : 2);
   HIP_TRY(c, hipSetDevice(c->device));
-  if (c->d_expl) { (void)hipFree(c->d_expl); c->d_expl = nullptr; }
+  c->d_expl = ftkx_block();                                  // (a new array every time, of exactly this size)
   const size_t count = (size_t)ncomp * n0 * n1;
-  HIP_TRY(c, hipMalloc((void **)&c->d_expl, count * sizeof(double)));
-  HIP_TRY(c, hipMemcpy(c->d_expl, coords, count * sizeof(double), hipMemcpyHostToDevice));
+  if (const int rc = c->d_expl.reserve(c, count * sizeof(double))) return rc;
+  HIP_TRY(c, hipMemcpy(c->d_expl.p, coords, count * sizeof(double), hipMemcpyHostToDevice));
   c->expl_ncomp = ncomp; c->expl_n0 = n0; c->expl_n1 = n1;
   c->opt.coords_mode = 3;
   return FTKX_OK;
@@ -607,7 +554,7 @@ static int push_common(ftkx_ctx *c, int t, const double *V, const double *J, con
       if (rc) { (void)hipFree(tmp); return rc; }
       from = tmp;
     }
-    ftkx::launch_conv(nd, from, (int)c->ext_sz[0], (int)c->ext_sz[1], (int)c->ext_sz[2], c->d_conv_w + kSmoothWeights, c->smooth_ksize, *dst, c->stream);
+    ftkx::launch_conv(nd, from, (int)c->ext_sz[0], (int)c->ext_sz[1], (int)c->ext_sz[2], c->d_conv_w.as<double>() + kSmoothWeights, c->smooth_ksize, *dst, c->stream);
     const hipError_t e = hipGetLastError();
     if (tmp) { if (c->pool_F.size() < 12) c->pool_F.push_back({tmp, count}); else { (void)hipStreamSynchronize(c->stream); (void)hipFree(tmp); } }
     HIP_TRY(c, e);
@@ -688,32 +635,28 @@ int ftkx_slices_resolution(ftkx_ctx *c, const int *ts, int n, double *res, doubl
   Mesh m; fill_mesh(c, m);
   if (todo.size() > 1) {
     const size_t k = todo.size();
-    if (c->red_cap < k) {
-      if (c->d_red) { (void)hipFree(c->d_red); c->d_red = nullptr; c->red_cap = 0; }
-      HIP_TRY(c, hipMalloc((void **)&c->d_red, k * 128 * sizeof(u64)));
-      c->red_cap = k;
-    }
+    int rc = ensure_red(c, k);
     // descriptors and results share the pinned staging buffer (stream order: upload, kernel, download)
-    int rc = ensure_desc(c, std::max(k * sizeof(MaskJob), k * 128 * sizeof(u64)));
+    if (rc == FTKX_OK) rc = ensure_desc(c, std::max(k * sizeof(MaskJob), k * 128 * sizeof(u64)));
     if (rc) return rc;
-    launch_init_red(c->d_red, k * 64, nullptr, c->stream);
+    launch_init_red(c->d_red.as<u64>(), k * 64, nullptr, c->stream);
     if (c->scalar_mode == 1 && ftkx::march2_supported(m)) {
       // the marching stencil kernel in reduce-only mode over all slices at once
-      MaskJob *jobs = (MaskJob *)c->h_desc;
-      for (size_t i = 0; i < k; i ++) jobs[i] = MaskJob{todo[i]->S, nullptr, nullptr, nullptr, c->d_red + i * 128, 1.0};
-      HIP_TRY(c, hipMemcpyAsync(c->d_desc, c->h_desc, k * sizeof(MaskJob), hipMemcpyHostToDevice, c->stream));
-      ftkx::launch_reduce_march(m, (const MaskJob *)c->d_desc, (int)k, c->stream);
+      MaskJob *jobs = (MaskJob *)c->h_desc.p;
+      for (size_t i = 0; i < k; i ++) jobs[i] = MaskJob{todo[i]->S, nullptr, nullptr, nullptr, c->d_red.as<u64>() + i * 128, 1.0};
+      HIP_TRY(c, hipMemcpyAsync(c->d_desc.p, c->h_desc.p, k * sizeof(MaskJob), hipMemcpyHostToDevice, c->stream));
+      ftkx::launch_reduce_march(m, (const MaskJob *)c->d_desc.p, (int)k, c->stream);
     } else {
       // one launch per slice, back to back, each into its own slots
       for (size_t i = 0; i < k; i ++) {
-        if (c->scalar_mode == 1) ftkx::launch_resolution_scalar(m, todo[i]->S, c->d_red + i * 128, c->stream);
-        else ftkx::launch_resolution(todo[i]->V, n_vertices(c) * (size_t)c->nd, c->d_red + i * 128, c->stream);
+        if (c->scalar_mode == 1) ftkx::launch_resolution_scalar(m, todo[i]->S, c->d_red.as<u64>() + i * 128, c->stream);
+        else ftkx::launch_resolution(todo[i]->V, n_vertices(c) * (size_t)c->nd, c->d_red.as<u64>() + i * 128, c->stream);
       }
     }
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(c->h_desc, c->d_red, k * 128 * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->h_desc.p, c->d_red.as<u64>(), k * 128 * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    const u64 *host = (const u64 *)c->h_desc;
+    const u64 *host = (const u64 *)c->h_desc.p;
     for (size_t i = 0; i < k; i ++) {
       u64 mn = host[i * 128], mx = host[i * 128 + 1];
       for (int q = 1; q < 64; q ++) { mn = std::min(mn, host[i * 128 + 2 * q]); mx = std::max(mx, host[i * 128 + 2 * q + 1]); }
@@ -781,7 +724,7 @@ int ftkx_debug_stream_read(ftkx_ctx *c, const void *device_ptr, size_t bytes)
 {
   if (!c || !device_ptr) return fail(c, FTKX_E_INVALID, "null argument");
   HIP_TRY(c, hipSetDevice(c->device));
-  ftkx::launch_calib_read(device_ptr, bytes, (double *)(c->sr_tail[0].counters + ftkx::CNT_N), c->stream);
+  ftkx::launch_calib_read(device_ptr, bytes, (double *)(c->sr_tail[0].counters.as<u64>() + ftkx::CNT_N), c->stream);
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return FTKX_OK;
@@ -906,8 +849,8 @@ int ftkx_gaussian_kernel(int nd, double sigma, int ksize, double *weights)
 
 static int conv_weights(ftkx_ctx *c, const double *weights, int n, size_t at)
 {
-  if (!c->d_conv_w) HIP_TRY(c, hipMalloc((void **)&c->d_conv_w, 2 * kSmoothWeights * sizeof(double)));
-  HIP_TRY(c, hipMemcpyAsync(c->d_conv_w + at, weights, (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  if (const int rc = c->d_conv_w.reserve(c, 2 * kSmoothWeights * sizeof(double))) return rc;
+  HIP_TRY(c, hipMemcpyAsync(c->d_conv_w.as<double>() + at, weights, (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
   return FTKX_OK;
 }
 
@@ -921,7 +864,7 @@ static int conv_common(ftkx_ctx *c, int nd, const double *S, int DW, int DH, int
   if (S < out + n && out < S + n) return fail(c, FTKX_E_INVALID, "ftkx_conv%dD: input and output overlap", nd);
   int taps = ksize * ksize * (nd == 3 ? ksize : 1);
   if (int rc = conv_weights(c, weights, taps, 0)) return rc;
-  ftkx::launch_conv(nd, S, DW, DH, DD, c->d_conv_w, ksize, out, c->stream);
+  ftkx::launch_conv(nd, S, DW, DH, DD, c->d_conv_w.as<double>(), ksize, out, c->stream);
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipStreamSynchronize(c->stream));      // (the next call may overwrite the weights; the caller may read `out`)
   return FTKX_OK;
@@ -944,7 +887,7 @@ int ftkx_debug_conv_relaunch(ftkx_ctx *c, int nd, const double *S, int DW, int D
     for (hipEvent_t &e : ev) HIP_TRY(c, hipEventCreate(&e));
     for (int i = 0; i < reps; i ++) {
       HIP_TRY(c, hipEventRecord(ev[2 * (size_t)i], c->stream));
-      ftkx::launch_conv(nd, S, DW, DH, nd == 3 ? DD : 1, c->d_conv_w, ksize, out, c->stream);
+      ftkx::launch_conv(nd, S, DW, DH, nd == 3 ? DD : 1, c->d_conv_w.as<double>(), ksize, out, c->stream);
       HIP_TRY(c, hipEventRecord(ev[2 * (size_t)i + 1], c->stream));
     }
     HIP_TRY(c, hipGetLastError());

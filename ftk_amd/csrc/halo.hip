@@ -5,6 +5,34 @@
 
 using namespace ftkxh;
 
+// ---- staging and the masks-only slice ----------------------------------------------------------------------------------------------
+namespace {
+// the compacted mask words: an index and a word per entry, each array admitted by its own bytes; `room` entries are allocated where it grows
+int reserve_words(ftkx_ctx *c, size_t n, size_t room)
+{
+  if (const int rc = c->d_word_idx.reserve(c, n * sizeof(unsigned), room * sizeof(unsigned))) return rc;
+  return c->d_words.reserve(c, n * sizeof(u64), room * sizeof(u64));
+}
+size_t words_capacity(const ftkx_ctx *c) { return std::min(c->d_word_idx.count<unsigned>(), c->d_words.count<u64>()); }   // what a compaction may write
+
+// a packed mask message of a host-side caller (gloo) goes through device memory
+int stage_packed(ftkx_ctx *c, size_t total) { return c->d_packed.reserve(c, total); }
+
+// a slice becomes masks-only: a zeroed field array (only patches are ever read; zeros elsewhere, not garbage), mask and summary arrays
+int make_sparse(ftkx_ctx *c, Slice &s, int scalar_input)
+{
+  if (s.sparse) return FTKX_OK;
+  const size_t bytes = n_vertices(c) * (scalar_input ? 1 : (size_t)c->nd) * sizeof(double);
+  double **field = scalar_input ? &s.S : &s.V;
+  HIP_TRY(c, hipMalloc((void **)field, bytes));
+  (scalar_input ? s.ownS : s.ownV) = true;
+  HIP_TRY(c, hipMemsetAsync(*field, 0, bytes, c->stream));
+  if (const int rc = ensure_mask_arrays(c, s, true)) return rc;
+  s.sparse = true;
+  return FTKX_OK;
+}
+}  // namespace
+
 extern "C" {
 
 // ---- compact t-slab halo ------------------------------------------------------------------------------------------------------
@@ -27,20 +55,15 @@ int ftkx_export_masks_size(ftkx_ctx *c, int t, size_t *u_bytes_out, size_t *n_wo
   HIP_TRY(c, hipSetDevice(c->device));
   Mesh m; fill_mesh(c, m);
   for (int attempt = 0; attempt < 2; attempt ++) {
-    HIP_TRY(c, hipMemsetAsync(c->sr_tail[0].counters + ftkx::CNT_SPARSE, 0, sizeof(u64), c->stream));
-    ftkx::launch_compact_words(m, s.U, s.M, c->d_word_idx, c->d_words, c->words_cap, c->sr_tail[0].counters + ftkx::CNT_SPARSE, c->stream);
+    HIP_TRY(c, hipMemsetAsync(c->sr_tail[0].counters.as<u64>() + ftkx::CNT_SPARSE, 0, sizeof(u64), c->stream));
+    ftkx::launch_compact_words(m, s.U, s.M, c->d_word_idx.as<unsigned>(), c->d_words.as<u64>(), words_capacity(c), c->sr_tail[0].counters.as<u64>() + ftkx::CNT_SPARSE, c->stream);
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(c->h_counters, c->sr_tail[0].counters + ftkx::CNT_SPARSE, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    const u64 *hc = c->h_counters.as<u64>();
+    HIP_TRY(c, hipMemcpyAsync(c->h_counters.p, c->sr_tail[0].counters.as<u64>() + ftkx::CNT_SPARSE, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    const size_t n = (size_t)c->h_counters[0];
-    if (n <= c->words_cap) { c->n_words = n; c->words_t = t; break; }
-    if (c->d_word_idx) (void)hipFree(c->d_word_idx);
-    if (c->d_words) (void)hipFree(c->d_words);
-    c->d_word_idx = nullptr; c->d_words = nullptr; c->words_cap = 0;
-    const size_t cap = n + n / 8 + 1024;
-    HIP_TRY(c, hipMalloc((void **)&c->d_word_idx, cap * sizeof(unsigned)));
-    HIP_TRY(c, hipMalloc((void **)&c->d_words, cap * sizeof(u64)));
-    c->words_cap = cap;
+    const size_t n = (size_t)hc[0];
+    if (n <= words_capacity(c)) { c->n_words = n; c->words_t = t; break; }
+    if (const int rc = reserve_words(c, n, n + n / 8 + 1024)) return rc;
   }
   if (u_bytes_out) *u_bytes_out = u_bytes_used(c, m);
   if (n_words) *n_words = c->n_words;
@@ -59,14 +82,14 @@ int ftkx_export_masks(ftkx_ctx *c, int t, void *U_dst, unsigned *word_index_dst,
   Mesh m; fill_mesh(c, m);
   if ((rc = copy_out(c, U_dst, it->second.U, u_bytes_used(c, m), dst_on_device))) return rc;
   if (c->n_words && (!word_index_dst || !words_dst)) return fail(c, FTKX_E_INVALID, "ftkx_export_masks: null list buffers");
-  if ((rc = copy_out(c, word_index_dst, c->d_word_idx, c->n_words * sizeof(unsigned), dst_on_device))) return rc;
-  if ((rc = copy_out(c, words_dst, c->d_words, c->n_words * sizeof(u64), dst_on_device))) return rc;
+  if ((rc = copy_out(c, word_index_dst, c->d_word_idx.as<unsigned>(), c->n_words * sizeof(unsigned), dst_on_device))) return rc;
+  if ((rc = copy_out(c, words_dst, c->d_words.as<u64>(), c->n_words * sizeof(u64), dst_on_device))) return rc;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return FTKX_OK;
 }
 
 namespace {
-u64 *halo_bad_flag(ftkx_ctx *c) { return c->sr_tail[0].counters + ftkx::CNT_N + 128; }
+u64 *halo_bad_flag(ftkx_ctx *c) { return c->sr_tail[0].counters.as<u64>() + ftkx::CNT_N + 128; }
 size_t pad8(size_t v) { return (v + 7) / 8 * 8; }
 int factor_log2(unsigned long long f) { int b = 0; while (b < 63 && (1ull << b) < f) b ++; return b; }
 // capacity of the word list in a packed mask message: the mask kernels write a word only where its summary is 0 -- a thin shell around
@@ -96,19 +119,8 @@ int ensure_sparse_slice(ftkx_ctx *c, int t, int scalar_input)
   if (it != c->slices.end()) return it->second.sparse ? FTKX_OK : fail(c, FTKX_E_INVALID, "halo slice: timestep %d is resident as a full slice (drop it first)", t);
   c->scalar_mode = scalar_input ? 1 : 0;
   Slice s;
-  const size_t n = n_vertices(c), ncomp = scalar_input ? 1 : (size_t)c->nd;
-  auto fill = [&]() -> int {
-    int rc;
-    double **field = scalar_input ? &s.S : &s.V;
-    HIP_TRY(c, hipMalloc((void **)field, n * ncomp * sizeof(double)));
-    (scalar_input ? s.ownS : s.ownV) = true;
-    HIP_TRY(c, hipMemsetAsync(*field, 0, n * ncomp * sizeof(double), c->stream));
-    if ((rc = ensure_mask_arrays(c, s, true))) return rc;
-    return FTKX_OK;
-  };
-  const int rc = fill();
+  const int rc = make_sparse(c, s, scalar_input);
   if (rc != FTKX_OK) { free_slice(s, c); return rc; }
-  s.sparse = true;
   s.mask_gen = ++ c->mask_epoch;
   c->slices[t] = s;
   return FTKX_OK;
@@ -140,39 +152,24 @@ int ftkx_push_masked_slice(ftkx_ctx *c, int t, int scalar_input, const void *U, 
   Slice s;
   if (it != c->slices.end() && it->second.sparse) { s = it->second; c->slices.erase(it); }          // the same halo slice again: keep its arrays
   else if (it != c->slices.end()) { free_slice(it->second, c); c->slices.erase(it); }
-  const size_t n = n_vertices(c), ncomp = scalar_input ? 1 : (size_t)c->nd;
   // everything below that can fail runs inside `fill`: on failure the half-built slice is released, not leaked
   auto fill = [&]() -> int {
   int rc;
-  if (!s.sparse) {
-    double **field = scalar_input ? &s.S : &s.V;
-    HIP_TRY(c, hipMalloc((void **)field, n * ncomp * sizeof(double)));
-    (scalar_input ? s.ownS : s.ownV) = true;
-    HIP_TRY(c, hipMemsetAsync(*field, 0, n * ncomp * sizeof(double), c->stream));      // only patches are ever read; zeros elsewhere, not garbage
-    if ((rc = ensure_mask_arrays(c, s, true))) return rc;
-    s.sparse = true;
-  }
+  if ((rc = make_sparse(c, s, scalar_input))) return rc;
   const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
   HIP_TRY(c, hipMemcpyAsync(s.U, U, u_bytes_used(c, m), kind, c->stream));
   if (n_words) {
-    if (c->words_cap < n_words) {
-      if (c->d_word_idx) (void)hipFree(c->d_word_idx);
-      if (c->d_words) (void)hipFree(c->d_words);
-      c->d_word_idx = nullptr; c->d_words = nullptr; c->words_cap = 0;
-      HIP_TRY(c, hipMalloc((void **)&c->d_word_idx, n_words * sizeof(unsigned)));
-      HIP_TRY(c, hipMalloc((void **)&c->d_words, n_words * sizeof(u64)));
-      c->words_cap = n_words;
-    }
+    if ((rc = reserve_words(c, n_words, n_words))) return rc;
     c->words_t = -1;
-    HIP_TRY(c, hipMemcpyAsync(c->d_word_idx, word_index, n_words * sizeof(unsigned), kind, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->d_words, words, n_words * sizeof(u64), kind, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->d_word_idx.as<unsigned>(), word_index, n_words * sizeof(unsigned), kind, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->d_words.as<u64>(), words, n_words * sizeof(u64), kind, c->stream));
     HIP_TRY(c, hipMemsetAsync(halo_bad_flag(c), 0, sizeof(u64), c->stream));
-    ftkx::launch_scatter_words(c->d_word_idx, c->d_words, n_words, s.M, mask_bytes(c) / 8, halo_bad_flag(c), c->stream);
+    ftkx::launch_scatter_words(c->d_word_idx.as<unsigned>(), c->d_words.as<u64>(), n_words, s.M, mask_bytes(c) / 8, halo_bad_flag(c), c->stream);
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(c->h_counters, halo_bad_flag(c), sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->h_counters.p, halo_bad_flag(c), sizeof(u64), hipMemcpyDeviceToHost, c->stream));
   }
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (n_words && c->h_counters[0]) return fail(c, FTKX_E_INVALID, "ftkx_push_masked_slice: word indices outside the mask array (a sender with another mesh?)");
+  if (n_words && c->h_counters.as<u64>()[0]) return fail(c, FTKX_E_INVALID, "ftkx_push_masked_slice: word indices outside the mask array (a sender with another mesh?)");
   return FTKX_OK;
   };
   const int frc = fill();
@@ -210,15 +207,15 @@ int ftkx_export_masks_packed(ftkx_ctx *c, int t, void *dst, int dst_on_device)
   const size_t total = ftkx_packed_masks_bytes(c, &cap), ub = u_bytes_used(c, m);
   char *out = (char *)dst;
   if (!dst_on_device) {                                    // host-side callers (gloo): build it in device memory, copy out
-    if (c->packed_cap < total) { if (c->d_packed) (void)hipFree(c->d_packed); c->d_packed = nullptr; c->packed_cap = 0; HIP_TRY(c, hipMalloc(&c->d_packed, total)); c->packed_cap = total; }
-    out = (char *)c->d_packed;
+    if (const int rc = stage_packed(c, total)) return rc;
+    out = (char *)c->d_packed.p;
   }
   unsigned *idx = (unsigned *)(out + 32 + pad8(ub));
   u64 *words = (u64 *)(out + 32 + pad8(ub) + pad8(cap * sizeof(unsigned)));
-  HIP_TRY(c, hipMemsetAsync(c->sr_tail[0].counters + ftkx::CNT_SPARSE, 0, sizeof(u64), c->stream));
-  ftkx::launch_compact_words(m, s.U, s.M, idx, words, cap, c->sr_tail[0].counters + ftkx::CNT_SPARSE, c->stream);
+  HIP_TRY(c, hipMemsetAsync(c->sr_tail[0].counters.as<u64>() + ftkx::CNT_SPARSE, 0, sizeof(u64), c->stream));
+  ftkx::launch_compact_words(m, s.U, s.M, idx, words, cap, c->sr_tail[0].counters.as<u64>() + ftkx::CNT_SPARSE, c->stream);
   // (the header says under which factor the masks were built and how many rows a summary byte stands for: the receiver checks both)
-  ftkx::launch_pack_masks((u64 *)out, c->sr_tail[0].counters + ftkx::CNT_SPARSE, s.U, ub, cap, s.u_rows, factor_log2(s.mask_factor), c->stream);
+  ftkx::launch_pack_masks((u64 *)out, c->sr_tail[0].counters.as<u64>() + ftkx::CNT_SPARSE, s.U, ub, cap, s.u_rows, factor_log2(s.mask_factor), c->stream);
   HIP_TRY(c, hipGetLastError());
   if (!dst_on_device) { HIP_TRY(c, hipMemcpyAsync(dst, out, total, hipMemcpyDeviceToHost, c->stream)); HIP_TRY(c, hipStreamSynchronize(c->stream)); }
   return FTKX_OK;                                          // (device destination: queued on the context's stream, nothing waited for)
@@ -244,22 +241,14 @@ int ftkx_push_masked_slice_packed(ftkx_ctx *c, int t, int scalar_input, const vo
   Slice s;
   if (it != c->slices.end() && it->second.sparse) { s = it->second; c->slices.erase(it); }          // the same halo slice again: keep its arrays
   else if (it != c->slices.end()) { free_slice(it->second, c); c->slices.erase(it); }
-  const size_t n = n_vertices(c), ncomp = scalar_input ? 1 : (size_t)c->nd;
   auto fill = [&]() -> int {
     int rc;
-    if (!s.sparse) {
-      double **field = scalar_input ? &s.S : &s.V;
-      HIP_TRY(c, hipMalloc((void **)field, n * ncomp * sizeof(double)));
-      (scalar_input ? s.ownS : s.ownV) = true;
-      HIP_TRY(c, hipMemsetAsync(*field, 0, n * ncomp * sizeof(double), c->stream));      // only patches are ever read; zeros elsewhere, not garbage
-      if ((rc = ensure_mask_arrays(c, s, true))) return rc;
-      s.sparse = true;
-    }
+    if ((rc = make_sparse(c, s, scalar_input))) return rc;
     const char *in = (const char *)src;
     if (!src_on_device) {
-      if (c->packed_cap < total) { if (c->d_packed) (void)hipFree(c->d_packed); c->d_packed = nullptr; c->packed_cap = 0; HIP_TRY(c, hipMalloc(&c->d_packed, total)); c->packed_cap = total; }
-      HIP_TRY(c, hipMemcpyAsync(c->d_packed, src, total, hipMemcpyHostToDevice, c->stream));
-      in = (const char *)c->d_packed;
+      if ((rc = stage_packed(c, total))) return rc;
+      HIP_TRY(c, hipMemcpyAsync(c->d_packed.p, src, total, hipMemcpyHostToDevice, c->stream));
+      in = (const char *)c->d_packed.p;
     }
     // summaries and words: count, geometry, the sender's mask settings and factor (it must not exceed the factor the receiver was told:
     // masks serve their own factor and larger ones) and every index are checked on the device; a message that does not fit raises the
@@ -294,15 +283,11 @@ int ftkx_sweep_cull(ftkx_ctx *c, int t_sparse, size_t *n_cells)
   if ((rc = ensure_hit_buffer(c, std::max<u64>(c->capacity, 1u << 16)))) return rc;
   if ((rc = ensure_list(c, c->sr_tail[0], std::max<u64>(c->sr_tail[0].list_capacity, 1u << 20))) || (rc = ensure_refine(c, c->sr_tail[0], std::max<u64>(c->sr_tail[0].refine_capacity, 1u << 20)))) return rc;
   for (int attempt = 0; attempt < 4; attempt ++) {
-    if (c->cells_cap < c->sr_tail[0].list_capacity) {
-      if (c->d_cells) (void)hipFree(c->d_cells);
-      c->d_cells = nullptr; c->cells_cap = 0;
-      HIP_TRY(c, hipMalloc((void **)&c->d_cells, c->sr_tail[0].list_capacity * sizeof(u64)));
-      c->cells_cap = c->sr_tail[0].list_capacity;
-    }
-    HIP_TRY(c, hipMemsetAsync(c->sr_tail[0].counters, 0, ftkx::CNT_N * sizeof(u64), c->stream));
+    if ((rc = c->d_cells.reserve(c, c->sr_tail[0].list_capacity * sizeof(u64)))) return rc;      // (run_batch hands launch_sparse_cells its count)
+    HIP_TRY(c, hipMemsetAsync(c->sr_tail[0].counters.as<u64>(), 0, ftkx::CNT_N * sizeof(u64), c->stream));
     if ((rc = run_batch(c, field))) return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->h_counters, c->sr_tail[0].counters, ftkx::CNT_N * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    const u64 *hc = c->h_counters.as<u64>();
+    HIP_TRY(c, hipMemcpyAsync(c->h_counters.p, c->sr_tail[0].counters.as<u64>(), ftkx::CNT_N * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
     u64 halo_bad = 0;
     HIP_TRY(c, hipMemcpyAsync(&halo_bad, halo_bad_flag(c), sizeof(u64), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -312,8 +297,8 @@ int ftkx_sweep_cull(ftkx_ctx *c, int t_sparse, size_t *n_cells)
     }
     for (auto &e : c->events) { ev_give(c, e.second.first); ev_give(c, e.second.second); }
     c->events.clear();
-    const u64 listed = c->h_counters[ftkx::CNT_SURVIVOR_LIST], refined = std::max(c->h_counters[ftkx::CNT_REFINE_LIST], c->h_counters[ftkx::CNT_REFINE_PEAK]);
-    if (listed <= c->sr_tail[0].list_capacity && refined <= c->sr_tail[0].refine_capacity) { c->n_cells = (size_t)c->h_counters[ftkx::CNT_SPARSE]; *n_cells = c->n_cells; return FTKX_OK; }
+    const u64 listed = hc[ftkx::CNT_SURVIVOR_LIST], refined = std::max(hc[ftkx::CNT_REFINE_LIST], hc[ftkx::CNT_REFINE_PEAK]);
+    if (listed <= c->sr_tail[0].list_capacity && refined <= c->sr_tail[0].refine_capacity) { c->n_cells = (size_t)hc[ftkx::CNT_SPARSE]; *n_cells = c->n_cells; return FTKX_OK; }
     if (refined > c->sr_tail[0].refine_capacity && (rc = ensure_refine(c, c->sr_tail[0], refined + refined / 8 + 1024))) return rc;
     if (listed > c->sr_tail[0].list_capacity && (rc = ensure_list(c, c->sr_tail[0], 2 * listed + 1024))) return rc;
   }
@@ -324,7 +309,7 @@ int ftkx_get_sparse_cells(ftkx_ctx *c, unsigned long long *dst, int dst_on_devic
 {
   if (!c || (c->n_cells && !dst)) return fail(c, FTKX_E_INVALID, "null argument");
   HIP_TRY(c, hipSetDevice(c->device));
-  int rc = copy_out(c, dst, c->d_cells, c->n_cells * sizeof(u64), dst_on_device);
+  int rc = copy_out(c, dst, c->d_cells.as<u64>(), c->n_cells * sizeof(u64), dst_on_device);
   if (rc) return rc;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return FTKX_OK;
@@ -346,21 +331,16 @@ static int patches_common(ftkx_ctx *c, int t, const unsigned long long *cells, s
   const size_t pd = ftkx_patch_doubles(c);
   const u64 *d_cells = cells; double *d_patches = patches;
   if (!on_device) {                              // host-side callers (gloo tests): stage through device buffers
-    if (c->patch_cap < n) {
-      if (c->d_patch_cells) (void)hipFree(c->d_patch_cells);
-      if (c->d_patches) (void)hipFree(c->d_patches);
-      c->d_patch_cells = nullptr; c->d_patches = nullptr; c->patch_cap = 0;
-      HIP_TRY(c, hipMalloc((void **)&c->d_patch_cells, n * sizeof(u64)));
-      HIP_TRY(c, hipMalloc((void **)&c->d_patches, n * pd * sizeof(double)));
-      c->patch_cap = n;
-    }
-    HIP_TRY(c, hipMemcpyAsync(c->d_patch_cells, cells, n * sizeof(u64), hipMemcpyHostToDevice, c->stream));
-    if (scatter) HIP_TRY(c, hipMemcpyAsync(c->d_patches, patches, n * pd * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    d_cells = c->d_patch_cells; d_patches = c->d_patches;
+    // (admitted by bytes: a context whose slices went from scalar to vector keeps its cell count and needs nd times the patches)
+    int rc;
+    if ((rc = c->d_patch_cells.reserve(c, n * sizeof(u64))) || (rc = c->d_patches.reserve(c, n * pd * sizeof(double)))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(c->d_patch_cells.as<u64>(), cells, n * sizeof(u64), hipMemcpyHostToDevice, c->stream));
+    if (scatter) HIP_TRY(c, hipMemcpyAsync(c->d_patches.as<double>(), patches, n * pd * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    d_cells = c->d_patch_cells.as<u64>(); d_patches = c->d_patches.as<double>();
   }
   ftkx::launch_patches(m, scatter, d_cells, n, ncomp, field, d_patches, c->stream);
   HIP_TRY(c, hipGetLastError());
-  if (!on_device && !scatter) HIP_TRY(c, hipMemcpyAsync(patches, c->d_patches, n * pd * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (!on_device && !scatter) HIP_TRY(c, hipMemcpyAsync(patches, c->d_patches.as<double>(), n * pd * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return FTKX_OK;
 }

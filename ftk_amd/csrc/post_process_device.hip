@@ -21,8 +21,8 @@ PpPlan plan_of(size_t n_rec, size_t np, size_t nc) { return PpPlan(n_rec, np, nc
 // the context's blocks for the plan, and its work arrays bound to the device block
 int prepare(ftkx_ctx *c, PpPlan &pl)
 {
-  if (const int rc = c->p2.pp_dev.reserve(c, pl.dev_bytes, false)) return rc;
-  if (const int rc = c->p2.pp_host.reserve(c, pl.host_bytes, true)) return rc;
+  if (const int rc = c->p2.pp_dev.reserve(c, pl.dev_bytes, pass2_room(pl.dev_bytes))) return rc;
+  if (const int rc = c->p2.pp_host.reserve(c, pl.host_bytes, pass2_room(pl.host_bytes))) return rc;
   pl.bind(c->p2.pp_dev.p);
   return FTKX_OK;
 }

@@ -91,11 +91,13 @@ bool ahead_steps(ftkx_ctx *c, bool two_level, u64 hint, std::vector<Fields> &ste
   return !steps.empty();
 }
 
+unsigned *red_flag(ftkx_ctx *c) { return reinterpret_cast<unsigned *>(c->h_red.as<u64>() + c->h_red.count<u64>() - 8); }   // behind the slots
+
 void ahead_launch(ftkx_ctx *c, const Mesh &m, bool two_level, const Fields *d_steps, int nsteps)
 {
   ev_begin(c, K_CULL);
-  if (two_level) ftkx::launch_cull_two_level(m, d_steps, nsteps, c->sr_tail[0].refine, c->sr_tail[0].refine_capacity, c->sr_tail[0].list, c->sr_tail[0].list_capacity, c->stream);
-  else ftkx::launch_cull(m, d_steps, nsteps, c->sr_tail[0].list, c->sr_tail[0].list_capacity, c->stream);
+  if (two_level) ftkx::launch_cull_two_level(m, d_steps, nsteps, c->sr_tail[0].refine.as<u64>(), c->sr_tail[0].refine_capacity, c->sr_tail[0].list.as<u64>(), c->sr_tail[0].list_capacity, c->stream);
+  else ftkx::launch_cull(m, d_steps, nsteps, c->sr_tail[0].list.as<u64>(), c->sr_tail[0].list_capacity, c->stream);
   ev_end(c);
 }
 
@@ -138,11 +140,7 @@ int ftkx_slices_prepare(ftkx_ctx *c, const int *ts, int n, unsigned long long fa
   }
   if (!todo.empty()) {
     const size_t k = todo.size();
-    if (c->red_cap < k) {
-      if (c->d_red) { (void)hipFree(c->d_red); c->d_red = nullptr; c->red_cap = 0; }
-      HIP_TRY(c, hipMalloc((void **)&c->d_red, k * 128 * sizeof(u64)));
-      c->red_cap = k;
-    }
+    if ((rc = ensure_red(c, k))) return rc;
     for (Slice *s : todo) if ((rc = ensure_mask_arrays(c, *s, two_level))) return rc;
     // cull-ahead: the masks are about to be built under the hint -- mark them so (the validation further down may take that back).
     // Everything that could synchronise the device happens before the mask launch; the announced sweeps' descriptors are put
@@ -158,23 +156,12 @@ int ftkx_slices_prepare(ftkx_ctx *c, const int *ts, int n, unsigned long long fa
       const size_t bytes = c->announced.size() * sizeof(Fields);
       rc = FTKX_OK;
       if (c->ahead_staged) { HIP_TRY(c, hipStreamSynchronize(c->stream)); c->ahead_staged = false; }   // (prepare after prepare, no collect in between)
-      if (c->ahead_cap < bytes) {
-        if (c->h_ahead) { HIP_TRY(c, hipStreamSynchronize(c->stream)); (void)hipHostFree(c->h_ahead); c->h_ahead = nullptr; }
-        if (c->d_ahead) { (void)hipFree(c->d_ahead); c->d_ahead = nullptr; }
-        c->ahead_cap = 0;
-        const size_t capb = (bytes * 2 + 4095) / 4096 * 4096;
-        HIP_TRY(c, hipHostMalloc(&c->h_ahead, capb, hipHostMallocCoherent));
-        HIP_TRY(c, hipMalloc(&c->d_ahead, capb));
-        c->ahead_cap = capb;
-      }
-      if (c->h_red_cap < k * 2) {
-        if (c->h_red) { HIP_TRY(c, hipStreamSynchronize(c->stream)); (void)hipHostFree(c->h_red); c->h_red = nullptr; c->h_red_cap = 0; }
-        const size_t slots = (k + k / 4 + 8) * 2;
-        HIP_TRY(c, hipHostMalloc((void **)&c->h_red, (slots + 8) * sizeof(u64), hipHostMallocCoherent));
-        c->h_red_cap = slots;
-        *reinterpret_cast<volatile unsigned *>(c->h_red + slots) = 0u;
-        c->red_seq = 0;
-      }
+      const size_t capb = (bytes * 2 + 4095) / 4096 * 4096;
+      if ((rc = c->h_ahead.reserve(c, bytes, capb, c->stream)) || (rc = c->d_ahead.reserve(c, bytes, capb))) return rc;
+      // two words per slice, and 8 words behind them of which the first holds the flag
+      bool fresh = false;
+      if ((rc = c->h_red.reserve(c, (k * 2 + 8) * sizeof(u64), ((k + k / 4 + 8) * 2 + 8) * sizeof(u64), c->stream, &fresh))) return rc;
+      if (fresh) { *reinterpret_cast<volatile unsigned *>(red_flag(c)) = 0u; c->red_seq = 0; }
       if ((rc = ensure_list(c, c->sr_tail[0], std::max<u64>(c->sr_tail[0].list_capacity, 1u << 20))) || (rc = ensure_refine(c, c->sr_tail[0], std::max<u64>(c->sr_tail[0].refine_capacity, 1u << 20)))) return rc;
     }
     else {                         // (no cull-ahead: the masks are rewritten all the same -- whatever they were valid for is gone)
@@ -182,29 +169,29 @@ int ftkx_slices_prepare(ftkx_ctx *c, const int *ts, int n, unsigned long long fa
       for (Slice *s : todo) s->mask_factor = 0;
     }
     if ((rc = ensure_desc(c, std::max(k * sizeof(MaskJob), k * 128 * sizeof(u64))))) return rc;
-    launch_init_red(c->d_red, k * 64, ahead_ok ? c->sr_tail[0].counters : nullptr, c->stream);
-    MaskJob *jobs = (MaskJob *)c->h_desc;
+    launch_init_red(c->d_red.as<u64>(), k * 64, ahead_ok ? c->sr_tail[0].counters.as<u64>() : nullptr, c->stream);
+    MaskJob *jobs = (MaskJob *)c->h_desc.p;
     for (size_t i = 0; i < k; i ++)
-      jobs[i] = with_lean_thresholds(MaskJob{todo[i]->S, todo[i]->V, todo[i]->M, two_level ? todo[i]->U : nullptr, c->d_red + i * 128, cap, HUGE_VAL}, m);   // rule off: validated below
-    HIP_TRY(c, hipMemcpyAsync(c->d_desc, c->h_desc, k * sizeof(MaskJob), hipMemcpyHostToDevice, c->stream));
-    ev_begin(c, K_MASK); ftkx::launch_masks(m, (const MaskJob *)c->d_desc, (int)k, c->stream); ev_end(c);
+      jobs[i] = with_lean_thresholds(MaskJob{todo[i]->S, todo[i]->V, todo[i]->M, two_level ? todo[i]->U : nullptr, c->d_red.as<u64>() + i * 128, cap, HUGE_VAL}, m);   // rule off: validated below
+    HIP_TRY(c, hipMemcpyAsync(c->d_desc.p, c->h_desc.p, k * sizeof(MaskJob), hipMemcpyHostToDevice, c->stream));
+    ev_begin(c, K_MASK); ftkx::launch_masks(m, (const MaskJob *)c->d_desc.p, (int)k, c->stream); ev_end(c);
     HIP_TRY(c, hipGetLastError());
-    const u64 *host = (const u64 *)c->h_desc;
+    const u64 *host = (const u64 *)c->h_desc.p;
     std::vector<Fields> a_steps;
     std::vector<ftkx_ctx::AheadStep> a_rec;
     if (ahead_ok) ahead_ok = ahead_steps(c, two_level, hint, a_steps, a_rec);
     if (ahead_ok) {
       // behind the mask kernel, kernels only: the reduction folded and written to pinned memory with a flag behind it, the
       // descriptors fetched from pinned memory, the cull.  The host waits for the flag ONLY; the cull runs while it forms the factors
-      unsigned *flag = reinterpret_cast<unsigned *>(c->h_red + c->h_red_cap);
+      unsigned *flag = red_flag(c);
       const unsigned seq = ++ c->red_seq;
-      hipLaunchKernelGGL(readback_kernel, dim3(1), dim3(256), 0, c->stream, (const u64 *)c->d_red, c->h_red, (unsigned)k, flag, seq);
+      hipLaunchKernelGGL(readback_kernel, dim3(1), dim3(256), 0, c->stream, (const u64 *)c->d_red.as<u64>(), c->h_red.as<u64>(), (unsigned)k, flag, seq);
       const size_t bytes = a_steps.size() * sizeof(Fields);
       static_assert(sizeof(Fields) % 8 == 0, "descriptors are fetched as 8-byte words");
-      memcpy(c->h_ahead, a_steps.data(), bytes);
+      memcpy(c->h_ahead.p, a_steps.data(), bytes);
       c->ahead_staged = true;
-      launch_fetch_desc(c->h_ahead, c->d_ahead, bytes, c->stream);
-      ahead_launch(c, m, two_level, (const Fields *)c->d_ahead, (int)a_steps.size());
+      launch_fetch_desc(c->h_ahead.p, c->d_ahead.p, bytes, c->stream);
+      ahead_launch(c, m, two_level, (const Fields *)c->d_ahead.p, (int)a_steps.size());
       HIP_TRY(c, hipGetLastError());
       c->ahead = a_rec;
       // spin on the flag; a device error would leave it unset: look at the stream now and then, give up after a generous while
@@ -214,14 +201,14 @@ int ftkx_slices_prepare(ftkx_ctx *c, const int *ts, int n, unsigned long long fa
       }
       ev_harvest(c, false);
     } else {
-      HIP_TRY(c, hipMemcpyAsync(c->h_desc, c->d_red, k * 128 * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipMemcpyAsync(c->h_desc.p, c->d_red.as<u64>(), k * 128 * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
       HIP_TRY(c, hipStreamSynchronize(c->stream));
       ev_harvest(c);
     }
     std::vector<Slice *> with_inf;
     for (size_t i = 0; i < k; i ++) {
       u64 mn, mx;
-      if (ahead_ok) { mn = c->h_red[2 * i]; mx = c->h_red[2 * i + 1]; }     // folded on the device
+      if (ahead_ok) { mn = c->h_red.as<u64>()[2 * i]; mx = c->h_red.as<u64>()[2 * i + 1]; }     // folded on the device
       else {
         mn = host[i * 128]; mx = host[i * 128 + 1];
         for (int q = 1; q < 64; q ++) { mn = std::min(mn, host[i * 128 + 2 * q]); mx = std::max(mx, host[i * 128 + 2 * q + 1]); }
@@ -259,13 +246,13 @@ int ftkx_debug_mask_relaunch(ftkx_ctx *c, int t, int reps, int nstreams, int wit
   Slice &s = it->second;
   Mesh m; fill_mesh(c, m);
   const bool two_level = ftkx::masks_have_summary(m);
-  if (!s.M || (two_level && !s.U) || !c->d_red || s.sparse) return fail(c, FTKX_E_INVALID, "ftkx_debug_mask_relaunch: ftkx_slices_prepare first");
+  if (!s.M || (two_level && !s.U) || !c->d_red.as<u64>() || s.sparse) return fail(c, FTKX_E_INVALID, "ftkx_debug_mask_relaunch: ftkx_slices_prepare first");
   HIP_TRY(c, hipSetDevice(c->device));
   int rc;
   if ((rc = ensure_desc(c, 2 * 4096))) return rc;
-  MaskJob *job = (MaskJob *)c->h_desc;
-  *job = with_lean_thresholds(MaskJob{s.S, s.V, s.M, two_level ? s.U : nullptr, c->d_red, 1.0 / 256.0, HUGE_VAL}, m);
-  HIP_TRY(c, hipMemcpyAsync(c->d_desc, c->h_desc, sizeof(MaskJob), hipMemcpyHostToDevice, c->stream));
+  MaskJob *job = (MaskJob *)c->h_desc.p;
+  *job = with_lean_thresholds(MaskJob{s.S, s.V, s.M, two_level ? s.U : nullptr, c->d_red.as<u64>(), 1.0 / 256.0, HUGE_VAL}, m);
+  HIP_TRY(c, hipMemcpyAsync(c->d_desc.p, c->h_desc.p, sizeof(MaskJob), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   hipStream_t st[2] = {c->stream, nullptr};
   if (nstreams == 2 && (rc = aux_stream_get(c, false, &st[1]))) return rc;
@@ -275,8 +262,8 @@ int ftkx_debug_mask_relaunch(ftkx_ctx *c, int t, int reps, int nstreams, int wit
   if (nstreams == 2) HIP_TRY(c, hipStreamWaitEvent(st[1], e0, 0));
   for (int r = 0; r < reps; r ++) {
     hipStream_t q = st[r % nstreams];
-    if (with_begin) launch_fetch_desc(c->h_desc, (char *)c->d_desc + 4096, 4096, q);
-    ftkx::launch_masks(m, (const MaskJob *)c->d_desc, 1, q);
+    if (with_begin) launch_fetch_desc(c->h_desc.p, (char *)c->d_desc.p + 4096, 4096, q);
+    ftkx::launch_masks(m, (const MaskJob *)c->d_desc.p, 1, q);
   }
   if (nstreams == 2) { HIP_TRY(c, hipEventRecord(eb, st[1])); HIP_TRY(c, hipStreamWaitEvent(st[0], eb, 0)); }
   HIP_TRY(c, hipEventRecord(e1, st[0]));

@@ -116,25 +116,32 @@ bool series_applicable(ftkx_ctx *c, const int *ts, const int *scopes, int n, con
   return ok;
 }
 
+// a slab pass's block of DB_N words, zeroed on the context's stream when it is made
+int ensure_dist_block(ftkx_ctx *c, ftkx_series_buffers &B)
+{
+  bool fresh = false;
+  if (const int rc = B.dist_block.reserve(c, (size_t)ftkx::DB_N * sizeof(u64), 0, nullptr, &fresh)) return rc;
+  if (fresh) HIP_TRY(c, hipMemsetAsync(B.dist_block.p, 0, (size_t)ftkx::DB_N * sizeof(u64), c->stream));
+  return FTKX_OK;
+}
+
+// the pass's flag words in the pinned copy of its results block: [0] the pass is done, [2] its records have been copied
+unsigned *series_flag(const ftkx_series_buffers &B) { return reinterpret_cast<unsigned *>(B.h_results.as<u64>() + B.h_results.count<u64>() - 8); }
+
 int ensure_series_buffers(ftkx_ctx *c, ftkx_series_buffers &B, size_t nwords, size_t desc_bytes, bool to_device)
 {
-  if (B.results_cap < std::max<size_t>(nwords, 1024)) {
-    if (B.results) { HIP_TRY(c, hipFree(B.results)); B.results = nullptr; B.results_cap = 0; }
-    HIP_TRY(c, hipMalloc((void **)&B.results, std::max<size_t>(nwords, 1024) * sizeof(u64)));
-    B.results_cap = std::max<size_t>(nwords, 1024);
-  }
+  int rc;
+  if ((rc = B.results.reserve(c, std::max<size_t>(nwords, 1024) * sizeof(u64)))) return rc;
+  // the pinned copy: the block's words, the fragile list, and 8 words behind them that hold the flags (series_flag)
   const size_t h_words = nwords + (size_t)c->sr_tail[0].fragile_capacity * 10;
-  if (B.h_results_cap < h_words) {
-    if (B.h_results) { HIP_TRY(c, hipStreamSynchronize(c->stream)); (void)hipHostFree(B.h_results); B.h_results = nullptr; B.h_results_cap = 0; }
-    const size_t cap = h_words + h_words / 4 + 1024;
-    HIP_TRY(c, hipHostMalloc((void **)&B.h_results, (cap + 8) * sizeof(u64), hipHostMallocCoherent));
-    B.h_results_cap = cap;
-    *reinterpret_cast<volatile unsigned *>(B.h_results + cap) = 0u;
-    *(reinterpret_cast<volatile unsigned *>(B.h_results + cap) + 2) = 0u;          // (the copy kernel's flag)
+  bool fresh = false;
+  if ((rc = B.h_results.reserve(c, (h_words + 8) * sizeof(u64), (h_words + h_words / 4 + 1024 + 8) * sizeof(u64), c->stream, &fresh))) return rc;
+  if (fresh) {
+    *reinterpret_cast<volatile unsigned *>(series_flag(B)) = 0u;
+    *reinterpret_cast<volatile unsigned *>(series_flag(B) + 2) = 0u;          // (the copy kernel's flag)
     B.seq = 0;
   }
-  if (B.out_cap < (size_t)c->capacity) {
-    if (B.out) { HIP_TRY(c, hipStreamSynchronize(c->stream)); HIP_TRY(c, hipHostFree(B.out)); B.out = nullptr; B.out_cap = 0; }
+  if (B.out.bytes < (size_t)c->capacity * sizeof(ftkx_cp_t)) {
     // The host reads the records after it has seen the flag, which a LATER kernel on the same stream (series_finish / the copy kernel's
     // last workgroup) stores with system scope behind a __threadfence_system() -- there is no synchronisation point of the runtime in
     // between.  The HIP programming model promises visibility of such stores for COHERENT (fine-grained) host memory; that is what the
@@ -143,28 +150,20 @@ int ensure_series_buffers(ftkx_ctx *c, ftkx_series_buffers &B, size_t nwords, si
     // FTKX_SERIES_OUT_COHERENT=0: coarse-grained as in rounds 3-5, which relies on gfx950 behaviour -- the record kernel's system-scope
     // stores have left the device when the later kernel starts, and PCIe writes snoop the CPU's caches.
     const bool coherent_out = !(getenv("FTKX_SERIES_OUT_COHERENT") && atoi(getenv("FTKX_SERIES_OUT_COHERENT")) == 0);
-    HIP_TRY(c, hipHostMalloc((void **)&B.out, (size_t)c->capacity * sizeof(ftkx_cp_t), coherent_out ? hipHostMallocCoherent : hipHostMallocNonCoherent));
-    B.out_cap = (size_t)c->capacity;
+    const ftkx_block_kind kind = coherent_out ? FTKX_BLOCK_PINNED_COHERENT : FTKX_BLOCK_PINNED_NONCOHERENT;
+    if (B.out.p && (rc = ftkx_block_drain(c, c->stream))) return rc;
+    B.out = ftkx_block(kind);                                // (the kind is decided whenever the buffer is made)
+    if ((rc = B.out.reserve(c, (size_t)c->capacity * sizeof(ftkx_cp_t)))) return rc;
   }
-  if (to_device && B.d_out_cap < (size_t)c->capacity) {
-    if (B.d_out) { HIP_TRY(c, hipFree(B.d_out)); B.d_out = nullptr; B.d_out_cap = 0; }
-    HIP_TRY(c, hipMalloc((void **)&B.d_out, (size_t)c->capacity * sizeof(ftkx_cp_t)));
-    B.d_out_cap = (size_t)c->capacity;
-  }
-  if (to_device && !B.copy_done) {
-    HIP_TRY(c, hipMalloc((void **)&B.copy_done, sizeof(unsigned)));
-    HIP_TRY(c, hipMemsetAsync(B.copy_done, 0, sizeof(unsigned), c->stream));
+  if (to_device && (rc = B.d_out.reserve(c, (size_t)c->capacity * sizeof(ftkx_cp_t)))) return rc;
+  if (to_device && !B.copy_done.p) {
+    if ((rc = B.copy_done.reserve(c, sizeof(unsigned)))) return rc;
+    HIP_TRY(c, hipMemsetAsync(B.copy_done.p, 0, sizeof(unsigned), c->stream));
     HIP_TRY(c, hipEventCreateWithFlags(&B.ev_copied, hipEventDisableTiming));
   }
-  if (B.desc_cap < desc_bytes) {
-    if (B.h_desc) { HIP_TRY(c, hipStreamSynchronize(c->stream)); HIP_TRY(c, hipHostFree(B.h_desc)); B.h_desc = nullptr; }
-    if (B.d_desc) { HIP_TRY(c, hipFree(B.d_desc)); B.d_desc = nullptr; }
-    const size_t cap = std::max<size_t>(desc_bytes + desc_bytes / 4, 1 << 16);
-    HIP_TRY(c, hipHostMalloc(&B.h_desc, cap, hipHostMallocDefault));
-    HIP_TRY(c, hipMalloc(&B.d_desc, cap));
-    B.desc_cap = cap;
-  }
-  return FTKX_OK;
+  const size_t desc_room = std::max<size_t>(desc_bytes + desc_bytes / 4, 1 << 16);
+  if ((rc = B.h_desc.reserve(c, desc_bytes, desc_room, c->stream))) return rc;
+  return B.d_desc.reserve(c, desc_bytes, desc_room);
 }
 
 // ---- the tail next to the next mask kernel (round 5) -------------------------------------------------------------------------------------
@@ -191,14 +190,15 @@ int ensure_set1(ftkx_ctx *c)
 {
   const ftkx_tail_set &S0 = c->sr_tail[0];
   ftkx_tail_set &S = c->sr_tail[1];
-  if (!S.counters) {
-    HIP_TRY(c, hipMalloc((void **)&S.counters, (ftkx::CNT_N + 128 + 8) * sizeof(u64)));
-    HIP_TRY(c, hipMemsetAsync(S.counters, 0, (ftkx::CNT_N + 128 + 8) * sizeof(u64), c->stream));
+  bool fresh = false;
+  int rc = S.counters.reserve(c, (ftkx::CNT_N + 128 + 8) * sizeof(u64), 0, nullptr, &fresh);
+  if (rc) return rc;
+  if (fresh) {
+    HIP_TRY(c, hipMemsetAsync(S.counters.p, 0, (ftkx::CNT_N + 128 + 8) * sizeof(u64), c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
   }
-  int rc;
   if ((rc = ensure_list(c, S, S0.list_capacity)) || (rc = ensure_refine(c, S, S0.refine_capacity)) || (rc = ensure_pass(c, S, c->capacity)) ||
-      (rc = ensure_fragile(c, S, S0.fragile_capacity)) || (rc = ensure_order(c, S, c->capacity)) || (rc = ensure_bins(c, S, S0.bins_cap))) return rc;
+      (rc = ensure_fragile(c, S, S0.fragile_capacity)) || (rc = ensure_order(c, S, c->capacity)) || (rc = ensure_bins(c, S, S0.hist.count<unsigned>()))) return rc;
   return FTKX_OK;
 }
 
@@ -224,21 +224,21 @@ bool short_chain_now(const ftkx_ctx *c, bool to_device, bool *small_now)
 void series_queue_rest(ftkx_ctx *c, const ftkx_series_pending &P, const Mesh &m, unsigned seq)
 {
   ftkx_series_buffers &B = c->sr_buf[P.buf];
-  Fields *d_steps = (Fields *)((char *)B.d_desc + P.off_steps);
-  unsigned *flag = reinterpret_cast<unsigned *>(B.h_results + B.h_results_cap);
+  Fields *d_steps = (Fields *)((char *)B.d_desc.p + P.off_steps);
+  unsigned *flag = series_flag(B);
   hipStream_t st = tail_stream(c, P);
   // (a split pass: sparse data next to a mask kernel -- every workgroup of these kernels waits for a wavefront slot: few of them)
   const bool few = P.split_sparse;
   const ftkx_tail_set &T = tail_of(c, P);
-  if (P.two_level && !P.refined) ftkx::launch_refine(m, d_steps, T.refine, T.refine_capacity, T.list, T.list_capacity, st, few ? 64 : 0);   // (a slab pass refines before it asks for patches)
-  ftkx::launch_exact(m, d_steps, 0, T.list, T.list_capacity, st, few ? 64 : 0);
-  ftkx::launch_bucket_scan(T.hist, T.boff, (unsigned)P.nbins, T.counters, st, P.split);
-  ftkx::launch_bucket_scatter(m, T.boff, T.bucketed, st, few ? 16 : 0);
-  ftkx::launch_bucket_rank(m, T.bucketed, T.boff, T.sorted, B.results, st, few ? 16 : 0);
+  if (P.two_level && !P.refined) ftkx::launch_refine(m, d_steps, T.refine.as<u64>(), T.refine_capacity, T.list.as<u64>(), T.list_capacity, st, few ? 64 : 0);   // (a slab pass refines before it asks for patches)
+  ftkx::launch_exact(m, d_steps, 0, T.list.as<u64>(), T.list_capacity, st, few ? 64 : 0);
+  ftkx::launch_bucket_scan(T.hist.as<unsigned>(), T.boff.as<unsigned>(), (unsigned)P.nbins, T.counters.as<u64>(), st, P.split);
+  ftkx::launch_bucket_scatter(m, T.boff.as<unsigned>(), T.bucketed.as<u64>(), st, few ? 16 : 0);
+  ftkx::launch_bucket_rank(m, T.bucketed.as<u64>(), T.boff.as<unsigned>(), T.sorted.as<u64>(), B.results.as<u64>(), st, few ? 16 : 0);
   if (B.copy_out) { (void)hipStreamWaitEvent(st, B.ev_copied, 0); B.copy_out = false; }   // (the copy of the pass that used these buffers last: long through)
-  ftkx::launch_series_records(m, d_steps, T.sorted, P.to_device ? B.d_out : B.out, st, P.split);
+  ftkx::launch_series_records(m, d_steps, T.sorted.as<u64>(), P.to_device ? B.d_out.as<ftkx_cp_t>() : B.out.as<ftkx_cp_t>(), st, P.split);
   if (!P.split) ev_end(c);
-  ftkx::launch_series_finish(m, B.results, P.nwords, T.list_capacity, T.refine_capacity, B.h_results, flag, seq, st);
+  ftkx::launch_series_finish(m, B.results.as<u64>(), P.nwords, T.list_capacity, T.refine_capacity, B.h_results.as<u64>(), flag, seq, st);
 }
 
 // the records' way over PCIe: a small kernel on its own stream, behind the finish kernel (the count is final) and next to whatever the
@@ -246,11 +246,11 @@ void series_queue_rest(ftkx_ctx *c, const ftkx_series_pending &P, const Mesh &m,
 void series_queue_copy(ftkx_ctx *c, ftkx_series_pending &P, const unsigned *wait_flag, unsigned wait_val)
 {
   ftkx_series_buffers &B = c->sr_buf[P.buf];
-  unsigned *flag = reinterpret_cast<unsigned *>(B.h_results + B.h_results_cap);
+  unsigned *flag = series_flag(B);
   // (no event between the pass and its copy: with a pass queued behind, the word its begin kernel stores says that THIS pass's finish kernel
   // is through as well -- same stream, in order; without one, ftkx_sweep_series_complete has already waited for the finish kernel's flag.
   // An event recorded behind the finish kernel stood between it and the next pass's begin kernel: ~5 us per pipelined pass)
-  ftkx::launch_series_copy_out(B.d_out, B.out, (u64)B.d_out_cap, B.results, B.copy_done, flag + 2, P.seq, c->sr_copy_stream, wait_flag, wait_val);
+  ftkx::launch_series_copy_out(B.d_out.as<ftkx_cp_t>(), B.out.as<ftkx_cp_t>(), (u64)B.d_out.count<ftkx_cp_t>(), B.results.as<u64>(), B.copy_done.as<unsigned>(), flag + 2, P.seq, c->sr_copy_stream, wait_flag, wait_val);
   (void)hipEventRecord(B.ev_copied, c->sr_copy_stream);
   B.copy_out = true;
   P.copy_pending = false;
@@ -273,7 +273,7 @@ int series_queue_copy_behind(ftkx_ctx *c, ftkx_series_pending &before, int route
     HIP_TRY(c, hipEventRecord(c->sr_ev_fetched, c->stream));
     HIP_TRY(c, hipStreamWaitEvent(c->sr_copy_stream, c->sr_ev_fetched, 0));
   }
-  series_queue_copy(c, before, route == COPY_BY_FLAG ? c->sr_fetch_flag : nullptr, route == COPY_BY_FLAG ? fetch_val : 0u);
+  series_queue_copy(c, before, route == COPY_BY_FLAG ? c->sr_fetch_flag.as<unsigned>() : nullptr, route == COPY_BY_FLAG ? fetch_val : 0u);
   return FTKX_OK;
 }
 
@@ -330,10 +330,9 @@ int series_plan_one(ftkx_ctx *c, ftkx_series_pending &P, const int *ts, const in
   P.buf = (int)(&P - c->sr_pend);
   ftkx_series_buffers &B = c->sr_buf[P.buf];
   if ((rc = ensure_series_buffers(c, B, nwords, 256, false))) return rc;
-  if (!c->sr_one_scratch) {
-    HIP_TRY(c, hipMalloc((void **)&c->sr_one_scratch, (size_t)ftkx::ONE_WORDS * sizeof(u64)));
-    HIP_TRY(c, hipMemsetAsync(c->sr_one_scratch, 0, (size_t)ftkx::ONE_WORDS * sizeof(u64), c->stream));
-  }
+  bool fresh = false;
+  if ((rc = c->sr_one_scratch.reserve(c, (size_t)ftkx::ONE_WORDS * sizeof(u64), 0, nullptr, &fresh))) return rc;
+  if (fresh) HIP_TRY(c, hipMemsetAsync(c->sr_one_scratch.p, 0, (size_t)ftkx::ONE_WORDS * sizeof(u64), c->stream));
   Mesh m; fill_mesh(c, m);
   m.core_cells = P.cells;
   ftkx::OneArgs a;
@@ -347,14 +346,14 @@ int series_plan_one(ftkx_ctx *c, ftkx_series_pending &P, const int *ts, const in
   }
   a.running_in = prev ? DBL_MAX : P.running_in;
   a.cap = 1.0 / (double)P.hint;
-  a.running_from = prev ? c->sr_buf[prev->buf].results : nullptr;
-  a.scratch = c->sr_one_scratch;
-  a.results = B.results; a.h_results = B.h_results; a.nwords = nwords;
-  a.flag = reinterpret_cast<unsigned *>(B.h_results + B.h_results_cap);
+  a.running_from = prev ? c->sr_buf[prev->buf].results.as<u64>() : nullptr;
+  a.scratch = c->sr_one_scratch.as<u64>();
+  a.results = B.results.as<u64>(); a.h_results = B.h_results.as<u64>(); a.nwords = nwords;
+  a.flag = series_flag(B);
   a.seq = ++ B.seq;
   P.seq = a.seq;
-  a.out = B.out; a.capacity = std::min<u64>(c->capacity, (u64)B.out_cap);
-  a.fragile = T.fragile; a.fragile_capacity = T.fragile_capacity;
+  a.out = B.out.as<ftkx_cp_t>(); a.capacity = std::min<u64>(c->capacity, (u64)B.out.count<ftkx_cp_t>());
+  a.fragile = T.fragile.as<u64>(); a.fragile_capacity = T.fragile_capacity;
   // (the pass before left its records in device memory: their copy needs this pass's launch position, no more)
   if (before && before->open && before->copy_pending && (rc = series_queue_copy_behind(c, *before, COPY_BY_EVENT, 0))) return rc;
   if ((rc = wait_for_open_tails(c, &P))) return rc;         // (their tails share the fragile list and the counters)
@@ -377,8 +376,8 @@ void series_mesh(ftkx_ctx *c, const ftkx_series_pending &P, Mesh &m)
 {
   fill_mesh(c, m);
   const ftkx_tail_set &T = tail_of(c, P);
-  m.counters = T.counters; m.pass = T.pass; m.fragile = T.fragile;
-  m.hist = T.hist; m.hist_shift = P.shift; m.core_cells = P.cells;
+  m.counters = T.counters.as<u64>(); m.pass = T.pass.as<u64>(); m.fragile = T.fragile.as<u64>();
+  m.hist = T.hist.as<unsigned>(); m.hist_shift = P.shift; m.core_cells = P.cells;
 }
 
 // ---- stage 1 of the first half, piece by piece (series_plan) -------------------------------------------------------------------------------
@@ -405,7 +404,7 @@ void series_slice_readiness(ftkx_ctx *c, ftkx_series_pending &P, const std::vect
       if (it != before->slice_ts.end() && *it == slice_ts[j]) {
         const size_t jj = (size_t)(it - before->slice_ts.begin());
         if (before->red_index[jj] >= 0 && before->gen[jj] == s.mask_gen && s.M && (!P.two_level || s.U)) {
-          const u64 *R = c->sr_buf[before->buf].results;
+          const u64 *R = c->sr_buf[before->buf].results.as<u64>();
           from_res[j] = R + ftkx::SR_HEAD + (size_t)before->n + jj;
           from_max[j] = R + ftkx::SR_HEAD + (size_t)before->n + before->k + jj;
           ready = true;
@@ -509,10 +508,10 @@ void series_write_desc(ftkx_ctx *c, const ftkx_series_pending &P, const Mesh &m,
                        const std::vector<const u64 *> &from_max)
 {
   ftkx_series_buffers &B = c->sr_buf[P.buf];
-  MaskJob *jobs = (MaskJob *)B.h_desc;
-  Fields *steps = (Fields *)((char *)B.h_desc + P.off_steps);
-  ftkx::SeriesSlice *ss = (ftkx::SeriesSlice *)((char *)B.h_desc + P.off_slices);
-  ftkx::SeriesStep *si = (ftkx::SeriesStep *)((char *)B.h_desc + P.off_sinfo);
+  MaskJob *jobs = (MaskJob *)B.h_desc.p;
+  Fields *steps = (Fields *)((char *)B.h_desc.p + P.off_steps);
+  ftkx::SeriesSlice *ss = (ftkx::SeriesSlice *)((char *)B.h_desc.p + P.off_slices);
+  ftkx::SeriesStep *si = (ftkx::SeriesStep *)((char *)B.h_desc.p + P.off_sinfo);
   const double cap = 1.0 / (double)P.hint;
   for (size_t j = 0; j < P.k; j ++) {
     const Slice &s = *sl[j];
@@ -523,7 +522,7 @@ void series_write_desc(ftkx_ctx *c, const ftkx_series_pending &P, const Mesh &m,
     if (s.have_res) { ss[j].known_res = s.res < cap ? s.res : DBL_MAX; ss[j].known_max = s.maxabs; }
     else if (ri < 0 && !from_res[j]) { ss[j].known_res = s.res_below; ss[j].known_max = s.maxabs; }
     if (from_res[j] && s.sparse) { ss[j].known_res = DBL_MAX; ss[j].known_max = 0.0; }      // (the halo slice: nothing of an earlier pass stands)
-    if (ri >= 0) jobs[ri] = with_lean_thresholds(MaskJob{s.S, s.V, s.M, P.two_level ? s.U : nullptr, B.red + (size_t)ri * 128, cap, HUGE_VAL}, m);   // rule off: validated by the factor kernel
+    if (ri >= 0) jobs[ri] = with_lean_thresholds(MaskJob{s.S, s.V, s.M, P.two_level ? s.U : nullptr, B.red.as<u64>() + (size_t)ri * 128, cap, HUGE_VAL}, m);   // rule off: validated by the factor kernel
   }
   size_t last = 0;
   for (int i = 0; i < P.n; i ++) {
@@ -557,19 +556,19 @@ void series_claim_masks(ftkx_ctx *c, ftkx_series_pending &P, const std::vector<S
 int series_queue_masks(ftkx_ctx *c, ftkx_series_pending &P, const Mesh &m, const std::vector<Slice *> &sl, const DistPlan *dist)
 {
   ftkx_series_buffers &B = c->sr_buf[P.buf];
-  const MaskJob *d_jobs = (const MaskJob *)B.d_desc;
+  const MaskJob *d_jobs = (const MaskJob *)B.d_desc.p;
   if (dist && dist->masks_out) {
     // A slab pass with a lower neighbour: the FIRST slice's masks are that neighbour's halo.  They are built first, by a launch of their
     // own, and packed into the message right behind it -- the message can then cross xGMI (on the caller's side stream, which is made to
     // wait for the export here) while the masks of the slab's other slices are still being built.
-    if (!B.dist_block) { HIP_TRY(c, hipMalloc((void **)&B.dist_block, (size_t)ftkx::DB_N * sizeof(u64))); HIP_TRY(c, hipMemsetAsync(B.dist_block, 0, (size_t)ftkx::DB_N * sizeof(u64), c->stream)); }
+    if (const int rc = ensure_dist_block(c, B)) return rc;
     size_t ub, cap, off_idx, off_words, total_msg;
     if (!packed_layout(c, m, &ub, &cap, &off_idx, &off_words, &total_msg)) return fail(c, FTKX_E_UNSUPPORTED, "slab pass: this mesh has no summarised masks");
     const bool first_now = P.red_index[0] == 0;            // (its masks are built in this pass: job 0)
     size_t done = 0;
     if (first_now) { ev_begin(c, K_MASK); ftkx::launch_masks(m, d_jobs, 1, c->stream); ev_end(c); done = 1; }
     char *out = (char *)dist->masks_out;
-    ftkx::launch_dist_export(m, sl[0]->U, sl[0]->M, ub, (u64 *)out, (unsigned *)(out + off_idx), (u64 *)(out + off_words), cap, factor_log2_of(P.hint), B.dist_block, c->stream);
+    ftkx::launch_dist_export(m, sl[0]->U, sl[0]->M, ub, (u64 *)out, (unsigned *)(out + off_idx), (u64 *)(out + off_words), cap, factor_log2_of(P.hint), B.dist_block.as<u64>(), c->stream);
     if (dist->side) {
       if (!B.ev_export) HIP_TRY(c, hipEventCreateWithFlags(&B.ev_export, hipEventDisableTiming));
       HIP_TRY(c, hipEventRecord(B.ev_export, c->stream));
@@ -587,7 +586,10 @@ int series_queue_begin(ftkx_ctx *c, ftkx_series_pending &P, ftkx_series_pending 
   const ftkx_tail_set &T = tail_of(c, P);
   int rc;
   const int route = !(before && before->open && before->copy_pending) ? COPY_NONE : before->split ? COPY_BY_TAIL : (slab_now || before->dist) ? COPY_BY_EVENT : COPY_BY_FLAG;
-  if (route == COPY_BY_FLAG && !c->sr_fetch_flag) { HIP_TRY(c, hipMalloc((void **)&c->sr_fetch_flag, 2 * sizeof(unsigned))); HIP_TRY(c, hipMemsetAsync(c->sr_fetch_flag, 0, 2 * sizeof(unsigned), c->stream)); HIP_TRY(c, hipStreamSynchronize(c->stream)); }   // (once per context; waited for: the copy stream reads it)
+  if (route == COPY_BY_FLAG && !c->sr_fetch_flag.p) {        // (once per context; waited for: the copy stream reads it)
+    if (const int rc = c->sr_fetch_flag.reserve(c, 2 * sizeof(unsigned))) return rc;
+    HIP_TRY(c, hipMemsetAsync(c->sr_fetch_flag.p, 0, 2 * sizeof(unsigned), c->stream)); HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
   const unsigned fetch_val = route == COPY_BY_FLAG ? ++ c->sr_fetch_seq : 0u;
   // (the pass before this one has its tail on the tail stream: a pass that is not split itself shares the counters with it in STREAM order,
   // so the context's stream waits for that tail; a split pass only needs that pass's cull -- its mask kernel must not start before the fused
@@ -596,8 +598,8 @@ int series_queue_begin(ftkx_ctx *c, ftkx_series_pending &P, ftkx_series_pending 
   // (a split pass: what its TAIL owns -- counters, histogram, the results block, which the tail of the pass before may still be reading as the
   // block it continues from -- is zeroed on the tail stream)
   // (between choosing the copy's route and queuing the copy: by flag the copy waits for the word this kernel stores, by event for an event recorded behind it)
-  ftkx::launch_series_begin(P.split ? nullptr : T.counters, B.red, P.ntodo * 64, P.split ? nullptr : T.hist, P.split ? 0 : P.nbins + 1, P.split ? nullptr : B.results, P.split ? 0 : P.nwords,
-                            c->stream, B.h_desc, B.d_desc, desc_bytes, route == COPY_BY_FLAG ? c->sr_fetch_flag : nullptr, fetch_val);
+  ftkx::launch_series_begin(P.split ? nullptr : T.counters.as<u64>(), B.red.as<u64>(), P.ntodo * 64, P.split ? nullptr : T.hist.as<unsigned>(), P.split ? 0 : P.nbins + 1, P.split ? nullptr : B.results.as<u64>(), P.split ? 0 : P.nwords,
+                            c->stream, B.h_desc.p, B.d_desc.p, desc_bytes, route == COPY_BY_FLAG ? c->sr_fetch_flag.as<unsigned>() : nullptr, fetch_val);
   c->sr_lists_owner = 0;                                      // (the begin kernel zeroes the counters and the histogram: they are nobody's until this pass's cull is queued)
   return route == COPY_NONE ? FTKX_OK : series_queue_copy_behind(c, *before, route, fetch_val);
 }
@@ -657,11 +659,8 @@ int series_plan(ftkx_ctx *c, ftkx_series_pending &P, const int *ts, const int *s
   P.buf = (int)(&P - c->sr_pend);                             // (a pass's buffers go with its place in sr_pend: nothing to undo when a step below fails)
   ftkx_series_buffers &B = c->sr_buf[P.buf];
   if ((rc = ensure_series_buffers(c, B, P.nwords, desc_bytes, P.to_device))) return rc;
-  if (B.red_cap < std::max<size_t>(P.ntodo, 1)) {            // (the pass's own reduction slots: a buffer in use by an open pass is never this one -- two buffers, two passes)
-    if (B.red) { HIP_TRY(c, hipFree(B.red)); B.red = nullptr; B.red_cap = 0; }
-    HIP_TRY(c, hipMalloc((void **)&B.red, std::max<size_t>(P.ntodo, 1) * 128 * sizeof(u64)));
-    B.red_cap = std::max<size_t>(P.ntodo, 1);
-  }
+  // (the pass's own reduction slots: a buffer in use by an open pass is never this one -- two buffers, two passes)
+  if ((rc = B.red.reserve(c, std::max<size_t>(P.ntodo, 1) * 128 * sizeof(u64)))) return rc;
   if ((rc = series_tail_resources(c, P, before, mask_bytes))) return rc;
   series_mesh(c, P, m);                                      // (the buffers may have moved)
   series_write_desc(c, P, m, sl, from_res, from_max);
@@ -675,9 +674,9 @@ int series_plan(ftkx_ctx *c, ftkx_series_pending &P, const int *ts, const int *s
     HIP_TRY(c, hipEventRecord(B.ev_masks, c->stream));
     const ftkx_tail_set &T = tail_of(c, P);
     HIP_TRY(c, hipStreamWaitEvent(T.stream, B.ev_masks, 0));
-    ftkx::launch_series_tail_begin(T.counters, T.hist, P.nbins + 1, B.results, P.nwords, T.stream);
+    ftkx::launch_series_tail_begin(T.counters.as<u64>(), T.hist.as<unsigned>(), P.nbins + 1, B.results.as<u64>(), P.nwords, T.stream);
   }
-  P.running_from = prev ? c->sr_buf[prev->buf].results : nullptr;
+  P.running_from = prev ? c->sr_buf[prev->buf].results.as<u64>() : nullptr;
   HIP_TRY(c, hipGetLastError());
   return FTKX_OK;
 }
@@ -689,9 +688,9 @@ int series_queue_cull(ftkx_ctx *c, ftkx_series_pending &P)
   const size_t k = P.k;
   ftkx_series_buffers &B = c->sr_buf[P.buf];
   Mesh m; series_mesh(c, P, m);
-  Fields *d_steps = (Fields *)((char *)B.d_desc + P.off_steps);
-  const ftkx::SeriesSlice *d_slices = (const ftkx::SeriesSlice *)((char *)B.d_desc + P.off_slices);
-  const ftkx::SeriesStep *d_sinfo = (const ftkx::SeriesStep *)((char *)B.d_desc + P.off_sinfo);
+  Fields *d_steps = (Fields *)((char *)B.d_desc.p + P.off_steps);
+  const ftkx::SeriesSlice *d_slices = (const ftkx::SeriesSlice *)((char *)B.d_desc.p + P.off_slices);
+  const ftkx::SeriesStep *d_sinfo = (const ftkx::SeriesStep *)((char *)B.d_desc.p + P.off_sinfo);
   hipStream_t st = tail_stream(c, P);
   const ftkx_tail_set &T = tail_of(c, P);
   if (!P.split) ev_begin(c, K_CULL);
@@ -707,13 +706,13 @@ int series_queue_cull(ftkx_ctx *c, ftkx_series_pending &P)
     const u64 *running_from = P.running_from;
     ftkx::FactorJob fj;
     memset(&fj, 0, sizeof(fj));
-    fj.steps = d_steps; fj.slices = d_slices; fj.sinfo = d_sinfo; fj.red = B.red; fj.running_from = running_from; fj.results = B.results; fj.counters = T.counters;
+    fj.steps = d_steps; fj.slices = d_slices; fj.sinfo = d_sinfo; fj.red = B.red.as<u64>(); fj.running_from = running_from; fj.results = B.results.as<u64>(); fj.counters = T.counters.as<u64>();
     fj.running_in = running_from ? DBL_MAX : P.running_in; fj.safe_m = safe_m; fj.nsteps = n; fj.nslices = (int)k;
     const bool fold_on = ftkx::env_hook("FTKX_SERIES_HOOKS", "fold", 1) != 0;
     fj.enabled = (fold_on && k <= (size_t)ftkx::kFoldMaxSlices) ? 1 : 0;
-    if (P.two_level) ftkx::launch_cull_coarse(m, d_steps, n, T.refine, T.refine_capacity, st, &fj);
-    else ftkx::launch_cull(m, d_steps, n, T.list, T.list_capacity, st, &fj);
-    if (!fj.enabled) ftkx::launch_series_factors(d_steps, n, d_slices, (int)k, d_sinfo, B.red, fj.running_in, running_from, safe_m, B.results, T.counters, st);
+    if (P.two_level) ftkx::launch_cull_coarse(m, d_steps, n, T.refine.as<u64>(), T.refine_capacity, st, &fj);
+    else ftkx::launch_cull(m, d_steps, n, T.list.as<u64>(), T.list_capacity, st, &fj);
+    if (!fj.enabled) ftkx::launch_series_factors(d_steps, n, d_slices, (int)k, d_sinfo, B.red.as<u64>(), fj.running_in, running_from, safe_m, B.results.as<u64>(), T.counters.as<u64>(), st);
   }
   if (P.split) HIP_TRY(c, hipEventRecord(B.ev_factors, st));
   else ev_end(c);
@@ -726,8 +725,8 @@ int series_queue_tail(ftkx_ctx *c, ftkx_series_pending &P)
 {
   ftkx_series_buffers &B = c->sr_buf[P.buf];
   Mesh m; series_mesh(c, P, m);
-  Fields *d_steps = (Fields *)((char *)B.d_desc + P.off_steps);
-  unsigned *flag = reinterpret_cast<unsigned *>(B.h_results + B.h_results_cap);
+  Fields *d_steps = (Fields *)((char *)B.d_desc.p + P.off_steps);
+  unsigned *flag = series_flag(B);
   hipStream_t st = tail_stream(c, P);
   if (!P.split) ev_begin(c, K_EXACT);
   // sparse data: one kernel does the rest of the pass (and the kernels below leave at once).  (A pass that has just found far more
@@ -741,8 +740,8 @@ int series_queue_tail(ftkx_ctx *c, ftkx_series_pending &P)
   if (c->sr_skip_small > 0) c->sr_skip_small --;
   P.small_now = small_now;
   const ftkx_tail_set &T = tail_of(c, P);
-  if (small_now) ftkx::launch_series_small(m, P.two_level ? ftkx::coarse_view(m) : m, d_steps, P.two_level, T.refine, T.list, B.out, B.results, P.nwords,
-                                          B.h_results, flag, P.seq, reinterpret_cast<unsigned *>(T.counters + ftkx::CNT_SMALL_DONE), P.short_chain, st);
+  if (small_now) ftkx::launch_series_small(m, P.two_level ? ftkx::coarse_view(m) : m, d_steps, P.two_level, T.refine.as<u64>(), T.list.as<u64>(), B.out.as<ftkx_cp_t>(), B.results.as<u64>(), P.nwords,
+                                          B.h_results.as<u64>(), flag, P.seq, reinterpret_cast<unsigned *>(T.counters.as<u64>() + ftkx::CNT_SMALL_DONE), P.short_chain, st);
   if (!P.short_chain) series_queue_rest(c, P, m, P.seq);
   if (P.split) HIP_TRY(c, hipEventRecord(B.ev_tail, st));
   P.copy_pending = P.to_device;
@@ -780,7 +779,7 @@ int series_complete(ftkx_ctx *c, ftkx_series_pending &P, double *running_resolut
     return rc;
   }
   ftkx_series_buffers &B = c->sr_buf[P.buf];
-  unsigned *flag = reinterpret_cast<unsigned *>(B.h_results + B.h_results_cap);
+  unsigned *flag = series_flag(B);
   Mesh m; series_mesh(c, P, m);
   if (const char *why = ftkx::wait_flag(flag, P.seq, tail_stream(c, P))) return fail(c, FTKX_E_DEVICE, "ftkx_sweep_series: %s", why);
   release_retired(c, P);                                     // (the tail that read them is through)
@@ -792,7 +791,7 @@ int series_complete(ftkx_ctx *c, ftkx_series_pending &P, double *running_resolut
   // (whoever stored the flag -- the fused tail, finishing or declining, or the finish kernel -- copied the whole results block first: the
   // reductions, the status, a slab pass's gathered contributions.  Everything below that does not depend on HOW the records get made comes
   // first, so that every way out of this function has done it.)
-  const u64 *R = B.h_results;
+  const u64 *R = B.h_results.as<u64>();
   unsigned long long status = R[ftkx::SR_STATUS];
   c->sr_last_status = status;
   // the masks and reductions of this pass stand whichever way the records are made: the slices are marked like ftkx_slices_prepare marks
@@ -899,7 +898,7 @@ int series_complete(ftkx_ctx *c, ftkx_series_pending &P, double *running_resolut
   c->sr_late_streak = (status & ftkx::SERIES_LATE_DECLINE) ? c->sr_late_streak + 1 : 0;
   if (c->sr_late_streak >= 2) c->sr_skip_small = 16;
   const size_t nrec = (size_t)R[ftkx::SR_NHITS];
-  ftkx_cp_t *H = B.out;
+  ftkx_cp_t *H = B.out.as<ftkx_cp_t>();
   if (P.to_device) {                                         // (the copy kernel; the mask kernel of the pass queued behind this one is running meanwhile)
     if (P.copy_pending) series_queue_copy(c, P, nullptr, 0);    // (no pass was queued behind this one)
     if (const char *why = ftkx::wait_flag(flag + 2, P.seq, c->sr_copy_stream)) {
@@ -1065,12 +1064,12 @@ int ftkx_series_dist_begin(ftkx_ctx *c, const int *ts, const int *scopes, int n,
     return fail(c, FTKX_E_UNSUPPORTED, "ftkx_series_dist_begin: these options / this mesh are not covered by the device-driven pass (use the host-driven calls)");
   }
   ftkx_series_buffers &B = c->sr_buf[Q.buf];
-  if (!B.dist_block) { HIP_TRY(c, hipMalloc((void **)&B.dist_block, (size_t)ftkx::DB_N * sizeof(u64))); HIP_TRY(c, hipMemsetAsync(B.dist_block, 0, (size_t)ftkx::DB_N * sizeof(u64), c->stream)); }
-  Q.running_from = B.dist_block + ftkx::DB_PSEUDO;
+  if ((rc = ensure_dist_block(c, B))) return rc;
+  Q.running_from = B.dist_block.as<u64>() + ftkx::DB_PSEUDO;
   // this rank's contribution to the all_gather: its slab's reductions folded (the first slice's masks went out inside the plan)
-  const ftkx::SeriesSlice *d_slices = (const ftkx::SeriesSlice *)((char *)B.d_desc + Q.off_slices);
+  const ftkx::SeriesSlice *d_slices = (const ftkx::SeriesSlice *)((char *)B.d_desc.p + Q.off_slices);
   const int nown = (int)Q.k - (halo ? 1 : 0);
-  ftkx::launch_dist_contrib(d_slices, nown, B.red, (u64 *)contrib, B.dist_block, c->stream);
+  ftkx::launch_dist_contrib(d_slices, nown, B.red.as<u64>(), (u64 *)contrib, B.dist_block.as<u64>(), c->stream);
   HIP_TRY(c, hipGetLastError());
   Q.dist_stage = 1;
   return FTKX_OK;
@@ -1088,7 +1087,7 @@ int ftkx_series_dist_cull(ftkx_ctx *c, const void *masks_in, void *request_out)
   Mesh m; series_mesh(c, P, m);
   // the running minimum before this slab (and the gathered block into the results, for the host); the halo's masks into its slice
   {
-    u64 *tail = B.results + (size_t)ftkx::SR_HEAD + (size_t)P.n + 2 * P.k;
+    u64 *tail = B.results.as<u64>() + (size_t)ftkx::SR_HEAD + (size_t)P.n + 2 * P.k;
     if (P.t_halo >= 0) {
       size_t ub, cap, off_idx, off_words, total;
       if (!packed_layout(c, m, &ub, &cap, &off_idx, &off_words, &total)) return fail(c, FTKX_E_UNSUPPORTED, "ftkx_series_dist_cull: this mesh has no summarised masks");
@@ -1096,23 +1095,23 @@ int ftkx_series_dist_cull(ftkx_ctx *c, const void *masks_in, void *request_out)
       if (hit == c->slices.end() || !hit->second.sparse) return fail(c, FTKX_E_NOSLICE, "ftkx_series_dist_cull: the halo slice %d was dropped or replaced between the stages", P.t_halo);
       Slice &h = hit->second;
       const char *in = (const char *)masks_in;
-      ftkx::launch_dist_import(P.gathered, P.dist_rank, P.dist_nranks, P.running_in, B.dist_block, tail, (const u64 *)in, (const unsigned *)(in + off_idx), (const u64 *)(in + off_words), ub, cap,
+      ftkx::launch_dist_import(P.gathered, P.dist_rank, P.dist_nranks, P.running_in, B.dist_block.as<u64>(), tail, (const u64 *)in, (const unsigned *)(in + off_idx), (const u64 *)(in + off_words), ub, cap,
                                m.u_rows, factor_log2_of(P.hint), h.U, h.M, mask_bytes(c) / 8, c->stream);
     } else
-      ftkx::launch_dist_import(P.gathered, P.dist_rank, P.dist_nranks, P.running_in, B.dist_block, tail, nullptr, nullptr, nullptr, 0, 0, m.u_rows, 0, nullptr, nullptr, 0, c->stream);
+      ftkx::launch_dist_import(P.gathered, P.dist_rank, P.dist_nranks, P.running_in, B.dist_block.as<u64>(), tail, nullptr, nullptr, nullptr, 0, 0, m.u_rows, 0, nullptr, nullptr, 0, c->stream);
   }
   int rc;
   if ((rc = series_queue_cull(c, P))) return rc;
   if (P.t_halo >= 0) {
     // the cells whose exact test reads the halo slice: refine now (the rest of the chain will not refine again), list them, write the request
-    Fields *d_steps = (Fields *)((char *)B.d_desc + P.off_steps);
+    Fields *d_steps = (Fields *)((char *)B.d_desc.p + P.off_steps);
     const Slice &h = c->slices.find(P.t_halo)->second;          // (checked above)
     const ftkx_tail_set &T = tail_of(c, P);
-    ftkx::launch_refine(m, d_steps, T.refine, T.refine_capacity, T.list, T.list_capacity, c->stream);
+    ftkx::launch_refine(m, d_steps, T.refine.as<u64>(), T.refine_capacity, T.list.as<u64>(), T.list_capacity, c->stream);
     P.refined = true;
     u64 *req = (u64 *)request_out;
     const size_t cap = dist_cells_cap(c);
-    ftkx::launch_dist_cells(m, d_steps, T.list, T.list_capacity, T.refine_capacity, h.S ? h.S : h.V, req, cap, B.dist_block, B.results, c->stream);
+    ftkx::launch_dist_cells(m, d_steps, T.list.as<u64>(), T.list_capacity, T.refine_capacity, h.S ? h.S : h.V, req, cap, B.dist_block.as<u64>(), B.results.as<u64>(), c->stream);
     P.request_out = req;
   }
   HIP_TRY(c, hipGetLastError());
@@ -1136,7 +1135,7 @@ int ftkx_series_dist_serve(ftkx_ctx *c, const void *request_in, void *reply_out)
     if (it0 == c->slices.end() || it0->second.sparse) return fail(c, FTKX_E_NOSLICE, "ftkx_series_dist_serve: this rank's first slice %d was dropped between the stages", P.slice_ts[0]);
     const Slice &s0 = it0->second;
     const int ncomp = c->scalar_mode == 1 ? 1 : c->nd;
-    ftkx::launch_dist_patches(m, false, (const u64 *)request_in, dist_cells_cap(c), ncomp, c->scalar_mode == 1 ? s0.S : s0.V, (double *)reply_out, B.results + ftkx::SR_HALO_SERVED, c->stream);
+    ftkx::launch_dist_patches(m, false, (const u64 *)request_in, dist_cells_cap(c), ncomp, c->scalar_mode == 1 ? s0.S : s0.V, (double *)reply_out, B.results.as<u64>() + ftkx::SR_HALO_SERVED, c->stream);
     HIP_TRY(c, hipGetLastError());
   }
   P.dist_stage = 3;
@@ -1171,12 +1170,12 @@ int ftkx_series_dist_status(const ftkx_ctx *c, long long *asked, long long *serv
 {
   if (!c) return FTKX_E_INVALID;
   const ftkx_series_buffers &B = c->sr_buf[c->sr_last_buf];
-  if (!B.h_results || c->sr_last_nranks == 0) return FTKX_E_INVALID;
-  if (asked) *asked = (long long)B.h_results[ftkx::SR_HALO_ASKED];
-  if (served) *served = (long long)B.h_results[ftkx::SR_HALO_SERVED];
+  if (!B.h_results.as<u64>() || c->sr_last_nranks == 0) return FTKX_E_INVALID;
+  if (asked) *asked = (long long)B.h_results.as<u64>()[ftkx::SR_HALO_ASKED];
+  if (served) *served = (long long)B.h_results.as<u64>()[ftkx::SR_HALO_SERVED];
   if (gathered) {
     if (nranks != c->sr_last_nranks) return FTKX_E_INVALID;
-    memcpy(gathered, B.h_results + c->sr_last_gathered_off, (size_t)ftkx::kDistContrib * (size_t)nranks * sizeof(double));
+    memcpy(gathered, B.h_results.as<u64>() + c->sr_last_gathered_off, (size_t)ftkx::kDistContrib * (size_t)nranks * sizeof(double));
   }
   return FTKX_OK;
 }

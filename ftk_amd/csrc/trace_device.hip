@@ -110,11 +110,11 @@ static int trace_tables(int nd, const std::vector<int> **off, const std::vector<
 static int reserve_trace(ftkx_ctx *c, int nd, const TraceLayout &L, const std::vector<int> &cand_off, const std::vector<int> &cand_flat)
 {
   ftkx_pass2_state &s = c->p2;
-  if (const int rc = s.trace_dev.reserve(c, L.dev_bytes, false)) return rc;
-  if (const int rc = s.trace_host.reserve(c, L.host_bytes, true)) return rc;
+  if (const int rc = s.trace_dev.reserve(c, L.dev_bytes, pass2_room(L.dev_bytes))) return rc;
+  if (const int rc = s.trace_host.reserve(c, L.host_bytes, pass2_room(L.host_bytes))) return rc;
   if (s.tables_nd != nd) {
     s.tables_nd = 0;
-    if (const int rc = s.tables.reserve(c, (cand_off.size() + cand_flat.size()) * sizeof(int), false)) return rc;
+    if (const int rc = s.tables.reserve(c, (cand_off.size() + cand_flat.size()) * sizeof(int), pass2_room((cand_off.size() + cand_flat.size()) * sizeof(int)))) return rc;
     HIP_TRY(c, hipMemcpy(s.tables.p, cand_off.data(), cand_off.size() * sizeof(int), hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemcpy((int *)s.tables.p + cand_off.size(), cand_flat.data(), cand_flat.size() * sizeof(int), hipMemcpyHostToDevice));
     s.tables_nd = nd;
@@ -242,8 +242,8 @@ int ftkx_trace_curves_device(ftkx_ctx *c, int nd, const long long domain_st[3], 
   const TraceLayout L(maxnb, n);
   const OrderLayout O(n);
   if (const int rc = reserve_trace(c, nd, L, *p_off, *p_flat)) return rc;
-  if (const int rc = c->p2.order_dev.reserve(c, O.dev_bytes, false)) return rc;
-  if (const int rc = c->p2.order_host.reserve(c, O.host_bytes, true)) return rc;
+  if (const int rc = c->p2.order_dev.reserve(c, O.dev_bytes, pass2_room(O.dev_bytes))) return rc;
+  if (const int rc = c->p2.order_host.reserve(c, O.host_bytes, pass2_room(O.host_bytes))) return rc;
   void *d = c->p2.trace_dev.p, *od = c->p2.order_dev.p, *oh = c->p2.order_host.p;
   ftkx::TraceOrder o;
   memset(&o, 0, sizeof(o));

@@ -103,7 +103,7 @@ void check_post_process(size_t n_rec, size_t np, size_t nc)
   for (const Arr &x : d) memset(block.data() + x.at, 0, x.need);
 }
 
-// what pass2_block::reserve leaves for a request of `want` bytes
+// what a pass-2 block (ctx.hpp: pass2_room) holds for a request of `want` bytes
 size_t capacity_for(size_t want) { return want + want / 4; }
 
 }  // namespace
