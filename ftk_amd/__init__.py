@@ -13,7 +13,7 @@ from ._lib import (CP_DTYPE, FORMAT_BINARY, FORMAT_JSON, FORMAT_TEXT, SCOPE_BOTH
 
 __all__ = ["trace_curves", "pass2", "trace_and_post_process", "post_process", "post_process_curves", "TrajectorySet", "write_critical_points", "read_critical_points",
            "write_traced_critical_points", "read_traced_critical_points", "Context", "CriticalPointTracker2DRegular", "CriticalPointTracker3DRegular", "extract_cp2dt", "extract_cp3dt",
-           "scaling_factor", "gaussian_kernel", "CP_DTYPE", "FtkxError"]
+           "scaling_factor", "gaussian_kernel", "gaussian_kernel1d", "CP_DTYPE", "FtkxError"]
 
 
 def _ptr(a):
@@ -55,6 +55,13 @@ def gaussian_kernel(nd, sigma, ksize):
     w = np.zeros(max(1, int(ksize)) ** nd if nd in (2, 3) else 1, dtype=np.float64)
     _lib.check(_lib.load().ftkx_gaussian_kernel(int(nd), float(sigma), int(ksize), w.ctypes.data))
     return w.reshape((int(ksize),) * nd)
+
+
+def gaussian_kernel1d(sigma, ksize):
+    """ftkx_gaussian_kernel1d: the weights of the reference's temporal filter (gaussian_kernel; host), ksize doubles"""
+    w = np.zeros(max(1, int(ksize)), dtype=np.float64)
+    _lib.check(_lib.load().ftkx_gaussian_kernel1d(float(sigma), int(ksize), w.ctypes.data))
+    return w
 
 
 class Context:
@@ -112,6 +119,50 @@ class Context:
         rc = self._L.ftkx_set_spatial_smoothing(self._h, float(sigma), int(ksize))
         self._ck(rc)                                   # (raises: a refused setting leaves the context, and this flag, as they were)
         self._smoothing = int(ksize) != 0
+
+    def set_temporal_smoothing(self, sigma, ksize=5, t0=0):
+        """ftkx_set_temporal_smoothing: a series of raw snapshots for temporal_push starts, its first emission being timestep t0; ksize 0: off"""
+        self._ck(self._L.ftkx_set_temporal_smoothing(self._h, float(sigma), int(ksize), int(t0)))
+
+    def temporal_push(self, A, is_vector=False, on_device=None):
+        """ftkx_temporal_push: one raw snapshot (host array or device tensor; always copied) -> the timestep of the smoothed slice that became
+        resident, or -1.  on_device as in push_scalar_slice"""
+        p, k, d = _ptr(A)
+        if on_device is not None:
+            if int(on_device) not in (0, 1, 2) or (int(on_device) != 0) != bool(d):
+                raise ValueError("on_device: 0 for a host array, 1 or 2 for a device tensor")
+            d = int(on_device)
+        t = C.c_int(-1)
+        self._ck(self._L.ftkx_temporal_push(self._h, p, int(bool(is_vector)), d, C.byref(t)))
+        if t.value >= 0:
+            self._keep[t.value] = None
+        return t.value
+
+    def temporal_flush(self):
+        """ftkx_temporal_flush: one finishing step -> the timestep of the trailing slice that became resident, or -1 when the series is over"""
+        t = C.c_int(-1)
+        self._ck(self._L.ftkx_temporal_flush(self._h, C.byref(t)))
+        if t.value >= 0:
+            self._keep[t.value] = None
+        return t.value
+
+    def _temporal_args(self, arrays, weights):
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        if len(arrays) != w.size:
+            raise ValueError("temporal_combine: one weight per array")
+        return (C.c_void_p * len(arrays))(*[int(a) for a in arrays]), w
+
+    def temporal_combine(self, array_ptrs, weights, count, out_ptr):
+        """ftkx_temporal_combine on device pointers (repeats allowed): out[e] = w[0] * a0[e] + w[1] * a1[e] + ..., every step rounded"""
+        ptrs, w = self._temporal_args(array_ptrs, weights)
+        self._ck(self._L.ftkx_temporal_combine(self._h, ptrs, w.size, w.ctypes.data, int(count), out_ptr))
+
+    def debug_temporal_relaunch(self, array_ptrs, weights, count, out_ptr, reps):
+        """profiling aid: the temporal kernel `reps` times back to back -> device ms per launch (HIP events)"""
+        ptrs, w = self._temporal_args(array_ptrs, weights)
+        ms = (C.c_double * int(reps))()
+        self._ck(self._L.ftkx_debug_temporal_relaunch(self._h, ptrs, w.size, w.ctypes.data, int(count), out_ptr, int(reps), ms))
+        return list(ms)
 
     def push_slice(self, t, V, J=None, S=None):
         pv, kv, dv = _ptr(V); pj, kj, dj = _ptr(J); ps, ks, ds = _ptr(S)
@@ -776,6 +827,24 @@ class _TrackerRegular:
         (conv_gaussian(snapshot, sigma, ksize, ksize // 2)); ksize 0: off"""
         self._ck(self._L.ftkx_tracker_set_spatial_smoothing(self._h, float(sigma), int(ksize)))
 
+    def set_temporal_smoothing(self, sigma, ksize=5):
+        """before initialize(): the pushed snapshots are raw and feed the reference stream's temporal filter on the device; the tracker sees
+        the smoothed series, ksize // 2 pushes late (snapshots_from_last_push, flush_temporal_smoothing); ksize 0: off"""
+        self._ck(self._L.ftkx_tracker_set_temporal_smoothing(self._h, float(sigma), int(ksize)))
+
+    def snapshots_from_last_push(self):
+        """0 or 1: whether the last push_* appended a snapshot (always 1 without temporal smoothing)"""
+        n = C.c_int(0)
+        self._ck(self._L.ftkx_tracker_snapshots_from_last_push(self._h, C.byref(n)))
+        return n.value
+
+    def flush_temporal_smoothing(self):
+        """after the last push: appends one trailing smoothed snapshot -> True, or False when none is left; loop it in front of finalize(),
+        with advance_timestep() between the calls"""
+        n = C.c_int(0)
+        self._ck(self._L.ftkx_tracker_flush_temporal_smoothing(self._h, C.byref(n)))
+        return bool(n.value)
+
     def trace_last_path(self):
         """Context.trace_last_path() of the tracker's (first) context"""
         return int(self._L.ftkx_tracker_trace_last_path(self._h))
@@ -839,6 +908,12 @@ class _TrackerRegular:
         self._keep = self._keep[-((3 * getattr(self, "_deferred_depth", 1) + 2) if getattr(self, "_deferred", False) else 2):]
 
     def update_timestep(self): self._ck(self._L.ftkx_tracker_update_timestep(self._h))
+
+    def reset(self):
+        """critical_point_tracker_regular::reset: the points and the queued snapshots go, the next push is timestep 0; a temporal filter is emptied"""
+        self._ck(self._L.ftkx_tracker_reset(self._h))
+        self._keep = []
+
     def sync(self): self._ck(self._L.ftkx_tracker_sync(self._h))
 
     def get_critical_points(self):

@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
 #include <map>
 #include <string>
 #include <vector>
@@ -21,6 +22,7 @@
 #include "internal.hpp"
 #include "pass2_layout.hpp"
 #include "ctx_block.hpp"
+#include "temporal_steps.hpp"
 
 struct ftkx_phase_clock;
 
@@ -52,6 +54,7 @@ void launch_gradient3d(const double *S, int DW, int DH, int DD, double *V, hipSt
 void launch_jacobian3d(const double *V, int DW, int DH, int DD, double *J, hipStream_t st);
 void launch_resolution(const double *p, size_t n, u64 *out2, hipStream_t st);
 void launch_conv(int nd, const double *S, int DW, int DH, int DD, const double *d_weights, int ksize, double *out, hipStream_t st);   // conv_kernels.hip
+void launch_temporal(const double *const *arrays, int ksize, const double *weights, size_t count, double *out, hipStream_t st);   // temporal_kernels.hip
 void launch_calib_read(const void *p, size_t bytes, double *scratch, hipStream_t stream);
 const char *last_mask_kernel();
 void launch_cull_coarse(const Mesh &m, const Fields *d_steps, int nsteps, u64 *d_refine, u64 refine_cap, hipStream_t stream, const FactorJob *job = nullptr);
@@ -298,6 +301,15 @@ struct ftkx_ctx {
   int smooth_ksize = 0;
   double smooth_sigma = 0;
   ftkx_block d_conv_w;              // double
+  // temporal smoothing (ftkx_set_temporal_smoothing): the filter's state (temporal_steps.hpp), its weights and the ring of RAW snapshots
+  // (after the spatial smoothing where that is set) -- at most ksize arrays of tm_count doubles each, taken from and given back to pool_F.
+  // Only kernels on the context's stream read them.  tm_next: the timestep the next emission gets.
+  ftkx::TemporalSeries tm;
+  double tm_sigma = 0, tm_w[ftkx::kTemporalMaxK] = {0};
+  std::deque<double *> tm_ring;
+  size_t tm_count = 0;
+  int tm_next = 0;
+  hipEvent_t tm_read = nullptr;     // behind the staging of a device source: what ftkx_temporal_push waits for before it returns
   std::vector<ftkxh::Request> pending;
   // Cull-ahead: the sweeps the caller announced (ftkx_sweep_announce) for the slices of the next ftkx_slices_prepare, and -- once that
   // call has queued their cull right behind the mask kernel -- the survivor list it left on the device.  The cull needs the masks

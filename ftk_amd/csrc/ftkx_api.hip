@@ -404,6 +404,8 @@ int ftkx_create(ftkx_ctx **out, int nd, int device_id)
   return FTKX_OK;
 }
 
+static void temporal_release(ftkx_ctx *c);
+
 void ftkx_destroy(ftkx_ctx *c)
 {
   if (!c) return;
@@ -413,6 +415,8 @@ void ftkx_destroy(ftkx_ctx *c)
   if (c->sr_copy_stream) (void)hipStreamSynchronize(c->sr_copy_stream);
   for (auto &kv : c->slices) release_slice(kv.second);
   for (ftkx_series_pending &P : c->sr_pend) { for (Slice &sl : P.parked) release_slice(sl); P.parked.clear(); }
+  temporal_release(c);
+  if (c->tm_read) (void)hipEventDestroy(c->tm_read);
   release_pools(c);
   for (auto &e : c->events) { (void)hipEventDestroy(e.second.first); (void)hipEventDestroy(e.second.second); }
   for (hipEvent_t e : c->event_pool) (void)hipEventDestroy(e);
@@ -489,6 +493,7 @@ int ftkx_set_mesh(ftkx_ctx *c, const long long dst[3], const long long dsz[3], c
   if (!c) return fail(nullptr, FTKX_E_INVALID, "null context");
   if (!c->slices.empty()) return fail(c, FTKX_E_INVALID, "ftkx_set_mesh: drop all slices first");
   (void)hipSetDevice(c->device);
+  temporal_release(c);                    // a temporal series that was open starts afresh: its raw snapshots have the old lattice's size
   release_pools(c);                       // pooled mask arrays have the old lattice's size
   for (int d = 0; d < c->nd; d ++) {
     if (dsz[d] < 0 || csz[d] < 0 || esz[d] <= 0) return fail(c, FTKX_E_INVALID, "ftkx_set_mesh: negative size on axis %d", d);
@@ -508,62 +513,100 @@ int ftkx_set_mesh(ftkx_ctx *c, const long long dst[3], const long long dsz[3], c
 
 constexpr size_t kSmoothWeights = 729;      // ftkx_ctx::d_conv_w: where the smoothing's weights start
 
-static int push_common(ftkx_ctx *c, int t, const double *V, const double *J, const double *S, int on_device, bool scalar_only)
+// ---- what every way of making a slice resident shares -----------------------------------------------------------------------------------
+// the checks in front of a push of timestep t
+static int push_checks(ftkx_ctx *c, int t, int on_device, bool scalar_only, bool have_field)
 {
-  if (c) c->ahead.clear();
-  if (!c) return fail(nullptr, FTKX_E_INVALID, "null context");
   if (!c->mesh_set) return fail(c, FTKX_E_INVALID, "push: call ftkx_set_mesh first");
   if (t < 0) return fail(c, FTKX_E_INVALID, "push: negative timestep");
   if (on_device < 0 || on_device > 2) return fail(c, FTKX_E_INVALID, "push: on_device must be 0, 1 or 2");
-  if (scalar_only ? !S : !V) return fail(c, FTKX_E_INVALID, "push: missing field pointer");
+  if (!have_field) return fail(c, FTKX_E_INVALID, "push: missing field pointer");
   if (!c->pending.empty()) return fail(c, FTKX_E_INVALID, "push: sweeps pending, collect first");
   if (c->slices.empty()) c->scalar_mode = -1;
   if (c->scalar_mode >= 0 && c->scalar_mode != (scalar_only ? 1 : 0))
     return fail(c, FTKX_E_INVALID, "push: scalar and vector slices cannot be mixed in one context");
+  return FTKX_OK;
+}
+
+// a field array of `count` doubles out of the pool, or a new one
+static int take_pooled(ftkx_ctx *c, size_t count, double **dst)
+{
+  *dst = nullptr;
+  for (size_t i = 0; i < c->pool_F.size(); i ++)
+    if (c->pool_F[i].second == count) { *dst = c->pool_F[i].first; c->pool_F.erase(c->pool_F.begin() + (long)i); break; }
+  if (!*dst) HIP_TRY(c, hipMalloc((void **)dst, count * sizeof(double)));
+  return FTKX_OK;
+}
+
+// ... and back, behind work queued on the context's stream that may still read it: whatever takes it out next is ordered behind that work
+// by the same stream (upload.cpp waits for it too)
+static void give_pooled(ftkx_ctx *c, double *p, size_t count)
+{
+  if (c->pool_F.size() < 12) c->pool_F.push_back({p, count});
+  else { (void)hipStreamSynchronize(c->stream); (void)hipFree(p); }
+}
+
+// the slice of timestep t, where there is one, leaves (its arrays are in the pool for what replaces it)
+static void evict_slice(ftkx_ctx *c, int t)
+{
+  auto it = c->slices.find(t);
+  if (it != c->slices.end()) { free_slice(it->second, c); c->slices.erase(it); }
+}
+
+// `s` -- arrays the context owns or borrows, complete in the order of its stream -- becomes the resident slice t
+static void install_slice(ftkx_ctx *c, int t, Slice &s, bool scalar_only)
+{
+  s.mask_gen = ++ c->mask_epoch;
+  c->slices[t] = s;
+  c->scalar_mode = scalar_only ? 1 : 0;
+}
+
+// spatial smoothing: dst = conv(src), dst being a buffer of the context's own whatever on_device says.  A host source, and a device source
+// that lives on another device, goes through a pooled buffer first (the kernel reads this device's memory only); that buffer goes back
+// to the pool at once.
+static int stage_smoothed(ftkx_ctx *c, const double *src, size_t count, int on_device, double *dst)
+{
+  const double *from = src;
+  double *tmp = nullptr;
+  if (on_device == 0 || ftkx_pointer_device(src) != c->device) {
+    if (int rc = take_pooled(c, count, &tmp)) return rc;
+    int rc = FTKX_OK;
+    if (on_device == 0) rc = upload_from_host(c, tmp, src, count * sizeof(double));
+    else if (hipMemcpyAsync(tmp, src, count * sizeof(double), hipMemcpyDefault, c->stream) != hipSuccess) rc = fail(c, FTKX_E_DEVICE, "push: copy of the source failed");
+    // (a failed copy: nothing of it is in flight any more -- upload.cpp drains its DMA streams before it reports an error, and a
+    // hipMemcpyAsync that was refused was never queued -- but what the buffer holds is unknown and the device may be in an error state:
+    // it is freed, not pooled)
+    if (rc) { (void)hipFree(tmp); return rc; }
+    from = tmp;
+  }
+  ftkx::launch_conv(c->nd, from, (int)c->ext_sz[0], (int)c->ext_sz[1], (int)c->ext_sz[2], c->d_conv_w.as<double>() + kSmoothWeights, c->smooth_ksize, dst, c->stream);
+  const hipError_t e = hipGetLastError();
+  if (tmp) give_pooled(c, tmp, count);
+  HIP_TRY(c, e);
+  return FTKX_OK;
+}
+
+static int push_common(ftkx_ctx *c, int t, const double *V, const double *J, const double *S, int on_device, bool scalar_only)
+{
+  if (c) c->ahead.clear();
+  if (!c) return fail(nullptr, FTKX_E_INVALID, "null context");
+  if (int rc = push_checks(c, t, on_device, scalar_only, scalar_only ? S != nullptr : V != nullptr)) return rc;
   // conv_gaussian dispatches on the array's nd(): a vector field would be convolved across its components (conv.hh:213-221) -- not reproduced
   if (c->smooth_ksize && !scalar_only) return fail(c, FTKX_E_UNSUPPORTED, "push: spatial smoothing is set and takes scalar slices only (ftkx_push_scalar_slice)");
   HIP_TRY(c, hipSetDevice(c->device));
-  auto it = c->slices.find(t);
-  if (it != c->slices.end()) { free_slice(it->second, c); c->slices.erase(it); }
+  evict_slice(c, t);
   Slice s;
   const size_t n = n_vertices(c);
   const int nd = c->nd;
-  auto pooled = [&](size_t count, double **dst) -> int {
-    *dst = nullptr;
-    for (size_t i = 0; i < c->pool_F.size(); i ++)
-      if (c->pool_F[i].second == count) { *dst = c->pool_F[i].first; c->pool_F.erase(c->pool_F.begin() + (long)i); break; }
-    if (!*dst) HIP_TRY(c, hipMalloc((void **)dst, count * sizeof(double)));
-    return FTKX_OK;
-  };
-  // spatial smoothing: the slice is conv(src), in a buffer of the context's own whatever on_device says.  A host source, and a device source
-  // that lives on another device, goes through a pooled buffer first (the kernel reads this device's memory only); that buffer goes back
-  // to the pool at once: whatever takes it out next is ordered behind the kernel by the context's stream (upload.cpp waits for it too).
   auto take_smoothed = [&](const double *src, size_t count, double **dst, bool *own) -> int {
-    if (int rc = pooled(count, dst)) return rc;
+    if (int rc = take_pooled(c, count, dst)) return rc;
     *own = true;
-    const double *from = src;
-    double *tmp = nullptr;
-    if (on_device == 0 || ftkx_pointer_device(src) != c->device) {
-      if (int rc = pooled(count, &tmp)) return rc;
-      int rc = FTKX_OK;
-      if (on_device == 0) rc = upload_from_host(c, tmp, src, count * sizeof(double));
-      else if (hipMemcpyAsync(tmp, src, count * sizeof(double), hipMemcpyDefault, c->stream) != hipSuccess) rc = fail(c, FTKX_E_DEVICE, "push: copy of the source failed");
-      // (a failed copy: nothing of it is in flight any more -- upload.cpp drains its DMA streams before it reports an error, and a
-      // hipMemcpyAsync that was refused was never queued -- but what the buffer holds is unknown and the device may be in an error state:
-      // it is freed, not pooled)
-      if (rc) { (void)hipFree(tmp); return rc; }
-      from = tmp;
-    }
-    ftkx::launch_conv(nd, from, (int)c->ext_sz[0], (int)c->ext_sz[1], (int)c->ext_sz[2], c->d_conv_w.as<double>() + kSmoothWeights, c->smooth_ksize, *dst, c->stream);
-    const hipError_t e = hipGetLastError();
-    if (tmp) { if (c->pool_F.size() < 12) c->pool_F.push_back({tmp, count}); else { (void)hipStreamSynchronize(c->stream); (void)hipFree(tmp); } }
-    HIP_TRY(c, e);
-    return FTKX_OK;
+    return stage_smoothed(c, src, count, on_device, *dst);
   };
   auto take = [&](const double *src, size_t count, double **dst, bool *own) -> int {
     if (!src) { *dst = nullptr; *own = false; return FTKX_OK; }
     if (on_device == 1) { *dst = const_cast<double *>(src); *own = false; return FTKX_OK; }
-    if (int rc = pooled(count, dst)) return rc;
+    if (int rc = take_pooled(c, count, dst)) return rc;
     *own = true;
     // 0: host memory; 2: device memory of ANY device (a multi-device tracker hands one snapshot to two contexts), copied
     if (on_device == 0) return upload_from_host(c, *dst, src, count * sizeof(double));
@@ -582,9 +625,7 @@ static int push_common(ftkx_ctx *c, int t, const double *V, const double *J, con
   // completely by upload_from_host (nothing to wait for: the DMAs run on while the caller produces its next snapshot)
   // (smoothing: a borrowed array (1) is read by the kernel and never adopted -- the call returns once it has been read, like 2)
   if (on_device == 2 || (on_device == 1 && c->smooth_ksize)) HIP_TRY(c, hipStreamSynchronize(c->stream));
-  s.mask_gen = ++ c->mask_epoch;
-  c->slices[t] = s;
-  c->scalar_mode = scalar_only ? 1 : 0;
+  install_slice(c, t, s, scalar_only);
   return FTKX_OK;
 }
 
@@ -915,6 +956,201 @@ int ftkx_set_spatial_smoothing(ftkx_ctx *c, double sigma, int ksize)
   if (int rc = conv_weights(c, w, ksize * ksize * (c->nd == 3 ? ksize : 1), kSmoothWeights)) return rc;
   HIP_TRY(c, hipStreamSynchronize(c->stream));      // (`w` is this call's)
   c->smooth_ksize = ksize; c->smooth_sigma = sigma;
+  return FTKX_OK;
+}
+
+// ---- temporal Gaussian smoothing (filters/streaming_filter.hh) ---------------------------------------------------------------------------
+// gaussian_kernel (conv.hh:50-72) with the host's exp; `sum` grows in index order
+int ftkx_gaussian_kernel1d(double sigma, int ksize, double *weights)
+{
+  if (!ftkx::temporal_ksize_ok(ksize)) return fail(nullptr, FTKX_E_INVALID, "ftkx_gaussian_kernel1d: ksize must be odd and in [1, 9] (got %d)", ksize);
+  if (!std::isfinite(sigma) || !(sigma > 0)) return fail(nullptr, FTKX_E_INVALID, "ftkx_gaussian_kernel1d: sigma must be finite and positive");
+  if (!weights) return fail(nullptr, FTKX_E_INVALID, "ftkx_gaussian_kernel1d: null output");
+  const double center = static_cast<double>(ksize - 1) * 0.5;
+  const double s = 2. * sigma * sigma;
+  double sum = 0.;
+  for (int i = 0; i < ksize; ++ i) {
+    const double x = static_cast<double>(i) - center;
+    const double r = x * x;
+    weights[i] = std::exp(-r / s);
+    sum += weights[i];
+  }
+  for (int i = 0; i < ksize; ++ i) weights[i] /= sum;
+  return FTKX_OK;
+}
+
+static int temporal_combine_args(ftkx_ctx *c, const char *who, const double *const *arrays, int ksize, const double *weights, size_t count, const double *out)
+{
+  if (!arrays || !weights || !out) return fail(c, FTKX_E_INVALID, "%s: null argument", who);
+  if (!ftkx::temporal_ksize_ok(ksize)) return fail(c, FTKX_E_INVALID, "%s: ksize must be odd and in [1, 9] (got %d)", who, ksize);
+  if (count < 1) return fail(c, FTKX_E_INVALID, "%s: count must be positive", who);
+  for (int i = 0; i < ksize; i ++) {
+    if (!arrays[i]) return fail(c, FTKX_E_INVALID, "%s: array %d is null", who, i);
+    if (arrays[i] < out + count && out < arrays[i] + count) return fail(c, FTKX_E_INVALID, "%s: the output overlaps array %d", who, i);
+  }
+  return FTKX_OK;
+}
+
+int ftkx_temporal_combine(ftkx_ctx *c, const double *const *arrays, int ksize, const double *weights, size_t count, double *out)
+{
+  DERIVE_PROLOGUE(c);
+  if (int rc = temporal_combine_args(c, "ftkx_temporal_combine", arrays, ksize, weights, count, out)) return rc;
+  ftkx::launch_temporal(arrays, ksize, weights, count, out, c->stream);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipStreamSynchronize(c->stream));      // (the caller may read `out`)
+  return FTKX_OK;
+}
+
+// profiling aid (tools/temporal_time.py): the kernel `reps` times back to back, a pair of events around every launch
+int ftkx_debug_temporal_relaunch(ftkx_ctx *c, const double *const *arrays, int ksize, const double *weights, size_t count, double *out, int reps, double *ms)
+{
+  DERIVE_PROLOGUE(c);
+  if (!ms || reps < 1) return fail(c, FTKX_E_INVALID, "ftkx_debug_temporal_relaunch: bad argument");
+  if (int rc = temporal_combine_args(c, "ftkx_debug_temporal_relaunch", arrays, ksize, weights, count, out)) return rc;
+  std::vector<hipEvent_t> ev(2 * (size_t)reps, nullptr);
+  auto run = [&]() -> int {
+    for (hipEvent_t &e : ev) HIP_TRY(c, hipEventCreate(&e));
+    for (int i = 0; i < reps; i ++) {
+      HIP_TRY(c, hipEventRecord(ev[2 * (size_t)i], c->stream));
+      ftkx::launch_temporal(arrays, ksize, weights, count, out, c->stream);
+      HIP_TRY(c, hipEventRecord(ev[2 * (size_t)i + 1], c->stream));
+    }
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (int i = 0; i < reps; i ++) { float t = 0; HIP_TRY(c, hipEventElapsedTime(&t, ev[2 * (size_t)i], ev[2 * (size_t)i + 1])); ms[i] = t; }
+    return FTKX_OK;
+  };
+  const int rc = run();
+  if (rc) (void)hipStreamSynchronize(c->stream);
+  for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+  return rc;
+}
+
+// the ring's arrays go back to the pool and the filter is as it was constructed (also from ftkx_destroy and ftkx_set_mesh, in front of
+// release_pools)
+static void temporal_release(ftkx_ctx *c)
+{
+  for (double *p : c->tm_ring) give_pooled(c, p, c->tm_count);
+  c->tm_ring.clear();
+  c->tm_count = 0;
+  c->tm.restart();
+}
+
+int ftkx_set_temporal_smoothing(ftkx_ctx *c, double sigma, int ksize, int t0)
+{
+  if (c) c->ahead.clear();
+  if (!c) return fail(nullptr, FTKX_E_INVALID, "null context");
+  if (!c->pending.empty()) return fail(c, FTKX_E_INVALID, "ftkx_set_temporal_smoothing: sweeps pending, collect first");
+  if (c->sr_open && !c->sr_internal) return fail(c, FTKX_E_INVALID, "ftkx_set_temporal_smoothing: series passes open (ftkx_sweep_series_submit), complete them first");
+  double w[ftkx::kTemporalMaxK] = {0};
+  if (ksize != 0) {
+    if (int rc = ftkx_gaussian_kernel1d(sigma, ksize, w)) { c->err = g_last_error; return rc; }
+    if (t0 < 0) return fail(c, FTKX_E_INVALID, "ftkx_set_temporal_smoothing: negative first timestep");
+  }
+  (void)hipSetDevice(c->device);
+  temporal_release(c);
+  c->tm.ksize = ksize;
+  c->tm_sigma = ksize ? sigma : 0;
+  for (int i = 0; i < ftkx::kTemporalMaxK; i ++) c->tm_w[i] = w[i];
+  c->tm_next = ksize ? t0 : 0;
+  return FTKX_OK;
+}
+
+// the emission whose taps read the ring places idx[] (the ring as it will be: `ring`) becomes the resident slice tm_next, in `out`
+// (a slice of that timestep which was resident leaves only once the emission has been queued)
+static int temporal_emit(ftkx_ctx *c, const std::deque<double *> &ring, const int *idx, size_t count, double *out, bool scalar, int *t_emitted)
+{
+  const double *arrays[ftkx::kTemporalMaxK];
+  for (int i = 0; i < c->tm.ksize; i ++) arrays[i] = ring[(size_t)idx[i]];
+  ftkx::launch_temporal(arrays, c->tm.ksize, c->tm_w, count, out, c->stream);
+  HIP_TRY(c, hipGetLastError());
+  evict_slice(c, c->tm_next);
+  Slice s;
+  if (scalar) { s.S = out; s.ownS = true; } else { s.V = out; s.ownV = true; }
+  install_slice(c, c->tm_next, s, scalar);
+  *t_emitted = c->tm_next ++;
+  return FTKX_OK;
+}
+
+int ftkx_temporal_push(ftkx_ctx *c, const double *A, int is_vector, int on_device, int *t_emitted)
+{
+  if (c) c->ahead.clear();
+  if (!c) return fail(nullptr, FTKX_E_INVALID, "null context");
+  if (!t_emitted) return fail(c, FTKX_E_INVALID, "ftkx_temporal_push: null argument");
+  *t_emitted = -1;
+  switch (ftkx::temporal_admit(c->tm, is_vector)) {
+  case ftkx::TEMPORAL_ADMIT_OFF: return fail(c, FTKX_E_INVALID, "ftkx_temporal_push: call ftkx_set_temporal_smoothing first");
+  case ftkx::TEMPORAL_ADMIT_FINISHING: return fail(c, FTKX_E_INVALID, "ftkx_temporal_push: the series is being finished (ftkx_temporal_flush until it says -1)");
+  case ftkx::TEMPORAL_ADMIT_MIXED: return fail(c, FTKX_E_INVALID, "ftkx_temporal_push: scalar and vector snapshots cannot be mixed in one series");
+  default: break;
+  }
+  const bool scalar = !is_vector;
+  if (int rc = push_checks(c, c->tm_next, on_device, scalar, A != nullptr)) return rc;
+  if (c->smooth_ksize && !scalar) return fail(c, FTKX_E_UNSUPPORTED, "ftkx_temporal_push: spatial smoothing is set and takes scalar snapshots only");
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t count = n_vertices(c) * (scalar ? 1 : (size_t)c->nd);
+  if (!c->tm_ring.empty() && c->tm_count != count) return fail(c, FTKX_E_INVALID, "ftkx_temporal_push: the mesh changed within a series");
+  // the raw snapshot (spatially smoothed first where that is set: the stream's order) into a ring slot of the context's own
+  if (on_device != 0 && !c->tm_read) HIP_TRY(c, hipEventCreateWithFlags(&c->tm_read, hipEventDisableTiming));
+  double *slot = nullptr;
+  if (int rc = take_pooled(c, count, &slot)) return rc;
+  int rc = FTKX_OK;
+  if (c->smooth_ksize) rc = stage_smoothed(c, A, count, on_device, slot);
+  else if (on_device == 0) rc = upload_from_host(c, slot, A, count * sizeof(double));
+  else if (hipMemcpyAsync(slot, A, count * sizeof(double), hipMemcpyDefault, c->stream) != hipSuccess) rc = fail(c, FTKX_E_DEVICE, "ftkx_temporal_push: copy of the source failed");
+  if (rc) { (void)hipFree(slot); return rc; }      // (what the slot holds is unknown: freed, not pooled)
+  // A device source has to be read before the caller may overwrite it (a host source has been staged completely by upload_from_host):
+  // the call ends by waiting for THIS point of the stream, not for the stream -- sweeps queued before the push (deferred collection) and
+  // the emission queued behind it run on.
+  if (on_device != 0) {
+    if (hipEventRecord(c->tm_read, c->stream) != hipSuccess) { (void)hipStreamSynchronize(c->stream); (void)hipFree(slot); return fail(c, FTKX_E_DEVICE, "ftkx_temporal_push: hipEventRecord failed"); }
+  }
+  // the state machine on a copy; the context's is replaced when everything has been queued
+  ftkx::TemporalSeries next = c->tm;
+  std::deque<double *> ring = c->tm_ring;
+  ring.push_back(slot);
+  bool pop = false;
+  int idx[ftkx::kTemporalMaxK];
+  const bool emits = ftkx::temporal_push(next, is_vector, &pop, idx);
+  double *left = nullptr;
+  if (pop) { left = ring.front(); ring.pop_front(); }
+  if (emits) {
+    // the array that left the ring is read by nothing any more (the emissions that read it are in front of this one in the stream): it
+    // takes the new emission; otherwise a pooled one
+    double *out = left;
+    if (!out) rc = take_pooled(c, count, &out);
+    if (rc == FTKX_OK) rc = temporal_emit(c, ring, idx, count, out, scalar, t_emitted);
+    // (the emission was not queued, or the device is in an error state: ring, filter and resident slices are as they were before this call)
+    if (rc) { (void)hipStreamSynchronize(c->stream); if (out && out != left) (void)hipFree(out); (void)hipFree(slot); return rc; }
+  } else if (left) give_pooled(c, left, count);
+  c->tm = next;
+  c->tm_ring.swap(ring);
+  c->tm_count = count;
+  if (on_device != 0) HIP_TRY(c, hipEventSynchronize(c->tm_read));
+  return FTKX_OK;
+}
+
+int ftkx_temporal_flush(ftkx_ctx *c, int *t_emitted)
+{
+  if (c) c->ahead.clear();
+  if (!c) return fail(nullptr, FTKX_E_INVALID, "null context");
+  if (!t_emitted) return fail(c, FTKX_E_INVALID, "ftkx_temporal_flush: null argument");
+  *t_emitted = -1;
+  if (!c->tm.ksize) return fail(c, FTKX_E_INVALID, "ftkx_temporal_flush: call ftkx_set_temporal_smoothing first");
+  if (!c->pending.empty()) return fail(c, FTKX_E_INVALID, "ftkx_temporal_flush: sweeps pending, collect first");
+  HIP_TRY(c, hipSetDevice(c->device));
+  ftkx::TemporalSeries next = c->tm;
+  bool pop = false;
+  int idx[ftkx::kTemporalMaxK];
+  const bool emits = ftkx::temporal_finish_step(next, &pop, idx);
+  if (!emits) { temporal_release(c); return FTKX_OK; }      // the loop stops: the filter as it was constructed, tm_next the next unused timestep
+  // the array that leaves the ring takes the emission (nothing queued behind this point reads it)
+  std::deque<double *> ring = c->tm_ring;
+  double *out = ring.front();
+  ring.pop_front();
+  if (int rc = temporal_emit(c, ring, idx, c->tm_count, out, c->tm.kind == 0, t_emitted)) return rc;
+  c->tm = next;
+  c->tm_ring.swap(ring);
   return FTKX_OK;
 }
 

@@ -279,6 +279,7 @@ void critical_point_tracker_regular::enter_slab_mode(int rank, int nranks, int n
   if (multi) throw ftkx_error(FTKX_E_UNSUPPORTED, "slab mode: a tracker with one device (several devices of one process: one tracker per device over a ftkx_slab_hub)");
   if (slab || !field_data_snapshots.empty()) throw ftkx_error(FTKX_E_INVALID, "slab mode: set it once, before the first snapshot is pushed");
   if (enable_streaming_trajectories) throw ftkx_error(FTKX_E_UNSUPPORTED, "slab mode: not with streaming trajectories");
+  if (temporal_smoothing_ksize) throw ftkx_error(FTKX_E_UNSUPPORTED, "slab mode: not with temporal smoothing (a slab needs raw halo snapshots of its neighbours)");
   if (nt <= 0 || nranks <= 0 || rank < 0 || rank >= nranks) throw ftkx_error(FTKX_E_INVALID, "slab mode: bad rank / nranks / nt");
   slab_rank = rank;
   ftkx_slab_range(nt, nranks, rank, &slab_t0, &slab_t1);
@@ -488,11 +489,14 @@ void critical_point_tracker_regular::apply_configuration(ftkx_ctx *c)
   for (size_t i = 0; i < 6 && i < bounds_coords.size(); i ++) o.coords_bounds[i] = bounds_coords[i];
   check_on(c, ftkx_set_options(c, &o));
   check_on(c, ftkx_set_spatial_smoothing(c, spatial_smoothing_sigma, spatial_smoothing_ksize));
+  check_on(c, ftkx_set_temporal_smoothing(c, temporal_smoothing_sigma, temporal_smoothing_ksize, next_push_timestep));
 }
 
 void critical_point_tracker_regular::initialize()
 {
   if ((int)domain.nd() != nd || (int)array_domain.nd() != nd) throw ftkx_error(FTKX_E_INVALID, "initialize: set_domain / set_array_domain first");
+  if (temporal_smoothing_ksize && (multi || slab))
+    throw ftkx_error(FTKX_E_UNSUPPORTED, "initialize: temporal smoothing with one device and no slab mode only (a slab needs raw halo snapshots of its neighbours)");
   sync();
   if (multi) { for (auto &W : multi->w) apply_configuration(W->ctx); }
   else apply_configuration(ctx);
@@ -521,6 +525,8 @@ void critical_point_tracker_regular::reset()
   current_timestep = 0;
   while (pop_field_data_snapshot()) {}
   next_push_timestep = 0;
+  last_push_snapshots = 1;
+  if (initialized && temporal_smoothing_ksize) check(ftkx_set_temporal_smoothing(ctx, temporal_smoothing_sigma, temporal_smoothing_ksize, 0));   // the ring is emptied
   if (slab) restart_slab();
   pending_points.clear(); pending_ascending = true;
   points.clear(); point_keys.clear();
@@ -530,12 +536,41 @@ void critical_point_tracker_regular::reset()
 // one snapshot -> the context(s) whose steps read it (kind: see push_to)
 void critical_point_tracker_regular::push_snapshot(int kind, const double *s, const double *v, const double *j, bool device)
 {
+  if (temporal_smoothing_ksize) {
+    // the raw snapshot feeds the filter; what the filter emits is the snapshot the tracker sees (a device source is read, not adopted)
+    if (kind == 2) throw ftkx_error(FTKX_E_UNSUPPORTED, "push_field_data_snapshot: temporal smoothing takes a scalar or a vector snapshot alone");
+    int t_emitted = -1;
+    last_push_snapshots = 0;
+    check(ftkx_temporal_push(ctx, kind == 0 ? s : v, kind, device ? 1 : 0, &t_emitted));
+    take_emitted(t_emitted);
+    return;
+  }
+  last_push_snapshots = 1;
   const int t = next_push_timestep;
   if (slab && (t < slab_t0 || t >= slab_t1)) throw ftkx_error(FTKX_E_INVALID, "slab mode: timestep " + std::to_string(t) + " is not in this rank's slab [" + std::to_string(slab_t0) + ", " + std::to_string(slab_t1) + ")");
   if (multi) multi->push(kind, t, s, v, j, device);
   else check(push_to(ctx, kind, t, s, v, j, device ? 1 : 0));
   field_data_snapshots.push_back(t);
   next_push_timestep ++;
+}
+
+// the filter's emission `t` (-1: none) is the next snapshot of the series
+void critical_point_tracker_regular::take_emitted(int t)
+{
+  if (t < 0) return;
+  if (t != next_push_timestep) throw ftkx_error(FTKX_E_INVALID, "temporal smoothing: emission " + std::to_string(t) + " where timestep " + std::to_string(next_push_timestep) + " was due");
+  field_data_snapshots.push_back(t);
+  next_push_timestep ++;
+  last_push_snapshots = 1;
+}
+
+bool critical_point_tracker_regular::flush_temporal_smoothing()
+{
+  if (!initialized || !temporal_smoothing_ksize) return false;
+  int t_emitted = -1;
+  check(ftkx_temporal_flush(ctx, &t_emitted));
+  take_emitted(t_emitted);
+  return t_emitted >= 0;
 }
 
 void critical_point_tracker_regular::push_scalar_field_snapshot(const double *s, bool device)
@@ -966,6 +1001,12 @@ int ftkx_tracker_set_flags(ftkx_tracker *h, int robust, int use_tf, unsigned tf,
 }
 int ftkx_tracker_set_stream(ftkx_tracker *h, void *s) { return guarded(h, [&] { h->t->set_stream(s); }); }
 int ftkx_tracker_set_spatial_smoothing(ftkx_tracker *h, double sigma, int ksize) { return guarded(h, [&] { h->t->set_spatial_smoothing(sigma, ksize); }); }
+int ftkx_tracker_set_temporal_smoothing(ftkx_tracker *h, double sigma, int ksize) { return guarded(h, [&] { h->t->set_temporal_smoothing(sigma, ksize); }); }
+int ftkx_tracker_snapshots_from_last_push(const ftkx_tracker *h, int *n)
+{ return guarded(h, [&] { if (!n) throw ftkx::ftkx_error(FTKX_E_INVALID, "null argument"); *n = h->t->snapshots_from_last_push(); }); }
+int ftkx_tracker_reset(ftkx_tracker *h) { return guarded(h, [&] { h->t->reset(); }); }
+int ftkx_tracker_flush_temporal_smoothing(ftkx_tracker *h, int *appended)
+{ return guarded(h, [&] { const bool b = h->t->flush_temporal_smoothing(); if (appended) *appended = b ? 1 : 0; }); }
 int ftkx_tracker_set_trace_on_device(ftkx_tracker *h, int on) { return guarded(h, [&] { h->t->set_trace_on_device(on != 0); }); }
 int ftkx_tracker_set_post_process_on_device(ftkx_tracker *h, int on) { return guarded(h, [&] { h->t->set_post_process_on_device(on != 0); }); }
 int ftkx_tracker_set_deferred_collection(ftkx_tracker *h, int on) { return guarded(h, [&] { h->t->set_deferred_collection(on != 0, on); }); }

@@ -449,6 +449,48 @@ int ftkx_set_spatial_smoothing(ftkx_ctx *ctx, double sigma, int ksize);
  * stream, a pair of events around every launch; ms: reps device times. */
 int ftkx_debug_conv_relaunch(ftkx_ctx *ctx, int nd, const double *S, int DW, int DH, int DD, const double *weights, int ksize, double *out, int reps, double *ms);
 
+/* ---- temporal Gaussian smoothing of a series of snapshots (filters/streaming_filter.hh; the stream's --temporal-smoothing-kernel[-size]) ---- */
+/* The filter ndarray_stream::modified_callback puts in front of the tracker, bit for bit, as this state machine (K = ksize, odd;
+ * H = (K + 1) / 2; `data` the deque of raw snapshots):
+ *     push(a):  data.push_back(a); if |data| > K: data.pop_front(), cursor--
+ *               if |data| >= H: emit sum_i w[i] * data[max(0, i + cursor - H + 1)], cursor++
+ *     finish(): loop: data.pop_front(); if |data| >= H: emit sum_i w[i] * data[min(|data| - 1, i)], cursor--; else stop
+ * Per element the sum starts as the rounded product w[0] * x0; every later tap is a rounded multiply and a rounded add in order; nothing
+ * is fused and taps on the same snapshot are not merged.  N >= K snapshots give N emissions, emission n (0-based) being
+ * sum_i w[i] * in[clamp(n + i - (H - 1), 0, N - 1)], H - 1 pushes late; H <= N < K give 2 (N - H) + 1, fewer than H none -- the reference's
+ * behaviour, reproduced.  Emissions are numbered here, from the series' first timestep t0 (the reference's callback index is not
+ * reproduced).  Element-wise: scalar and vector snapshots alike.
+ * ftkx_gaussian_kernel1d: host only.  gaussian_kernel (conv.hh:50-72) with the host's exp; ksize doubles.  FTKX_E_INVALID: ksize even or
+ * outside [1, 9], sigma not finite or not positive. */
+int ftkx_gaussian_kernel1d(double sigma, int ksize, double *weights);
+/* The bare kernel: out[e] = the sum above over arrays[0 .. ksize - 1][e], e < count.  arrays: a HOST array of ksize DEVICE pointers of
+ * count doubles each, the same pointer allowed several times (it is then read once per element, and still takes part once per tap);
+ * weights: ksize doubles on the HOST (any, not only ftkx_gaussian_kernel1d's); out: count doubles on the device that overlap none of the
+ * arrays.  Queued on the context's stream; the call returns when `out` is complete. */
+int ftkx_temporal_combine(ftkx_ctx *ctx, const double *const *arrays, int ksize, const double *weights, size_t count, double *out);
+/* ksize 0 (the default): off, the ring of raw snapshots is released.  Otherwise a series starts whose first emission gets timestep t0
+ * (a series that was open is abandoned).  Refused while sweeps are pending or series passes are open, like ftkx_set_spatial_smoothing.
+ * The push functions above are not affected by it: they install a slice unfiltered.  ftkx_set_mesh starts the series afresh, too.
+ * MEMORY: the ring holds at most ksize raw arrays (n doubles each for scalar, n * nd for vector snapshots); they come from and return to
+ * the pool that dropped slices' arrays go to.  With the filter on, the context holds those ksize arrays plus the emitted slices the
+ * caller has not dropped (ftkx_drop_slice) -- an emission is written into the array that leaves the ring where one does. */
+int ftkx_set_temporal_smoothing(ftkx_ctx *ctx, double sigma, int ksize, int t0);
+/* One RAW snapshot: S (n doubles; is_vector == 0) or V (n * nd doubles, no J, no S; is_vector != 0), n the vertices of the mesh's array
+ * extent.  on_device: 0 host memory, 1 or 2 device memory -- the ring always owns a copy; with 1 the source is read and never adopted,
+ * and the call returns once it has been read (as with 2; it waits for that point of the stream only, not for work queued before or behind it).  Where spatial smoothing is set a scalar snapshot is convolved into its ring
+ * slot first (the stream's order); vector input then fails with FTKX_E_UNSUPPORTED.  If the filter emits, the combined array becomes the
+ * resident slice *t_emitted in a buffer of the context's own, like one that ftkx_push_scalar_slice / ftkx_push_slice (V only) installed
+ * (masks, resolution, halo export, patches); otherwise *t_emitted = -1.  Scalar and vector snapshots cannot be mixed in one series, nor
+ * with resident slices of the other kind (FTKX_E_INVALID). */
+int ftkx_temporal_push(ftkx_ctx *ctx, const double *A, int is_vector, int on_device, int *t_emitted);
+/* One round of finish() per call: the trailing emission becomes the resident slice *t_emitted; or *t_emitted = -1: the reference's loop
+ * would stop -- the ring is released, the filter is in its initial state and the next series' first timestep is the next unused one.
+ * Between the first flush and that -1, ftkx_temporal_push is refused. */
+int ftkx_temporal_flush(ftkx_ctx *ctx, int *t_emitted);
+/* profiling aid (tools/temporal_time.py): the kernel of ftkx_temporal_combine launched `reps` times back to back on the context's stream,
+ * a pair of events around every launch; ms: reps device times. */
+int ftkx_debug_temporal_relaunch(ftkx_ctx *ctx, const double *const *arrays, int ksize, const double *weights, size_t count, double *out, int reps, double *ms);
+
 /* profiling aid: streams `bytes` of device memory with the mask kernel's load shape (16 B per lane) and nothing else, so that
  * rocprofv3's FETCH_SIZE can be calibrated on a known byte count (tools/calibrate_fetch.py) */
 int ftkx_debug_stream_read(ftkx_ctx *ctx, const void *device_ptr, size_t bytes);

@@ -159,6 +159,19 @@ public:
   // ksize, ksize / 2) on the device (ftkx_set_spatial_smoothing).  Set before initialize(); ksize 0: off (the default).  Scalar input only:
   // a push that hands over a vector field while this is set throws FTKX_E_UNSUPPORTED.
   void set_spatial_smoothing(double sigma, int ksize = 3) { spatial_smoothing_sigma = sigma; spatial_smoothing_ksize = ksize; }
+  // The stream's --temporal-smoothing-kernel / --temporal-smoothing-kernel-size (ftk::streaming_filter behind ndarray_stream; 5 is the
+  // stream's default size): the snapshots pushed after initialize() are RAW and feed the filter on the device (ftkx_temporal_push, behind
+  // the spatial smoothing where that is set too); the tracker sees the smoothed series.  The filter answers H - 1 = ksize / 2 pushes late:
+  // a push appends a snapshot to field_data_snapshots only when the filter emitted one -- snapshots_from_last_push() says so, and the
+  // caller's advance_timestep() belongs to the pushes that did.  After the last push, flush_temporal_smoothing() appends one trailing
+  // snapshot per call and returns false when there is none left (the filter is then ready for another series); the caller loops it in front
+  // of finalize(), with its usual advance_timestep() between the calls.  Set before initialize(); ksize 0: off (the default).
+  // push_scalar_field_snapshot and push_vector_field_snapshot feed the filter; push_field_data_snapshot (S, V and J given) throws
+  // FTKX_E_UNSUPPORTED while it is on.  reset() empties the filter.  Slab mode and multi-device trackers: initialize() throws
+  // FTKX_E_UNSUPPORTED (a slab would need ksize / 2 raw halo snapshots of each neighbour).
+  void set_temporal_smoothing(double sigma, int ksize = 5) { temporal_smoothing_sigma = sigma; temporal_smoothing_ksize = ksize; }
+  int snapshots_from_last_push() const { return last_push_snapshots; }      // 0 or 1; always 1 with the filter off
+  bool flush_temporal_smoothing();
   // Several RANKS behind the tracker -- one process per GPU, or one tracker per device and thread in one process.  The reference keeps an
   // MPI communicator on the filter and distributes inside the tracker (regular_tracker.hh:127-149), gathering the discrete points on the
   // root in front of pass 2 (critical_point_tracker.hh:689).  Here the series of `nt` timesteps is cut in TIME (include/ftkx_slab.h): this
@@ -251,6 +264,7 @@ protected:
   int current_timestep = 0;
   std::vector<int> field_data_snapshots;                    // timesteps resident on the device (<= 2, a deque in the reference)
   int next_push_timestep = 0;
+  void take_emitted(int t);                                 // temporal smoothing: the filter's emission t (-1: none) joins field_data_snapshots
   void push_snapshot(int kind, const double *s, const double *v, const double *j, bool device);   // behind the three push_* methods: one snapshot -> the context(s) that read it
   double vector_field_resolution = std::numeric_limits<double>::max();   // sticky running minimum (never reset)
   unsigned long long vector_field_scaling_factor = 1;
@@ -272,6 +286,9 @@ protected:
   bool trace_on_device = false;
   double spatial_smoothing_sigma = 0;
   int spatial_smoothing_ksize = 0;
+  double temporal_smoothing_sigma = 0;
+  int temporal_smoothing_ksize = 0;
+  int last_push_snapshots = 1;
   bool post_process_on_device = false;
   int deferred_depth = 1;
   std::vector<int> open_steps;                              // the timesteps of the sweeps that are queued and not yet collected (at most three; -1: a batch)
@@ -353,6 +370,10 @@ int  ftkx_tracker_set_flags(ftkx_tracker *, int robust, int use_type_filter, uns
 int  ftkx_tracker_set_stream(ftkx_tracker *, void *hip_stream);
 int  ftkx_tracker_set_current_timestep(ftkx_tracker *, int t);
 int  ftkx_tracker_set_spatial_smoothing(ftkx_tracker *, double sigma, int ksize);   /* the stream's spatial smoothing in front of the tracker; ksize 0: off */
+int  ftkx_tracker_set_temporal_smoothing(ftkx_tracker *, double sigma, int ksize);  /* the stream's temporal smoothing in front of the tracker; ksize 0: off */
+int  ftkx_tracker_snapshots_from_last_push(const ftkx_tracker *, int *n);           /* 0 or 1: did the last push_* append a (smoothed) snapshot */
+int  ftkx_tracker_flush_temporal_smoothing(ftkx_tracker *, int *appended);          /* one trailing snapshot per call; *appended = 0: none left */
+int  ftkx_tracker_reset(ftkx_tracker *);                                            /* critical_point_tracker_regular::reset: a new series; the temporal filter is emptied */
 int  ftkx_tracker_set_trace_on_device(ftkx_tracker *, int on);       /* not in the reference: see critical_point_tracker_regular::set_trace_on_device */
 int  ftkx_tracker_set_post_process_on_device(ftkx_tracker *, int on);   /* not in the reference: see critical_point_tracker_regular::set_post_process_on_device */
 int  ftkx_tracker_set_deferred_collection(ftkx_tracker *, int on);   /* not in the reference: see critical_point_tracker_regular::set_deferred_collection; on > 1: batches of `on` steps */
