@@ -17,18 +17,30 @@ __all__ = ["trace_curves", "pass2", "trace_and_post_process", "post_process", "p
 
 
 def _ptr(a):
-    """host numpy array / torch tensor / raw int -> (address, keepalive, on_device)"""
+    """host numpy array / torch tensor / raw int -> (address, keepalive, on_device, f32).  A float32 array or tensor is kept as it is (f32
+    True: it goes to the library's *_f32 entries, 4 bytes per value, and is widened on the device); a raw int is taken for float64"""
     if a is None:
-        return None, None, 0
+        return None, None, 0, False
     if isinstance(a, int):
-        return a, None, 1
+        return a, None, 1, False
     if hasattr(a, "data_ptr"):          # torch tensor (device memory is torch's job: plumbing, not the product)
-        if a.dtype.is_floating_point and a.element_size() != 8:
-            raise TypeError("fields must be float64")
+        if a.dtype.is_floating_point and a.element_size() not in (4, 8):
+            raise TypeError("fields must be float64 or float32")
         a = a.contiguous()
-        return a.data_ptr(), a, 1 if a.is_cuda else 0
+        return a.data_ptr(), a, 1 if a.is_cuda else 0, bool(a.dtype.is_floating_point and a.element_size() == 4)
+    if isinstance(a, np.ndarray) and a.dtype == np.float32:
+        a = np.ascontiguousarray(a)
+        return a.ctypes.data, a, 0, True
     a = np.ascontiguousarray(a, dtype=np.float64)
-    return a.ctypes.data, a, 0
+    return a.ctypes.data, a, 0, False
+
+
+def _same_type(*f32):
+    """the arrays of one push (those that are given) are all float32 or all float64 -> which"""
+    kinds = {bool(f) for f in f32 if f is not None}
+    if len(kinds) > 1:
+        raise TypeError("the arrays of one push must all be float32 or all float64")
+    return bool(kinds and kinds.pop())
 
 
 def default_options(**kw):
@@ -127,13 +139,13 @@ class Context:
     def temporal_push(self, A, is_vector=False, on_device=None):
         """ftkx_temporal_push: one raw snapshot (host array or device tensor; always copied) -> the timestep of the smoothed slice that became
         resident, or -1.  on_device as in push_scalar_slice"""
-        p, k, d = _ptr(A)
+        p, k, d, f32 = _ptr(A)
         if on_device is not None:
             if int(on_device) not in (0, 1, 2) or (int(on_device) != 0) != bool(d):
                 raise ValueError("on_device: 0 for a host array, 1 or 2 for a device tensor")
             d = int(on_device)
         t = C.c_int(-1)
-        self._ck(self._L.ftkx_temporal_push(self._h, p, int(bool(is_vector)), d, C.byref(t)))
+        self._ck((self._L.ftkx_temporal_push_f32 if f32 else self._L.ftkx_temporal_push)(self._h, p, int(bool(is_vector)), d, C.byref(t)))
         if t.value >= 0:
             self._keep[t.value] = None
         return t.value
@@ -165,23 +177,24 @@ class Context:
         return list(ms)
 
     def push_slice(self, t, V, J=None, S=None):
-        pv, kv, dv = _ptr(V); pj, kj, dj = _ptr(J); ps, ks, ds = _ptr(S)
+        pv, kv, dv, fv = _ptr(V); pj, kj, dj, fj = _ptr(J); ps, ks, ds, fs = _ptr(S)
         devs = {d for p, d in ((pv, dv), (pj, dj), (ps, ds)) if p is not None}
         if len(devs) != 1:
             raise ValueError("V, J, S must all be host arrays or all device tensors")
         on_dev = devs.pop()
-        self._ck(self._L.ftkx_push_slice(self._h, t, pv, pj, ps, on_dev))
-        self._keep[t] = (kv, kj, ks) if on_dev else None
+        f32 = _same_type(*[f for p, f in ((pv, fv), (pj, fj), (ps, fs)) if p is not None])
+        self._ck((self._L.ftkx_push_slice_f32 if f32 else self._L.ftkx_push_slice)(self._h, t, pv, pj, ps, on_dev))
+        self._keep[t] = (kv, kj, ks) if on_dev and not f32 else None       # (float32: read before the call returned, the context owns FP64 copies)
 
     def push_scalar_slice(self, t, S, on_device=None):
         """on_device: None = 0 for a host array, 1 (borrowed) for a device tensor; 2: a device tensor, copied"""
-        ps, ks, ds = _ptr(S)
+        ps, ks, ds, f32 = _ptr(S)
         if on_device is not None:
             if int(on_device) not in (0, 1, 2) or (int(on_device) != 0) != bool(ds):
                 raise ValueError("on_device: 0 for a host array, 1 or 2 for a device tensor")
             ds = int(on_device)
-        self._ck(self._L.ftkx_push_scalar_slice(self._h, t, ps, ds))
-        self._keep[t] = ks if ds == 1 and not self._smoothing else None     # (2, and smoothing: the context owns a copy)
+        self._ck((self._L.ftkx_push_scalar_slice_f32 if f32 else self._L.ftkx_push_scalar_slice)(self._h, t, ps, ds))
+        self._keep[t] = ks if ds == 1 and not self._smoothing and not f32 else None     # (2, smoothing, float32: the context owns a copy)
 
     def drop_slice(self, t):
         self._ck(self._L.ftkx_drop_slice(self._h, t))
@@ -438,17 +451,34 @@ class Context:
     def jacobian3D(self, V_ptr, DW, DH, DD, J_ptr): self._ck(self._L.ftkx_jacobian3D(self._h, V_ptr, DW, DH, DD, J_ptr))
 
     # spatial smoothing on device tensors (ndarray/conv.hh); weights: a host array of ksize ** nd doubles, x fastest
-    def conv2D(self, S_ptr, DW, DH, weights, ksize, out_ptr):
+    def conv2D(self, S_ptr, DW, DH, weights, ksize, out_ptr, f32=False):
         w = np.ascontiguousarray(weights, dtype=np.float64)
         if w.size != int(ksize) ** 2:
             raise ValueError("conv2D: ksize ** 2 weights")
-        self._ck(self._L.ftkx_conv2D(self._h, S_ptr, DW, DH, w.ctypes.data, int(ksize), out_ptr))
+        self._ck((self._L.ftkx_conv2D_f32 if f32 else self._L.ftkx_conv2D)(self._h, S_ptr, DW, DH, w.ctypes.data, int(ksize), out_ptr))
 
-    def conv3D(self, S_ptr, DW, DH, DD, weights, ksize, out_ptr):
+    def conv3D(self, S_ptr, DW, DH, DD, weights, ksize, out_ptr, f32=False):
         w = np.ascontiguousarray(weights, dtype=np.float64)
         if w.size != int(ksize) ** 3:
             raise ValueError("conv3D: ksize ** 3 weights")
-        self._ck(self._L.ftkx_conv3D(self._h, S_ptr, DW, DH, DD, w.ctypes.data, int(ksize), out_ptr))
+        self._ck((self._L.ftkx_conv3D_f32 if f32 else self._L.ftkx_conv3D)(self._h, S_ptr, DW, DH, DD, w.ctypes.data, int(ksize), out_ptr))
+
+    # float32 -> FP64 on device pointers (widen_kernels.hip); conv2D / conv3D take f32=True for a float32 source
+    def widen_f32(self, src_ptr, count, dst_ptr):
+        """ftkx_widen_f32: dst[e] = double(src[e]) for `count` floats"""
+        self._ck(self._L.ftkx_widen_f32(self._h, src_ptr, int(count), dst_ptr))
+
+    def debug_widen_relaunch(self, src_ptr, count, dst_ptr, reps):
+        """profiling aid: the widen kernel `reps` times back to back -> device ms per launch (HIP events)"""
+        ms = (C.c_double * int(reps))()
+        self._ck(self._L.ftkx_debug_widen_relaunch(self._h, src_ptr, int(count), dst_ptr, int(reps), ms))
+        return list(ms)
+
+    def f32_counts(self):
+        """(widened, convolved_direct): float32 arrays pushed into this context that took the widen kernel / went straight through the convolution"""
+        a = C.c_ulonglong(0); b = C.c_ulonglong(0)
+        self._ck(self._L.ftkx_debug_f32_counts(self._h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
 
     def debug_conv_relaunch(self, S_ptr, dims, weights, ksize, out_ptr, reps):
         """profiling aid: the convolution kernel `reps` times back to back -> device ms per launch (HIP events)"""
@@ -890,16 +920,18 @@ class _TrackerRegular:
         self._ck(self._L.ftkx_tracker_initialize(self._h))
 
     def push_scalar_field_snapshot(self, s):
-        p, k, d = _ptr(s); self._keep.append(k)
-        self._ck(self._L.ftkx_tracker_push_scalar_field_snapshot(self._h, p, d))
+        p, k, d, f32 = _ptr(s); self._keep.append(None if f32 else k)      # (float32: read before the call returns, never borrowed)
+        self._ck((self._L.ftkx_tracker_push_scalar_field_snapshot_f32 if f32 else self._L.ftkx_tracker_push_scalar_field_snapshot)(self._h, p, d))
 
     def push_vector_field_snapshot(self, v):
-        p, k, d = _ptr(v); self._keep.append(k)
-        self._ck(self._L.ftkx_tracker_push_vector_field_snapshot(self._h, p, d))
+        p, k, d, f32 = _ptr(v); self._keep.append(None if f32 else k)
+        self._ck((self._L.ftkx_tracker_push_vector_field_snapshot_f32 if f32 else self._L.ftkx_tracker_push_vector_field_snapshot)(self._h, p, d))
 
     def push_field_data_snapshot(self, s, v, j):
-        ps, ks, ds = _ptr(s); pv, kv, dv = _ptr(v); pj, kj, dj = _ptr(j); self._keep.append((ks, kv, kj))
-        self._ck(self._L.ftkx_tracker_push_field_data_snapshot(self._h, ps, pv, pj, dv))
+        ps, ks, ds, fs = _ptr(s); pv, kv, dv, fv = _ptr(v); pj, kj, dj, fj = _ptr(j)
+        f32 = _same_type(*[f for p, f in ((ps, fs), (pv, fv), (pj, fj)) if p is not None])
+        self._keep.append(None if f32 else (ks, kv, kj))
+        self._ck((self._L.ftkx_tracker_push_field_data_snapshot_f32 if f32 else self._L.ftkx_tracker_push_field_data_snapshot)(self._h, ps, pv, pj, dv))
 
     def advance_timestep(self):
         self._ck(self._L.ftkx_tracker_advance_timestep(self._h))

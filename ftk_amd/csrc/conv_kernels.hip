@@ -1,4 +1,5 @@
-// Spatial Gaussian smoothing of a scalar snapshot on the device: 2D and 3D FP64 convolution with K^nd given weights, out of place.
+// Spatial Gaussian smoothing of a scalar snapshot on the device: 2D and 3D FP64 convolution with K^nd given weights, out of place; the source
+// is FP64 or float32 (widened as the tile is staged: the arithmetic is the same).
 //
 // Reference (a single-threaded host loop): include/ftk/ndarray/conv.hh, conv2D 11-47 / conv3D 117-163 with padding = ksize / 2, called per
 // snapshot by ndarray_stream::modified_callback (include/ftk/ndarray/stream.hh:1597-1603).  The kernel reproduces it bit for bit: per
@@ -18,8 +19,8 @@
 
 namespace ftkx {
 
-template <int ND, int K>
-__global__ __launch_bounds__(kConvThreads) void conv_kernel(const double *__restrict__ S, ConvDims d, const double *__restrict__ w, double *__restrict__ out)
+template <int ND, int K, class SRC>
+__global__ __launch_bounds__(kConvThreads) void conv_kernel(const SRC *__restrict__ S, ConvDims d, const double *__restrict__ w, double *__restrict__ out)
 {
   typedef ConvTile<ND, K> T;
   __shared__ __attribute__((aligned(16))) double tile[T::DOUBLES];
@@ -46,20 +47,23 @@ __global__ __launch_bounds__(kConvThreads) void conv_kernel(const double *__rest
   }
 }
 
-template <int ND, int K> static void launch_conv_k(const double *S, const ConvDims &d, const double *d_weights, double *out, hipStream_t st)
+template <int ND, int K, class SRC> static void launch_conv_k(const SRC *S, const ConvDims &d, const double *d_weights, double *out, hipStream_t st)
 {
   const size_t ntiles = conv_tiles<ND, K>(d);
   const unsigned grid = (unsigned)(ntiles < (size_t)(1u << 30) ? ntiles : (size_t)(1u << 30));
-  hipLaunchKernelGGL((conv_kernel<ND, K>), dim3(grid), dim3(kConvThreads), 0, st, S, d, d_weights, out);
+  hipLaunchKernelGGL((conv_kernel<ND, K, SRC>), dim3(grid), dim3(kConvThreads), 0, st, S, d, d_weights, out);
 }
 
 // nd 2 or 3 (2D: DD == 1), ksize odd in [1, 9], extents >= 1: checked by the callers (ftkx_api.hip).  d_weights: ksize^nd doubles on the device.
-void launch_conv(int nd, const double *S, int DW, int DH, int DD, const double *d_weights, int ksize, double *out, hipStream_t st)
+// SRC double or float: a float32 source is widened where the tile is staged, so no widened copy of it is written and read back.
+template <class SRC> void launch_conv(int nd, const SRC *S, int DW, int DH, int DD, const double *d_weights, int ksize, double *out, hipStream_t st)
 {
   const ConvDims d{DW, DH, nd == 2 ? 1 : DD};
 #define CONV_CASE(k) case k: if (nd == 2) launch_conv_k<2, k>(S, d, d_weights, out, st); else launch_conv_k<3, k>(S, d, d_weights, out, st); break
   switch (ksize) { CONV_CASE(1); CONV_CASE(3); CONV_CASE(5); CONV_CASE(7); CONV_CASE(9); default: break; }
 #undef CONV_CASE
 }
+template void launch_conv<double>(int, const double *, int, int, int, const double *, int, double *, hipStream_t);
+template void launch_conv<float>(int, const float *, int, int, int, const double *, int, double *, hipStream_t);
 
 }  // namespace ftkx

@@ -84,15 +84,16 @@ template <int ND, int K> CONV_HD void conv_lane(int tid, int *tx, int *ty, int *
   *tz = half / (T::LY / 4);
 }
 
-// staged value number `i` (0 <= i < STAGED, x fastest) of the tile at (x0, y0, z0): where it goes in the tile and what it is
-template <int ND, int K> CONV_HD void conv_stage(const double *S, const ConvDims &d, int x0, int y0, int z0, int i, double *tile)
+// staged value number `i` (0 <= i < STAGED, x fastest) of the tile at (x0, y0, z0): where it goes in the tile and what it is.  SRC: double, or
+// float -- a float32 snapshot is widened (exactly: widen_steps.hpp) as it is staged, and the tile holds doubles either way
+template <int ND, int K, class SRC> CONV_HD void conv_stage(const SRC *S, const ConvDims &d, int x0, int y0, int z0, int i, double *tile)
 {
   typedef ConvTile<ND, K> T;
   const int lx = i % T::SX, ly = (i / T::SX) % T::PY, lz = i / (T::SX * T::PY);
   const int gx = x0 - T::H + lx, gy = y0 - T::H + ly, gz = ND == 2 ? 0 : z0 - T::H + lz;
   double v = 0.0;
   if (gx >= 0 && gx < d.DW && gy >= 0 && gy < d.DH && gz >= 0 && gz < d.DD)
-    v = S[((size_t)gz * (size_t)d.DH + (size_t)gy) * (size_t)d.DW + (size_t)gx];
+    v = static_cast<double>(S[((size_t)gz * (size_t)d.DH + (size_t)gy) * (size_t)d.DW + (size_t)gx]);
   tile[(lz * T::PY + ly) * T::PX + lx] = v;
 }
 

@@ -53,7 +53,8 @@ void launch_jacobian2d(const double *V, int DW, int DH, int symmetric, double *J
 void launch_gradient3d(const double *S, int DW, int DH, int DD, double *V, hipStream_t st);
 void launch_jacobian3d(const double *V, int DW, int DH, int DD, double *J, hipStream_t st);
 void launch_resolution(const double *p, size_t n, u64 *out2, hipStream_t st);
-void launch_conv(int nd, const double *S, int DW, int DH, int DD, const double *d_weights, int ksize, double *out, hipStream_t st);   // conv_kernels.hip
+template <class SRC> void launch_conv(int nd, const SRC *S, int DW, int DH, int DD, const double *d_weights, int ksize, double *out, hipStream_t st);   // conv_kernels.hip: SRC double or float
+void launch_widen(const float *src, size_t count, double *dst, hipStream_t st);   // widen_kernels.hip
 void launch_temporal(const double *const *arrays, int ksize, const double *weights, size_t count, double *out, hipStream_t st);   // temporal_kernels.hip
 void launch_calib_read(const void *p, size_t bytes, double *scratch, hipStream_t stream);
 const char *last_mask_kernel();
@@ -310,6 +311,14 @@ struct ftkx_ctx {
   size_t tm_count = 0;
   int tm_next = 0;
   hipEvent_t tm_read = nullptr;     // behind the staging of a device source: what ftkx_temporal_push waits for before it returns
+  // float32 sources (ftkx_push_scalar_slice_f32, ftkx_push_slice_f32, ftkx_temporal_push_f32): a host array, or an array of another device, lies
+  // here as it came, 4 bytes per value, until the widen kernel or the convolution has made the FP64 slice of it.  Reserved by the bytes of
+  // that very array (count * sizeof(float)), drained by the stream that read it last.  Written by the upload's DMAs or a copy on the
+  // context's stream, read by one kernel on the context's stream: how the next push's writes are ordered behind that kernel is said where
+  // it is filled (ftkx_api.hip, stage_into).
+  ftkx_block f32_stage;
+  hipStream_t f32_stage_reader = nullptr;      // the stream of the kernel that read it last
+  unsigned long long f32_widened = 0, f32_direct = 0;   // ftkx_debug_f32_counts: float32 arrays through the widen kernel / straight through the convolution
   std::vector<ftkxh::Request> pending;
   // Cull-ahead: the sweeps the caller announced (ftkx_sweep_announce) for the slices of the next ftkx_slices_prepare, and -- once that
   // call has queued their cull right behind the mask kernel -- the survivor list it left on the device.  The cull needs the masks

@@ -5,6 +5,7 @@
 // and the hit buffer is persistent (grown and the batch replayed if a launch overflows it).
 #include <map>
 #include <mutex>
+#include <type_traits>
 #include "ctx.hpp"
 #include "cp_device.hpp"
 #include <sched.h>
@@ -561,33 +562,67 @@ static void install_slice(ftkx_ctx *c, int t, Slice &s, bool scalar_only)
   c->scalar_mode = scalar_only ? 1 : 0;
 }
 
-// spatial smoothing: dst = conv(src), dst being a buffer of the context's own whatever on_device says.  A host source, and a device source
-// that lives on another device, goes through a pooled buffer first (the kernel reads this device's memory only); that buffer goes back
-// to the pool at once.
-static int stage_smoothed(ftkx_ctx *c, const double *src, size_t count, int on_device, double *dst)
+extern "C++" {      // (templates on the source's element type)
+// dst -- `count` doubles of the context's own -- becomes the snapshot `src` as a resident slice holds it: widened where T is float,
+// convolved where `smooth` says so.  T = double without smoothing is a plain copy into dst.  Otherwise ONE kernel on the context's stream
+// reads the source and writes dst (float + smoothing: the convolution stages the floats as doubles itself, no widened copy is written and
+// read back).  That kernel reads this device's memory only: a host source, and a device source that lives on another device, goes through
+// a staging buffer first -- FP64: a pooled array, which goes back to the pool at once; float32: the context's f32_stage block.
+//
+// The staging block is written by every float32 push and read by the kernel of the push before, which may still run.  What orders them:
+// upload_from_host either copies on the context's stream itself, or -- staged_upload, on DMA streams of its own -- makes those streams wait
+// for an event recorded on the context's stream unless that stream is idle (upload.cpp, E.gate); a peer copy is queued on the context's
+// stream; a block that has to grow is freed only after the stream of its last reader has been waited for (reserve's drain).  All of that
+// holds for ONE stream: where ftkx_set_stream has changed it since the last reader was queued, that reader's stream is waited for here.
+template <class T> static int stage_into(ftkx_ctx *c, const T *src, size_t count, int on_device, bool smooth, double *dst)
 {
-  const double *from = src;
+  constexpr bool f32 = std::is_same<T, float>::value;
+  if (!f32 && !smooth) {
+    // 0: host memory; 2: device memory of ANY device (a multi-device tracker hands one snapshot to two contexts), copied
+    if (on_device == 0) return upload_from_host(c, dst, src, count * sizeof(T));
+    if (hipMemcpyAsync(dst, src, count * sizeof(T), hipMemcpyDefault, c->stream) != hipSuccess) return fail(c, FTKX_E_DEVICE, "push: copy of the source failed");
+    return FTKX_OK;
+  }
+  const T *from = src;
   double *tmp = nullptr;
   if (on_device == 0 || ftkx_pointer_device(src) != c->device) {
-    if (int rc = take_pooled(c, count, &tmp)) return rc;
+    void *stage = nullptr;
+    if (f32) {
+      if (c->f32_stage_reader && c->f32_stage_reader != c->stream) HIP_TRY(c, hipStreamSynchronize(c->f32_stage_reader));
+      c->f32_stage_reader = nullptr;
+      if (int rc = c->f32_stage.reserve(c, count * sizeof(T), 0, c->stream)) return rc;
+      stage = c->f32_stage.p;
+    } else {
+      if (int rc = take_pooled(c, count, &tmp)) return rc;
+      stage = tmp;
+    }
     int rc = FTKX_OK;
-    if (on_device == 0) rc = upload_from_host(c, tmp, src, count * sizeof(double));
-    else if (hipMemcpyAsync(tmp, src, count * sizeof(double), hipMemcpyDefault, c->stream) != hipSuccess) rc = fail(c, FTKX_E_DEVICE, "push: copy of the source failed");
+    if (on_device == 0) rc = upload_from_host(c, stage, src, count * sizeof(T));
+    else if (hipMemcpyAsync(stage, src, count * sizeof(T), hipMemcpyDefault, c->stream) != hipSuccess) rc = fail(c, FTKX_E_DEVICE, "push: copy of the source failed");
     // (a failed copy: nothing of it is in flight any more -- upload.cpp drains its DMA streams before it reports an error, and a
     // hipMemcpyAsync that was refused was never queued -- but what the buffer holds is unknown and the device may be in an error state:
-    // it is freed, not pooled)
-    if (rc) { (void)hipFree(tmp); return rc; }
-    from = tmp;
+    // a pooled buffer is freed, not pooled; the staging block is overwritten by the next push anyway)
+    if (rc) { if (tmp) (void)hipFree(tmp); return rc; }
+    from = static_cast<const T *>(stage);
+    if (f32) c->f32_stage_reader = c->stream;
   }
-  ftkx::launch_conv(c->nd, from, (int)c->ext_sz[0], (int)c->ext_sz[1], (int)c->ext_sz[2], c->d_conv_w.as<double>() + kSmoothWeights, c->smooth_ksize, dst, c->stream);
+  if (smooth) {
+    ftkx::launch_conv<T>(c->nd, from, (int)c->ext_sz[0], (int)c->ext_sz[1], (int)c->ext_sz[2], c->d_conv_w.as<double>() + kSmoothWeights, c->smooth_ksize, dst, c->stream);
+    if (f32) c->f32_direct ++;
+  } else if constexpr (f32) {
+    ftkx::launch_widen(from, count, dst, c->stream);
+    c->f32_widened ++;
+  }
   const hipError_t e = hipGetLastError();
   if (tmp) give_pooled(c, tmp, count);
   HIP_TRY(c, e);
   return FTKX_OK;
 }
 
-static int push_common(ftkx_ctx *c, int t, const double *V, const double *J, const double *S, int on_device, bool scalar_only)
+// T: the element type of the caller's arrays (double, or float: ftkx_push_*_f32).  The resident slice is FP64 either way
+template <class T> static int push_common(ftkx_ctx *c, int t, const T *V, const T *J, const T *S, int on_device, bool scalar_only)
 {
+  constexpr bool f32 = std::is_same<T, float>::value;
   if (c) c->ahead.clear();
   if (!c) return fail(nullptr, FTKX_E_INVALID, "null context");
   if (int rc = push_checks(c, t, on_device, scalar_only, scalar_only ? S != nullptr : V != nullptr)) return rc;
@@ -598,42 +633,51 @@ static int push_common(ftkx_ctx *c, int t, const double *V, const double *J, con
   Slice s;
   const size_t n = n_vertices(c);
   const int nd = c->nd;
-  auto take_smoothed = [&](const double *src, size_t count, double **dst, bool *own) -> int {
-    if (int rc = take_pooled(c, count, dst)) return rc;
-    *own = true;
-    return stage_smoothed(c, src, count, on_device, *dst);
-  };
-  auto take = [&](const double *src, size_t count, double **dst, bool *own) -> int {
+  // (smoothing applies to S alone: vector pushes were refused above)
+  auto take = [&](const T *src, size_t count, bool smooth, double **dst, bool *own) -> int {
     if (!src) { *dst = nullptr; *own = false; return FTKX_OK; }
-    if (on_device == 1) { *dst = const_cast<double *>(src); *own = false; return FTKX_OK; }
+    if constexpr (!f32) if (on_device == 1 && !smooth) { *dst = const_cast<double *>(src); *own = false; return FTKX_OK; }      // borrowed: adopted as it is
     if (int rc = take_pooled(c, count, dst)) return rc;
     *own = true;
-    // 0: host memory; 2: device memory of ANY device (a multi-device tracker hands one snapshot to two contexts), copied
-    if (on_device == 0) return upload_from_host(c, *dst, src, count * sizeof(double));
-    HIP_TRY(c, hipMemcpyAsync(*dst, src, count * sizeof(double), hipMemcpyDefault, c->stream));
-    return FTKX_OK;
+    return stage_into(c, src, count, on_device, smooth, *dst);
   };
   int rc;
-  if ((rc = c->smooth_ksize ? take_smoothed(S, n, &s.S, &s.ownS) : take(S, n, &s.S, &s.ownS))) { release_slice(s); return rc; }
+  if ((rc = take(S, n, c->smooth_ksize != 0, &s.S, &s.ownS))) { release_slice(s); return rc; }
   if (!scalar_only) {
-    if ((rc = take(V, n * nd, &s.V, &s.ownV))) { release_slice(s); return rc; }      // what was already allocated goes back
-    if ((rc = take(J, n * nd * nd, &s.J, &s.ownJ))) { release_slice(s); return rc; }
+    if ((rc = take(V, n * nd, false, &s.V, &s.ownV))) { release_slice(s); return rc; }      // what was already allocated goes back
+    if ((rc = take(J, n * nd * nd, false, &s.J, &s.ownJ))) { release_slice(s); return rc; }
   }
   // scalar input: V = gradient2D/3D(S) is never materialised -- every kernel evaluates it where it needs it, with the
   // reference's exact operations (ndarray/grad.hh), so the slice costs 8 bytes per vertex of HBM instead of 8 + 8*nd.
   // the source buffers may be reused by the caller on return: a device source (2) has to be read first; a host source has been staged
   // completely by upload_from_host (nothing to wait for: the DMAs run on while the caller produces its next snapshot)
-  // (smoothing: a borrowed array (1) is read by the kernel and never adopted -- the call returns once it has been read, like 2)
-  if (on_device == 2 || (on_device == 1 && c->smooth_ksize)) HIP_TRY(c, hipStreamSynchronize(c->stream));
+  // (smoothing, and a float32 source: a borrowed array (1) is read by the kernel and never adopted -- the call returns once it has been read, like 2)
+  if (on_device == 2 || (on_device == 1 && (c->smooth_ksize || f32))) HIP_TRY(c, hipStreamSynchronize(c->stream));
   install_slice(c, t, s, scalar_only);
   return FTKX_OK;
 }
 
+}  // extern "C++"
+
 int ftkx_push_slice(ftkx_ctx *c, int t, const double *V, const double *J, const double *S, int on_device)
-{ return push_common(c, t, V, J, S, on_device, false); }
+{ return push_common<double>(c, t, V, J, S, on_device, false); }
 
 int ftkx_push_scalar_slice(ftkx_ctx *c, int t, const double *S, int on_device)
-{ return push_common(c, t, nullptr, nullptr, S, on_device, true); }
+{ return push_common<double>(c, t, nullptr, nullptr, S, on_device, true); }
+
+int ftkx_push_slice_f32(ftkx_ctx *c, int t, const float *V, const float *J, const float *S, int on_device)
+{ return push_common<float>(c, t, V, J, S, on_device, false); }
+
+int ftkx_push_scalar_slice_f32(ftkx_ctx *c, int t, const float *S, int on_device)
+{ return push_common<float>(c, t, nullptr, nullptr, S, on_device, true); }
+
+int ftkx_debug_f32_counts(const ftkx_ctx *c, unsigned long long *widened, unsigned long long *convolved_direct)
+{
+  if (!c) return fail(nullptr, FTKX_E_INVALID, "null context");
+  if (widened) *widened = c->f32_widened;
+  if (convolved_direct) *convolved_direct = c->f32_direct;
+  return FTKX_OK;
+}
 
 int ftkx_drop_slice(ftkx_ctx *c, int t)
 {
@@ -895,26 +939,77 @@ static int conv_weights(ftkx_ctx *c, const double *weights, int n, size_t at)
   return FTKX_OK;
 }
 
-static int conv_common(ftkx_ctx *c, int nd, const double *S, int DW, int DH, int DD, const double *weights, int ksize, double *out)
+extern "C++" {
+template <class T> static int conv_common(ftkx_ctx *c, int nd, const T *S, int DW, int DH, int DD, const double *weights, int ksize, double *out)
 {
   DERIVE_PROLOGUE(c);
   if (!S || !out || !weights) return fail(c, FTKX_E_INVALID, "ftkx_conv%dD: null argument", nd);
   if (DW < 1 || DH < 1 || DD < 1) return fail(c, FTKX_E_INVALID, "ftkx_conv%dD: extents must be positive", nd);
   if (!conv_ksize_ok(ksize)) return fail(c, FTKX_E_INVALID, "ftkx_conv%dD: ksize must be odd and in [1, 9] (got %d)", nd, ksize);
   const size_t n = (size_t)DW * (size_t)DH * (size_t)DD;
-  if (S < out + n && out < S + n) return fail(c, FTKX_E_INVALID, "ftkx_conv%dD: input and output overlap", nd);
+  if ((const char *)S < (const char *)(out + n) && (const char *)out < (const char *)(S + n)) return fail(c, FTKX_E_INVALID, "ftkx_conv%dD: input and output overlap", nd);
   int taps = ksize * ksize * (nd == 3 ? ksize : 1);
   if (int rc = conv_weights(c, weights, taps, 0)) return rc;
-  ftkx::launch_conv(nd, S, DW, DH, DD, c->d_conv_w.as<double>(), ksize, out, c->stream);
+  ftkx::launch_conv<T>(nd, S, DW, DH, DD, c->d_conv_w.as<double>(), ksize, out, c->stream);
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipStreamSynchronize(c->stream));      // (the next call may overwrite the weights; the caller may read `out`)
   return FTKX_OK;
 }
+}  // extern "C++"
 
 int ftkx_conv2D(ftkx_ctx *c, const double *S, int DW, int DH, const double *weights, int ksize, double *out)
-{ return conv_common(c, 2, S, DW, DH, 1, weights, ksize, out); }
+{ return conv_common<double>(c, 2, S, DW, DH, 1, weights, ksize, out); }
 int ftkx_conv3D(ftkx_ctx *c, const double *S, int DW, int DH, int DD, const double *weights, int ksize, double *out)
-{ return conv_common(c, 3, S, DW, DH, DD, weights, ksize, out); }
+{ return conv_common<double>(c, 3, S, DW, DH, DD, weights, ksize, out); }
+int ftkx_conv2D_f32(ftkx_ctx *c, const float *S, int DW, int DH, const double *weights, int ksize, double *out)
+{ return conv_common<float>(c, 2, S, DW, DH, 1, weights, ksize, out); }
+int ftkx_conv3D_f32(ftkx_ctx *c, const float *S, int DW, int DH, int DD, const double *weights, int ksize, double *out)
+{ return conv_common<float>(c, 3, S, DW, DH, DD, weights, ksize, out); }
+
+// ---- float32 -> FP64 (widen_kernels.hip) ---------------------------------------------------------------------------------------------------
+static int widen_args(ftkx_ctx *c, const char *who, const float *src, size_t count, const double *dst)
+{
+  if (!src || !dst) return fail(c, FTKX_E_INVALID, "%s: null argument", who);
+  if (count < 1) return fail(c, FTKX_E_INVALID, "%s: count must be positive", who);
+  if (((size_t)src & 3) || ((size_t)dst & 7)) return fail(c, FTKX_E_INVALID, "%s: src must be a multiple of 4 bytes and dst a multiple of 8", who);
+  if ((const char *)src < (const char *)(dst + count) && (const char *)dst < (const char *)(src + count)) return fail(c, FTKX_E_INVALID, "%s: input and output overlap", who);
+  return FTKX_OK;
+}
+
+int ftkx_widen_f32(ftkx_ctx *c, const float *src, size_t count, double *dst)
+{
+  DERIVE_PROLOGUE(c);
+  if (int rc = widen_args(c, "ftkx_widen_f32", src, count, dst)) return rc;
+  ftkx::launch_widen(src, count, dst, c->stream);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipStreamSynchronize(c->stream));      // (the caller may read `dst`)
+  return FTKX_OK;
+}
+
+// profiling aid (tools/push_f32_time.py): the widen kernel `reps` times back to back, a pair of events around every launch
+int ftkx_debug_widen_relaunch(ftkx_ctx *c, const float *src, size_t count, double *dst, int reps, double *ms)
+{
+  DERIVE_PROLOGUE(c);
+  if (!ms || reps < 1) return fail(c, FTKX_E_INVALID, "ftkx_debug_widen_relaunch: bad argument");
+  if (int rc = widen_args(c, "ftkx_debug_widen_relaunch", src, count, dst)) return rc;
+  std::vector<hipEvent_t> ev(2 * (size_t)reps, nullptr);
+  auto run = [&]() -> int {
+    for (hipEvent_t &e : ev) HIP_TRY(c, hipEventCreate(&e));
+    for (int i = 0; i < reps; i ++) {
+      HIP_TRY(c, hipEventRecord(ev[2 * (size_t)i], c->stream));
+      ftkx::launch_widen(src, count, dst, c->stream);
+      HIP_TRY(c, hipEventRecord(ev[2 * (size_t)i + 1], c->stream));
+    }
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (int i = 0; i < reps; i ++) { float t = 0; HIP_TRY(c, hipEventElapsedTime(&t, ev[2 * (size_t)i], ev[2 * (size_t)i + 1])); ms[i] = t; }
+    return FTKX_OK;
+  };
+  const int rc = run();
+  if (rc) (void)hipStreamSynchronize(c->stream);
+  for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+  return rc;
+}
 
 // profiling aid (tools/conv_time.py): the convolution kernel `reps` times back to back, a pair of events around every launch
 int ftkx_debug_conv_relaunch(ftkx_ctx *c, int nd, const double *S, int DW, int DH, int DD, const double *weights, int ksize, double *out, int reps, double *ms)
@@ -1072,7 +1167,9 @@ static int temporal_emit(ftkx_ctx *c, const std::deque<double *> &ring, const in
   return FTKX_OK;
 }
 
-int ftkx_temporal_push(ftkx_ctx *c, const double *A, int is_vector, int on_device, int *t_emitted)
+// T: the element type of the caller's snapshot (double, or float: ftkx_temporal_push_f32); the ring holds FP64 arrays either way
+extern "C++" {
+template <class T> static int temporal_push_common(ftkx_ctx *c, const T *A, int is_vector, int on_device, int *t_emitted)
 {
   if (c) c->ahead.clear();
   if (!c) return fail(nullptr, FTKX_E_INVALID, "null context");
@@ -1095,9 +1192,7 @@ int ftkx_temporal_push(ftkx_ctx *c, const double *A, int is_vector, int on_devic
   double *slot = nullptr;
   if (int rc = take_pooled(c, count, &slot)) return rc;
   int rc = FTKX_OK;
-  if (c->smooth_ksize) rc = stage_smoothed(c, A, count, on_device, slot);
-  else if (on_device == 0) rc = upload_from_host(c, slot, A, count * sizeof(double));
-  else if (hipMemcpyAsync(slot, A, count * sizeof(double), hipMemcpyDefault, c->stream) != hipSuccess) rc = fail(c, FTKX_E_DEVICE, "ftkx_temporal_push: copy of the source failed");
+  rc = stage_into(c, A, count, on_device, c->smooth_ksize != 0, slot);      // widened where it is float32, convolved where smoothing is set
   if (rc) { (void)hipFree(slot); return rc; }      // (what the slot holds is unknown: freed, not pooled)
   // A device source has to be read before the caller may overwrite it (a host source has been staged completely by upload_from_host):
   // the call ends by waiting for THIS point of the stream, not for the stream -- sweeps queued before the push (deferred collection) and
@@ -1129,6 +1224,13 @@ int ftkx_temporal_push(ftkx_ctx *c, const double *A, int is_vector, int on_devic
   if (on_device != 0) HIP_TRY(c, hipEventSynchronize(c->tm_read));
   return FTKX_OK;
 }
+
+}  // extern "C++"
+
+int ftkx_temporal_push(ftkx_ctx *c, const double *A, int is_vector, int on_device, int *t_emitted)
+{ return temporal_push_common<double>(c, A, is_vector, on_device, t_emitted); }
+int ftkx_temporal_push_f32(ftkx_ctx *c, const float *A, int is_vector, int on_device, int *t_emitted)
+{ return temporal_push_common<float>(c, A, is_vector, on_device, t_emitted); }
 
 int ftkx_temporal_flush(ftkx_ctx *c, int *t_emitted)
 {

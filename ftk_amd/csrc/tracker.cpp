@@ -57,12 +57,19 @@ unsigned long long factor_of(double resolution, int minbits, int maxbits)
   return 1ull << std::max(minbits, std::min(nbits, maxbits));
 }
 
-// one snapshot -> one context.  kind: 0 scalar (V derived), 1 vector, 2 all three given
-int push_to(ftkx_ctx *c, int kind, int t, const double *s, const double *v, const double *j, int on_device)
+// one snapshot -> one context.  kind: 0 scalar (V derived), 1 vector, 2 all three given; f32: the arrays are floats (widened on the device)
+int push_to(ftkx_ctx *c, int kind, int t, const void *s, const void *v, const void *j, int on_device, bool f32 = false)
 {
-  if (kind == 0) return ftkx_push_scalar_slice(c, t, s, on_device);
-  if (kind == 1) return ftkx_push_slice(c, t, v, nullptr, nullptr, on_device);
-  return ftkx_push_slice(c, t, v, j, s, on_device);
+  if (f32) {
+    const float *fs = static_cast<const float *>(s), *fv = static_cast<const float *>(v), *fj = static_cast<const float *>(j);
+    if (kind == 0) return ftkx_push_scalar_slice_f32(c, t, fs, on_device);
+    if (kind == 1) return ftkx_push_slice_f32(c, t, fv, nullptr, nullptr, on_device);
+    return ftkx_push_slice_f32(c, t, fv, fj, fs, on_device);
+  }
+  const double *ds = static_cast<const double *>(s), *dv = static_cast<const double *>(v), *dj = static_cast<const double *>(j);
+  if (kind == 0) return ftkx_push_scalar_slice(c, t, ds, on_device);
+  if (kind == 1) return ftkx_push_slice(c, t, dv, nullptr, nullptr, on_device);
+  return ftkx_push_slice(c, t, dv, dj, ds, on_device);
 }
 }  // namespace
 
@@ -534,22 +541,25 @@ void critical_point_tracker_regular::reset()
 }
 
 // one snapshot -> the context(s) whose steps read it (kind: see push_to)
-void critical_point_tracker_regular::push_snapshot(int kind, const double *s, const double *v, const double *j, bool device)
+void critical_point_tracker_regular::push_snapshot(int kind, const void *s, const void *v, const void *j, bool device, bool f32)
 {
+  if (f32 && multi) throw ftkx_error(FTKX_E_UNSUPPORTED, "push: float32 snapshots with one device only (a multi-device tracker takes FP64 arrays)");
   if (temporal_smoothing_ksize) {
     // the raw snapshot feeds the filter; what the filter emits is the snapshot the tracker sees (a device source is read, not adopted)
     if (kind == 2) throw ftkx_error(FTKX_E_UNSUPPORTED, "push_field_data_snapshot: temporal smoothing takes a scalar or a vector snapshot alone");
     int t_emitted = -1;
     last_push_snapshots = 0;
-    check(ftkx_temporal_push(ctx, kind == 0 ? s : v, kind, device ? 1 : 0, &t_emitted));
+    const void *a = kind == 0 ? s : v;
+    check(f32 ? ftkx_temporal_push_f32(ctx, static_cast<const float *>(a), kind, device ? 1 : 0, &t_emitted)
+              : ftkx_temporal_push(ctx, static_cast<const double *>(a), kind, device ? 1 : 0, &t_emitted));
     take_emitted(t_emitted);
     return;
   }
   last_push_snapshots = 1;
   const int t = next_push_timestep;
   if (slab && (t < slab_t0 || t >= slab_t1)) throw ftkx_error(FTKX_E_INVALID, "slab mode: timestep " + std::to_string(t) + " is not in this rank's slab [" + std::to_string(slab_t0) + ", " + std::to_string(slab_t1) + ")");
-  if (multi) multi->push(kind, t, s, v, j, device);
-  else check(push_to(ctx, kind, t, s, v, j, device ? 1 : 0));
+  if (multi) multi->push(kind, t, static_cast<const double *>(s), static_cast<const double *>(v), static_cast<const double *>(j), device);
+  else check(push_to(ctx, kind, t, s, v, j, device ? 1 : 0, f32));
   field_data_snapshots.push_back(t);
   next_push_timestep ++;
 }
@@ -573,26 +583,33 @@ bool critical_point_tracker_regular::flush_temporal_smoothing()
   return t_emitted >= 0;
 }
 
-void critical_point_tracker_regular::push_scalar_field_snapshot(const double *s, bool device)
+void critical_point_tracker_regular::push_scalar(const void *s, bool device, bool f32)
 {
   if (!initialized) throw ftkx_error(FTKX_E_INVALID, "push: initialize() first");
   if (vector_field_source != SOURCE_DERIVED) throw ftkx_error(FTKX_E_INVALID, "push_scalar_field_snapshot: vector_field_source must be SOURCE_DERIVED");
-  push_snapshot(0, s, nullptr, nullptr, device);            // V = gradientND(s) on the device
+  push_snapshot(0, s, nullptr, nullptr, device, f32);       // V = gradientND(s) on the device
 }
 
-void critical_point_tracker_regular::push_vector_field_snapshot(const double *v, bool device)
+void critical_point_tracker_regular::push_vector(const void *v, bool device, bool f32)
 {
   if (!initialized) throw ftkx_error(FTKX_E_INVALID, "push: initialize() first");
   if (spatial_smoothing_ksize) throw ftkx_error(FTKX_E_UNSUPPORTED, "push_vector_field_snapshot: spatial smoothing takes scalar snapshots only");
-  push_snapshot(1, nullptr, v, nullptr, device);            // J derived at hits when jacobian_field_source == SOURCE_DERIVED
+  push_snapshot(1, nullptr, v, nullptr, device, f32);       // J derived at hits when jacobian_field_source == SOURCE_DERIVED
 }
 
-void critical_point_tracker_regular::push_field_data_snapshot(const double *s, const double *v, const double *j, bool device)
+void critical_point_tracker_regular::push_field_data(const void *s, const void *v, const void *j, bool device, bool f32)
 {
   if (!initialized) throw ftkx_error(FTKX_E_INVALID, "push: initialize() first");
   if (spatial_smoothing_ksize) throw ftkx_error(FTKX_E_UNSUPPORTED, "push_field_data_snapshot: spatial smoothing takes scalar snapshots only");
-  push_snapshot(2, s, v, j, device);
+  push_snapshot(2, s, v, j, device, f32);
 }
+
+void critical_point_tracker_regular::push_scalar_field_snapshot(const double *s, bool device) { push_scalar(s, device, false); }
+void critical_point_tracker_regular::push_vector_field_snapshot(const double *v, bool device) { push_vector(v, device, false); }
+void critical_point_tracker_regular::push_field_data_snapshot(const double *s, const double *v, const double *j, bool device) { push_field_data(s, v, j, device, false); }
+void critical_point_tracker_regular::push_scalar_field_snapshot(const float *s, bool device) { push_scalar(s, device, true); }
+void critical_point_tracker_regular::push_vector_field_snapshot(const float *v, bool device) { push_vector(v, device, true); }
+void critical_point_tracker_regular::push_field_data_snapshot(const float *s, const float *v, const float *j, bool device) { push_field_data(s, v, j, device, true); }
 
 bool critical_point_tracker_regular::pop_field_data_snapshot()
 {
@@ -1033,6 +1050,10 @@ int ftkx_tracker_initialize(ftkx_tracker *h) { return guarded(h, [&] { h->t->ini
 int ftkx_tracker_push_scalar_field_snapshot(ftkx_tracker *h, const double *s, int dev) { return guarded(h, [&] { h->t->push_scalar_field_snapshot(s, dev != 0); }); }
 int ftkx_tracker_push_vector_field_snapshot(ftkx_tracker *h, const double *v, int dev) { return guarded(h, [&] { h->t->push_vector_field_snapshot(v, dev != 0); }); }
 int ftkx_tracker_push_field_data_snapshot(ftkx_tracker *h, const double *s, const double *v, const double *j, int dev)
+{ return guarded(h, [&] { h->t->push_field_data_snapshot(s, v, j, dev != 0); }); }
+int ftkx_tracker_push_scalar_field_snapshot_f32(ftkx_tracker *h, const float *s, int dev) { return guarded(h, [&] { h->t->push_scalar_field_snapshot(s, dev != 0); }); }
+int ftkx_tracker_push_vector_field_snapshot_f32(ftkx_tracker *h, const float *v, int dev) { return guarded(h, [&] { h->t->push_vector_field_snapshot(v, dev != 0); }); }
+int ftkx_tracker_push_field_data_snapshot_f32(ftkx_tracker *h, const float *s, const float *v, const float *j, int dev)
 { return guarded(h, [&] { h->t->push_field_data_snapshot(s, v, j, dev != 0); }); }
 int ftkx_tracker_advance_timestep(ftkx_tracker *h) { return guarded(h, [&] { h->t->advance_timestep(); }); }
 int ftkx_tracker_update_timestep(ftkx_tracker *h) { return guarded(h, [&] { h->t->update_timestep(); }); }

@@ -491,6 +491,31 @@ int ftkx_temporal_flush(ftkx_ctx *ctx, int *t_emitted);
  * a pair of events around every launch; ms: reps device times. */
 int ftkx_debug_temporal_relaunch(ftkx_ctx *ctx, const double *const *arrays, int ksize, const double *weights, size_t count, double *out, int reps, double *ms);
 
+/* ---- float32 snapshots (the stream's "format": "float32"; ndarray::from_array, ndarray.hh:403-410) ---- */
+/* The reference reads a float32 file into an ndarray<float> and widens it on the host, p[i] = static_cast<double>(a[i]).  Here the floats
+ * go to the device as they are -- 4 bytes per value over PCIe -- and are widened there, in front of everything else: the resident slice is
+ * FP64, and from there on a slice that arrived as float32 cannot be told apart from one that arrived as the widened doubles.  Widening is
+ * exact (subnormal floats become normal doubles, -0.0f becomes -0.0, a NaN stays a NaN with its sign), so every entry below gives, byte for
+ * byte, what its FP64 counterpart gives for the widened array.  Checks, error codes and refusals are the counterpart's.  float32 and FP64
+ * pushes may be mixed in one context.
+ * on_device: 0 host memory, uploaded as floats; 2 device memory of any device, copied; 1 device memory of this context's device, READ where
+ * it lies and never adopted -- the call returns once it has been read.  In all three the caller may overwrite its array on return.
+ * Where spatial smoothing is set the convolution reads the floats itself: one kernel, float source to smoothed FP64 slice. */
+int ftkx_push_scalar_slice_f32(ftkx_ctx *ctx, int t, const float *S, int on_device);
+int ftkx_push_slice_f32(ftkx_ctx *ctx, int t, const float *V, const float *J, const float *S, int on_device);
+int ftkx_temporal_push_f32(ftkx_ctx *ctx, const float *A, int is_vector, int on_device, int *t_emitted);
+/* src: `count` floats, dst: `count` doubles, DEVICE pointers that do not overlap; src a multiple of 4 bytes, dst of 8 (16-byte accesses are
+ * used where both can be brought to 16 by the same 0-3 leading elements).  The call returns when `dst` is complete. */
+int ftkx_widen_f32(ftkx_ctx *ctx, const float *src, size_t count, double *dst);
+/* ftkx_conv2D / ftkx_conv3D from a float32 source: what they give for the widened array */
+int ftkx_conv2D_f32(ftkx_ctx *ctx, const float *S, int DW, int DH, const double *weights, int ksize, double *out);
+int ftkx_conv3D_f32(ftkx_ctx *ctx, const float *S, int DW, int DH, int DD, const double *weights, int ksize, double *out);
+/* profiling aid (tools/push_f32_time.py): the kernel of ftkx_widen_f32 launched `reps` times back to back on the context's stream, a pair of
+ * events around every launch; ms: reps device times. */
+int ftkx_debug_widen_relaunch(ftkx_ctx *ctx, const float *src, size_t count, double *dst, int reps, double *ms);
+/* how many float32 arrays this context was pushed went through the widen kernel, and how many straight through the convolution */
+int ftkx_debug_f32_counts(const ftkx_ctx *ctx, unsigned long long *widened, unsigned long long *convolved_direct);
+
 /* profiling aid: streams `bytes` of device memory with the mask kernel's load shape (16 B per lane) and nothing else, so that
  * rocprofv3's FETCH_SIZE can be calibrated on a known byte count (tools/calibrate_fetch.py) */
 int ftkx_debug_stream_read(ftkx_ctx *ctx, const void *device_ptr, size_t bytes);

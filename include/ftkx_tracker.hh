@@ -196,6 +196,12 @@ public:
   void push_scalar_field_snapshot(const double *scalar, bool device = false);               // 2d:238-250, 3d:125-137
   void push_vector_field_snapshot(const double *vector, bool device = false);               // 2d:252-261, 3d:139-148
   void push_field_data_snapshot(const double *scalar, const double *vector, const double *jacobian, bool device = false);  // critical_point_tracker.hh:137-140
+  // float32 snapshots (the stream's "format": "float32"): the floats go to the device as they are and are widened there, exactly (ftkx.h:
+  // ftkx_push_scalar_slice_f32); the tracker gives what it gives for the widened arrays.  A device pointer is read before the call returns,
+  // never borrowed.  One device (slab ranks included); a multi-device tracker throws FTKX_E_UNSUPPORTED.
+  void push_scalar_field_snapshot(const float *scalar, bool device = false);
+  void push_vector_field_snapshot(const float *vector, bool device = false);
+  void push_field_data_snapshot(const float *scalar, const float *vector, const float *jacobian, bool device = false);
   bool pop_field_data_snapshot();
 
   bool advance_timestep();                                  // critical_point_tracker.hh:841-848
@@ -265,7 +271,10 @@ protected:
   std::vector<int> field_data_snapshots;                    // timesteps resident on the device (<= 2, a deque in the reference)
   int next_push_timestep = 0;
   void take_emitted(int t);                                 // temporal smoothing: the filter's emission t (-1: none) joins field_data_snapshots
-  void push_snapshot(int kind, const double *s, const double *v, const double *j, bool device);   // behind the three push_* methods: one snapshot -> the context(s) that read it
+  void push_snapshot(int kind, const void *s, const void *v, const void *j, bool device, bool f32);   // behind the push_* methods: one snapshot (f32: of floats) -> the context(s) that read it
+  void push_scalar(const void *s, bool device, bool f32);                                          // the push_* methods' checks, in front of push_snapshot
+  void push_vector(const void *v, bool device, bool f32);
+  void push_field_data(const void *s, const void *v, const void *j, bool device, bool f32);
   double vector_field_resolution = std::numeric_limits<double>::max();   // sticky running minimum (never reset)
   unsigned long long vector_field_scaling_factor = 1;
   ftkx_stats last_stats;
@@ -390,6 +399,9 @@ int  ftkx_tracker_initialize(ftkx_tracker *);
 int  ftkx_tracker_push_scalar_field_snapshot(ftkx_tracker *, const double *s, int on_device);
 int  ftkx_tracker_push_vector_field_snapshot(ftkx_tracker *, const double *v, int on_device);
 int  ftkx_tracker_push_field_data_snapshot(ftkx_tracker *, const double *s, const double *v, const double *j, int on_device);
+int  ftkx_tracker_push_scalar_field_snapshot_f32(ftkx_tracker *, const float *s, int on_device);   /* float32 snapshots, widened on the device */
+int  ftkx_tracker_push_vector_field_snapshot_f32(ftkx_tracker *, const float *v, int on_device);
+int  ftkx_tracker_push_field_data_snapshot_f32(ftkx_tracker *, const float *s, const float *v, const float *j, int on_device);
 int  ftkx_tracker_advance_timestep(ftkx_tracker *);
 int  ftkx_tracker_update_timestep(ftkx_tracker *);
 int  ftkx_tracker_num_critical_points(const ftkx_tracker *, size_t *n);
