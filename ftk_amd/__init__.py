@@ -363,6 +363,20 @@ class Context:
         st = C.c_ulonglong()
         return int(self._L.ftkx_series_last_path(self._h, C.byref(st))), int(st.value)
 
+    def series_order(self):
+        """ftkx_debug_series_order: {"nbins", "shift", "fullest", "rank_max"} of the ordering step of the series pass completed last (all
+        zero where its records did not come through the bucket chain)"""
+        o = (C.c_ulonglong * 4)()
+        self._ck(self._L.ftkx_debug_series_order(self._h, o))
+        return dict(nbins=int(o[0]), shift=int(o[1]), fullest=int(o[2]), rank_max=int(o[3]))
+
+    def debug_sort_records(self, recs, key_bits):
+        """ftkx_debug_sort_records: CP_DTYPE records through the host-driven batch's device sort (tags below 2 ** key_bits) -> a new array"""
+        recs = np.ascontiguousarray(recs, dtype=CP_DTYPE)
+        out = np.empty_like(recs)
+        self._ck(self._L.ftkx_debug_sort_records(self._h, recs.ctypes.data, len(recs), int(key_bits), out.ctypes.data))
+        return out
+
     def trace_last_path(self):
         """which way the last trace on this context went: 0 host, 1 device phases + host walks (ftkx_trace_curves_ctx), 2 all on the
         device (ftkx_trace_curves_device)"""

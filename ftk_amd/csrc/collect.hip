@@ -519,6 +519,26 @@ int ftkx_sweep_cancel(ftkx_ctx *c)
   return FTKX_OK;
 }
 
+// test aid: the host-driven batch's ordering step on records of the caller's -- into the hit buffer, through sort_hits_on_device as
+// ftkx_sweep_collect calls it, out of d_sorted
+int ftkx_debug_sort_records(ftkx_ctx *c, const ftkx_cp_t *in, size_t n, int key_bits, ftkx_cp_t *out)
+{
+  if (!c) return fail(nullptr, FTKX_E_INVALID, "null context");
+  if (key_bits < 1 || key_bits > 64) return fail(c, FTKX_E_INVALID, "ftkx_debug_sort_records: key_bits %d (1 .. 64)", key_bits);
+  if (n == 0) return FTKX_OK;
+  if (!in || !out) return fail(c, FTKX_E_INVALID, "ftkx_debug_sort_records: null argument");
+  if (!c->pending.empty() || c->sr_open) return fail(c, FTKX_E_INVALID, "ftkx_debug_sort_records: sweeps pending or series passes open, collect them first");
+  HIP_TRY(c, hipSetDevice(c->device));
+  int rc;
+  if (n > c->capacity && (rc = ensure_hit_buffer(c, n))) return rc;
+  c->ahead.clear(); c->announced.clear();                    // (a cull queued ahead counted on the buffers as they were)
+  HIP_TRY(c, hipMemcpyAsync(c->d_hits.as<ftkx_cp_t>(), in, n * sizeof(ftkx_cp_t), hipMemcpyHostToDevice, c->stream));
+  if ((rc = sort_hits_on_device(c, n, key_bits))) return rc;
+  HIP_TRY(c, hipMemcpyAsync(out, c->d_sorted.as<ftkx_cp_t>(), n * sizeof(ftkx_cp_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return FTKX_OK;
+}
+
 int ftkx_sweep(ftkx_ctx *c, int t, int scope, unsigned long long factor, const ftkx_cp_t **out, size_t *n_out)
 {
   if (!c) return fail(nullptr, FTKX_E_INVALID, "null context");

@@ -66,7 +66,7 @@ void launch_series_one(const Mesh &m, const OneArgs &a, int nwg, hipStream_t st)
 void launch_series_tail_begin(u64 *counters, unsigned *hist, size_t nbins, u64 *results, size_t nresults, hipStream_t st);
 void launch_series_factors(Fields *steps, int nsteps, const SeriesSlice *slices, int nslices, const SeriesStep *sinfo, const u64 *red, double running_in, const u64 *running_from,
                            double safe_m, u64 *results, u64 *counters, hipStream_t st);
-void launch_bucket_rank(const Mesh &m, const u64 *bucketed, const unsigned *boff, u64 *sorted, u64 *results, hipStream_t st, int few_wgs = 0);
+unsigned launch_bucket_rank(const Mesh &m, const u64 *bucketed, const unsigned *boff, u64 *sorted, u64 *results, hipStream_t st, int few_wgs = 0);   // -> the rank_max it was launched with
 void launch_bucket_scan(unsigned *hist, unsigned *boff, unsigned nbins, u64 *counters, hipStream_t st, bool small_wg = false);
 void launch_bucket_scatter(const Mesh &m, unsigned *boff, u64 *bucketed, hipStream_t st, int few_wgs = 0);
 void launch_series_records(const Mesh &m, const Fields *d_fields, const u64 *sorted, ftkx_cp_t *out, hipStream_t st, bool lean = false);
@@ -221,6 +221,7 @@ struct ftkx_series_buffers {
   ftkx_block results;                                  // u64: the device block
   ftkx_block h_results{FTKX_BLOCK_PINNED_COHERENT};    // u64: its pinned copy; the last 8 words are the flag words (series.hip: series_flag)
   unsigned seq = 0;
+  unsigned rank_max = 0;                               // what the rank kernel of the pass on these buffers was launched with (launch_bucket_rank)
   ftkx_block out{FTKX_BLOCK_PINNED_COHERENT};          // ftkx_cp_t: the records as the caller reads them (kind: series.hip, ensure_series_buffers)
   ftkx_block d_out;                                    // ftkx_cp_t: the records of a pass whose way over PCIe is left to the copy kernel on its own stream
   ftkx_block copy_done;                                // unsigned: that kernel's workgroup counter
@@ -375,6 +376,7 @@ struct ftkx_ctx {
   int sr_last_path = 0;              // which way the last ftkx_sweep_series went: 0 the host-driven batch, 1 device-driven (the kernel chain), 2 early single-workgroup tail,
                                      // 4 the one-launch pass, 5 a split pass
   unsigned long long sr_last_status = 0;
+  unsigned long long sr_last_order[4] = {0, 0, 0, 0};   // ftkx_debug_series_order: nbins, shift, fullest bucket, rank_max of the pass completed last (zero: not through the bucket chain)
   ftkx_pass2_state p2;
   ftkx_stats stats;
   // optional kernel timing (hipEvents on the context's stream)

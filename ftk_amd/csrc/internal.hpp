@@ -11,7 +11,9 @@ void set_global_error(const char *msg);
 #include "../../include/ftkx.h"
 namespace ftkx {
 // The library's test hooks come in two families, one environment variable each, "name=value,name=value" (DESIGN.md section 8):
-// FTKX_SERIES_HOOKS (small, short, fold, split, one, rank_max: which forms of the device-driven pass are taken) and FTKX_MASK_PLAN (swizzle,
+// FTKX_SERIES_HOOKS (small, short, fold, split, one: which forms of the device-driven pass are taken; rank_max=N: buckets of the ordering
+// step fuller than N are left to the host; bins=K: 2^K buckets, 0 .. 16, in place of the 2^14 -- 2^10 in a sparse split pass -- that
+// series_bucket_geometry spreads the keys over, so that a small series fills its buckets like a large one) and FTKX_MASK_PLAN (swizzle,
 // yg, zchunk, lmin, lcap, order, rows, lean: launch geometry of the mask kernels; parsed by read_mask_hooks, mask_plan.hpp).  Read at every use: tests switch them
 // inside one process.  env_hook reads one knob of the first family.
 inline long env_hook(const char *var, const char *name, long dflt)

@@ -14,6 +14,7 @@
 #include <chrono>
 #include "ctx.hpp"
 #include "cp_device.hpp"   // classify3 on the HOST (fragile 3D records)
+#include "series_order.hpp"   // the bucket geometry and the repair of unranked buckets: host code, tested without a GPU
 
 using namespace ftkxh;
 
@@ -234,7 +235,7 @@ void series_queue_rest(ftkx_ctx *c, const ftkx_series_pending &P, const Mesh &m,
   ftkx::launch_exact(m, d_steps, 0, T.list.as<u64>(), T.list_capacity, st, few ? 64 : 0);
   ftkx::launch_bucket_scan(T.hist.as<unsigned>(), T.boff.as<unsigned>(), (unsigned)P.nbins, T.counters.as<u64>(), st, P.split);
   ftkx::launch_bucket_scatter(m, T.boff.as<unsigned>(), T.bucketed.as<u64>(), st, few ? 16 : 0);
-  ftkx::launch_bucket_rank(m, T.bucketed.as<u64>(), T.boff.as<unsigned>(), T.sorted.as<u64>(), B.results.as<u64>(), st, few ? 16 : 0);
+  B.rank_max = ftkx::launch_bucket_rank(m, T.bucketed.as<u64>(), T.boff.as<unsigned>(), T.sorted.as<u64>(), B.results.as<u64>(), st, few ? 16 : 0);
   if (B.copy_out) { (void)hipStreamWaitEvent(st, B.ev_copied, 0); B.copy_out = false; }   // (the copy of the pass that used these buffers last: long through)
   ftkx::launch_series_records(m, d_steps, T.sorted.as<u64>(), P.to_device ? B.d_out.as<ftkx_cp_t>() : B.out.as<ftkx_cp_t>(), st, P.split);
   if (!P.split) ev_end(c);
@@ -467,15 +468,16 @@ void series_retire_masks(const ftkx_series_pending &P, const std::vector<Slice *
 // one-workgroup kernel (18 us over 2^16 of them), the ranking inside a bucket costs next to nothing more with four records than with one
 constexpr int kBinsLog2 = 14;
 
-// order key -> bucket (P.shift), and how many buckets that makes over the keys this pass can produce (P.nbins)
+static_assert((1 << ftkxh::kSeriesMaxBinsLog2) == ftkx::kSeriesMaxBins, "series_order.hpp clamps to what the scan kernel and the bins' buffers take");
+
+// order key -> bucket (P.shift), and how many buckets that makes over the keys this pass can produce (P.nbins): series_order.hpp
 void series_bucket_geometry(ftkx_series_pending &P)
 {
-  const u64 max_key = (u64)P.n * P.cells * 64ull;
-  int key_bits = 1;
-  while (key_bits < 63 && (1ull << key_bits) < max_key) key_bits ++;
   // (a split pass: few records, and its scan -- one workgroup of four wavefronts next to a mask kernel -- pays several us per round of loads: 2^10)
-  P.shift = std::max(0, key_bits - (P.split_sparse ? 10 : kBinsLog2));
-  P.nbins = (size_t)((max_key - 1) >> P.shift) + 1;
+  // (FTKX_SERIES_HOOKS bins=K, tests: 2^K buckets whichever form the pass takes, so that small series fill buckets the way large ones do)
+  const int bins_log2 = (int)std::max(0l, std::min<long>(ftkx::env_hook("FTKX_SERIES_HOOKS", "bins", P.split_sparse ? 10 : kBinsLog2), ftkxh::kSeriesMaxBinsLog2));
+  const ftkxh::bucket_geometry g = ftkxh::series_bucket_geometry((u64)P.n, P.cells, bins_log2);
+  P.shift = g.shift; P.nbins = g.nbins;
 }
 
 // what a split pass, or a pass behind one, needs beyond its buffers: the tail streams and events, and which tail set it works on (P.tail_set,
@@ -768,6 +770,7 @@ int series_complete(ftkx_ctx *c, ftkx_series_pending &P, double *running_resolut
   const int nd = c->nd, n = P.n;
   const size_t k = P.k;
   P.open = false;
+  memset(c->sr_last_order, 0, sizeof(c->sr_last_order));      // (ftkx_debug_series_order: zero unless this pass's records came through the bucket chain)
   double running = *running_resolution;                       // (what the pass started from: the host-driven batch, if it comes to that, starts there too)
   // (the split pass's self-check samples the time between two completions by the plain way out of this function: any other way out breaks the chain)
   const double last_complete_s = c->sr_last_complete_s;
@@ -879,6 +882,10 @@ int series_complete(ftkx_ctx *c, ftkx_series_pending &P, double *running_resolut
     return rc;
   }
   c->sr_last_path = (status & ftkx::SERIES_ONE) ? 4 : P.split ? 5 : (status & ftkx::SERIES_EARLY) ? 2 : 1;
+  if (!(status & (ftkx::SERIES_ONE | ftkx::SERIES_EARLY))) {
+    const unsigned long long order[4] = {(unsigned long long)P.nbins, (unsigned long long)P.shift, R[ftkx::SR_COUNTERS + ftkx::CNT_BUCKET_MAX], B.rank_max};
+    memcpy(c->sr_last_order, order, sizeof(order));
+  }
   {
     // the split pass's self-check: the time since the last completion is a sample of this pass's form if the pipeline was full all the while
     // (another pass is open now and one was when the last one completed) and the last completion was of the same form
@@ -930,25 +937,8 @@ int series_complete(ftkx_ctx *c, ftkx_series_pending &P, double *running_resolut
     if (e[0] < nrec) H[e[0]].type = (unsigned)ftkx::classify3(A, c->opt.jacobian_symmetric != 0);
   }
   c->stats.reclassified = nf;
-  if (status & ftkx::SERIES_FIX_ORDER) {
-    // A bucket too full to rank on the device: its records sit in their own run of the output, unordered among themselves; everything
-    // before the run is smaller, everything behind it larger.  Find each such run from an inversion, widen it until both ends are in
-    // order with their neighbours, sort it.
-    auto less = [](const ftkx_cp_t &p, const ftkx_cp_t &q) { return p.tag < q.tag; };
-    ftkx_cp_t *h = H;
-    for (size_t a = 0; a + 1 < nrec; a ++) {
-      if (h[a].tag <= h[a + 1].tag) continue;
-      size_t lo = a, hi = a + 2;
-      unsigned long long mn = std::min(h[a].tag, h[a + 1].tag), mx = std::max(h[a].tag, h[a + 1].tag);
-      for (bool grown = true; grown;) {
-        grown = false;
-        while (lo > 0 && h[lo - 1].tag > mn) { lo --; mn = std::min(mn, h[lo].tag); mx = std::max(mx, h[lo].tag); grown = true; }
-        while (hi < nrec && h[hi].tag < mx) { mn = std::min(mn, h[hi].tag); mx = std::max(mx, h[hi].tag); hi ++; grown = true; }
-      }
-      std::sort(h + lo, h + hi, less);
-      a = hi - 2;                                            // (the loop's increment moves on to the run's last element)
-    }
-  }
+  // (a bucket too full to rank on the device: its records are unordered among themselves -- series_order.hpp)
+  if (status & ftkx::SERIES_FIX_ORDER) ftkxh::series_fix_order(H, nrec);
   double run;
   memcpy(&run, &R[ftkx::SR_RUNNING], 8);
   *running_resolution = run;
@@ -1242,6 +1232,13 @@ int ftkx_series_split_decision(const ftkx_ctx *c, int *state, double *median_in_
   if (state) *state = ftkxh::split_state(K, c->sr_split_forced);
   if (median_in_order_ms) *median_in_order_ms = K.median_order * 1e3;
   if (median_split_ms) *median_split_ms = K.median_split * 1e3;
+  return FTKX_OK;
+}
+
+int ftkx_debug_series_order(const ftkx_ctx *c, unsigned long long out[4])
+{
+  if (!c || !out) return fail(nullptr, FTKX_E_INVALID, "ftkx_debug_series_order: null argument");
+  memcpy(out, c->sr_last_order, sizeof(c->sr_last_order));
   return FTKX_OK;
 }
 

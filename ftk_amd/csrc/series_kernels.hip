@@ -825,11 +825,11 @@ void launch_bucket_scan(unsigned *hist, unsigned *boff, unsigned nbins, u64 *cou
 void launch_bucket_scatter(const Mesh &m, unsigned *boff, u64 *bucketed, hipStream_t st, int few_wgs)
 { hipLaunchKernelGGL(bucket_scatter_kernel, dim3(few_wgs > 0 ? (unsigned)few_wgs : 256u), dim3(256), 0, st, m.pass, m.capacity, boff, m.hist, m.hist_shift, m.core_cells, bucketed, m.counters); }
 
-void launch_bucket_rank(const Mesh &m, const u64 *bucketed, const unsigned *boff, u64 *sorted, u64 *results, hipStream_t st, int few_wgs)
+unsigned launch_bucket_rank(const Mesh &m, const u64 *bucketed, const unsigned *boff, u64 *sorted, u64 *results, hipStream_t st, int few_wgs)
 {
-  unsigned rank_max = 4096;
-  rank_max = (unsigned)env_hook("FTKX_SERIES_HOOKS", "rank_max", 4096);
+  const unsigned rank_max = (unsigned)env_hook("FTKX_SERIES_HOOKS", "rank_max", 4096);
   hipLaunchKernelGGL(bucket_rank_kernel, dim3(few_wgs > 0 ? (unsigned)few_wgs : 256u), dim3(256), 0, st, bucketed, m.capacity, boff, m.hist_shift, rank_max, sorted, m.counters, results);
+  return rank_max;
 }
 
 void launch_series_records(const Mesh &m, const Fields *d_fields, const u64 *sorted, ftkx_cp_t *out, hipStream_t st, bool lean)

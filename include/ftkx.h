@@ -516,6 +516,16 @@ int ftkx_debug_widen_relaunch(ftkx_ctx *ctx, const float *src, size_t count, dou
 /* how many float32 arrays this context was pushed went through the widen kernel, and how many straight through the convolution */
 int ftkx_debug_f32_counts(const ftkx_ctx *ctx, unsigned long long *widened, unsigned long long *convolved_direct);
 
+/* test aid: the ordering step of the device-driven pass completed last on this context (ftkx_sweep_series, ftkx_sweep_series_complete), as
+ * it ran: out[0] the number of buckets, out[1] the shift that takes an order key to its bucket, out[2] the fullest bucket, out[3] the
+ * size up to which a bucket was ranked on the device (fuller ones: the host orders them, status bit 16).  All zero where the pass's records
+ * did not come through the bucket chain (ftkx_series_last_path 0, 2, 4).  Reads the context, changes nothing. */
+int ftkx_debug_series_order(const ftkx_ctx *ctx, unsigned long long out[4]);
+/* test aid: the host-driven batch's ordering step (the radix sort behind ftkx_sweep_collect for 4 096 records and more) on `n` records of
+ * the caller's, whatever their number: in -> the context's hit buffer -> the sort -> out, both host memory.  key_bits: 1 .. 64, every
+ * tag below 2^key_bits.  Equal tags keep their order.  Not while sweeps are pending or series passes are open. */
+int ftkx_debug_sort_records(ftkx_ctx *ctx, const ftkx_cp_t *in, size_t n, int key_bits, ftkx_cp_t *out);
+
 /* profiling aid: streams `bytes` of device memory with the mask kernel's load shape (16 B per lane) and nothing else, so that
  * rocprofv3's FETCH_SIZE can be calibrated on a known byte count (tools/calibrate_fetch.py) */
 int ftkx_debug_stream_read(ftkx_ctx *ctx, const void *device_ptr, size_t bytes);
