@@ -494,6 +494,13 @@ class Context:
         self._ck(self._L.ftkx_debug_f32_counts(self._h, C.byref(a), C.byref(b)))
         return int(a.value), int(b.value)
 
+    def array_counts(self):
+        """(allocated, pooled), each a tuple (field, mask, summary): slice arrays this context has had to allocate since it was made, and
+        those that lie in its pool right now"""
+        a = (C.c_ulonglong * 3)(); p = (C.c_ulonglong * 3)()
+        self._ck(self._L.ftkx_debug_array_counts(self._h, a, p))
+        return tuple(int(v) for v in a), tuple(int(v) for v in p)
+
     def debug_conv_relaunch(self, S_ptr, dims, weights, ksize, out_ptr, reps):
         """profiling aid: the convolution kernel `reps` times back to back -> device ms per launch (HIP events)"""
         w = np.ascontiguousarray(weights, dtype=np.float64)

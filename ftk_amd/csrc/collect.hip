@@ -197,8 +197,8 @@ int run_batch(ftkx_ctx *c, const double *sparse_field, bool cull_done)
     Slice *s1 = (r.scope & FTKX_SCOPE_INTERVAL) ? &c->slices[r.t + 1] : nullptr;
     Fields f;
     memset(&f, 0, sizeof(f));
-    f.S[0] = s0.S; f.V[0] = s0.V; f.J[0] = s0.J;
-    if (s1) { f.S[1] = s1->S; f.V[1] = s1->V; f.J[1] = s1->J; }
+    f.S[0] = s0.S.as<double>(); f.V[0] = s0.V.as<double>(); f.J[0] = s0.J.as<double>();
+    if (s1) { f.S[1] = s1->S.as<double>(); f.V[1] = s1->V.as<double>(); f.J[1] = s1->J.as<double>(); }
     f.factor = (double)r.factor; f.t = r.t; f.scope_mask = r.scope;
     if (r.mode == MODE_FAST) {
       for (Slice *s : {&s0, s1}) {
@@ -209,16 +209,16 @@ int run_batch(ftkx_ctx *c, const double *sparse_field, bool cull_done)
         if (rc) return rc;
         // masks of this slice already (re)built or used in the current sub-batch under another factor -> close it
         bool touched = false;
-        for (const MaskJob &j : subs.back().jobs) touched = touched || j.M == s->M;
-        for (const Fields &g : subs.back().steps) touched = touched || g.M[0] == s->M || g.M[1] == s->M;
+        for (const MaskJob &j : subs.back().jobs) touched = touched || j.M == s->M.p;
+        for (const Fields &g : subs.back().steps) touched = touched || g.M[0] == s->M.p || g.M[1] == s->M.p;
         if (touched) subs.emplace_back();
         bool rule_on;
         const double big = job_big(c, *s, r.factor, &rule_on);
-        subs.back().jobs.push_back(with_lean_thresholds(MaskJob{s->S, s->V, s->M, two_level ? s->U : nullptr, nullptr, 1.0 / (double)r.factor, big}, m));
+        subs.back().jobs.push_back(with_lean_thresholds(MaskJob{s->S.as<double>(), s->V.as<double>(), s->M.as<unsigned char>(), two_level ? s->U.as<unsigned char>() : nullptr, nullptr, 1.0 / (double)r.factor, big}, m));
         s->mask_factor = r.factor; s->mask_big = rule_on; s->u_rows = m.u_rows;
       }
-      f.M[0] = s0.M; f.M[1] = s1 ? s1->M : nullptr;
-      f.U[0] = two_level ? s0.U : nullptr; f.U[1] = (two_level && s1) ? s1->U : nullptr;
+      f.M[0] = s0.M.as<unsigned char>(); f.M[1] = s1 ? s1->M.as<unsigned char>() : nullptr;
+      f.U[0] = two_level ? s0.U.as<unsigned char>() : nullptr; f.U[1] = (two_level && s1) ? s1->U.as<unsigned char>() : nullptr;
       subs.back().steps.push_back(f);
     } else {
       TileParams p;
@@ -321,10 +321,10 @@ bool ahead_serves_pending(const ftkx_ctx *c, const Mesh &m, bool two_level)
     const ftkx_ctx::AheadStep &a = c->ahead[i];
     if (r.t != a.t || r.scope != a.scope || r.mode != MODE_FAST) return false;
     auto s0 = c->slices.find(r.t);
-    if (s0 == c->slices.end() || s0->second.M != a.M[0] || (two_level ? s0->second.U : nullptr) != a.U[0] || !masks_valid(c, s0->second, r.factor, two_level, m.u_rows)) return false;
+    if (s0 == c->slices.end() || s0->second.M.p != a.M[0] || (two_level ? s0->second.U.p : nullptr) != a.U[0] || !masks_valid(c, s0->second, r.factor, two_level, m.u_rows)) return false;
     if (r.scope & FTKX_SCOPE_INTERVAL) {
       auto s1 = c->slices.find(r.t + 1);
-      if (s1 == c->slices.end() || s1->second.M != a.M[1] || (two_level ? s1->second.U : nullptr) != a.U[1] || !masks_valid(c, s1->second, r.factor, two_level, m.u_rows)) return false;
+      if (s1 == c->slices.end() || s1->second.M.p != a.M[1] || (two_level ? s1->second.U.p : nullptr) != a.U[1] || !masks_valid(c, s1->second, r.factor, two_level, m.u_rows)) return false;
     }
   }
   return true;
@@ -351,7 +351,7 @@ int ftkx_sweep_enqueue(ftkx_ctx *c, int t, int scope, unsigned long long factor)
     if (it1 == c->slices.end()) return fail(c, FTKX_E_NOSLICE, "sweep: interval [%d, %d] needs slice %d", t, t + 1, t + 1);
     s1 = &it1->second;
   }
-  if (s1 && ((s0->J == nullptr) != (s1->J == nullptr) || (s0->S == nullptr) != (s1->S == nullptr)))
+  if (s1 && ((s0->J.p == nullptr) != (s1->J.p == nullptr) || (s0->S.p == nullptr) != (s1->S.p == nullptr)))
     return fail(c, FTKX_E_INVALID, "sweep: slices %d and %d disagree on which of J / S are given", t, t + 1);
   // coordinate arrays are indexed by vertex coordinates: they must cover the vertex box
   if (c->opt.coords_mode == 2)

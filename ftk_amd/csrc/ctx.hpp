@@ -144,11 +144,10 @@ inline MaskJob with_lean_thresholds(MaskJob j, const Mesh &m)
   return j;
 }
 
-struct Slice {
-  double *V = nullptr, *J = nullptr, *S = nullptr;
-  unsigned char *M = nullptr;       // vertex sign masks, built lazily for `mask_factor`
-  unsigned char *U = nullptr;       // per-8-vertex summaries of M (two-level cull)
-  bool ownV = false, ownJ = false, ownS = false;
+struct Slice {                      // move-only: it owns its arrays
+  ftkx_block V, J, S;               // double: out of the context's pool (class field), or lent by the caller (ftkx_block::lent)
+  ftkx_block M;                     // unsigned char: vertex sign masks, built lazily for `mask_factor`
+  ftkx_block U;                     // unsigned char: per-8-vertex summaries of M (two-level cull)
   unsigned long long mask_factor = 0;   // the (power-of-two) factor M / U were built under; 0 = not built
   int u_rows = 1;                   // rows a byte of U stands for (Mesh::u_rows at the time the masks were built)
   bool mask_big = false;            // built with the per-vertex overflow rule of that factor (MaskJob::big finite)
@@ -204,7 +203,7 @@ struct ftkx_series_pending {
   int tail_set = 0;                 // which of ftkx_ctx::sr_tail its tail works on (series.hip: tail_of): 0 unless it is every other split pass of a short mask launch
   bool split_sparse = false;        // ... of a sparse pass: few workgroups per chain kernel, 2^10 buckets
   bool one = false;                 // the one-launch pass for small series (one_kernel.hip)
-  std::vector<std::pair<unsigned char *, unsigned char *>> retired;   // (M, U) arrays this pass still reads, replaced in their slices by the pass queued behind it
+  std::vector<std::pair<ftkx_block, ftkx_block>> retired;   // (M, U) arrays this pass still reads, replaced in their slices by the pass queued behind it
   std::vector<ftkxh::Slice> parked;        // slices dropped (or replaced) while this split pass was the newest one open: its tail -- on a stream of its own -- may still read
                                     // their arrays, which go back to the pools when it has been completed (release_retired)
   // slab pass (ftkx_series_dist_*): one rank's part of a series cut into timestep slabs, queued in stages with the caller's collectives between them
@@ -287,10 +286,9 @@ struct ftkx_ctx {
   ftkx_block d_sort_tmp;            // unsigned: digit counts per tile
   // per-batch descriptors: pinned staging + device copies
   ftkx_block h_desc{FTKX_BLOCK_PINNED}, d_desc;
-  // mask / summary arrays of dropped slices, kept for the next slice (a streaming tracker pushes and pops one slice per step:
-  // hipMalloc + hipFree per step cost more than the sweep itself).  Their padding bytes stay valid: kernels never write them.
-  std::vector<unsigned char *> pool_M, pool_U;
-  std::vector<std::pair<double *, size_t>> pool_F;   // owned field arrays (S / V / J copies) of dropped slices, by size in doubles
+  // field (S / V / J copies), mask and summary arrays of dropped slices, kept for the next slice (ctx_block.hpp).  The padding bytes of a
+  // mask or summary array stay valid: kernels never write them.
+  ftkx_array_pool arrays;
   ftkx_block d_red;                 // u64: {min, max} slots of a batched resolution reduction, 128 words per slice (ensure_red)
   // physical coordinates (REGULAR_COORDS_RECTILINEAR / _EXPLICIT): device copies
   ftkx_block d_rect[3];             // double
@@ -304,12 +302,11 @@ struct ftkx_ctx {
   double smooth_sigma = 0;
   ftkx_block d_conv_w;              // double
   // temporal smoothing (ftkx_set_temporal_smoothing): the filter's state (temporal_steps.hpp), its weights and the ring of RAW snapshots
-  // (after the spatial smoothing where that is set) -- at most ksize arrays of tm_count doubles each, taken from and given back to pool_F.
+  // (after the spatial smoothing where that is set) -- at most ksize arrays of one size, taken from and given back to `arrays`.
   // Only kernels on the context's stream read them.  tm_next: the timestep the next emission gets.
   ftkx::TemporalSeries tm;
   double tm_sigma = 0, tm_w[ftkx::kTemporalMaxK] = {0};
-  std::deque<double *> tm_ring;
-  size_t tm_count = 0;
+  std::deque<ftkx_block> tm_ring;
   int tm_next = 0;
   hipEvent_t tm_read = nullptr;     // behind the staging of a device source: what ftkx_temporal_push waits for before it returns
   // float32 sources (ftkx_push_scalar_slice_f32, ftkx_push_slice_f32, ftkx_temporal_push_f32): a host array, or an array of another device, lies
@@ -412,9 +409,10 @@ int u_pitch(const ftkx_ctx *c);
 size_t u_bytes(const ftkx_ctx *c);
 size_t u_bytes_used(const ftkx_ctx *c, const Mesh &m);
 size_t mask_bytes(const ftkx_ctx *c);
-void release_slice(Slice &s, ftkx_ctx *pool_owner = nullptr);   // its arrays back to the owner's pools, or (no owner) freed
+constexpr size_t kPoolCap = 12;                                 // arrays of a class kept where a slice or a staging array is given back: a batch of steps parked with a split pass comes back at once
+void release_slice(Slice &s, ftkx_ctx *c);                      // its arrays back to the context's pool (kPoolCap); `s` is empty afterwards
 void free_slice(Slice &s, ftkx_ctx *c);                         // a slice of a live context is dropped: parked with the newest open split pass, or released
-void release_pools(ftkx_ctx *c);
+void release_retired(ftkx_ctx *c, ftkx_series_pending &P);      // what a pass kept for its tail goes back to the pool: where it completes, where its slot is reused, on abort
 int ensure_hit_buffer(ftkx_ctx *c, u64 want);                   // d_hits and set 0's pass array
 int ensure_pass(ftkx_ctx *c, ftkx_tail_set &S, u64 want);
 int ensure_fragile(ftkx_ctx *c, ftkx_tail_set &S, u64 want);

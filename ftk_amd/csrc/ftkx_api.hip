@@ -71,21 +71,12 @@ size_t u_bytes(const ftkx_ctx *c) { return (size_t)u_pitch(c) * (size_t)c->ext_s
 size_t u_bytes_used(const ftkx_ctx *c, const Mesh &m) { return (size_t)u_pitch(c) * (size_t)((c->ext_sz[1] + m.u_rows - 1) / m.u_rows) * (size_t)(c->nd == 3 ? c->ext_sz[2] : 1); }
 size_t mask_bytes(const ftkx_ctx *c) { return (size_t)mask_pitch(c) * (size_t)c->ext_sz[1] * (size_t)(c->nd == 3 ? c->ext_sz[2] : 1); }
 
-void release_slice(Slice &s, ftkx_ctx *pool_owner)
+void release_slice(Slice &s, ftkx_ctx *c)
 {
-  // owned copies go back to the context's pool: a streaming caller pushes and pops one slice per step, and hipMalloc + hipFree of a
-  // slice-sized array cost more than sweeping a 256^3 slice
-  auto give_back = [&](double *p, size_t count) {
-    if (pool_owner && pool_owner->pool_F.size() < 12) pool_owner->pool_F.push_back({p, count});      // (12: a batch of steps parked with a split pass comes back at once)
-    else (void)hipFree(p);
-  };
-  const size_t nv = pool_owner ? n_vertices(pool_owner) : 0, nd_ = pool_owner ? (size_t)pool_owner->nd : 0;
-  if (s.ownV && s.V) give_back(s.V, nv * nd_);
-  if (s.ownJ && s.J) give_back(s.J, nv * nd_ * nd_);
-  if (s.ownS && s.S) give_back(s.S, nv);
-  s.ownV = s.ownJ = s.ownS = false;
-  if (s.M) { if (pool_owner && pool_owner->pool_M.size() < 12) pool_owner->pool_M.push_back(s.M); else (void)hipFree(s.M); }
-  if (s.U) { if (pool_owner && pool_owner->pool_U.size() < 12) pool_owner->pool_U.push_back(s.U); else (void)hipFree(s.U); }
+  // owned copies go back to the context's pool, each under its own bytes (ctx_block.hpp); lent arrays are let go
+  for (ftkx_block *f : {&s.V, &s.J, &s.S}) c->arrays.give(FTKX_ARRAY_FIELD, std::move(*f), kPoolCap);
+  c->arrays.give(FTKX_ARRAY_MASK, std::move(s.M), kPoolCap);
+  c->arrays.give(FTKX_ARRAY_SUMMARY, std::move(s.U), kPoolCap);
   s = Slice();
 }
 
@@ -96,17 +87,19 @@ void free_slice(Slice &s, ftkx_ctx *c)
   // The slice is parked with that pass and is released when it has been completed (series.hip, release_retired).
   if (c->sr_open > 0) {
     ftkx_series_pending &N = c->sr_pend[c->sr_place(c->sr_open - 1)];
-    if (N.open && N.split) { N.parked.push_back(s); s = Slice(); return; }
+    if (N.open && N.split) { N.parked.push_back(std::move(s)); s = Slice(); return; }
   }
   release_slice(s, c);
 }
 
-void release_pools(ftkx_ctx *c)
+void release_retired(ftkx_ctx *c, ftkx_series_pending &P)
 {
-  for (unsigned char *p : c->pool_M) (void)hipFree(p);
-  for (unsigned char *p : c->pool_U) (void)hipFree(p);
-  for (auto &p : c->pool_F) (void)hipFree(p.first);
-  c->pool_M.clear(); c->pool_U.clear(); c->pool_F.clear();
+  // (no cap: a pass of 32 slices would free, and its successor allocate again, 40 arrays per pass)
+  for (auto &mu : P.retired) { c->arrays.give(FTKX_ARRAY_MASK, std::move(mu.first)); c->arrays.give(FTKX_ARRAY_SUMMARY, std::move(mu.second)); }
+  P.retired.clear();
+  // (slices dropped while this pass was the newest one open: its tail is through, a pass queued behind it was planned after the drop)
+  for (Slice &sl : P.parked) release_slice(sl, c);
+  P.parked.clear();
 }
 
 // ---- the tail sets (ctx.hpp) ---------------------------------------------------------------------------------------------------------
@@ -206,12 +199,12 @@ int slice_resolution(ftkx_ctx *c, Slice &s)
       // the marching stencil kernel in reduce-only mode: same single pass over S as the mask kernel, nothing stored
       int rc = ensure_desc(c, sizeof(MaskJob));
       if (rc) return rc;
-      const MaskJob job{s.S, nullptr, nullptr, nullptr, d, 1.0};
+      const MaskJob job{s.S.as<double>(), nullptr, nullptr, nullptr, d, 1.0};
       HIP_TRY(c, hipMemcpyAsync(c->d_desc.p, &job, sizeof(job), hipMemcpyHostToDevice, c->stream));
       ftkx::launch_reduce_march(m, (const MaskJob *)c->d_desc.p, 1, c->stream);
-    } else ftkx::launch_resolution_scalar(m, s.S, d, c->stream);
+    } else ftkx::launch_resolution_scalar(m, s.S.as<double>(), d, c->stream);
   }
-  else ftkx::launch_resolution(s.V, n_vertices(c) * (size_t)c->nd, d, c->stream);
+  else ftkx::launch_resolution(s.V.as<double>(), n_vertices(c) * (size_t)c->nd, d, c->stream);
   HIP_TRY(c, hipGetLastError());
   u64 out[128];
   HIP_TRY(c, hipMemcpyAsync(out, d, sizeof(out), hipMemcpyDeviceToHost, c->stream));
@@ -241,7 +234,7 @@ bool pow2_factor(u64 factor) { return factor != 0 && (factor & (factor - 1)) == 
 // larger factor is accepted only when the slice's max |v| shows that no vertex is big under it either.
 bool masks_valid(const ftkx_ctx *c, const Slice &s, u64 factor, bool two_level, int u_rows)
 {
-  if (!s.M || (two_level && !s.U) || s.mask_factor == 0 || s.mask_factor > factor) return false;
+  if (!s.M.p || (two_level && !s.U.p) || s.mask_factor == 0 || s.mask_factor > factor) return false;
   if (two_level && s.u_rows != u_rows) return false;           // summaries of another geometry (FTKX_MASK_* changed since)
   if (s.mask_big && s.mask_factor == factor) return true;
   return s.max_known() && overflow_free(c->nd, s.maxabs, factor);   // no vertex is big under `factor`: the rule would change nothing
@@ -294,24 +287,16 @@ void aux_stream_put(ftkx_ctx *c, bool high, hipStream_t st)
 int ensure_mask_arrays(ftkx_ctx *c, Slice &s, bool two_level)
 {
   s.mask_gen = ++ c->mask_epoch;    // (every builder of masks comes through here: a series pass collected later leaves this slice's marks alone)
-  if (!s.M) {
-    if (!c->pool_M.empty()) { s.M = c->pool_M.back(); c->pool_M.pop_back(); }   // padding still neutral from its first life
-    else {
-      HIP_TRY(c, hipMalloc((void **)&s.M, mask_bytes(c)));
-      // row padding and anything a kernel does not write is cull-neutral
-      HIP_TRY(c, hipMemsetAsync(s.M, 0x3f, mask_bytes(c), c->stream));
-    }
-    s.mask_factor = 0;
-  }
-  if (two_level && !s.U) {
-    if (!c->pool_U.empty()) { s.U = c->pool_U.back(); c->pool_U.pop_back(); }
-    else {
-      HIP_TRY(c, hipMalloc((void **)&s.U, u_bytes(c)));
-      HIP_TRY(c, hipMemsetAsync(s.U, 0x3f, u_bytes(c), c->stream));
-    }
-    s.mask_factor = 0;      // summaries must be produced together with the masks
-  }
-  return FTKX_OK;
+  // (a pooled array's padding is still neutral from its first life; a new one: row padding and whatever no kernel writes is made cull-neutral)
+  auto take = [&](ftkx_array_class k, size_t bytes, ftkx_block &dst) -> int {
+    bool fresh = false;
+    if (const int rc = c->arrays.take(c, k, bytes, dst, &fresh)) return rc;
+    if (fresh) HIP_TRY(c, hipMemsetAsync(dst.p, 0x3f, bytes, c->stream));
+    s.mask_factor = 0;      // (summaries must be produced together with the masks)
+    return FTKX_OK;
+  };
+  if (!s.M.p) { if (const int rc = take(FTKX_ARRAY_MASK, mask_bytes(c), s.M)) return rc; }
+  return two_level && !s.U.p ? take(FTKX_ARRAY_SUMMARY, u_bytes(c), s.U) : FTKX_OK;
 }
 
 }  // namespace ftkxh
@@ -325,6 +310,7 @@ int ftkx_block_alloc(ftkx_ctx *c, ftkx_block_kind kind, size_t bytes, void **p)
     case FTKX_BLOCK_PINNED: HIP_TRY(c, hipHostMalloc(p, bytes, hipHostMallocDefault)); break;
     case FTKX_BLOCK_PINNED_COHERENT: HIP_TRY(c, hipHostMalloc(p, bytes, hipHostMallocCoherent)); break;
     case FTKX_BLOCK_PINNED_NONCOHERENT: HIP_TRY(c, hipHostMalloc(p, bytes, hipHostMallocNonCoherent)); break;
+    case FTKX_BLOCK_LENT: return fail(c, FTKX_E_INVALID, "a block the caller lent cannot be reserved");
   }
   return FTKX_OK;
 }
@@ -414,11 +400,7 @@ void ftkx_destroy(ftkx_ctx *c)
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   (void)sync_tails(c);                                        // (passes left open: their tails and copies read what is freed below)
   if (c->sr_copy_stream) (void)hipStreamSynchronize(c->sr_copy_stream);
-  for (auto &kv : c->slices) release_slice(kv.second);
-  for (ftkx_series_pending &P : c->sr_pend) { for (Slice &sl : P.parked) release_slice(sl); P.parked.clear(); }
-  temporal_release(c);
   if (c->tm_read) (void)hipEventDestroy(c->tm_read);
-  release_pools(c);
   for (auto &e : c->events) { (void)hipEventDestroy(e.second.first); (void)hipEventDestroy(e.second.second); }
   for (hipEvent_t e : c->event_pool) (void)hipEventDestroy(e);
   for (ftkx_series_buffers &B : c->sr_buf)
@@ -427,7 +409,7 @@ void ftkx_destroy(ftkx_ctx *c)
   aux_stream_put(c, false, c->sr_copy_stream);
   for (ftkx_tail_set &S : c->sr_tail) aux_stream_put(c, true, S.stream);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-  delete c;                                                   // every block (ctx_block.hpp) goes with it
+  delete c;                                                   // every block (ctx_block.hpp) goes with it: the slices, parked and retired arrays, the ring and the pool too
 }
 
 int ftkx_set_stream(ftkx_ctx *c, void *s)
@@ -493,9 +475,13 @@ int ftkx_set_mesh(ftkx_ctx *c, const long long dst[3], const long long dsz[3], c
   if (c) c->ahead.clear();
   if (!c) return fail(nullptr, FTKX_E_INVALID, "null context");
   if (!c->slices.empty()) return fail(c, FTKX_E_INVALID, "ftkx_set_mesh: drop all slices first");
-  (void)hipSetDevice(c->device);
+  HIP_TRY(c, hipSetDevice(c->device));
+  // nothing of the old lattice stays: slices dropped under an open split pass are parked with it, not in `slices` -- its tail is waited for
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, sync_tails(c));
+  for (ftkx_series_pending &P : c->sr_pend) release_retired(c, P);
   temporal_release(c);                    // a temporal series that was open starts afresh: its raw snapshots have the old lattice's size
-  release_pools(c);                       // pooled mask arrays have the old lattice's size
+  c->arrays.clear();
   for (int d = 0; d < c->nd; d ++) {
     if (dsz[d] < 0 || csz[d] < 0 || esz[d] <= 0) return fail(c, FTKX_E_INVALID, "ftkx_set_mesh: negative size on axis %d", d);
     if (dst[d] + dsz[d] > 2147483647LL || est[d] + esz[d] > 2147483647LL || cst[d] + csz[d] > 2147483647LL)
@@ -529,22 +515,15 @@ static int push_checks(ftkx_ctx *c, int t, int on_device, bool scalar_only, bool
   return FTKX_OK;
 }
 
-// a field array of `count` doubles out of the pool, or a new one
-static int take_pooled(ftkx_ctx *c, size_t count, double **dst)
-{
-  *dst = nullptr;
-  for (size_t i = 0; i < c->pool_F.size(); i ++)
-    if (c->pool_F[i].second == count) { *dst = c->pool_F[i].first; c->pool_F.erase(c->pool_F.begin() + (long)i); break; }
-  if (!*dst) HIP_TRY(c, hipMalloc((void **)dst, count * sizeof(double)));
-  return FTKX_OK;
-}
+// a field array of `count` doubles out of the pool, or a new one (a caller that fails afterwards lets it go out of scope: freed, not pooled)
+static int take_pooled(ftkx_ctx *c, size_t count, ftkx_block &dst) { return c->arrays.take(c, FTKX_ARRAY_FIELD, count * sizeof(double), dst); }
 
 // ... and back, behind work queued on the context's stream that may still read it: whatever takes it out next is ordered behind that work
-// by the same stream (upload.cpp waits for it too)
-static void give_pooled(ftkx_ctx *c, double *p, size_t count)
+// by the same stream (upload.cpp waits for it too); where the pool is full it is freed, once that work is through
+static void give_pooled(ftkx_ctx *c, ftkx_block &&b)
 {
-  if (c->pool_F.size() < 12) c->pool_F.push_back({p, count});
-  else { (void)hipStreamSynchronize(c->stream); (void)hipFree(p); }
+  if (c->arrays.held[FTKX_ARRAY_FIELD].size() >= kPoolCap) (void)hipStreamSynchronize(c->stream);
+  c->arrays.give(FTKX_ARRAY_FIELD, std::move(b), kPoolCap);
 }
 
 // the slice of timestep t, where there is one, leaves (its arrays are in the pool for what replaces it)
@@ -558,7 +537,7 @@ static void evict_slice(ftkx_ctx *c, int t)
 static void install_slice(ftkx_ctx *c, int t, Slice &s, bool scalar_only)
 {
   s.mask_gen = ++ c->mask_epoch;
-  c->slices[t] = s;
+  c->slices[t] = std::move(s);
   c->scalar_mode = scalar_only ? 1 : 0;
 }
 
@@ -584,7 +563,7 @@ template <class T> static int stage_into(ftkx_ctx *c, const T *src, size_t count
     return FTKX_OK;
   }
   const T *from = src;
-  double *tmp = nullptr;
+  ftkx_block tmp;
   if (on_device == 0 || ftkx_pointer_device(src) != c->device) {
     void *stage = nullptr;
     if (f32) {
@@ -593,16 +572,16 @@ template <class T> static int stage_into(ftkx_ctx *c, const T *src, size_t count
       if (int rc = c->f32_stage.reserve(c, count * sizeof(T), 0, c->stream)) return rc;
       stage = c->f32_stage.p;
     } else {
-      if (int rc = take_pooled(c, count, &tmp)) return rc;
-      stage = tmp;
+      if (int rc = take_pooled(c, count, tmp)) return rc;
+      stage = tmp.p;
     }
     int rc = FTKX_OK;
     if (on_device == 0) rc = upload_from_host(c, stage, src, count * sizeof(T));
     else if (hipMemcpyAsync(stage, src, count * sizeof(T), hipMemcpyDefault, c->stream) != hipSuccess) rc = fail(c, FTKX_E_DEVICE, "push: copy of the source failed");
     // (a failed copy: nothing of it is in flight any more -- upload.cpp drains its DMA streams before it reports an error, and a
     // hipMemcpyAsync that was refused was never queued -- but what the buffer holds is unknown and the device may be in an error state:
-    // a pooled buffer is freed, not pooled; the staging block is overwritten by the next push anyway)
-    if (rc) { if (tmp) (void)hipFree(tmp); return rc; }
+    // a pooled buffer is freed with `tmp`, not pooled; the staging block is overwritten by the next push anyway)
+    if (rc) return rc;
     from = static_cast<const T *>(stage);
     if (f32) c->f32_stage_reader = c->stream;
   }
@@ -614,7 +593,7 @@ template <class T> static int stage_into(ftkx_ctx *c, const T *src, size_t count
     c->f32_widened ++;
   }
   const hipError_t e = hipGetLastError();
-  if (tmp) give_pooled(c, tmp, count);
+  if (tmp.p) give_pooled(c, std::move(tmp));
   HIP_TRY(c, e);
   return FTKX_OK;
 }
@@ -634,18 +613,16 @@ template <class T> static int push_common(ftkx_ctx *c, int t, const T *V, const 
   const size_t n = n_vertices(c);
   const int nd = c->nd;
   // (smoothing applies to S alone: vector pushes were refused above)
-  auto take = [&](const T *src, size_t count, bool smooth, double **dst, bool *own) -> int {
-    if (!src) { *dst = nullptr; *own = false; return FTKX_OK; }
-    if constexpr (!f32) if (on_device == 1 && !smooth) { *dst = const_cast<double *>(src); *own = false; return FTKX_OK; }      // borrowed: adopted as it is
+  auto take = [&](const T *src, size_t count, bool smooth, ftkx_block &dst) -> int {
+    if (!src) return FTKX_OK;
+    if constexpr (!f32) if (on_device == 1 && !smooth) { dst = ftkx_block::lent(const_cast<double *>(src), count * sizeof(double)); return FTKX_OK; }      // adopted as it is
     if (int rc = take_pooled(c, count, dst)) return rc;
-    *own = true;
-    return stage_into(c, src, count, on_device, smooth, *dst);
+    return stage_into(c, src, count, on_device, smooth, dst.as<double>());
   };
-  int rc;
-  if ((rc = take(S, n, c->smooth_ksize != 0, &s.S, &s.ownS))) { release_slice(s); return rc; }
+  if (int rc = take(S, n, c->smooth_ksize != 0, s.S)) return rc;      // (here and below: what was already taken is freed with `s`)
   if (!scalar_only) {
-    if ((rc = take(V, n * nd, false, &s.V, &s.ownV))) { release_slice(s); return rc; }      // what was already allocated goes back
-    if ((rc = take(J, n * nd * nd, false, &s.J, &s.ownJ))) { release_slice(s); return rc; }
+    if (int rc = take(V, n * nd, false, s.V)) return rc;
+    if (int rc = take(J, n * nd * nd, false, s.J)) return rc;
   }
   // scalar input: V = gradient2D/3D(S) is never materialised -- every kernel evaluates it where it needs it, with the
   // reference's exact operations (ndarray/grad.hh), so the slice costs 8 bytes per vertex of HBM instead of 8 + 8*nd.
@@ -676,6 +653,13 @@ int ftkx_debug_f32_counts(const ftkx_ctx *c, unsigned long long *widened, unsign
   if (!c) return fail(nullptr, FTKX_E_INVALID, "null context");
   if (widened) *widened = c->f32_widened;
   if (convolved_direct) *convolved_direct = c->f32_direct;
+  return FTKX_OK;
+}
+
+int ftkx_debug_array_counts(const ftkx_ctx *c, unsigned long long allocated[3], unsigned long long pooled[3])
+{
+  if (!c) return fail(nullptr, FTKX_E_INVALID, "null context");
+  for (int k = 0; k < FTKX_ARRAY_CLASSES; k ++) { if (allocated) allocated[k] = c->arrays.allocated[k]; if (pooled) pooled[k] = c->arrays.held[k].size(); }
   return FTKX_OK;
 }
 
@@ -728,14 +712,14 @@ int ftkx_slices_resolution(ftkx_ctx *c, const int *ts, int n, double *res, doubl
     if (c->scalar_mode == 1 && ftkx::march2_supported(m)) {
       // the marching stencil kernel in reduce-only mode over all slices at once
       MaskJob *jobs = (MaskJob *)c->h_desc.p;
-      for (size_t i = 0; i < k; i ++) jobs[i] = MaskJob{todo[i]->S, nullptr, nullptr, nullptr, c->d_red.as<u64>() + i * 128, 1.0};
+      for (size_t i = 0; i < k; i ++) jobs[i] = MaskJob{todo[i]->S.as<double>(), nullptr, nullptr, nullptr, c->d_red.as<u64>() + i * 128, 1.0};
       HIP_TRY(c, hipMemcpyAsync(c->d_desc.p, c->h_desc.p, k * sizeof(MaskJob), hipMemcpyHostToDevice, c->stream));
       ftkx::launch_reduce_march(m, (const MaskJob *)c->d_desc.p, (int)k, c->stream);
     } else {
       // one launch per slice, back to back, each into its own slots
       for (size_t i = 0; i < k; i ++) {
-        if (c->scalar_mode == 1) ftkx::launch_resolution_scalar(m, todo[i]->S, c->d_red.as<u64>() + i * 128, c->stream);
-        else ftkx::launch_resolution(todo[i]->V, n_vertices(c) * (size_t)c->nd, c->d_red.as<u64>() + i * 128, c->stream);
+        if (c->scalar_mode == 1) ftkx::launch_resolution_scalar(m, todo[i]->S.as<double>(), c->d_red.as<u64>() + i * 128, c->stream);
+        else ftkx::launch_resolution(todo[i]->V.as<double>(), n_vertices(c) * (size_t)c->nd, c->d_red.as<u64>() + i * 128, c->stream);
       }
     }
     HIP_TRY(c, hipGetLastError());
@@ -1121,13 +1105,11 @@ int ftkx_debug_temporal_relaunch(ftkx_ctx *c, const double *const *arrays, int k
   return rc;
 }
 
-// the ring's arrays go back to the pool and the filter is as it was constructed (also from ftkx_destroy and ftkx_set_mesh, in front of
-// release_pools)
+// the ring's arrays go back to the pool and the filter is as it was constructed (also from ftkx_set_mesh, in front of the pool's clear())
 static void temporal_release(ftkx_ctx *c)
 {
-  for (double *p : c->tm_ring) give_pooled(c, p, c->tm_count);
+  for (ftkx_block &b : c->tm_ring) give_pooled(c, std::move(b));
   c->tm_ring.clear();
-  c->tm_count = 0;
   c->tm.restart();
 }
 
@@ -1151,17 +1133,32 @@ int ftkx_set_temporal_smoothing(ftkx_ctx *c, double sigma, int ksize, int t0)
   return FTKX_OK;
 }
 
-// the emission whose taps read the ring places idx[] (the ring as it will be: `ring`) becomes the resident slice tm_next, in `out`
-// (a slice of that timestep which was resident leaves only once the emission has been queued)
-static int temporal_emit(ftkx_ctx *c, const std::deque<double *> &ring, const int *idx, size_t count, double *out, bool scalar, int *t_emitted)
+// One emission, as a transaction: it becomes the resident slice tm_next (a slice of that timestep which was resident leaves only once the
+// emission has been queued).  `next`: the filter's state behind it; `pop`, idx[]: the state machine's answers; `slot`: the snapshot that joins
+// the ring (null: a flush).  The taps are read off a view of the ring as it will be; the kernel writes into the array that leaves the ring
+// (the emissions that read it are in front of this one in the stream) or, where none leaves, into a pooled one.  Blocks move only once the
+// kernel has been queued: after a failure ring, filter and resident slices are as before the call, and what was taken is freed, not pooled.
+static int temporal_emit(ftkx_ctx *c, const ftkx::TemporalSeries &next, bool pop, const int *idx, size_t count, ftkx_block *slot, bool scalar, int *t_emitted)
 {
-  const double *arrays[ftkx::kTemporalMaxK];
+  const double *ring[ftkx::kTemporalMaxK + 1], *arrays[ftkx::kTemporalMaxK];
+  size_t n = 0;
+  for (size_t i = pop ? 1 : 0; i < c->tm_ring.size() && n < (size_t)ftkx::kTemporalMaxK; i ++) ring[n ++] = c->tm_ring[i].as<double>();
+  if (slot) ring[n ++] = slot->as<double>();
   for (int i = 0; i < c->tm.ksize; i ++) arrays[i] = ring[(size_t)idx[i]];
-  ftkx::launch_temporal(arrays, c->tm.ksize, c->tm_w, count, out, c->stream);
-  HIP_TRY(c, hipGetLastError());
-  evict_slice(c, c->tm_next);
+  ftkx_block spare;
+  auto queue = [&]() -> int {
+    if (!pop) { if (int rc = take_pooled(c, count, spare)) return rc; }
+    ftkx::launch_temporal(arrays, c->tm.ksize, c->tm_w, count, pop ? c->tm_ring.front().as<double>() : spare.as<double>(), c->stream);
+    HIP_TRY(c, hipGetLastError());
+    return FTKX_OK;
+  };
+  if (int rc = queue()) { (void)hipStreamSynchronize(c->stream); return rc; }
   Slice s;
-  if (scalar) { s.S = out; s.ownS = true; } else { s.V = out; s.ownV = true; }
+  ftkx_block &out = scalar ? s.S : s.V;
+  if (pop) { out = std::move(c->tm_ring.front()); c->tm_ring.pop_front(); } else out = std::move(spare);
+  if (slot) c->tm_ring.push_back(std::move(*slot));
+  c->tm = next;
+  evict_slice(c, c->tm_next);
   install_slice(c, c->tm_next, s, scalar);
   *t_emitted = c->tm_next ++;
   return FTKX_OK;
@@ -1186,41 +1183,27 @@ template <class T> static int temporal_push_common(ftkx_ctx *c, const T *A, int 
   if (c->smooth_ksize && !scalar) return fail(c, FTKX_E_UNSUPPORTED, "ftkx_temporal_push: spatial smoothing is set and takes scalar snapshots only");
   HIP_TRY(c, hipSetDevice(c->device));
   const size_t count = n_vertices(c) * (scalar ? 1 : (size_t)c->nd);
-  if (!c->tm_ring.empty() && c->tm_count != count) return fail(c, FTKX_E_INVALID, "ftkx_temporal_push: the mesh changed within a series");
+  if (!c->tm_ring.empty() && c->tm_ring.front().count<double>() != count) return fail(c, FTKX_E_INVALID, "ftkx_temporal_push: the mesh changed within a series");
   // the raw snapshot (spatially smoothed first where that is set: the stream's order) into a ring slot of the context's own
   if (on_device != 0 && !c->tm_read) HIP_TRY(c, hipEventCreateWithFlags(&c->tm_read, hipEventDisableTiming));
-  double *slot = nullptr;
-  if (int rc = take_pooled(c, count, &slot)) return rc;
-  int rc = FTKX_OK;
-  rc = stage_into(c, A, count, on_device, c->smooth_ksize != 0, slot);      // widened where it is float32, convolved where smoothing is set
-  if (rc) { (void)hipFree(slot); return rc; }      // (what the slot holds is unknown: freed, not pooled)
+  ftkx_block slot;      // (what it holds after a failure is unknown: freed with this call, not pooled)
+  if (int rc = take_pooled(c, count, slot)) return rc;
+  if (int rc = stage_into(c, A, count, on_device, c->smooth_ksize != 0, slot.as<double>())) return rc;      // widened where it is float32, convolved where smoothing is set
   // A device source has to be read before the caller may overwrite it (a host source has been staged completely by upload_from_host):
   // the call ends by waiting for THIS point of the stream, not for the stream -- sweeps queued before the push (deferred collection) and
   // the emission queued behind it run on.
-  if (on_device != 0) {
-    if (hipEventRecord(c->tm_read, c->stream) != hipSuccess) { (void)hipStreamSynchronize(c->stream); (void)hipFree(slot); return fail(c, FTKX_E_DEVICE, "ftkx_temporal_push: hipEventRecord failed"); }
-  }
+  if (on_device != 0 && hipEventRecord(c->tm_read, c->stream) != hipSuccess) { (void)hipStreamSynchronize(c->stream); return fail(c, FTKX_E_DEVICE, "ftkx_temporal_push: hipEventRecord failed"); }
   // the state machine on a copy; the context's is replaced when everything has been queued
   ftkx::TemporalSeries next = c->tm;
-  std::deque<double *> ring = c->tm_ring;
-  ring.push_back(slot);
   bool pop = false;
   int idx[ftkx::kTemporalMaxK];
-  const bool emits = ftkx::temporal_push(next, is_vector, &pop, idx);
-  double *left = nullptr;
-  if (pop) { left = ring.front(); ring.pop_front(); }
-  if (emits) {
-    // the array that left the ring is read by nothing any more (the emissions that read it are in front of this one in the stream): it
-    // takes the new emission; otherwise a pooled one
-    double *out = left;
-    if (!out) rc = take_pooled(c, count, &out);
-    if (rc == FTKX_OK) rc = temporal_emit(c, ring, idx, count, out, scalar, t_emitted);
-    // (the emission was not queued, or the device is in an error state: ring, filter and resident slices are as they were before this call)
-    if (rc) { (void)hipStreamSynchronize(c->stream); if (out && out != left) (void)hipFree(out); (void)hipFree(slot); return rc; }
-  } else if (left) give_pooled(c, left, count);
-  c->tm = next;
-  c->tm_ring.swap(ring);
-  c->tm_count = count;
+  if (ftkx::temporal_push(next, is_vector, &pop, idx)) {
+    if (int rc = temporal_emit(c, next, pop, idx, count, &slot, scalar, t_emitted)) return rc;
+  } else {
+    if (pop) { give_pooled(c, std::move(c->tm_ring.front())); c->tm_ring.pop_front(); }
+    c->tm_ring.push_back(std::move(slot));
+    c->tm = next;
+  }
   if (on_device != 0) HIP_TRY(c, hipEventSynchronize(c->tm_read));
   return FTKX_OK;
 }
@@ -1244,16 +1227,9 @@ int ftkx_temporal_flush(ftkx_ctx *c, int *t_emitted)
   ftkx::TemporalSeries next = c->tm;
   bool pop = false;
   int idx[ftkx::kTemporalMaxK];
-  const bool emits = ftkx::temporal_finish_step(next, &pop, idx);
-  if (!emits) { temporal_release(c); return FTKX_OK; }      // the loop stops: the filter as it was constructed, tm_next the next unused timestep
-  // the array that leaves the ring takes the emission (nothing queued behind this point reads it)
-  std::deque<double *> ring = c->tm_ring;
-  double *out = ring.front();
-  ring.pop_front();
-  if (int rc = temporal_emit(c, ring, idx, c->tm_count, out, c->tm.kind == 0, t_emitted)) return rc;
-  c->tm = next;
-  c->tm_ring.swap(ring);
-  return FTKX_OK;
+  if (!ftkx::temporal_finish_step(next, &pop, idx)) { temporal_release(c); return FTKX_OK; }      // the loop stops: the filter as it was constructed, tm_next the next unused timestep
+  // the array that leaves the ring takes the emission
+  return temporal_emit(c, next, pop, idx, c->tm_ring.front().count<double>(), nullptr, c->tm.kind == 0, t_emitted);
 }
 
 }  // extern "C"

@@ -23,10 +23,9 @@ int make_sparse(ftkx_ctx *c, Slice &s, int scalar_input)
 {
   if (s.sparse) return FTKX_OK;
   const size_t bytes = n_vertices(c) * (scalar_input ? 1 : (size_t)c->nd) * sizeof(double);
-  double **field = scalar_input ? &s.S : &s.V;
-  HIP_TRY(c, hipMalloc((void **)field, bytes));
-  (scalar_input ? s.ownS : s.ownV) = true;
-  HIP_TRY(c, hipMemsetAsync(*field, 0, bytes, c->stream));
+  ftkx_block &field = scalar_input ? s.S : s.V;
+  if (const int rc = c->arrays.take(c, FTKX_ARRAY_FIELD, bytes, field)) return rc;
+  HIP_TRY(c, hipMemsetAsync(field.p, 0, bytes, c->stream));
   if (const int rc = ensure_mask_arrays(c, s, true)) return rc;
   s.sparse = true;
   return FTKX_OK;
@@ -50,13 +49,13 @@ int ftkx_export_masks_size(ftkx_ctx *c, int t, size_t *u_bytes_out, size_t *n_wo
   auto it = c->slices.find(t);
   if (it == c->slices.end()) return fail(c, FTKX_E_NOSLICE, "ftkx_export_masks_size: timestep %d not resident", t);
   Slice &s = it->second;
-  if (!s.M || !s.U || !s.mask_factor || !s.max_known())
+  if (!s.M.p || !s.U.p || !s.mask_factor || !s.max_known())
     return fail(c, FTKX_E_UNSUPPORTED, "ftkx_export_masks_size: slice %d has no summarised masks (ftkx_slices_prepare first; needs a mesh the two-level cull supports)", t);
   HIP_TRY(c, hipSetDevice(c->device));
   Mesh m; fill_mesh(c, m);
   for (int attempt = 0; attempt < 2; attempt ++) {
     HIP_TRY(c, hipMemsetAsync(c->sr_tail[0].counters.as<u64>() + ftkx::CNT_SPARSE, 0, sizeof(u64), c->stream));
-    ftkx::launch_compact_words(m, s.U, s.M, c->d_word_idx.as<unsigned>(), c->d_words.as<u64>(), words_capacity(c), c->sr_tail[0].counters.as<u64>() + ftkx::CNT_SPARSE, c->stream);
+    ftkx::launch_compact_words(m, s.U.as<unsigned char>(), s.M.as<unsigned char>(), c->d_word_idx.as<unsigned>(), c->d_words.as<u64>(), words_capacity(c), c->sr_tail[0].counters.as<u64>() + ftkx::CNT_SPARSE, c->stream);
     HIP_TRY(c, hipGetLastError());
     const u64 *hc = c->h_counters.as<u64>();
     HIP_TRY(c, hipMemcpyAsync(c->h_counters.p, c->sr_tail[0].counters.as<u64>() + ftkx::CNT_SPARSE, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
@@ -80,7 +79,7 @@ int ftkx_export_masks(ftkx_ctx *c, int t, void *U_dst, unsigned *word_index_dst,
   HIP_TRY(c, hipSetDevice(c->device));
   int rc;
   Mesh m; fill_mesh(c, m);
-  if ((rc = copy_out(c, U_dst, it->second.U, u_bytes_used(c, m), dst_on_device))) return rc;
+  if ((rc = copy_out(c, U_dst, it->second.U.p, u_bytes_used(c, m), dst_on_device))) return rc;
   if (c->n_words && (!word_index_dst || !words_dst)) return fail(c, FTKX_E_INVALID, "ftkx_export_masks: null list buffers");
   if ((rc = copy_out(c, word_index_dst, c->d_word_idx.as<unsigned>(), c->n_words * sizeof(unsigned), dst_on_device))) return rc;
   if ((rc = copy_out(c, words_dst, c->d_words.as<u64>(), c->n_words * sizeof(u64), dst_on_device))) return rc;
@@ -122,7 +121,7 @@ int ensure_sparse_slice(ftkx_ctx *c, int t, int scalar_input)
   const int rc = make_sparse(c, s, scalar_input);
   if (rc != FTKX_OK) { free_slice(s, c); return rc; }
   s.mask_gen = ++ c->mask_epoch;
-  c->slices[t] = s;
+  c->slices[t] = std::move(s);
   return FTKX_OK;
 }
 }  // namespace ftkxh
@@ -150,21 +149,21 @@ int ftkx_push_masked_slice(ftkx_ctx *c, int t, int scalar_input, const void *U, 
   if (n_words > mask_bytes(c) / 8) { c->scalar_mode = saved_mode; return fail(c, FTKX_E_INVALID, "ftkx_push_masked_slice: more mask words (%zu) than the slice has", n_words); }
   auto it = c->slices.find(t);
   Slice s;
-  if (it != c->slices.end() && it->second.sparse) { s = it->second; c->slices.erase(it); }          // the same halo slice again: keep its arrays
+  if (it != c->slices.end() && it->second.sparse) { s = std::move(it->second); c->slices.erase(it); }          // the same halo slice again: keep its arrays
   else if (it != c->slices.end()) { free_slice(it->second, c); c->slices.erase(it); }
   // everything below that can fail runs inside `fill`: on failure the half-built slice is released, not leaked
   auto fill = [&]() -> int {
   int rc;
   if ((rc = make_sparse(c, s, scalar_input))) return rc;
   const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-  HIP_TRY(c, hipMemcpyAsync(s.U, U, u_bytes_used(c, m), kind, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(s.U.p, U, u_bytes_used(c, m), kind, c->stream));
   if (n_words) {
     if ((rc = reserve_words(c, n_words, n_words))) return rc;
     c->words_t = -1;
     HIP_TRY(c, hipMemcpyAsync(c->d_word_idx.as<unsigned>(), word_index, n_words * sizeof(unsigned), kind, c->stream));
     HIP_TRY(c, hipMemcpyAsync(c->d_words.as<u64>(), words, n_words * sizeof(u64), kind, c->stream));
     HIP_TRY(c, hipMemsetAsync(halo_bad_flag(c), 0, sizeof(u64), c->stream));
-    ftkx::launch_scatter_words(c->d_word_idx.as<unsigned>(), c->d_words.as<u64>(), n_words, s.M, mask_bytes(c) / 8, halo_bad_flag(c), c->stream);
+    ftkx::launch_scatter_words(c->d_word_idx.as<unsigned>(), c->d_words.as<u64>(), n_words, s.M.as<unsigned char>(), mask_bytes(c) / 8, halo_bad_flag(c), c->stream);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(c->h_counters.p, halo_bad_flag(c), sizeof(u64), hipMemcpyDeviceToHost, c->stream));
   }
@@ -177,7 +176,7 @@ int ftkx_push_masked_slice(ftkx_ctx *c, int t, int scalar_input, const void *U, 
   s.mask_factor = mask_factor; s.mask_big = false; s.u_rows = m.u_rows;
   s.maxabs = max_abs;                                                                  // (all a masked slice knows of its values)
   s.mask_gen = ++ c->mask_epoch;
-  c->slices[t] = s;
+  c->slices[t] = std::move(s);
   return FTKX_OK;
 }
 
@@ -199,7 +198,7 @@ int ftkx_export_masks_packed(ftkx_ctx *c, int t, void *dst, int dst_on_device)
   auto it = c->slices.find(t);
   if (it == c->slices.end()) return fail(c, FTKX_E_NOSLICE, "ftkx_export_masks_packed: timestep %d not resident", t);
   Slice &s = it->second;
-  if (!s.M || !s.U || !s.mask_factor || !s.max_known())
+  if (!s.M.p || !s.U.p || !s.mask_factor || !s.max_known())
     return fail(c, FTKX_E_UNSUPPORTED, "ftkx_export_masks_packed: slice %d has no summarised masks (ftkx_slices_prepare first; needs a mesh the two-level cull supports)", t);
   HIP_TRY(c, hipSetDevice(c->device));
   Mesh m; fill_mesh(c, m);
@@ -213,9 +212,9 @@ int ftkx_export_masks_packed(ftkx_ctx *c, int t, void *dst, int dst_on_device)
   unsigned *idx = (unsigned *)(out + 32 + pad8(ub));
   u64 *words = (u64 *)(out + 32 + pad8(ub) + pad8(cap * sizeof(unsigned)));
   HIP_TRY(c, hipMemsetAsync(c->sr_tail[0].counters.as<u64>() + ftkx::CNT_SPARSE, 0, sizeof(u64), c->stream));
-  ftkx::launch_compact_words(m, s.U, s.M, idx, words, cap, c->sr_tail[0].counters.as<u64>() + ftkx::CNT_SPARSE, c->stream);
+  ftkx::launch_compact_words(m, s.U.as<unsigned char>(), s.M.as<unsigned char>(), idx, words, cap, c->sr_tail[0].counters.as<u64>() + ftkx::CNT_SPARSE, c->stream);
   // (the header says under which factor the masks were built and how many rows a summary byte stands for: the receiver checks both)
-  ftkx::launch_pack_masks((u64 *)out, c->sr_tail[0].counters.as<u64>() + ftkx::CNT_SPARSE, s.U, ub, cap, s.u_rows, factor_log2(s.mask_factor), c->stream);
+  ftkx::launch_pack_masks((u64 *)out, c->sr_tail[0].counters.as<u64>() + ftkx::CNT_SPARSE, s.U.as<unsigned char>(), ub, cap, s.u_rows, factor_log2(s.mask_factor), c->stream);
   HIP_TRY(c, hipGetLastError());
   if (!dst_on_device) { HIP_TRY(c, hipMemcpyAsync(dst, out, total, hipMemcpyDeviceToHost, c->stream)); HIP_TRY(c, hipStreamSynchronize(c->stream)); }
   return FTKX_OK;                                          // (device destination: queued on the context's stream, nothing waited for)
@@ -239,7 +238,7 @@ int ftkx_push_masked_slice_packed(ftkx_ctx *c, int t, int scalar_input, const vo
   if (!total) { c->scalar_mode = saved_mode; return fail(c, FTKX_E_UNSUPPORTED, "ftkx_push_masked_slice_packed: this mesh has no summarised masks"); }
   auto it = c->slices.find(t);
   Slice s;
-  if (it != c->slices.end() && it->second.sparse) { s = it->second; c->slices.erase(it); }          // the same halo slice again: keep its arrays
+  if (it != c->slices.end() && it->second.sparse) { s = std::move(it->second); c->slices.erase(it); }          // the same halo slice again: keep its arrays
   else if (it != c->slices.end()) { free_slice(it->second, c); c->slices.erase(it); }
   auto fill = [&]() -> int {
     int rc;
@@ -254,7 +253,7 @@ int ftkx_push_masked_slice_packed(ftkx_ctx *c, int t, int scalar_input, const vo
     // masks serve their own factor and larger ones) and every index are checked on the device; a message that does not fit raises the
     // flag ftkx_sweep_cull looks at
     ftkx::launch_scatter_packed((const u64 *)in, (const unsigned *)(in + 32 + pad8(ub)), (const u64 *)(in + 32 + pad8(ub) + pad8(cap * sizeof(unsigned))), ub, cap, m.u_rows,
-                                factor_log2(mask_factor), s.U, s.M, mask_bytes(c) / 8, halo_bad_flag(c), c->stream);
+                                factor_log2(mask_factor), s.U.as<unsigned char>(), s.M.as<unsigned char>(), mask_bytes(c) / 8, halo_bad_flag(c), c->stream);
     HIP_TRY(c, hipGetLastError());
     if (!src_on_device) HIP_TRY(c, hipStreamSynchronize(c->stream));
     return FTKX_OK;
@@ -264,7 +263,7 @@ int ftkx_push_masked_slice_packed(ftkx_ctx *c, int t, int scalar_input, const vo
   s.mask_factor = mask_factor; s.mask_big = false; s.u_rows = m.u_rows;
   s.maxabs = max_abs;
   s.mask_gen = ++ c->mask_epoch;
-  c->slices[t] = s;
+  c->slices[t] = std::move(s);
   return FTKX_OK;
 }
 
@@ -278,7 +277,7 @@ int ftkx_sweep_cull(ftkx_ctx *c, int t_sparse, size_t *n_cells)
   if (c->pending.empty()) return FTKX_OK;
   for (const Request &r : c->pending) if (r.mode != MODE_FAST) return fail(c, FTKX_E_UNSUPPORTED, "ftkx_sweep_cull: the pending sweeps do not use the cull (send the slice itself)");
   HIP_TRY(c, hipSetDevice(c->device));
-  const double *field = it->second.S ? it->second.S : it->second.V;
+  const double *field = (it->second.S.p ? it->second.S : it->second.V).as<double>();
   int rc;
   if ((rc = ensure_hit_buffer(c, std::max<u64>(c->capacity, 1u << 16)))) return rc;
   if ((rc = ensure_list(c, c->sr_tail[0], std::max<u64>(c->sr_tail[0].list_capacity, 1u << 20))) || (rc = ensure_refine(c, c->sr_tail[0], std::max<u64>(c->sr_tail[0].refine_capacity, 1u << 20)))) return rc;
@@ -327,7 +326,7 @@ static int patches_common(ftkx_ctx *c, int t, const unsigned long long *cells, s
   HIP_TRY(c, hipSetDevice(c->device));
   Mesh m; fill_mesh(c, m);
   const int ncomp = c->scalar_mode == 1 ? 1 : c->nd;
-  double *field = c->scalar_mode == 1 ? it->second.S : it->second.V;
+  double *field = (c->scalar_mode == 1 ? it->second.S : it->second.V).as<double>();
   const size_t pd = ftkx_patch_doubles(c);
   const u64 *d_cells = cells; double *d_patches = patches;
   if (!on_device) {                              // host-side callers (gloo tests): stage through device buffers

@@ -83,8 +83,8 @@ bool ahead_steps(ftkx_ctx *c, bool two_level, u64 hint, std::vector<Fields> &ste
     Fields f;
     memset(&f, 0, sizeof(f));
     f.t = ts.first; f.scope_mask = ts.second;
-    f.M[0] = a->second.M; f.M[1] = s1 ? s1->M : nullptr;
-    f.U[0] = two_level ? a->second.U : nullptr; f.U[1] = (two_level && s1) ? s1->U : nullptr;
+    f.M[0] = a->second.M.as<unsigned char>(); f.M[1] = s1 ? s1->M.as<unsigned char>() : nullptr;
+    f.U[0] = two_level ? a->second.U.as<unsigned char>() : nullptr; f.U[1] = (two_level && s1) ? s1->U.as<unsigned char>() : nullptr;
     steps.push_back(f);
     rec.push_back({ts.first, ts.second, {f.M[0], f.M[1]}, {f.U[0], f.U[1]}});
   }
@@ -172,7 +172,7 @@ int ftkx_slices_prepare(ftkx_ctx *c, const int *ts, int n, unsigned long long fa
     launch_init_red(c->d_red.as<u64>(), k * 64, ahead_ok ? c->sr_tail[0].counters.as<u64>() : nullptr, c->stream);
     MaskJob *jobs = (MaskJob *)c->h_desc.p;
     for (size_t i = 0; i < k; i ++)
-      jobs[i] = with_lean_thresholds(MaskJob{todo[i]->S, todo[i]->V, todo[i]->M, two_level ? todo[i]->U : nullptr, c->d_red.as<u64>() + i * 128, cap, HUGE_VAL}, m);   // rule off: validated below
+      jobs[i] = with_lean_thresholds(MaskJob{todo[i]->S.as<double>(), todo[i]->V.as<double>(), todo[i]->M.as<unsigned char>(), two_level ? todo[i]->U.as<unsigned char>() : nullptr, c->d_red.as<u64>() + i * 128, cap, HUGE_VAL}, m);   // rule off: validated below
     HIP_TRY(c, hipMemcpyAsync(c->d_desc.p, c->h_desc.p, k * sizeof(MaskJob), hipMemcpyHostToDevice, c->stream));
     ev_begin(c, K_MASK); ftkx::launch_masks(m, (const MaskJob *)c->d_desc.p, (int)k, c->stream); ev_end(c);
     HIP_TRY(c, hipGetLastError());
@@ -246,12 +246,12 @@ int ftkx_debug_mask_relaunch(ftkx_ctx *c, int t, int reps, int nstreams, int wit
   Slice &s = it->second;
   Mesh m; fill_mesh(c, m);
   const bool two_level = ftkx::masks_have_summary(m);
-  if (!s.M || (two_level && !s.U) || !c->d_red.as<u64>() || s.sparse) return fail(c, FTKX_E_INVALID, "ftkx_debug_mask_relaunch: ftkx_slices_prepare first");
+  if (!s.M.p || (two_level && !s.U.p) || !c->d_red.as<u64>() || s.sparse) return fail(c, FTKX_E_INVALID, "ftkx_debug_mask_relaunch: ftkx_slices_prepare first");
   HIP_TRY(c, hipSetDevice(c->device));
   int rc;
   if ((rc = ensure_desc(c, 2 * 4096))) return rc;
   MaskJob *job = (MaskJob *)c->h_desc.p;
-  *job = with_lean_thresholds(MaskJob{s.S, s.V, s.M, two_level ? s.U : nullptr, c->d_red.as<u64>(), 1.0 / 256.0, HUGE_VAL}, m);
+  *job = with_lean_thresholds(MaskJob{s.S.as<double>(), s.V.as<double>(), s.M.as<unsigned char>(), two_level ? s.U.as<unsigned char>() : nullptr, c->d_red.as<u64>(), 1.0 / 256.0, HUGE_VAL}, m);
   HIP_TRY(c, hipMemcpyAsync(c->d_desc.p, c->h_desc.p, sizeof(MaskJob), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   hipStream_t st[2] = {c->stream, nullptr};

@@ -110,8 +110,8 @@ bool series_applicable(ftkx_ctx *c, const int *ts, const int *scopes, int n, con
   for (int i = 0; ok && i < n; i ++) {                       // the same consistency rule as ftkx_sweep_enqueue
     if (!(scopes[i] & FTKX_SCOPE_INTERVAL)) continue;
     const Slice &a = c->slices[ts[i]], &b = c->slices[ts[i] + 1];
-    if (b.sparse) { if (a.J != nullptr) ok = false; continue; }      // (a masks-only slice carries S or V, never J)
-    if ((a.J == nullptr) != (b.J == nullptr) || (a.S == nullptr) != (b.S == nullptr)) ok = false;
+    if (b.sparse) { if (a.J.p != nullptr) ok = false; continue; }      // (a masks-only slice carries S or V, never J)
+    if ((a.J.p == nullptr) != (b.J.p == nullptr) || (a.S.p == nullptr) != (b.S.p == nullptr)) ok = false;
   }
   if (ok && (c->opt.coords_mode == 2 || c->opt.coords_mode == 3)) ok = false;     // (their bounds checks live in ftkx_sweep_enqueue)
   return ok;
@@ -201,16 +201,6 @@ int ensure_set1(ftkx_ctx *c)
   if ((rc = ensure_list(c, S, S0.list_capacity)) || (rc = ensure_refine(c, S, S0.refine_capacity)) || (rc = ensure_pass(c, S, c->capacity)) ||
       (rc = ensure_fragile(c, S, S0.fragile_capacity)) || (rc = ensure_order(c, S, c->capacity)) || (rc = ensure_bins(c, S, S0.hist.count<unsigned>()))) return rc;
   return FTKX_OK;
-}
-
-void release_retired(ftkx_ctx *c, ftkx_series_pending &P)
-{
-  for (auto &mu : P.retired) { if (mu.first) c->pool_M.push_back(mu.first); if (mu.second) c->pool_U.push_back(mu.second); }
-  P.retired.clear();
-  // (slices dropped while this pass was the newest one open: its tail is through, and a pass queued behind it was planned after the drop and
-  // never read them -- straight to the pools)
-  for (Slice &sl : P.parked) release_slice(sl, c);
-  P.parked.clear();
 }
 
 bool short_chain_now(const ftkx_ctx *c, bool to_device, bool *small_now)
@@ -339,7 +329,7 @@ int series_plan_one(ftkx_ctx *c, ftkx_series_pending &P, const int *ts, const in
   ftkx::OneArgs a;
   memset(&a, 0, sizeof(a));
   a.nsteps = n; a.nslices = (int)k;
-  for (size_t j = 0; j < k; j ++) { const Slice &s = *sl[j]; a.slice[j] = ftkx::OneSlice{s.S, s.V, s.J, P.slice_ts[j], 0}; }
+  for (size_t j = 0; j < k; j ++) { const Slice &s = *sl[j]; a.slice[j] = ftkx::OneSlice{s.S.as<double>(), s.V.as<double>(), s.J.as<double>(), P.slice_ts[j], 0}; }
   size_t last = 0;
   for (int i = 0; i < n; i ++) {
     const ftkx::SeriesStep s = series_step(P.slice_ts, ts[i], scopes[i], &last);
@@ -399,12 +389,12 @@ void series_slice_readiness(ftkx_ctx *c, ftkx_series_pending &P, const std::vect
   size_t ntodo = 0;
   for (size_t j = 0; j < k; j ++) {
     const Slice &s = *sl[j];
-    bool ready = s.M && (!P.two_level || (s.U && s.u_rows == P.u_rows)) && s.mask_factor != 0 && s.mask_factor <= P.hint && !s.mask_big && (s.have_fused || s.have_res);
+    bool ready = s.M.p && (!P.two_level || (s.U.p && s.u_rows == P.u_rows)) && s.mask_factor != 0 && s.mask_factor <= P.hint && !s.mask_big && (s.have_fused || s.have_res);
     if (!ready && before && before->open && !before->by_host && before->hint <= P.hint && before->two_level == P.two_level && before->u_rows == P.u_rows) {
       const auto it = std::lower_bound(before->slice_ts.begin(), before->slice_ts.end(), slice_ts[j]);
       if (it != before->slice_ts.end() && *it == slice_ts[j]) {
         const size_t jj = (size_t)(it - before->slice_ts.begin());
-        if (before->red_index[jj] >= 0 && before->gen[jj] == s.mask_gen && s.M && (!P.two_level || s.U)) {
+        if (before->red_index[jj] >= 0 && before->gen[jj] == s.mask_gen && s.M.p && (!P.two_level || s.U.p)) {
           const u64 *R = c->sr_buf[before->buf].results.as<u64>();
           from_res[j] = R + ftkx::SR_HEAD + (size_t)before->n + jj;
           from_max[j] = R + ftkx::SR_HEAD + (size_t)before->n + before->k + jj;
@@ -457,10 +447,9 @@ void series_decide_split(ftkx_ctx *c, ftkx_series_pending &P, bool pipelined, bo
 void series_retire_masks(const ftkx_series_pending &P, const std::vector<Slice *> &sl, ftkx_series_pending &before)
 {
   for (size_t j = 0; j < P.k; j ++) {
-    if (P.red_index[j] < 0 || !(sl[j]->M || sl[j]->U)) continue;
+    if (P.red_index[j] < 0 || !(sl[j]->M.p || sl[j]->U.p)) continue;
     if (!std::binary_search(before.slice_ts.begin(), before.slice_ts.end(), P.slice_ts[j])) continue;
-    before.retired.push_back({sl[j]->M, sl[j]->U});
-    sl[j]->M = nullptr; sl[j]->U = nullptr;
+    before.retired.emplace_back(std::move(sl[j]->M), std::move(sl[j]->U));      // (the slice's are empty now)
   }
 }
 
@@ -524,7 +513,7 @@ void series_write_desc(ftkx_ctx *c, const ftkx_series_pending &P, const Mesh &m,
     if (s.have_res) { ss[j].known_res = s.res < cap ? s.res : DBL_MAX; ss[j].known_max = s.maxabs; }
     else if (ri < 0 && !from_res[j]) { ss[j].known_res = s.res_below; ss[j].known_max = s.maxabs; }
     if (from_res[j] && s.sparse) { ss[j].known_res = DBL_MAX; ss[j].known_max = 0.0; }      // (the halo slice: nothing of an earlier pass stands)
-    if (ri >= 0) jobs[ri] = with_lean_thresholds(MaskJob{s.S, s.V, s.M, P.two_level ? s.U : nullptr, B.red.as<u64>() + (size_t)ri * 128, cap, HUGE_VAL}, m);   // rule off: validated by the factor kernel
+    if (ri >= 0) jobs[ri] = with_lean_thresholds(MaskJob{s.S.as<double>(), s.V.as<double>(), s.M.as<unsigned char>(), P.two_level ? s.U.as<unsigned char>() : nullptr, B.red.as<u64>() + (size_t)ri * 128, cap, HUGE_VAL}, m);   // rule off: validated by the factor kernel
   }
   size_t last = 0;
   for (int i = 0; i < P.n; i ++) {
@@ -532,8 +521,8 @@ void series_write_desc(ftkx_ctx *c, const ftkx_series_pending &P, const Mesh &m,
     const Slice &s0 = *sl[(size_t)si[i].slice0];
     Fields f;
     memset(&f, 0, sizeof(f));
-    f.S[0] = s0.S; f.V[0] = s0.V; f.J[0] = s0.J; f.M[0] = s0.M; f.U[0] = P.two_level ? s0.U : nullptr;
-    if (si[i].slice1 >= 0) { const Slice &s1 = *sl[(size_t)si[i].slice1]; f.S[1] = s1.S; f.V[1] = s1.V; f.J[1] = s1.J; f.M[1] = s1.M; f.U[1] = P.two_level ? s1.U : nullptr; }
+    f.S[0] = s0.S.as<double>(); f.V[0] = s0.V.as<double>(); f.J[0] = s0.J.as<double>(); f.M[0] = s0.M.as<unsigned char>(); f.U[0] = P.two_level ? s0.U.as<unsigned char>() : nullptr;
+    if (si[i].slice1 >= 0) { const Slice &s1 = *sl[(size_t)si[i].slice1]; f.S[1] = s1.S.as<double>(); f.V[1] = s1.V.as<double>(); f.J[1] = s1.J.as<double>(); f.M[1] = s1.M.as<unsigned char>(); f.U[1] = P.two_level ? s1.U.as<unsigned char>() : nullptr; }
     f.factor = 0.0; f.t = P.ts[i]; f.scope_mask = P.scopes[i];
     steps[i] = f;
   }
@@ -570,7 +559,7 @@ int series_queue_masks(ftkx_ctx *c, ftkx_series_pending &P, const Mesh &m, const
     size_t done = 0;
     if (first_now) { ev_begin(c, K_MASK); ftkx::launch_masks(m, d_jobs, 1, c->stream); ev_end(c); done = 1; }
     char *out = (char *)dist->masks_out;
-    ftkx::launch_dist_export(m, sl[0]->U, sl[0]->M, ub, (u64 *)out, (unsigned *)(out + off_idx), (u64 *)(out + off_words), cap, factor_log2_of(P.hint), B.dist_block.as<u64>(), c->stream);
+    ftkx::launch_dist_export(m, sl[0]->U.as<unsigned char>(), sl[0]->M.as<unsigned char>(), ub, (u64 *)out, (unsigned *)(out + off_idx), (u64 *)(out + off_words), cap, factor_log2_of(P.hint), B.dist_block.as<u64>(), c->stream);
     if (dist->side) {
       if (!B.ev_export) HIP_TRY(c, hipEventCreateWithFlags(&B.ev_export, hipEventDisableTiming));
       HIP_TRY(c, hipEventRecord(B.ev_export, c->stream));
@@ -1086,7 +1075,7 @@ int ftkx_series_dist_cull(ftkx_ctx *c, const void *masks_in, void *request_out)
       Slice &h = hit->second;
       const char *in = (const char *)masks_in;
       ftkx::launch_dist_import(P.gathered, P.dist_rank, P.dist_nranks, P.running_in, B.dist_block.as<u64>(), tail, (const u64 *)in, (const unsigned *)(in + off_idx), (const u64 *)(in + off_words), ub, cap,
-                               m.u_rows, factor_log2_of(P.hint), h.U, h.M, mask_bytes(c) / 8, c->stream);
+                               m.u_rows, factor_log2_of(P.hint), h.U.as<unsigned char>(), h.M.as<unsigned char>(), mask_bytes(c) / 8, c->stream);
     } else
       ftkx::launch_dist_import(P.gathered, P.dist_rank, P.dist_nranks, P.running_in, B.dist_block.as<u64>(), tail, nullptr, nullptr, nullptr, 0, 0, m.u_rows, 0, nullptr, nullptr, 0, c->stream);
   }
@@ -1101,7 +1090,7 @@ int ftkx_series_dist_cull(ftkx_ctx *c, const void *masks_in, void *request_out)
     P.refined = true;
     u64 *req = (u64 *)request_out;
     const size_t cap = dist_cells_cap(c);
-    ftkx::launch_dist_cells(m, d_steps, T.list.as<u64>(), T.list_capacity, T.refine_capacity, h.S ? h.S : h.V, req, cap, B.dist_block.as<u64>(), B.results.as<u64>(), c->stream);
+    ftkx::launch_dist_cells(m, d_steps, T.list.as<u64>(), T.list_capacity, T.refine_capacity, h.S.p ? h.S.as<double>() : h.V.as<double>(), req, cap, B.dist_block.as<u64>(), B.results.as<u64>(), c->stream);
     P.request_out = req;
   }
   HIP_TRY(c, hipGetLastError());
@@ -1125,7 +1114,7 @@ int ftkx_series_dist_serve(ftkx_ctx *c, const void *request_in, void *reply_out)
     if (it0 == c->slices.end() || it0->second.sparse) return fail(c, FTKX_E_NOSLICE, "ftkx_series_dist_serve: this rank's first slice %d was dropped between the stages", P.slice_ts[0]);
     const Slice &s0 = it0->second;
     const int ncomp = c->scalar_mode == 1 ? 1 : c->nd;
-    ftkx::launch_dist_patches(m, false, (const u64 *)request_in, dist_cells_cap(c), ncomp, c->scalar_mode == 1 ? s0.S : s0.V, (double *)reply_out, B.results.as<u64>() + ftkx::SR_HALO_SERVED, c->stream);
+    ftkx::launch_dist_patches(m, false, (const u64 *)request_in, dist_cells_cap(c), ncomp, (c->scalar_mode == 1 ? s0.S : s0.V).as<double>(), (double *)reply_out, B.results.as<u64>() + ftkx::SR_HALO_SERVED, c->stream);
     HIP_TRY(c, hipGetLastError());
   }
   P.dist_stage = 3;
@@ -1146,7 +1135,7 @@ int ftkx_series_dist_finish(ftkx_ctx *c, const void *reply_in)
     if (hit == c->slices.end() || !hit->second.sparse) return fail(c, FTKX_E_NOSLICE, "ftkx_series_dist_finish: the halo slice %d was dropped or replaced between the stages", P.t_halo);
     Slice &h = hit->second;
     const int ncomp = c->scalar_mode == 1 ? 1 : c->nd;
-    ftkx::launch_dist_patches(m, true, P.request_out, dist_cells_cap(c), ncomp, c->scalar_mode == 1 ? h.S : h.V, const_cast<double *>((const double *)reply_in), nullptr, c->stream);
+    ftkx::launch_dist_patches(m, true, P.request_out, dist_cells_cap(c), ncomp, (c->scalar_mode == 1 ? h.S : h.V).as<double>(), const_cast<double *>((const double *)reply_in), nullptr, c->stream);
   }
   int rc;
   if ((rc = series_queue_tail(c, P))) return rc;

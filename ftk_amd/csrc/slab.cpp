@@ -128,7 +128,7 @@ const void *rb_first_slice(void *u, int t)
   ftkx_ctx *c = (ftkx_ctx *)u;
   auto it = c->slices.find(t);
   if (it == c->slices.end() || it->second.sparse) return nullptr;
-  return c->scalar_mode == 1 ? (const void *)it->second.S : (const void *)it->second.V;
+  return (c->scalar_mode == 1 ? it->second.S : it->second.V).p;
 }
 void *rb_alloc(void *u, size_t bytes)
 {

@@ -515,6 +515,11 @@ int ftkx_conv3D_f32(ftkx_ctx *ctx, const float *S, int DW, int DH, int DD, const
 int ftkx_debug_widen_relaunch(ftkx_ctx *ctx, const float *src, size_t count, double *dst, int reps, double *ms);
 /* how many float32 arrays this context was pushed went through the widen kernel, and how many straight through the convolution */
 int ftkx_debug_f32_counts(const ftkx_ctx *ctx, unsigned long long *widened, unsigned long long *convolved_direct);
+/* test aid: the context's slice arrays by class -- [0] field arrays (the S / V / J copies of slices, staging arrays, the temporal ring),
+ * [1] mask arrays, [2] summary arrays.  allocated: how many the context has had to allocate since it was made (an array taken out of its
+ * pool is not counted; neither is one the caller lent with on_device = 1); pooled: how many lie in the pool right now, held by no slice.
+ * Either may be null.  Reads the context, changes nothing. */
+int ftkx_debug_array_counts(const ftkx_ctx *ctx, unsigned long long allocated[3], unsigned long long pooled[3]);
 
 /* test aid: the ordering step of the device-driven pass completed last on this context (ftkx_sweep_series, ftkx_sweep_series_complete), as
  * it ran: out[0] the number of buckets, out[1] the shift that takes an order key to its bucket, out[2] the fullest bucket, out[3] the

@@ -3,7 +3,11 @@
 ftkx_block over malloc and free, counts their calls and checks: a reserve at or below `bytes` does nothing; a growing one drains (only
 with a stream, only when the block held memory), then frees once, then allocates `alloc` bytes and reports fresh memory; a failed
 allocation leaves the block empty with the out-of-memory status and the next reserve succeeds; moving empties the source; an owning
-block is freed exactly once; and the patch staging that was admitted by cells (4 >= 4) and overran grows when admitted by bytes."""
+block is freed exactly once; and the patch staging that was admitted by cells (4 >= 4) and overran grows when admitted by bytes.
+The lent kind: never passed to ftkx_block_free, a move empties the source, reserve is an error, the pool lets it go.  The pool of the
+slice arrays (ftkx_array_pool): a take after a give of the same class and bytes returns the same memory; never another class's, never for
+more or fewer bytes; newest first; the cap frees the surplus once; clear frees all; a failed allocation leaves nothing behind; and an array
+of the old lattice that comes back after the pool was cleared for a larger one is not handed out for the larger one."""
 import os
 import subprocess
 
