@@ -86,6 +86,8 @@ class Context:
         _lib.check(self._L.ftkx_create(C.byref(self._h), nd, device_id))
         self._keep = {}
         self._smoothing = False
+        self._perturbing = False
+        self._clamping = False
 
     def close(self):
         if self._h:
@@ -131,6 +133,40 @@ class Context:
         rc = self._L.ftkx_set_spatial_smoothing(self._h, float(sigma), int(ksize))
         self._ck(rc)                                   # (raises: a refused setting leaves the context, and this flag, as they were)
         self._smoothing = int(ksize) != 0
+
+    def set_perturbation(self, sigma, seed=0):
+        """ftkx_set_perturbation: every snapshot pushed from now on gets sigma * N(0, 1) noise added on the device, the noise of element e of
+        timestep t being a function of (seed, t, e) alone; sigma 0: off"""
+        self._ck(self._L.ftkx_set_perturbation(self._h, float(sigma), int(seed)))
+        self._perturbing = float(sigma) > 0
+
+    def set_clamp(self, lo=None, hi=None):
+        """ftkx_set_clamp: every snapshot pushed from now on becomes min(max(lo, x), hi) on the device (behind the perturbation); no bounds: off"""
+        on = lo is not None or hi is not None
+        if on and (lo is None or hi is None):
+            raise ValueError("set_clamp: both bounds, or none")
+        self._ck(self._L.ftkx_set_clamp(self._h, int(on), float(lo) if on else 0.0, float(hi) if on else 0.0))
+        self._clamping = on
+
+    def adjust(self, src_ptr, count, dst_ptr, sigma=0.0, seed=0, t=0, clamp=None, f32=False):
+        """ftkx_adjust / ftkx_adjust_f32 on device pointers: dst[e] = clamp(double(src[e]) + sigma * z(seed, t, e)); clamp: (lo, hi) or None;
+        dst_ptr == src_ptr is allowed for doubles"""
+        lo, hi = clamp if clamp is not None else (0.0, 0.0)
+        self._ck((self._L.ftkx_adjust_f32 if f32 else self._L.ftkx_adjust)(self._h, src_ptr, int(count), float(sigma), int(seed), int(t), int(clamp is not None), float(lo), float(hi), dst_ptr))
+
+    def debug_adjust_relaunch(self, src_ptr, count, dst_ptr, reps, sigma=0.0, seed=0, t=0, clamp=None, f32=False):
+        """profiling aid: the adjust kernel `reps` times back to back -> device ms per launch (HIP events)"""
+        lo, hi = clamp if clamp is not None else (0.0, 0.0)
+        ms = (C.c_double * int(reps))()
+        self._ck(self._L.ftkx_debug_adjust_relaunch(self._h, src_ptr, int(bool(f32)), int(count), float(sigma), int(seed), int(t), int(clamp is not None), float(lo), float(hi), dst_ptr,
+                                                    int(reps), ms))
+        return list(ms)
+
+    def adjust_counts(self):
+        """(from_float, in_place, out_of_place): snapshots pushed into this context that went through the adjust kernel, by its kind"""
+        a = C.c_ulonglong(0); b = C.c_ulonglong(0); c = C.c_ulonglong(0)
+        self._ck(self._L.ftkx_debug_adjust_counts(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return int(a.value), int(b.value), int(c.value)
 
     def set_temporal_smoothing(self, sigma, ksize=5, t0=0):
         """ftkx_set_temporal_smoothing: a series of raw snapshots for temporal_push starts, its first emission being timestep t0; ksize 0: off"""
@@ -184,7 +220,8 @@ class Context:
         on_dev = devs.pop()
         f32 = _same_type(*[f for p, f in ((pv, fv), (pj, fj), (ps, fs)) if p is not None])
         self._ck((self._L.ftkx_push_slice_f32 if f32 else self._L.ftkx_push_slice)(self._h, t, pv, pj, ps, on_dev))
-        self._keep[t] = (kv, kj, ks) if on_dev and not f32 else None       # (float32: read before the call returned, the context owns FP64 copies)
+        owned = f32 or self._perturbing or self._clamping
+        self._keep[t] = (kv, kj, ks) if on_dev and not owned else None       # (float32, perturbation, clamp: read before the call returned, the context owns FP64 copies)
 
     def push_scalar_slice(self, t, S, on_device=None):
         """on_device: None = 0 for a host array, 1 (borrowed) for a device tensor; 2: a device tensor, copied"""
@@ -194,7 +231,8 @@ class Context:
                 raise ValueError("on_device: 0 for a host array, 1 or 2 for a device tensor")
             ds = int(on_device)
         self._ck((self._L.ftkx_push_scalar_slice_f32 if f32 else self._L.ftkx_push_scalar_slice)(self._h, t, ps, ds))
-        self._keep[t] = ks if ds == 1 and not self._smoothing and not f32 else None     # (2, smoothing, float32: the context owns a copy)
+        owned = self._smoothing or self._perturbing or self._clamping or f32
+        self._keep[t] = ks if ds == 1 and not owned else None     # (2, smoothing, perturbation, clamp, float32: the context owns a copy)
 
     def drop_slice(self, t):
         self._ck(self._L.ftkx_drop_slice(self._h, t))
@@ -877,6 +915,18 @@ class _TrackerRegular:
         """before initialize(): every scalar snapshot is smoothed on the device like the reference stream's --spatial-smoothing-kernel
         (conv_gaussian(snapshot, sigma, ksize, ksize // 2)); ksize 0: off"""
         self._ck(self._L.ftkx_tracker_set_spatial_smoothing(self._h, float(sigma), int(ksize)))
+
+    def set_perturbation(self, sigma, seed=0):
+        """before initialize(): every snapshot gets sigma * N(0, 1) noise on the device like the reference stream's "perturbation", the noise
+        of element e of timestep t being a function of (seed, t, e) alone; sigma 0: off"""
+        self._ck(self._L.ftkx_tracker_set_perturbation(self._h, float(sigma), int(seed)))
+
+    def set_clamp(self, lo=None, hi=None):
+        """before initialize(): every snapshot becomes min(max(lo, x), hi) on the device like the reference stream's "clamp"; no bounds: off"""
+        on = lo is not None or hi is not None
+        if on and (lo is None or hi is None):
+            raise ValueError("set_clamp: both bounds, or none")
+        self._ck(self._L.ftkx_tracker_set_clamp(self._h, int(on), float(lo) if on else 0.0, float(hi) if on else 0.0))
 
     def set_temporal_smoothing(self, sigma, ksize=5):
         """before initialize(): the pushed snapshots are raw and feed the reference stream's temporal filter on the device; the tracker sees

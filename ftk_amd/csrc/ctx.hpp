@@ -23,6 +23,7 @@
 #include "pass2_layout.hpp"
 #include "ctx_block.hpp"
 #include "temporal_steps.hpp"
+#include "adjust_steps.hpp"
 
 struct ftkx_phase_clock;
 
@@ -55,6 +56,7 @@ void launch_jacobian3d(const double *V, int DW, int DH, int DD, double *J, hipSt
 void launch_resolution(const double *p, size_t n, u64 *out2, hipStream_t st);
 template <class SRC> void launch_conv(int nd, const SRC *S, int DW, int DH, int DD, const double *d_weights, int ksize, double *out, hipStream_t st);   // conv_kernels.hip: SRC double or float
 void launch_widen(const float *src, size_t count, double *dst, hipStream_t st);   // widen_kernels.hip
+template <class T> void launch_adjust(const T *src, size_t count, bool perturb, bool clamp, const AdjustArgs &a, double *dst, hipStream_t st);   // adjust_kernels.hip: T double or float; src == dst allowed
 void launch_temporal(const double *const *arrays, int ksize, const double *weights, size_t count, double *out, hipStream_t st);   // temporal_kernels.hip
 void launch_calib_read(const void *p, size_t bytes, double *scratch, hipStream_t stream);
 const char *last_mask_kernel();
@@ -317,6 +319,18 @@ struct ftkx_ctx {
   ftkx_block f32_stage;
   hipStream_t f32_stage_reader = nullptr;      // the stream of the kernel that read it last
   unsigned long long f32_widened = 0, f32_direct = 0;   // ftkx_debug_f32_counts: float32 arrays through the widen kernel / straight through the convolution
+  // perturbation and clamp (ftkx_set_perturbation, ftkx_set_clamp; adjust_steps.hpp): both off by default.  While either is on, every
+  // snapshot pushed is adjusted by ONE kernel on the context's stream behind the widening and the spatial smoothing and in front of the
+  // temporal ring (the stream's order), with its timestep as the noise's snapshot number.  The counters: ftkx_debug_adjust_counts.
+  struct Adjust {
+    double sigma = 0, lo = 0, hi = 0;
+    unsigned long long seed = 0;
+    bool perturb = false, clamp = false;
+    bool on() const { return perturb || clamp; }
+  } adj;
+  unsigned long long tm_pushed = 0;            // raw pushes of the temporal series so far: t0 + tm_pushed is the next raw snapshot's number
+  int tm_t0 = 0;
+  unsigned long long adj_from_float = 0, adj_in_place = 0, adj_out_of_place = 0;
   std::vector<ftkxh::Request> pending;
   // Cull-ahead: the sweeps the caller announced (ftkx_sweep_announce) for the slices of the next ftkx_slices_prepare, and -- once that
   // call has queued their cull right behind the mask kernel -- the survivor list it left on the device.  The cull needs the masks

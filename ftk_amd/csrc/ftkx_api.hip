@@ -553,9 +553,34 @@ extern "C++" {      // (templates on the source's element type)
 // for an event recorded on the context's stream unless that stream is idle (upload.cpp, E.gate); a peer copy is queued on the context's
 // stream; a block that has to grow is freed only after the stream of its last reader has been waited for (reserve's drain).  All of that
 // holds for ONE stream: where ftkx_set_stream has changed it since the last reader was queued, that reader's stream is waited for here.
-template <class T> static int stage_into(ftkx_ctx *c, const T *src, size_t count, int on_device, bool smooth, double *dst)
+//
+// Perturbation and clamp (ftkx_set_perturbation, ftkx_set_clamp), where either is on: `t` is the snapshot's number, and the adjust kernel
+// (adjust_kernels.hip) is the LAST kernel of the chain -- the stream's order, widen -> conv -> perturb -> clamp.  Without smoothing it is the
+// only kernel: a float source goes through adjust_kernel<float> in place of the widen kernel; a host FP64 source (and one on another
+// device) is brought straight into dst and adjusted in place, no staging array; an FP64 source on this device is read where it lies and
+// written adjusted into dst.  With smoothing the convolution runs as ever and adjust_kernel<double> runs in place on its output.  With
+// both settings off nothing here is queued that was not queued before there were such settings.
+template <class T> static void queue_adjust(ftkx_ctx *c, const T *from, size_t count, int t, double *dst)
+{
+  const ftkx::AdjustArgs a{c->adj.sigma, c->adj.seed, t, c->adj.lo, c->adj.hi};
+  ftkx::launch_adjust<T>(from, count, c->adj.perturb, c->adj.clamp, a, dst, c->stream);
+  if (std::is_same<T, float>::value) c->adj_from_float ++;
+  else if ((const void *)from == (const void *)dst) c->adj_in_place ++;
+  else c->adj_out_of_place ++;
+}
+
+template <class T> static int stage_into(ftkx_ctx *c, const T *src, size_t count, int on_device, bool smooth, double *dst, int t)
 {
   constexpr bool f32 = std::is_same<T, float>::value;
+  const bool adjust = c->adj.on();
+  if constexpr (!f32) if (!smooth && adjust) {
+    const bool here = on_device != 0 && ftkx_pointer_device(src) == c->device;
+    if (on_device == 0) { if (int rc = upload_from_host(c, dst, src, count * sizeof(T))) return rc; }
+    else if (!here && hipMemcpyAsync(dst, src, count * sizeof(T), hipMemcpyDefault, c->stream) != hipSuccess) return fail(c, FTKX_E_DEVICE, "push: copy of the source failed");
+    queue_adjust<double>(c, here ? src : dst, count, t, dst);
+    HIP_TRY(c, hipGetLastError());
+    return FTKX_OK;
+  }
   if (!f32 && !smooth) {
     // 0: host memory; 2: device memory of ANY device (a multi-device tracker hands one snapshot to two contexts), copied
     if (on_device == 0) return upload_from_host(c, dst, src, count * sizeof(T));
@@ -588,9 +613,10 @@ template <class T> static int stage_into(ftkx_ctx *c, const T *src, size_t count
   if (smooth) {
     ftkx::launch_conv<T>(c->nd, from, (int)c->ext_sz[0], (int)c->ext_sz[1], (int)c->ext_sz[2], c->d_conv_w.as<double>() + kSmoothWeights, c->smooth_ksize, dst, c->stream);
     if (f32) c->f32_direct ++;
+    if (adjust) queue_adjust<double>(c, dst, count, t, dst);
   } else if constexpr (f32) {
-    ftkx::launch_widen(from, count, dst, c->stream);
-    c->f32_widened ++;
+    if (adjust) queue_adjust<float>(c, from, count, t, dst);
+    else { ftkx::launch_widen(from, count, dst, c->stream); c->f32_widened ++; }
   }
   const hipError_t e = hipGetLastError();
   if (tmp.p) give_pooled(c, std::move(tmp));
@@ -607,6 +633,9 @@ template <class T> static int push_common(ftkx_ctx *c, int t, const T *V, const 
   if (int rc = push_checks(c, t, on_device, scalar_only, scalar_only ? S != nullptr : V != nullptr)) return rc;
   // conv_gaussian dispatches on the array's nd(): a vector field would be convolved across its components (conv.hh:213-221) -- not reproduced
   if (c->smooth_ksize && !scalar_only) return fail(c, FTKX_E_UNSUPPORTED, "push: spatial smoothing is set and takes scalar slices only (ftkx_push_scalar_slice)");
+  // the stream delivers ONE array, which perturb() and clamp() walk over (all n * nd elements of a vector field, by their flat index)
+  const bool adjust = c->adj.on();
+  if (adjust && !scalar_only && (J || S)) return fail(c, FTKX_E_UNSUPPORTED, "push: perturbation or clamp is set and takes V alone (no J, no S beside it)");
   HIP_TRY(c, hipSetDevice(c->device));
   evict_slice(c, t);
   Slice s;
@@ -615,9 +644,9 @@ template <class T> static int push_common(ftkx_ctx *c, int t, const T *V, const 
   // (smoothing applies to S alone: vector pushes were refused above)
   auto take = [&](const T *src, size_t count, bool smooth, ftkx_block &dst) -> int {
     if (!src) return FTKX_OK;
-    if constexpr (!f32) if (on_device == 1 && !smooth) { dst = ftkx_block::lent(const_cast<double *>(src), count * sizeof(double)); return FTKX_OK; }      // adopted as it is
+    if constexpr (!f32) if (on_device == 1 && !smooth && !adjust) { dst = ftkx_block::lent(const_cast<double *>(src), count * sizeof(double)); return FTKX_OK; }      // adopted as it is
     if (int rc = take_pooled(c, count, dst)) return rc;
-    return stage_into(c, src, count, on_device, smooth, dst.as<double>());
+    return stage_into(c, src, count, on_device, smooth, dst.as<double>(), t);
   };
   if (int rc = take(S, n, c->smooth_ksize != 0, s.S)) return rc;      // (here and below: what was already taken is freed with `s`)
   if (!scalar_only) {
@@ -628,8 +657,8 @@ template <class T> static int push_common(ftkx_ctx *c, int t, const T *V, const 
   // reference's exact operations (ndarray/grad.hh), so the slice costs 8 bytes per vertex of HBM instead of 8 + 8*nd.
   // the source buffers may be reused by the caller on return: a device source (2) has to be read first; a host source has been staged
   // completely by upload_from_host (nothing to wait for: the DMAs run on while the caller produces its next snapshot)
-  // (smoothing, and a float32 source: a borrowed array (1) is read by the kernel and never adopted -- the call returns once it has been read, like 2)
-  if (on_device == 2 || (on_device == 1 && (c->smooth_ksize || f32))) HIP_TRY(c, hipStreamSynchronize(c->stream));
+  // (smoothing, perturbation or clamp, and a float32 source: a borrowed array (1) is read by the kernel and never adopted -- the call returns once it has been read, like 2)
+  if (on_device == 2 || (on_device == 1 && (c->smooth_ksize || f32 || adjust))) HIP_TRY(c, hipStreamSynchronize(c->stream));
   install_slice(c, t, s, scalar_only);
   return FTKX_OK;
 }
@@ -995,6 +1024,104 @@ int ftkx_debug_widen_relaunch(ftkx_ctx *c, const float *src, size_t count, doubl
   return rc;
 }
 
+// ---- perturbation and clamp (adjust_kernels.hip) ---------------------------------------------------------------------------------------------
+static int adjust_settings(ftkx_ctx *c, const char *who, double sigma, int clamp_on, double lo, double hi, bool need_one)
+{
+  if (!std::isfinite(sigma) || sigma < 0) return fail(c, FTKX_E_INVALID, "%s: sigma must be finite and not negative", who);
+  if (clamp_on && (std::isnan(lo) || std::isnan(hi))) return fail(c, FTKX_E_INVALID, "%s: a clamp bound is NaN", who);
+  if (need_one && sigma == 0 && !clamp_on) return fail(c, FTKX_E_INVALID, "%s: neither perturbation (sigma > 0) nor clamp asked for", who);
+  return FTKX_OK;
+}
+
+static int adjust_not_now(ftkx_ctx *c, const char *who)
+{
+  if (!c->pending.empty()) return fail(c, FTKX_E_INVALID, "%s: sweeps pending, collect first", who);
+  if (c->sr_open && !c->sr_internal) return fail(c, FTKX_E_INVALID, "%s: series passes open (ftkx_sweep_series_submit), complete them first", who);
+  return FTKX_OK;
+}
+
+int ftkx_set_perturbation(ftkx_ctx *c, double sigma, unsigned long long seed)
+{
+  if (c) c->ahead.clear();
+  if (!c) return fail(nullptr, FTKX_E_INVALID, "null context");
+  if (int rc = adjust_not_now(c, "ftkx_set_perturbation")) return rc;
+  if (int rc = adjust_settings(c, "ftkx_set_perturbation", sigma, 0, 0, 0, false)) return rc;
+  c->adj.perturb = sigma > 0; c->adj.sigma = sigma; c->adj.seed = seed;
+  return FTKX_OK;
+}
+
+int ftkx_set_clamp(ftkx_ctx *c, int on, double lo, double hi)
+{
+  if (c) c->ahead.clear();
+  if (!c) return fail(nullptr, FTKX_E_INVALID, "null context");
+  if (int rc = adjust_not_now(c, "ftkx_set_clamp")) return rc;
+  if (int rc = adjust_settings(c, "ftkx_set_clamp", 0, on, lo, hi, false)) return rc;
+  c->adj.clamp = on != 0; c->adj.lo = on ? lo : 0; c->adj.hi = on ? hi : 0;
+  return FTKX_OK;
+}
+
+extern "C++" {
+template <class T> static int adjust_args(ftkx_ctx *c, const char *who, const T *src, size_t count, double sigma, int clamp_on, double lo, double hi, const double *dst)
+{
+  if (!src || !dst) return fail(c, FTKX_E_INVALID, "%s: null argument", who);
+  if (count < 1) return fail(c, FTKX_E_INVALID, "%s: count must be positive", who);
+  if (((size_t)src & (sizeof(T) - 1)) || ((size_t)dst & 7)) return fail(c, FTKX_E_INVALID, "%s: src must be a multiple of its element's size and dst a multiple of 8", who);
+  if ((const void *)src != (const void *)dst && (const char *)src < (const char *)(dst + count) && (const char *)dst < (const char *)(src + count))
+    return fail(c, FTKX_E_INVALID, "%s: input and output overlap (and are not the same array)", who);
+  return adjust_settings(c, who, sigma, clamp_on, lo, hi, true);
+}
+
+template <class T> static int adjust_common(ftkx_ctx *c, const char *who, const T *src, size_t count, double sigma, unsigned long long seed, int t, int clamp_on, double lo, double hi,
+                                            double *dst, int reps, double *ms)
+{
+  DERIVE_PROLOGUE(c);
+  if (ms ? reps < 1 : reps != 1) return fail(c, FTKX_E_INVALID, "%s: bad argument", who);
+  if (int rc = adjust_args<T>(c, who, src, count, sigma, clamp_on, lo, hi, dst)) return rc;
+  const ftkx::AdjustArgs a{sigma, seed, t, lo, hi};
+  std::vector<hipEvent_t> ev(ms ? 2 * (size_t)reps : 0, nullptr);
+  auto run = [&]() -> int {
+    for (hipEvent_t &e : ev) HIP_TRY(c, hipEventCreate(&e));
+    for (int i = 0; i < reps; i ++) {
+      if (ms) HIP_TRY(c, hipEventRecord(ev[2 * (size_t)i], c->stream));
+      ftkx::launch_adjust<T>(src, count, sigma > 0, clamp_on != 0, a, dst, c->stream);
+      if (ms) HIP_TRY(c, hipEventRecord(ev[2 * (size_t)i + 1], c->stream));
+    }
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));      // (the caller may read `dst`)
+    for (int i = 0; ms && i < reps; i ++) { float tt = 0; HIP_TRY(c, hipEventElapsedTime(&tt, ev[2 * (size_t)i], ev[2 * (size_t)i + 1])); ms[i] = tt; }
+    return FTKX_OK;
+  };
+  const int rc = run();
+  if (rc) (void)hipStreamSynchronize(c->stream);
+  for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+  return rc;
+}
+}  // extern "C++"
+
+int ftkx_adjust(ftkx_ctx *c, const double *src, size_t count, double sigma, unsigned long long seed, int t, int clamp_on, double lo, double hi, double *dst)
+{ return adjust_common<double>(c, "ftkx_adjust", src, count, sigma, seed, t, clamp_on, lo, hi, dst, 1, nullptr); }
+int ftkx_adjust_f32(ftkx_ctx *c, const float *src, size_t count, double sigma, unsigned long long seed, int t, int clamp_on, double lo, double hi, double *dst)
+{ return adjust_common<float>(c, "ftkx_adjust_f32", src, count, sigma, seed, t, clamp_on, lo, hi, dst, 1, nullptr); }
+
+// profiling aid (tools/adjust_time.py): the adjust kernel `reps` times back to back, a pair of events around every launch.  In place with
+// sigma > 0 every launch perturbs what the one before left: the time is the same, the values are not those of one launch.
+int ftkx_debug_adjust_relaunch(ftkx_ctx *c, const void *src, int src_is_f32, size_t count, double sigma, unsigned long long seed, int t, int clamp_on, double lo, double hi,
+                               double *dst, int reps, double *ms)
+{
+  if (c && !ms) return fail(c, FTKX_E_INVALID, "ftkx_debug_adjust_relaunch: bad argument");
+  if (src_is_f32) return adjust_common<float>(c, "ftkx_debug_adjust_relaunch", (const float *)src, count, sigma, seed, t, clamp_on, lo, hi, dst, reps, ms);
+  return adjust_common<double>(c, "ftkx_debug_adjust_relaunch", (const double *)src, count, sigma, seed, t, clamp_on, lo, hi, dst, reps, ms);
+}
+
+int ftkx_debug_adjust_counts(const ftkx_ctx *c, unsigned long long *from_float, unsigned long long *in_place, unsigned long long *out_of_place)
+{
+  if (!c) return fail(nullptr, FTKX_E_INVALID, "null context");
+  if (from_float) *from_float = c->adj_from_float;
+  if (in_place) *in_place = c->adj_in_place;
+  if (out_of_place) *out_of_place = c->adj_out_of_place;
+  return FTKX_OK;
+}
+
 // profiling aid (tools/conv_time.py): the convolution kernel `reps` times back to back, a pair of events around every launch
 int ftkx_debug_conv_relaunch(ftkx_ctx *c, int nd, const double *S, int DW, int DH, int DD, const double *weights, int ksize, double *out, int reps, double *ms)
 {
@@ -1188,7 +1315,10 @@ template <class T> static int temporal_push_common(ftkx_ctx *c, const T *A, int 
   if (on_device != 0 && !c->tm_read) HIP_TRY(c, hipEventCreateWithFlags(&c->tm_read, hipEventDisableTiming));
   ftkx_block slot;      // (what it holds after a failure is unknown: freed with this call, not pooled)
   if (int rc = take_pooled(c, count, slot)) return rc;
-  if (int rc = stage_into(c, A, count, on_device, c->smooth_ksize != 0, slot.as<double>())) return rc;      // widened where it is float32, convolved where smoothing is set
+  // widened where it is float32, convolved where smoothing is set, perturbed and clamped where those are set -- as raw snapshot number t0 + the
+  // pushes of this series so far, which is the timestep of the emission centred on it
+  if (c->tm.kind < 0 && c->tm.size == 0) { c->tm_t0 = c->tm_next; c->tm_pushed = 0; }      // the series' first snapshot
+  if (int rc = stage_into(c, A, count, on_device, c->smooth_ksize != 0, slot.as<double>(), c->tm_t0 + (int)c->tm_pushed)) return rc;
   // A device source has to be read before the caller may overwrite it (a host source has been staged completely by upload_from_host):
   // the call ends by waiting for THIS point of the stream, not for the stream -- sweeps queued before the push (deferred collection) and
   // the emission queued behind it run on.
@@ -1204,6 +1334,7 @@ template <class T> static int temporal_push_common(ftkx_ctx *c, const T *A, int 
     c->tm_ring.push_back(std::move(slot));
     c->tm = next;
   }
+  c->tm_pushed ++;
   if (on_device != 0) HIP_TRY(c, hipEventSynchronize(c->tm_read));
   return FTKX_OK;
 }

@@ -521,6 +521,42 @@ int ftkx_debug_f32_counts(const ftkx_ctx *ctx, unsigned long long *widened, unsi
  * Either may be null.  Reads the context, changes nothing. */
 int ftkx_debug_array_counts(const ftkx_ctx *ctx, unsigned long long allocated[3], unsigned long long pooled[3]);
 
+/* ---- perturbation and clamp of snapshots (ndarray::perturb, ndarray::clamp; the stream's "perturbation" and "clamp") ---- */
+/* The two steps ndarray_stream::modified_callback (stream.hh:1570-1604) runs between the spatial smoothing and the temporal filter:
+ *     widen -> conv_gaussian -> perturb(sigma) -> clamp(lo, hi) -> temporal filter -> tracker
+ * Both are off by default; with both off every push queues exactly the kernels it queued before.  While either is on, every snapshot pushed
+ * (ftkx_push_scalar_slice, ftkx_push_slice with V alone, ftkx_temporal_push, and their _f32 forms) is adjusted on the device by ONE kernel
+ * behind the widening and the smoothing: a float32 source goes through it in place of the widen kernel; a host FP64 source is uploaded
+ * straight into the slice's array and adjusted in place; a device FP64 source is read where it lies and written adjusted into an array of
+ * the context's own; a smoothed snapshot is adjusted in place behind the convolution.  With on_device = 1 the caller's array is read, never
+ * written and NOT adopted, and the call returns once it has been read -- what smoothing does.  A snapshot that enters the temporal ring
+ * enters it adjusted.  ftkx_push_slice with J or S beside V fails with FTKX_E_UNSUPPORTED: the stream delivers one array.  For a vector
+ * snapshot all n * nd values are adjusted, the element index being the flat one.  Like smoothing, every push is taken for a RAW snapshot;
+ * ftkx_slab_* set the adjustment aside where they push a neighbour's resident slice whole.
+ * clamp: p[i] = std::min(std::max(lo, p[i]), hi), bit for bit -- m = (lo < x) ? x : lo; out = (hi < m) ? hi : m.  A NaN becomes lo (hi
+ * where hi < lo); -0.0 under lo = +0.0 becomes +0.0; lo > hi is legal and makes everything hi.  A NaN bound is FTKX_E_INVALID.
+ * perturbation: the reference adds std::normal_distribution<>{0, sigma} from an std::mt19937 seeded by std::random_device, different on
+ * every run.  Reproduced is the distribution: p[e] += sigma * z, z independent N(0, 1), DEFINED as a pure function of (seed, the
+ * snapshot's number t, the element index e) -- Philox4x32-10 with counter (e >> 1, t, 0) and key seed, 52 bits to a uniform in (0, 1),
+ * Wichura's AS 241 PPND16 (ftk_amd/csrc/adjust_steps.hpp) -- whatever the launch, the path, the device, the rank or the context: two
+ * contexts handed the same snapshot add the same noise.  t is the timestep the snapshot is pushed as; in a temporal series, t0 plus the
+ * number of snapshots pushed before it.  sigma 0: off.  A negative or non-finite sigma is FTKX_E_INVALID.
+ * Both are refused while sweeps are pending or series passes are open, like ftkx_set_spatial_smoothing. */
+int ftkx_set_perturbation(ftkx_ctx *ctx, double sigma, unsigned long long seed);
+int ftkx_set_clamp(ftkx_ctx *ctx, int on, double lo, double hi);
+/* The bare kernel: dst[e] = clamp(double(src[e]) + sigma * z(seed, t, e), lo, hi) for e < count -- the perturbation left out where sigma is
+ * 0, the clamp where clamp_on is 0 (one of them must be asked for).  DEVICE pointers; src a multiple of its element's size, dst of 8 bytes
+ * (a pair of elements is one access where src is a multiple of two elements and dst of 16 bytes); dst == src is allowed (ftkx_adjust), any
+ * other overlap is not.  The call returns when `dst` is complete. */
+int ftkx_adjust(ftkx_ctx *ctx, const double *src, size_t count, double sigma, unsigned long long seed, int t, int clamp_on, double lo, double hi, double *dst);
+int ftkx_adjust_f32(ftkx_ctx *ctx, const float *src, size_t count, double sigma, unsigned long long seed, int t, int clamp_on, double lo, double hi, double *dst);
+/* profiling aid (tools/adjust_time.py): the kernel of ftkx_adjust (src_is_f32 != 0: of ftkx_adjust_f32) launched `reps` times back to back
+ * on the context's stream, a pair of events around every launch; ms: reps device times. */
+int ftkx_debug_adjust_relaunch(ftkx_ctx *ctx, const void *src, int src_is_f32, size_t count, double sigma, unsigned long long seed, int t, int clamp_on, double lo, double hi,
+                               double *dst, int reps, double *ms);
+/* how many snapshots this context was pushed went through the adjust kernel: from a float32 source, FP64 in place, FP64 out of place */
+int ftkx_debug_adjust_counts(const ftkx_ctx *ctx, unsigned long long *from_float, unsigned long long *in_place, unsigned long long *out_of_place);
+
 /* test aid: the ordering step of the device-driven pass completed last on this context (ftkx_sweep_series, ftkx_sweep_series_complete), as
  * it ran: out[0] the number of buckets, out[1] the shift that takes an order key to its bucket, out[2] the fullest bucket, out[3] the
  * size up to which a bucket was ranked on the device (fuller ones: the host orders them, status bit 16).  All zero where the pass's records

@@ -170,6 +170,15 @@ public:
   // FTKX_E_UNSUPPORTED while it is on.  reset() empties the filter.  Slab mode and multi-device trackers: initialize() throws
   // FTKX_E_UNSUPPORTED (a slab would need ksize / 2 raw halo snapshots of each neighbour).
   void set_temporal_smoothing(double sigma, int ksize = 5) { temporal_smoothing_sigma = sigma; temporal_smoothing_ksize = ksize; }
+  // The stream's "perturbation" and "clamp" (ndarray_stream::modified_callback, stream.hh:1570-1604: ndarray::perturb, ndarray::clamp), on
+  // the device and in the stream's order: behind the spatial smoothing, in front of the temporal filter (ftkx_set_perturbation,
+  // ftkx_set_clamp).  The noise added to element e of the snapshot pushed as timestep t is a function of (seed, t, e) alone, so slab ranks
+  // and the contexts of a multi-device tracker add what a single tracker adds.  clamp: min(max(lo, x), hi) as the reference writes it (lo > hi
+  // is legal).  Set before initialize(); sigma 0 / unset_clamp(): off (the default).  While either is on a snapshot is ONE array:
+  // push_field_data_snapshot throws FTKX_E_UNSUPPORTED.
+  void set_perturbation(double sigma, unsigned long long seed = 0) { perturbation_sigma = sigma; perturbation_seed = seed; }
+  void set_clamp(double lo, double hi) { clamp_on = true; clamp_lo = lo; clamp_hi = hi; }
+  void unset_clamp() { clamp_on = false; }
   int snapshots_from_last_push() const { return last_push_snapshots; }      // 0 or 1; always 1 with the filter off
   bool flush_temporal_smoothing();
   // Several RANKS behind the tracker -- one process per GPU, or one tracker per device and thread in one process.  The reference keeps an
@@ -295,6 +304,9 @@ protected:
   bool trace_on_device = false;
   double spatial_smoothing_sigma = 0;
   int spatial_smoothing_ksize = 0;
+  double perturbation_sigma = 0, clamp_lo = 0, clamp_hi = 0;
+  unsigned long long perturbation_seed = 0;
+  bool clamp_on = false;
   double temporal_smoothing_sigma = 0;
   int temporal_smoothing_ksize = 0;
   int last_push_snapshots = 1;
@@ -379,6 +391,8 @@ int  ftkx_tracker_set_flags(ftkx_tracker *, int robust, int use_type_filter, uns
 int  ftkx_tracker_set_stream(ftkx_tracker *, void *hip_stream);
 int  ftkx_tracker_set_current_timestep(ftkx_tracker *, int t);
 int  ftkx_tracker_set_spatial_smoothing(ftkx_tracker *, double sigma, int ksize);   /* the stream's spatial smoothing in front of the tracker; ksize 0: off */
+int  ftkx_tracker_set_perturbation(ftkx_tracker *, double sigma, unsigned long long seed);   /* the stream's perturbation in front of the tracker; sigma 0: off */
+int  ftkx_tracker_set_clamp(ftkx_tracker *, int on, double lo, double hi);                  /* the stream's clamp in front of the tracker */
 int  ftkx_tracker_set_temporal_smoothing(ftkx_tracker *, double sigma, int ksize);  /* the stream's temporal smoothing in front of the tracker; ksize 0: off */
 int  ftkx_tracker_snapshots_from_last_push(const ftkx_tracker *, int *n);           /* 0 or 1: did the last push_* append a (smoothed) snapshot */
 int  ftkx_tracker_flush_temporal_smoothing(ftkx_tracker *, int *appended);          /* one trailing snapshot per call; *appended = 0: none left */
