@@ -43,6 +43,43 @@ def _same_type(*f32):
     return bool(kinds and kinds.pop())
 
 
+def _planes(planes):
+    """a vector snapshot as component planes -> (ctypes array of nc addresses, nc, keepalive, on_device, f32).  planes: a sequence of nc numpy
+    arrays / torch tensors of one dtype (float32 or float64) and one size, each contiguous; or ONE contiguous array / tensor of shape
+    (nc, ...), whose nc leading slices are the planes.  Nothing is copied: what is not contiguous is refused."""
+    whole = planes if isinstance(planes, np.ndarray) or hasattr(planes, "data_ptr") else None
+    if whole is not None:
+        if whole.ndim < 2:
+            raise ValueError("planes: one array of shape (nc, ...), or a sequence of nc arrays")
+        seq = [whole[k] for k in range(whole.shape[0])]
+    else:
+        seq = list(planes)
+    if not seq:
+        raise ValueError("planes: no components")
+    addrs, kinds, devs, sizes = [], set(), set(), set()
+    for a in seq:
+        if hasattr(a, "data_ptr"):
+            size = a.element_size() if a.dtype.is_floating_point else 0
+            contiguous, dev, addr, n = a.is_contiguous(), bool(a.is_cuda), a.data_ptr(), a.numel()
+        elif isinstance(a, np.ndarray):
+            size = a.dtype.itemsize if a.dtype.kind == "f" else 0
+            contiguous, dev, addr, n = a.flags.c_contiguous, False, a.ctypes.data, a.size
+        else:
+            raise TypeError("planes must be numpy arrays or torch tensors")
+        if size not in (4, 8):
+            raise TypeError("planes must be float64 or float32")
+        if not contiguous:
+            raise ValueError("every plane must be contiguous")
+        addrs.append(addr); kinds.add(size); devs.add(dev); sizes.add(n)
+    if len(kinds) > 1:
+        raise TypeError("the planes of one push must all be float32 or all float64")
+    if len(devs) > 1:
+        raise ValueError("the planes of one push must all be host arrays or all device tensors")
+    if len(sizes) > 1:
+        raise ValueError("the planes of one push must have one size")
+    return (C.c_void_p * len(addrs))(*addrs), len(addrs), (seq, whole), 1 if devs.pop() else 0, kinds.pop() == 4
+
+
 def default_options(**kw):
     o = Options()
     _lib.load().ftkx_default_options(C.byref(o))
@@ -222,6 +259,37 @@ class Context:
         self._ck((self._L.ftkx_push_slice_f32 if f32 else self._L.ftkx_push_slice)(self._h, t, pv, pj, ps, on_dev))
         owned = f32 or self._perturbing or self._clamping
         self._keep[t] = (kv, kj, ks) if on_dev and not owned else None       # (float32, perturbation, clamp: read before the call returned, the context owns FP64 copies)
+
+    def push_slice_planar(self, t, planes, J=None, S=None, on_device=None):
+        """ftkx_push_slice_planar / _f32: push_slice of the vector field whose components are `planes` (see _planes: nc = nd arrays or one
+        (nc, ...) array, float32 or float64), interleaved -- and widened -- on the device.  J and S as in push_slice (interleaved).  Device
+        planes are read before the call returns, never borrowed.  on_device as in push_scalar_slice"""
+        ptrs, nc, keep, dev, f32 = _planes(planes)
+        pj, kj, dj, fj = _ptr(J); ps, ks, ds, fs = _ptr(S)
+        if any(p is not None and bool(d) != bool(dev) for p, d in ((pj, dj), (ps, ds))):
+            raise ValueError("planes, J, S must all be host arrays or all device tensors")
+        if any(p is not None and bool(f) != f32 for p, f in ((pj, fj), (ps, fs))):
+            raise TypeError("the arrays of one push must all be float32 or all float64")
+        if on_device is not None:
+            if int(on_device) not in (0, 1, 2) or (int(on_device) != 0) != bool(dev):
+                raise ValueError("on_device: 0 for host arrays, 1 or 2 for device tensors")
+            dev = int(on_device)
+        self._ck((self._L.ftkx_push_slice_planar_f32 if f32 else self._L.ftkx_push_slice_planar)(self._h, t, ptrs, nc, pj, ps, dev))
+        owned = f32 or self._perturbing or self._clamping
+        self._keep[t] = (kj, ks) if dev == 1 and not owned else None       # (J and S of FP64 on this device are borrowed; the planes never are)
+
+    def temporal_push_planar(self, planes, on_device=None):
+        """ftkx_temporal_push_planar / _f32: temporal_push(is_vector=True) of the vector snapshot whose components are `planes`"""
+        ptrs, nc, keep, dev, f32 = _planes(planes)
+        if on_device is not None:
+            if int(on_device) not in (0, 1, 2) or (int(on_device) != 0) != bool(dev):
+                raise ValueError("on_device: 0 for host arrays, 1 or 2 for device tensors")
+            dev = int(on_device)
+        t = C.c_int(-1)
+        self._ck((self._L.ftkx_temporal_push_planar_f32 if f32 else self._L.ftkx_temporal_push_planar)(self._h, ptrs, nc, dev, C.byref(t)))
+        if t.value >= 0:
+            self._keep[t.value] = None
+        return t.value
 
     def push_scalar_slice(self, t, S, on_device=None):
         """on_device: None = 0 for a host array, 1 (borrowed) for a device tensor; 2: a device tensor, copied"""
@@ -525,6 +593,25 @@ class Context:
         ms = (C.c_double * int(reps))()
         self._ck(self._L.ftkx_debug_widen_relaunch(self._h, src_ptr, int(count), dst_ptr, int(reps), ms))
         return list(ms)
+
+    # component planes -> interleaved FP64 on device pointers (concat_kernels.hip)
+    def concat(self, plane_ptrs, count, dst_ptr, f32=False):
+        """ftkx_concat / ftkx_concat_f32: dst[v * nc + k] = double(plane_k[v]) for `count` vertices; plane_ptrs: nc device addresses"""
+        ptrs = (C.c_void_p * len(plane_ptrs))(*[None if p is None else int(p) for p in plane_ptrs])
+        self._ck((self._L.ftkx_concat_f32 if f32 else self._L.ftkx_concat)(self._h, ptrs, len(plane_ptrs), int(count), dst_ptr))
+
+    def debug_concat_relaunch(self, plane_ptrs, count, dst_ptr, reps, f32=False):
+        """profiling aid: the concat kernel `reps` times back to back -> device ms per launch (HIP events)"""
+        ptrs = (C.c_void_p * len(plane_ptrs))(*[int(p) for p in plane_ptrs])
+        ms = (C.c_double * int(reps))()
+        self._ck(self._L.ftkx_debug_concat_relaunch(self._h, ptrs, len(plane_ptrs), int(bool(f32)), int(count), dst_ptr, int(reps), ms))
+        return list(ms)
+
+    def planar_counts(self):
+        """(vec, scalar): launches of the concat kernel by this context, with its 16-byte body / vertex by vertex"""
+        a = C.c_ulonglong(0); b = C.c_ulonglong(0)
+        self._ck(self._L.ftkx_debug_planar_counts(self._h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
 
     def f32_counts(self):
         """(widened, convolved_direct): float32 arrays pushed into this context that took the widen kernel / went straight through the convolution"""
@@ -997,6 +1084,12 @@ class _TrackerRegular:
     def push_vector_field_snapshot(self, v):
         p, k, d, f32 = _ptr(v); self._keep.append(None if f32 else k)
         self._ck((self._L.ftkx_tracker_push_vector_field_snapshot_f32 if f32 else self._L.ftkx_tracker_push_vector_field_snapshot)(self._h, p, d))
+
+    def push_vector_field_components(self, planes):
+        """push_vector_field_snapshot of the vector field whose components are `planes` (nc arrays, or one (nc, ...) array; float32 or
+        float64; host or device), interleaved on the device.  Read before the call returns, never borrowed"""
+        ptrs, nc, keep, dev, f32 = _planes(planes); self._keep.append(None)
+        self._ck((self._L.ftkx_tracker_push_vector_field_components_f32 if f32 else self._L.ftkx_tracker_push_vector_field_components)(self._h, ptrs, nc, dev))
 
     def push_field_data_snapshot(self, s, v, j):
         ps, ks, ds, fs = _ptr(s); pv, kv, dv, fv = _ptr(v); pj, kj, dj, fj = _ptr(j)

@@ -57,6 +57,7 @@ void launch_resolution(const double *p, size_t n, u64 *out2, hipStream_t st);
 template <class SRC> void launch_conv(int nd, const SRC *S, int DW, int DH, int DD, const double *d_weights, int ksize, double *out, hipStream_t st);   // conv_kernels.hip: SRC double or float
 void launch_widen(const float *src, size_t count, double *dst, hipStream_t st);   // widen_kernels.hip
 template <class T> void launch_adjust(const T *src, size_t count, bool perturb, bool clamp, const AdjustArgs &a, double *dst, hipStream_t st);   // adjust_kernels.hip: T double or float; src == dst allowed
+template <class T> bool launch_concat(const T *const *planes, int nc, size_t count, double *dst, hipStream_t st);   // concat_kernels.hip: T double or float; whether the 16-byte body ran
 void launch_temporal(const double *const *arrays, int ksize, const double *weights, size_t count, double *out, hipStream_t st);   // temporal_kernels.hip
 void launch_calib_read(const void *p, size_t bytes, double *scratch, hipStream_t stream);
 const char *last_mask_kernel();
@@ -331,6 +332,10 @@ struct ftkx_ctx {
   unsigned long long tm_pushed = 0;            // raw pushes of the temporal series so far: t0 + tm_pushed is the next raw snapshot's number
   int tm_t0 = 0;
   unsigned long long adj_from_float = 0, adj_in_place = 0, adj_out_of_place = 0;
+  // vector snapshots given as one array per component (ftkx_push_slice_planar, ftkx_temporal_push_planar, ftkx_concat; concat_steps.hpp): the
+  // launches of the concat kernel by its path -- ftkx_debug_planar_counts.  Host planes are staged like every other source: floats in
+  // f32_stage (each plane at a multiple of 16 bytes), doubles in a pooled array.
+  unsigned long long planar_vec = 0, planar_scalar = 0;
   std::vector<ftkxh::Request> pending;
   // Cull-ahead: the sweeps the caller announced (ftkx_sweep_announce) for the slices of the next ftkx_slices_prepare, and -- once that
   // call has queued their cull right behind the mask kernel -- the survivor list it left on the device.  The cull needs the masks

@@ -624,6 +624,105 @@ template <class T> static int stage_into(ftkx_ctx *c, const T *src, size_t count
   return FTKX_OK;
 }
 
+// one array of a push (null: none) into `dst`: an FP64 array on this device from which nothing has to be computed is adopted as it is
+// (on_device 1); everything else becomes a pooled array that stage_into fills
+template <class T> static int take_array(ftkx_ctx *c, const T *src, size_t count, int on_device, bool smooth, int t, ftkx_block &dst)
+{
+  if (!src) return FTKX_OK;
+  if constexpr (!std::is_same<T, float>::value) if (on_device == 1 && !smooth && !c->adj.on()) { dst = ftkx_block::lent(const_cast<double *>(src), count * sizeof(double)); return FTKX_OK; }
+  if (int rc = take_pooled(c, count, dst)) return rc;
+  return stage_into(c, src, count, on_device, smooth, dst.as<double>(), t);
+}
+
+// ---- vector snapshots given as one array per component (concat_kernels.hip) --------------------------------------------------------------
+// what every launch of the concat kernel asks of its arguments (dst null: an array of the context's own, not taken yet); nothing is queued
+template <class T> static int planar_args(ftkx_ctx *c, const char *who, const T *const *planes, int nc, size_t count, const double *dst)
+{
+  if (!planes) return fail(c, FTKX_E_INVALID, "%s: null argument", who);
+  if (nc != 2 && nc != 3) return fail(c, FTKX_E_INVALID, "%s: 2 or 3 components, not %d", who, nc);
+  if (count < 1) return fail(c, FTKX_E_INVALID, "%s: count must be positive", who);
+  for (int k = 0; k < nc; k ++) {
+    if (!planes[k]) return fail(c, FTKX_E_INVALID, "%s: plane %d is null", who, k);
+    if ((size_t)planes[k] & (sizeof(T) - 1)) return fail(c, FTKX_E_INVALID, "%s: plane %d must be a multiple of its element's size", who, k);
+  }
+  if (!dst) return FTKX_OK;
+  if ((size_t)dst & 7) return fail(c, FTKX_E_INVALID, "%s: dst must be a multiple of 8", who);
+  for (int k = 0; k < nc; k ++)
+    if ((const char *)planes[k] < (const char *)(dst + count * (size_t)nc) && (const char *)dst < (const char *)(planes[k] + count))
+      return fail(c, FTKX_E_INVALID, "%s: plane %d and the output overlap", who, k);
+  return FTKX_OK;
+}
+
+template <class T> static void queue_concat(ftkx_ctx *c, const T *const *planes, int nc, size_t count, double *dst)
+{
+  if (ftkx::launch_concat<T>(planes, nc, count, dst, c->stream)) c->planar_vec ++; else c->planar_scalar ++;
+}
+
+// dst -- n * nc doubles of the context's own -- becomes what stage_into makes of the host-interleaved array of the nc planes (n elements
+// each): the concat kernel writes it, widening where T is float, and adjust_kernel<double> runs in place behind it where perturbation or
+// clamp is on (the stream's order: concat -> perturb -> clamp; the noise's index is the flat index of the interleaved array).  The kernel
+// reads this device's memory only.  on_device 1 with every plane on this device: read where they lie.  Everything else is staged first,
+// plane behind plane in ONE block -- float32: the context's f32_stage, every plane at a multiple of 16 bytes, ordered against its last
+// reader as stage_into orders it; FP64: a pooled array of n * nc doubles, which goes back to the pool at once.
+template <class T> static int concat_into(ftkx_ctx *c, const T *const *planes, int nc, size_t n, int on_device, double *dst, int t)
+{
+  constexpr bool f32 = std::is_same<T, float>::value;
+  bool here = on_device == 1;
+  for (int k = 0; here && k < nc; k ++) here = ftkx_pointer_device(planes[k]) == c->device;
+  const T *from[3] = {planes[0], planes[1], nc > 2 ? planes[2] : nullptr};
+  ftkx_block tmp;
+  if (!here) {
+    const size_t bytes = n * sizeof(T), pitch = f32 ? (bytes + 15) & ~(size_t)15 : bytes;
+    char *stage = nullptr;
+    if (f32) {
+      if (c->f32_stage_reader && c->f32_stage_reader != c->stream) HIP_TRY(c, hipStreamSynchronize(c->f32_stage_reader));
+      c->f32_stage_reader = nullptr;
+      if (int rc = c->f32_stage.reserve(c, pitch * (size_t)nc, 0, c->stream)) return rc;
+      stage = static_cast<char *>(c->f32_stage.p);
+    } else {
+      if (int rc = take_pooled(c, n * (size_t)nc, tmp)) return rc;
+      stage = static_cast<char *>(tmp.p);
+    }
+    for (int k = 0; k < nc; k ++) {
+      // (a failed copy: as in stage_into -- `tmp` is freed, not pooled; the staging block is overwritten by the next push)
+      if (on_device == 0) { if (int rc = upload_from_host(c, stage + (size_t)k * pitch, planes[k], bytes)) return rc; }
+      else if (hipMemcpyAsync(stage + (size_t)k * pitch, planes[k], bytes, hipMemcpyDefault, c->stream) != hipSuccess) return fail(c, FTKX_E_DEVICE, "push: copy of plane %d failed", k);
+      from[k] = reinterpret_cast<const T *>(stage + (size_t)k * pitch);
+    }
+    if (f32) c->f32_stage_reader = c->stream;
+  }
+  queue_concat<T>(c, from, nc, n, dst);
+  if (c->adj.on()) queue_adjust<double>(c, dst, n * (size_t)nc, t, dst);
+  const hipError_t e = hipGetLastError();
+  if (tmp.p) give_pooled(c, std::move(tmp));
+  HIP_TRY(c, e);
+  return FTKX_OK;
+}
+
+// ftkx_push_slice_planar*: push_common for a V that arrives as nc planes; J and S as there (interleaved)
+template <class T> static int push_planar_common(ftkx_ctx *c, int t, const T *const *Vc, int nc, const T *J, const T *S, int on_device)
+{
+  if (c) c->ahead.clear();
+  if (!c) return fail(nullptr, FTKX_E_INVALID, "null context");
+  if (int rc = push_checks(c, t, on_device, false, Vc != nullptr)) return rc;
+  if (nc != c->nd) return fail(c, FTKX_E_INVALID, "push: %d planes for a context of %d dimensions", nc, c->nd);
+  const size_t n = n_vertices(c);
+  if (int rc = planar_args<T>(c, "push", Vc, nc, n, nullptr)) return rc;
+  if (c->smooth_ksize) return fail(c, FTKX_E_UNSUPPORTED, "push: spatial smoothing is set and takes scalar slices only (ftkx_push_scalar_slice)");
+  if (c->adj.on() && (J || S)) return fail(c, FTKX_E_UNSUPPORTED, "push: perturbation or clamp is set and takes V alone (no J, no S beside it)");
+  HIP_TRY(c, hipSetDevice(c->device));
+  evict_slice(c, t);
+  Slice s;      // (what was already taken is freed with `s`)
+  if (int rc = take_array<T>(c, S, n, on_device, false, t, s.S)) return rc;
+  if (int rc = take_pooled(c, n * (size_t)nc, s.V)) return rc;
+  if (int rc = concat_into<T>(c, Vc, nc, n, on_device, s.V.as<double>(), t)) return rc;
+  if (int rc = take_array<T>(c, J, n * (size_t)nc * (size_t)nc, on_device, false, t, s.J)) return rc;
+  // planes on a device are read by the kernel and never adopted: the call returns once they have been read (a host source has been staged)
+  if (on_device != 0) HIP_TRY(c, hipStreamSynchronize(c->stream));
+  install_slice(c, t, s, false);
+  return FTKX_OK;
+}
+
 // T: the element type of the caller's arrays (double, or float: ftkx_push_*_f32).  The resident slice is FP64 either way
 template <class T> static int push_common(ftkx_ctx *c, int t, const T *V, const T *J, const T *S, int on_device, bool scalar_only)
 {
@@ -642,12 +741,7 @@ template <class T> static int push_common(ftkx_ctx *c, int t, const T *V, const 
   const size_t n = n_vertices(c);
   const int nd = c->nd;
   // (smoothing applies to S alone: vector pushes were refused above)
-  auto take = [&](const T *src, size_t count, bool smooth, ftkx_block &dst) -> int {
-    if (!src) return FTKX_OK;
-    if constexpr (!f32) if (on_device == 1 && !smooth && !adjust) { dst = ftkx_block::lent(const_cast<double *>(src), count * sizeof(double)); return FTKX_OK; }      // adopted as it is
-    if (int rc = take_pooled(c, count, dst)) return rc;
-    return stage_into(c, src, count, on_device, smooth, dst.as<double>(), t);
-  };
+  auto take = [&](const T *src, size_t count, bool smooth, ftkx_block &dst) -> int { return take_array<T>(c, src, count, on_device, smooth, t, dst); };
   if (int rc = take(S, n, c->smooth_ksize != 0, s.S)) return rc;      // (here and below: what was already taken is freed with `s`)
   if (!scalar_only) {
     if (int rc = take(V, n * nd, false, s.V)) return rc;
@@ -676,6 +770,20 @@ int ftkx_push_slice_f32(ftkx_ctx *c, int t, const float *V, const float *J, cons
 
 int ftkx_push_scalar_slice_f32(ftkx_ctx *c, int t, const float *S, int on_device)
 { return push_common<float>(c, t, nullptr, nullptr, S, on_device, true); }
+
+int ftkx_push_slice_planar(ftkx_ctx *c, int t, const double *const *Vc, int nc, const double *J, const double *S, int on_device)
+{ return push_planar_common<double>(c, t, Vc, nc, J, S, on_device); }
+
+int ftkx_push_slice_planar_f32(ftkx_ctx *c, int t, const float *const *Vc, int nc, const float *J, const float *S, int on_device)
+{ return push_planar_common<float>(c, t, Vc, nc, J, S, on_device); }
+
+int ftkx_debug_planar_counts(const ftkx_ctx *c, unsigned long long *vec_launches, unsigned long long *scalar_launches)
+{
+  if (!c) return fail(nullptr, FTKX_E_INVALID, "null context");
+  if (vec_launches) *vec_launches = c->planar_vec;
+  if (scalar_launches) *scalar_launches = c->planar_scalar;
+  return FTKX_OK;
+}
 
 int ftkx_debug_f32_counts(const ftkx_ctx *c, unsigned long long *widened, unsigned long long *convolved_direct)
 {
@@ -1024,6 +1132,47 @@ int ftkx_debug_widen_relaunch(ftkx_ctx *c, const float *src, size_t count, doubl
   return rc;
 }
 
+// ---- component planes -> interleaved FP64 (concat_kernels.hip) ------------------------------------------------------------------------------
+extern "C++" {
+// the kernel alone on device pointers, `reps` times back to back; ms (nullable: reps == 1): a pair of events around every launch
+template <class T> static int concat_common(ftkx_ctx *c, const char *who, const T *const *planes, int nc, size_t count, double *dst, int reps, double *ms)
+{
+  DERIVE_PROLOGUE(c);
+  if (!dst || (ms ? reps < 1 : reps != 1)) return fail(c, FTKX_E_INVALID, "%s: bad argument", who);
+  if (int rc = planar_args<T>(c, who, planes, nc, count, dst)) return rc;
+  std::vector<hipEvent_t> ev(ms ? 2 * (size_t)reps : 0, nullptr);
+  auto run = [&]() -> int {
+    for (hipEvent_t &e : ev) HIP_TRY(c, hipEventCreate(&e));
+    for (int i = 0; i < reps; i ++) {
+      if (ms) HIP_TRY(c, hipEventRecord(ev[2 * (size_t)i], c->stream));
+      queue_concat<T>(c, planes, nc, count, dst);
+      if (ms) HIP_TRY(c, hipEventRecord(ev[2 * (size_t)i + 1], c->stream));
+    }
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));      // (the caller may read `dst`)
+    for (int i = 0; ms && i < reps; i ++) { float tt = 0; HIP_TRY(c, hipEventElapsedTime(&tt, ev[2 * (size_t)i], ev[2 * (size_t)i + 1])); ms[i] = tt; }
+    return FTKX_OK;
+  };
+  const int rc = run();
+  if (rc) (void)hipStreamSynchronize(c->stream);
+  for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+  return rc;
+}
+}  // extern "C++"
+
+int ftkx_concat(ftkx_ctx *c, const double *const *planes, int nc, size_t count, double *dst)
+{ return concat_common<double>(c, "ftkx_concat", planes, nc, count, dst, 1, nullptr); }
+int ftkx_concat_f32(ftkx_ctx *c, const float *const *planes, int nc, size_t count, double *dst)
+{ return concat_common<float>(c, "ftkx_concat_f32", planes, nc, count, dst, 1, nullptr); }
+
+// profiling aid (tools/push_planar_time.py)
+int ftkx_debug_concat_relaunch(ftkx_ctx *c, const void *const *planes, int nc, int planes_are_f32, size_t count, double *dst, int reps, double *ms)
+{
+  if (c && !ms) return fail(c, FTKX_E_INVALID, "ftkx_debug_concat_relaunch: bad argument");
+  if (planes_are_f32) return concat_common<float>(c, "ftkx_debug_concat_relaunch", reinterpret_cast<const float *const *>(planes), nc, count, dst, reps, ms);
+  return concat_common<double>(c, "ftkx_debug_concat_relaunch", reinterpret_cast<const double *const *>(planes), nc, count, dst, reps, ms);
+}
+
 // ---- perturbation and clamp (adjust_kernels.hip) ---------------------------------------------------------------------------------------------
 static int adjust_settings(ftkx_ctx *c, const char *who, double sigma, int clamp_on, double lo, double hi, bool need_one)
 {
@@ -1291,9 +1440,10 @@ static int temporal_emit(ftkx_ctx *c, const ftkx::TemporalSeries &next, bool pop
   return FTKX_OK;
 }
 
-// T: the element type of the caller's snapshot (double, or float: ftkx_temporal_push_f32); the ring holds FP64 arrays either way
+// T: the element type of the caller's snapshot (double, or float: ftkx_temporal_push_f32); the ring holds FP64 arrays either way.
+// planes (ftkx_temporal_push_planar*; A is null then): a vector snapshot as nc arrays, one per component
 extern "C++" {
-template <class T> static int temporal_push_common(ftkx_ctx *c, const T *A, int is_vector, int on_device, int *t_emitted)
+template <class T> static int temporal_push_common(ftkx_ctx *c, const T *A, int is_vector, int on_device, int *t_emitted, const T *const *planes = nullptr, int nc = 0)
 {
   if (c) c->ahead.clear();
   if (!c) return fail(nullptr, FTKX_E_INVALID, "null context");
@@ -1306,7 +1456,11 @@ template <class T> static int temporal_push_common(ftkx_ctx *c, const T *A, int 
   default: break;
   }
   const bool scalar = !is_vector;
-  if (int rc = push_checks(c, c->tm_next, on_device, scalar, A != nullptr)) return rc;
+  if (int rc = push_checks(c, c->tm_next, on_device, scalar, A != nullptr || planes != nullptr)) return rc;
+  if (planes) {
+    if (nc != c->nd) return fail(c, FTKX_E_INVALID, "ftkx_temporal_push: %d planes for a context of %d dimensions", nc, c->nd);
+    if (int rc = planar_args<T>(c, "ftkx_temporal_push", planes, nc, n_vertices(c), nullptr)) return rc;
+  }
   if (c->smooth_ksize && !scalar) return fail(c, FTKX_E_UNSUPPORTED, "ftkx_temporal_push: spatial smoothing is set and takes scalar snapshots only");
   HIP_TRY(c, hipSetDevice(c->device));
   const size_t count = n_vertices(c) * (scalar ? 1 : (size_t)c->nd);
@@ -1318,7 +1472,9 @@ template <class T> static int temporal_push_common(ftkx_ctx *c, const T *A, int 
   // widened where it is float32, convolved where smoothing is set, perturbed and clamped where those are set -- as raw snapshot number t0 + the
   // pushes of this series so far, which is the timestep of the emission centred on it
   if (c->tm.kind < 0 && c->tm.size == 0) { c->tm_t0 = c->tm_next; c->tm_pushed = 0; }      // the series' first snapshot
-  if (int rc = stage_into(c, A, count, on_device, c->smooth_ksize != 0, slot.as<double>(), c->tm_t0 + (int)c->tm_pushed)) return rc;
+  const int t_raw = c->tm_t0 + (int)c->tm_pushed;
+  if (int rc = planes ? concat_into<T>(c, planes, nc, n_vertices(c), on_device, slot.as<double>(), t_raw)
+                      : stage_into(c, A, count, on_device, c->smooth_ksize != 0, slot.as<double>(), t_raw)) return rc;
   // A device source has to be read before the caller may overwrite it (a host source has been staged completely by upload_from_host):
   // the call ends by waiting for THIS point of the stream, not for the stream -- sweeps queued before the push (deferred collection) and
   // the emission queued behind it run on.
@@ -1345,6 +1501,11 @@ int ftkx_temporal_push(ftkx_ctx *c, const double *A, int is_vector, int on_devic
 { return temporal_push_common<double>(c, A, is_vector, on_device, t_emitted); }
 int ftkx_temporal_push_f32(ftkx_ctx *c, const float *A, int is_vector, int on_device, int *t_emitted)
 { return temporal_push_common<float>(c, A, is_vector, on_device, t_emitted); }
+
+int ftkx_temporal_push_planar(ftkx_ctx *c, const double *const *Vc, int nc, int on_device, int *t_emitted)
+{ return temporal_push_common<double>(c, nullptr, 1, on_device, t_emitted, Vc, nc); }
+int ftkx_temporal_push_planar_f32(ftkx_ctx *c, const float *const *Vc, int nc, int on_device, int *t_emitted)
+{ return temporal_push_common<float>(c, nullptr, 1, on_device, t_emitted, Vc, nc); }
 
 int ftkx_temporal_flush(ftkx_ctx *c, int *t_emitted)
 {

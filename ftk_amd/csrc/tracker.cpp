@@ -57,9 +57,14 @@ unsigned long long factor_of(double resolution, int minbits, int maxbits)
   return 1ull << std::max(minbits, std::min(nbits, maxbits));
 }
 
-// one snapshot -> one context.  kind: 0 scalar (V derived), 1 vector, 2 all three given; f32: the arrays are floats (widened on the device)
-int push_to(ftkx_ctx *c, int kind, int t, const void *s, const void *v, const void *j, int on_device, bool f32 = false)
+// one snapshot -> one context.  kind: 0 scalar (V derived), 1 vector, 2 all three given; f32: the arrays are floats (widened on the device);
+// planes (kind 1): v is an array of that many pointers, one per component (interleaved on the device)
+int push_to(ftkx_ctx *c, int kind, int t, const void *s, const void *v, const void *j, int on_device, bool f32 = false, int planes = 0)
 {
+  if (planes) {
+    if (f32) return ftkx_push_slice_planar_f32(c, t, static_cast<const float *const *>(v), planes, nullptr, nullptr, on_device);
+    return ftkx_push_slice_planar(c, t, static_cast<const double *const *>(v), planes, nullptr, nullptr, on_device);
+  }
   if (f32) {
     const float *fs = static_cast<const float *>(s), *fv = static_cast<const float *>(v), *fj = static_cast<const float *>(j);
     if (kind == 0) return ftkx_push_scalar_slice_f32(c, t, fs, on_device);
@@ -543,8 +548,9 @@ void critical_point_tracker_regular::reset()
 }
 
 // one snapshot -> the context(s) whose steps read it (kind: see push_to)
-void critical_point_tracker_regular::push_snapshot(int kind, const void *s, const void *v, const void *j, bool device, bool f32)
+void critical_point_tracker_regular::push_snapshot(int kind, const void *s, const void *v, const void *j, bool device, bool f32, int planes)
 {
+  if (planes && multi) throw ftkx_error(FTKX_E_UNSUPPORTED, "push: component planes with one device only (a multi-device tracker takes the interleaved FP64 array)");
   if (f32 && multi) throw ftkx_error(FTKX_E_UNSUPPORTED, "push: float32 snapshots with one device only (a multi-device tracker takes FP64 arrays)");
   if (temporal_smoothing_ksize) {
     // the raw snapshot feeds the filter; what the filter emits is the snapshot the tracker sees (a device source is read, not adopted)
@@ -552,8 +558,10 @@ void critical_point_tracker_regular::push_snapshot(int kind, const void *s, cons
     int t_emitted = -1;
     last_push_snapshots = 0;
     const void *a = kind == 0 ? s : v;
-    check(f32 ? ftkx_temporal_push_f32(ctx, static_cast<const float *>(a), kind, device ? 1 : 0, &t_emitted)
-              : ftkx_temporal_push(ctx, static_cast<const double *>(a), kind, device ? 1 : 0, &t_emitted));
+    if (planes) check(f32 ? ftkx_temporal_push_planar_f32(ctx, static_cast<const float *const *>(v), planes, device ? 1 : 0, &t_emitted)
+                          : ftkx_temporal_push_planar(ctx, static_cast<const double *const *>(v), planes, device ? 1 : 0, &t_emitted));
+    else check(f32 ? ftkx_temporal_push_f32(ctx, static_cast<const float *>(a), kind, device ? 1 : 0, &t_emitted)
+                   : ftkx_temporal_push(ctx, static_cast<const double *>(a), kind, device ? 1 : 0, &t_emitted));
     take_emitted(t_emitted);
     return;
   }
@@ -561,7 +569,7 @@ void critical_point_tracker_regular::push_snapshot(int kind, const void *s, cons
   const int t = next_push_timestep;
   if (slab && (t < slab_t0 || t >= slab_t1)) throw ftkx_error(FTKX_E_INVALID, "slab mode: timestep " + std::to_string(t) + " is not in this rank's slab [" + std::to_string(slab_t0) + ", " + std::to_string(slab_t1) + ")");
   if (multi) multi->push(kind, t, static_cast<const double *>(s), static_cast<const double *>(v), static_cast<const double *>(j), device);
-  else check(push_to(ctx, kind, t, s, v, j, device ? 1 : 0, f32));
+  else check(push_to(ctx, kind, t, s, v, j, device ? 1 : 0, f32, planes));
   field_data_snapshots.push_back(t);
   next_push_timestep ++;
 }
@@ -592,11 +600,11 @@ void critical_point_tracker_regular::push_scalar(const void *s, bool device, boo
   push_snapshot(0, s, nullptr, nullptr, device, f32);       // V = gradientND(s) on the device
 }
 
-void critical_point_tracker_regular::push_vector(const void *v, bool device, bool f32)
+void critical_point_tracker_regular::push_vector(const void *v, bool device, bool f32, int planes)
 {
   if (!initialized) throw ftkx_error(FTKX_E_INVALID, "push: initialize() first");
   if (spatial_smoothing_ksize) throw ftkx_error(FTKX_E_UNSUPPORTED, "push_vector_field_snapshot: spatial smoothing takes scalar snapshots only");
-  push_snapshot(1, nullptr, v, nullptr, device, f32);       // J derived at hits when jacobian_field_source == SOURCE_DERIVED
+  push_snapshot(1, nullptr, v, nullptr, device, f32, planes);       // J derived at hits when jacobian_field_source == SOURCE_DERIVED
 }
 
 void critical_point_tracker_regular::push_field_data(const void *s, const void *v, const void *j, bool device, bool f32)
@@ -613,6 +621,18 @@ void critical_point_tracker_regular::push_field_data_snapshot(const double *s, c
 void critical_point_tracker_regular::push_scalar_field_snapshot(const float *s, bool device) { push_scalar(s, device, true); }
 void critical_point_tracker_regular::push_vector_field_snapshot(const float *v, bool device) { push_vector(v, device, true); }
 void critical_point_tracker_regular::push_field_data_snapshot(const float *s, const float *v, const float *j, bool device) { push_field_data(s, v, j, device, true); }
+
+// nc < 1 never reaches push_snapshot, where 0 means "no planes"; whether nc is the tracker's dimension is the context's check
+void critical_point_tracker_regular::push_vector_field_components(const double *const *comps, int nc, bool device)
+{
+  if (!comps || nc < 1) throw ftkx_error(FTKX_E_INVALID, "push_vector_field_components: no components");
+  push_vector(comps, device, false, nc);
+}
+void critical_point_tracker_regular::push_vector_field_components(const float *const *comps, int nc, bool device)
+{
+  if (!comps || nc < 1) throw ftkx_error(FTKX_E_INVALID, "push_vector_field_components: no components");
+  push_vector(comps, device, true, nc);
+}
 
 bool critical_point_tracker_regular::pop_field_data_snapshot()
 {
@@ -1060,6 +1080,10 @@ int ftkx_tracker_push_scalar_field_snapshot_f32(ftkx_tracker *h, const float *s,
 int ftkx_tracker_push_vector_field_snapshot_f32(ftkx_tracker *h, const float *v, int dev) { return guarded(h, [&] { h->t->push_vector_field_snapshot(v, dev != 0); }); }
 int ftkx_tracker_push_field_data_snapshot_f32(ftkx_tracker *h, const float *s, const float *v, const float *j, int dev)
 { return guarded(h, [&] { h->t->push_field_data_snapshot(s, v, j, dev != 0); }); }
+int ftkx_tracker_push_vector_field_components(ftkx_tracker *h, const double *const *comps, int nc, int dev)
+{ return guarded(h, [&] { h->t->push_vector_field_components(comps, nc, dev != 0); }); }
+int ftkx_tracker_push_vector_field_components_f32(ftkx_tracker *h, const float *const *comps, int nc, int dev)
+{ return guarded(h, [&] { h->t->push_vector_field_components(comps, nc, dev != 0); }); }
 int ftkx_tracker_advance_timestep(ftkx_tracker *h) { return guarded(h, [&] { h->t->advance_timestep(); }); }
 int ftkx_tracker_update_timestep(ftkx_tracker *h) { return guarded(h, [&] { h->t->update_timestep(); }); }
 

@@ -521,6 +521,38 @@ int ftkx_debug_f32_counts(const ftkx_ctx *ctx, unsigned long long *widened, unsi
  * Either may be null.  Reads the context, changes nothing. */
 int ftkx_debug_array_counts(const ftkx_ctx *ctx, unsigned long long allocated[3], unsigned long long pooled[3]);
 
+/* ---- vector snapshots given as one array per component (the stream's "u, v, w in separate variables"; ndarray::concat, ndarray.hh:1157-1172) ---- */
+/* The reference reads a vector field that a file keeps as one variable per component into nv arrays and interleaves them on the host,
+ * result[i * nv + j] = arrays[j][i].  Here the nc = nd planes go to the device as they are, float32 or FP64, and ONE kernel writes the
+ * resident FP64 V from them, widening where they are float32: byte for byte the slice that ftkx_push_slice (ftkx_push_slice_f32) makes of the
+ * host-interleaved array, and everything behind it -- perturbation, clamp, the temporal filter, the sweep -- is as for that push.
+ * Vc: nc pointers, each to n_vertices elements at a multiple of the element's size; planes may be one another.  nc must be the context's nd.
+ * J and S keep the meaning and the (interleaved) layout they have in ftkx_push_slice, and are refused with FTKX_E_UNSUPPORTED while
+ * perturbation or clamp is on; spatial smoothing set: FTKX_E_UNSUPPORTED, as for every vector push.  A wrong nc, a null or misaligned plane:
+ * FTKX_E_INVALID, nothing is launched.
+ * on_device holds for all planes of a call (and for J and S): 0 host memory, staged plane behind plane at the bytes of the interleaved
+ * array; 2 device memory of any device, copied; 1 device memory of this context's device, READ where it lies and never adopted -- the call
+ * returns once the planes have been read (planes found on another device are copied, like 2).  The caller may overwrite them on return.
+ * With perturbation or clamp on, the concat kernel writes the slice and the adjust kernel runs in place behind it (the stream's order:
+ * concat -> perturb -> clamp -> temporal filter); the noise's element index is the flat index of the interleaved array. */
+int ftkx_push_slice_planar(ftkx_ctx *ctx, int t, const double *const *Vc, int nc, const double *J, const double *S, int on_device);
+int ftkx_push_slice_planar_f32(ftkx_ctx *ctx, int t, const float *const *Vc, int nc, const float *J, const float *S, int on_device);
+/* ftkx_temporal_push (is_vector = 1) of the snapshot the planes make */
+int ftkx_temporal_push_planar(ftkx_ctx *ctx, const double *const *Vc, int nc, int on_device, int *t_emitted);
+int ftkx_temporal_push_planar_f32(ftkx_ctx *ctx, const float *const *Vc, int nc, int on_device, int *t_emitted);
+/* The kernel alone: dst[v * nc + k] = (double)planes[k][v] for v < count; nc 2 or 3.  planes: a HOST array of nc DEVICE pointers, each a
+ * multiple of its element's size; dst: count * nc doubles on the device at a multiple of 8 that overlap no plane (there is no in-place
+ * form).  FP64 values are moved as bits (a NaN keeps its payload).  16-byte accesses are used where all planes have the same address
+ * modulo 16 and dst can be brought to 16 by the same leading vertices.  Anything else: FTKX_E_INVALID, nothing is launched.  The call returns
+ * when `dst` is complete. */
+int ftkx_concat(ftkx_ctx *ctx, const double *const *planes, int nc, size_t count, double *dst);
+int ftkx_concat_f32(ftkx_ctx *ctx, const float *const *planes, int nc, size_t count, double *dst);
+/* profiling aid (tools/push_planar_time.py): the kernel of ftkx_concat (planes_are_f32 != 0: of ftkx_concat_f32) launched `reps` times back to
+ * back on the context's stream, a pair of events around every launch; ms: reps device times. */
+int ftkx_debug_concat_relaunch(ftkx_ctx *ctx, const void *const *planes, int nc, int planes_are_f32, size_t count, double *dst, int reps, double *ms);
+/* launches of the concat kernel by this context so far: with the 16-byte body, and vertex by vertex.  Either may be null. */
+int ftkx_debug_planar_counts(const ftkx_ctx *ctx, unsigned long long *vec_launches, unsigned long long *scalar_launches);
+
 /* ---- perturbation and clamp of snapshots (ndarray::perturb, ndarray::clamp; the stream's "perturbation" and "clamp") ---- */
 /* The two steps ndarray_stream::modified_callback (stream.hh:1570-1604) runs between the spatial smoothing and the temporal filter:
  *     widen -> conv_gaussian -> perturb(sigma) -> clamp(lo, hi) -> temporal filter -> tracker

@@ -211,6 +211,13 @@ public:
   void push_scalar_field_snapshot(const float *scalar, bool device = false);
   void push_vector_field_snapshot(const float *vector, bool device = false);
   void push_field_data_snapshot(const float *scalar, const float *vector, const float *jacobian, bool device = false);
+  // a vector snapshot as one array per component (u, v, w in separate variables of a file): comps[0 .. nc - 1], nc the tracker's dimension,
+  // each a host (device = true: device) array of one value per vertex.  They are interleaved -- and widened where they are floats -- on
+  // the device (ftkx.h: ftkx_push_slice_planar); the tracker gives what push_vector_field_snapshot gives for the interleaved array.  Device
+  // planes are read before the call returns, never borrowed.  One device (slab ranks and temporal smoothing included); a multi-device
+  // tracker throws FTKX_E_UNSUPPORTED.
+  void push_vector_field_components(const double *const *comps, int nc, bool device = false);
+  void push_vector_field_components(const float *const *comps, int nc, bool device = false);
   bool pop_field_data_snapshot();
 
   bool advance_timestep();                                  // critical_point_tracker.hh:841-848
@@ -280,9 +287,9 @@ protected:
   std::vector<int> field_data_snapshots;                    // timesteps resident on the device (<= 2, a deque in the reference)
   int next_push_timestep = 0;
   void take_emitted(int t);                                 // temporal smoothing: the filter's emission t (-1: none) joins field_data_snapshots
-  void push_snapshot(int kind, const void *s, const void *v, const void *j, bool device, bool f32);   // behind the push_* methods: one snapshot (f32: of floats) -> the context(s) that read it
+  void push_snapshot(int kind, const void *s, const void *v, const void *j, bool device, bool f32, int planes = 0);   // behind the push_* methods: one snapshot (f32: of floats; planes: v is that many component pointers) -> the context(s) that read it
   void push_scalar(const void *s, bool device, bool f32);                                          // the push_* methods' checks, in front of push_snapshot
-  void push_vector(const void *v, bool device, bool f32);
+  void push_vector(const void *v, bool device, bool f32, int planes = 0);
   void push_field_data(const void *s, const void *v, const void *j, bool device, bool f32);
   double vector_field_resolution = std::numeric_limits<double>::max();   // sticky running minimum (never reset)
   unsigned long long vector_field_scaling_factor = 1;
@@ -416,6 +423,8 @@ int  ftkx_tracker_push_field_data_snapshot(ftkx_tracker *, const double *s, cons
 int  ftkx_tracker_push_scalar_field_snapshot_f32(ftkx_tracker *, const float *s, int on_device);   /* float32 snapshots, widened on the device */
 int  ftkx_tracker_push_vector_field_snapshot_f32(ftkx_tracker *, const float *v, int on_device);
 int  ftkx_tracker_push_field_data_snapshot_f32(ftkx_tracker *, const float *s, const float *v, const float *j, int on_device);
+int  ftkx_tracker_push_vector_field_components(ftkx_tracker *, const double *const *comps, int nc, int on_device);   /* one array per component, interleaved on the device */
+int  ftkx_tracker_push_vector_field_components_f32(ftkx_tracker *, const float *const *comps, int nc, int on_device);
 int  ftkx_tracker_advance_timestep(ftkx_tracker *);
 int  ftkx_tracker_update_timestep(ftkx_tracker *);
 int  ftkx_tracker_num_critical_points(const ftkx_tracker *, size_t *n);
