@@ -122,13 +122,18 @@ class resident_sweep {
     }
     check(ftkx_set_mesh(ctx_, dst, dsz, cst, csz, est, esz));
   }
-  void close() { if (ctx_) ftkx_destroy(ctx_); ctx_ = nullptr; n_ = 0; }
+  // Everything that describes the context goes with it: the snapshots, the timestep of the oldest one and the options it was given.
+  // opt_ / have_opt_ say what THIS context holds, so that set_options() can skip a call that changes nothing; a context opened
+  // later starts on the library's defaults (EXACT64 tags, robust, no filter) and must be told again -- the patched tracker's reset()
+  // closes, and its next push opens a new context and hands the same options over.  Forgetting here, in the one place a context
+  // dies, rather than keying the cache to the ctx_ pointer: the allocator may hand the next context the address of the destroyed one.
+  void close() { if (ctx_) ftkx_destroy(ctx_); ctx_ = nullptr; n_ = 0; t0_ = 0; have_opt_ = false; }
 
   // tag_mode is forced to FTKX_TAG_WORK_INDEX: what from_work_index() at the call sites expects (2d:387-395)
   void set_options(ftkx_options o)
   {
     o.tag_mode = FTKX_TAG_WORK_INDEX;
-    if (have_opt_ && std::memcmp(&o, &opt_, sizeof o) == 0) return;
+    if (have_opt_ && std::memcmp(&o, &opt_, sizeof o) == 0) return;       // (what the live context holds already; see close())
     check(ftkx_set_options(ctx_, &o));
     opt_ = o; have_opt_ = true;
   }

@@ -179,9 +179,9 @@ def synthetic(name, dims, k, DT, x0=None, dirv=None):
 
 
 def sweep(nd, scope, t, domain, core, ext, V, J, S, factor, jacobian_symmetric=True, robust=True,
-          type_filter=None, compute_degrees=False, tag_mode=TAG_EXACT64, nthreads=1, explicit=None):
+          type_filter=None, compute_degrees=False, tag_mode=TAG_EXACT64, nthreads=1, explicit=None, rectilinear=None):
     """domain/core/ext = (starts, sizes) spatial.  V/J/S = (cur, next) numpy arrays or None.
-    explicit: REGULAR_COORDS_EXPLICIT array of shape (n1, n0, ncomp)."""
+    explicit: REGULAR_COORDS_EXPLICIT array of shape (n1, n0, ncomp).  rectilinear: REGULAR_COORDS_RECTILINEAR, one 1-D array per axis."""
     a = SweepArgs()
     a.nd, a.scope, a.current_timestep = nd, scope, t
     for name, (st, sz) in (("domain", domain), ("core", core), ("ext", ext)):
@@ -203,6 +203,10 @@ def sweep(nd, scope, t, domain, core, ext, V, J, S, factor, jacobian_symmetric=T
     if explicit is not None:
         e = _f64(explicit); keep.append(e)
         a.coords_mode, a.expl, a.expl_ncomp, a.expl_n0 = 3, e.ctypes.data, e.shape[-1], e.shape[-2]
+    if rectilinear is not None:
+        a.coords_mode = 2
+        for d, r in enumerate(rectilinear):
+            r = _f64(r); keep.append(r); a.rect[d] = r.ctypes.data
     out = C.c_void_p()
     n = lib().ftko_sweep(C.byref(a), C.byref(out))
     return _take(out, n)

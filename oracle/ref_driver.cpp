@@ -17,6 +17,8 @@
 //   ftk_ref_driver file <in.bin> <out.bin> [nthreads]      (in.bin: see read_input())
 //   ftk_ref_driver time <in.bin> [nthreads]                (prints sweep seconds, no dump)
 //   ftk_ref_driver tables <out.txt>                         (dumps the unit-simplex tables)
+// options come from the environment (FTK_REF_NO_ROBUST, FTK_REF_TYPE_FILTER, FTK_REF_COORDS, ...); FTK_REF_RESET_RERUN: after the series,
+// tracker.reset() and the series again -- the dump holds the second run (see run())
 #include <cmath>
 #include <cstdio>
 #include <cstdint>
@@ -72,6 +74,7 @@ struct probe : public Base {
 #else
   bool resident() const { return false; }
 #endif
+  int timestep_now() const { return this->current_timestep; }
   void update_timestep() override {
     const auto t0 = std::chrono::high_resolution_clock::now();
     Base::update_timestep();
@@ -223,28 +226,47 @@ static void run(const input_t &in, int nthreads, const char *out, bool robust, u
   // loop_seconds = everything the tracker does per step (push + update_timestep + pop), without the making of the input array
   double loop_seconds = 0;
   bool resident = false;
-  for (int k = 0; k < in.DT; k ++) {
-    const auto a = make_array(in, k);
-    const auto t0 = std::chrono::high_resolution_clock::now();
-    if (push_all) {
-      // FTK_REF_PUSH_ALL: scalar, vector and Jacobian all GIVEN (critical_point_tracker::push_field_data_snapshot, critical_point_tracker.hh:202-213),
-      // derived here with the reference's own functions -- the arrays the tracker would have derived itself
-      ftk::ndarray<double> V, J;
-      if (in.nd == 2) { V = ftk::gradient2D(a); J = ftk::jacobian2D<double, true>(V); }
-      else { V = ftk::gradient3D(a); J = ftk::jacobian3D(V); }
-      tracker.push_field_data_snapshot(a, V, J);
-    } else
-    if (in.nv == 1) tracker.push_scalar_field_snapshot(a);
-    else tracker.push_vector_field_snapshot(a);
-    if (k != 0) tracker.advance_timestep();
-    if (k == in.DT - 1) tracker.update_timestep();
-    resident = resident || tracker.resident();
-    loop_seconds += std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count();
-  }
+  auto series = [&]() {
+    for (int k = 0; k < in.DT; k ++) {
+      const auto a = make_array(in, k);
+      const auto t0 = std::chrono::high_resolution_clock::now();
+      if (push_all) {
+        // FTK_REF_PUSH_ALL: scalar, vector and Jacobian all GIVEN (critical_point_tracker::push_field_data_snapshot, critical_point_tracker.hh:202-213),
+        // derived here with the reference's own functions -- the arrays the tracker would have derived itself
+        ftk::ndarray<double> V, J;
+        if (in.nd == 2) { V = ftk::gradient2D(a); J = ftk::jacobian2D<double, true>(V); }
+        else { V = ftk::gradient3D(a); J = ftk::jacobian3D(V); }
+        tracker.push_field_data_snapshot(a, V, J);
+      } else
+      if (in.nv == 1) tracker.push_scalar_field_snapshot(a);
+      else tracker.push_vector_field_snapshot(a);
+      if (k != 0) tracker.advance_timestep();
+      if (k == in.DT - 1) tracker.update_timestep();
+      resident = resident || tracker.resident();
+      loop_seconds += std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count();
+    }
+  };
+  series();
 
-  const auto cps = tracker.get_critical_points();
-  fprintf(stdout, "{\"sweep_seconds\": %.6f, \"push_seconds\": %.6f, \"loop_seconds\": %.6f, \"steps\": %d, \"records\": %zu, \"nthreads\": %d, \"hip_resident\": %s}\n",
-      tracker.sweep_seconds, tracker.push_seconds, loop_seconds, in.DT, cps.size(), tracker.get_number_of_threads(), resident ? "true" : "false");
+  auto cps = tracker.get_critical_points();
+  // FTK_REF_RESET_RERUN: reset() and the same series again, as a caller that reuses the tracker does (the reference's ParaView filter
+  // resets after every run); the dump then holds the SECOND run's factors, records and curves.  What reset() is depends on the tracker:
+  // critical_point_tracker_2d_regular::reset (2d:227-236) clears the snapshots, the discrete points and the curves and sets
+  // current_timestep = 0; the 3D tracker has none of its own, critical_point_tracker::reset (critical_point_tracker.hh:31-34) clears
+  // the snapshots and the curves only -- current_timestep goes on counting and the first run's points stay in the map.  Neither
+  // touches vector_field_resolution, so the second run's factors start from the first run's minimum.
+  int first_step = T0;
+  const bool rerun = getenv("FTK_REF_RESET_RERUN") != NULL;      // ("runs" below says that the mode was taken: a driver built before it existed prints none)
+  if (rerun) {
+    tracker.reset();
+    tracker.factors.clear(); tracker.factor_steps.clear();
+    first_step = tracker.timestep_now();
+    resident = false;                                 // (reported for the second run alone)
+    series();
+    cps = tracker.get_critical_points();
+  }
+  fprintf(stdout, "{\"sweep_seconds\": %.6f, \"push_seconds\": %.6f, \"loop_seconds\": %.6f, \"steps\": %d, \"records\": %zu, \"nthreads\": %d, \"runs\": %d, \"hip_resident\": %s}\n",
+      tracker.sweep_seconds, tracker.push_seconds, loop_seconds, in.DT, cps.size(), tracker.get_number_of_threads(), rerun ? 2 : 1, resident ? "true" : "false");
   if (getenv("FTK_REF_PER_CALL")) {      // one line more: the milliseconds of every push and every update_timestep()
     fprintf(stdout, "{\"push_ms\": [");
     for (size_t i = 0; i < tracker.push_ms.size(); i ++) fprintf(stdout, "%s%.4f", i ? ", " : "", tracker.push_ms[i]);
@@ -263,7 +285,7 @@ static void run(const input_t &in, int nthreads, const char *out, bool robust, u
   const uint64_t nf = tracker.factors.size();
   fwrite(&nf, sizeof(uint64_t), 1, fp);
   for (size_t i = 0; i < nf; i ++) {
-    const int64_t step = tracker.factor_steps[i] - T0;   // relative to the first timestep
+    const int64_t step = tracker.factor_steps[i] - first_step;   // relative to the first timestep of the run
     fwrite(&step, sizeof(int64_t), 1, fp);
     fwrite(&tracker.factors[i], sizeof(uint64_t), 1, fp);
   }

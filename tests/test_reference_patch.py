@@ -100,6 +100,25 @@ def test_cited_line_ranges_hold_what_the_docs_say(path, first, last, anchors):
 
 
 @needs_reference
+def test_reference_driver_was_made_from_this_tree():
+    """oracle/_ref/ftk_ref_driver -- the CPU side of every comparison with the real reference -- was compiled from the oracle/ref_driver.cpp of
+    this tree (oracle/Makefile records the SHA-256 beside it and makes it again when they differ): a driver left from an earlier tree would
+    ignore the modes added since (FTK_REF_RESET_RERUN) and answer with another run than the one a test asked for"""
+    drv = os.path.join(ROOT, "oracle", "_ref", "ftk_ref_driver")
+    if not os.path.exists(drv):
+        pytest.skip("oracle/_ref/ftk_ref_driver not built (make -C oracle ref)")
+    assert os.path.exists(drv + ".sha256"), "rebuild: make -C oracle ref"
+    made_from = {}
+    for line in open(drv + ".sha256"):
+        digest, name = line.split(None, 1)
+        made_from[os.path.normpath(os.path.join(ROOT, "oracle", name.strip()))] = digest
+    assert os.path.join(ROOT, "oracle", "ref_driver.cpp") in made_from
+    for path, digest in made_from.items():
+        assert hashlib.sha256(open(path, "rb").read()).hexdigest() == digest, f"rebuild: make -C oracle ref ({path} changed)"
+    assert "FTK_REF_RESET_RERUN" in open(drv, "rb").read().decode("latin-1")
+
+
+@needs_reference
 def test_shim_driver_is_the_patched_reference():
     drv = os.path.join(ROOT, "oracle", "_ref", "ftk_shim_driver")
     if not os.path.exists(drv):

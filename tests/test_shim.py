@@ -14,6 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = "/root/reference/include"
 REFCFG = os.path.join(ROOT, "oracle", "_ref", "include")
 SHIM_DRIVER = os.path.join(ROOT, "oracle", "_ref", "ftk_shim_driver")
+REF_DRIVER = os.path.join(ROOT, "oracle", "_ref", "ftk_ref_driver")
 
 
 def _lib_dir():
@@ -101,19 +102,21 @@ def _driver_env(name, g, mode):
         env["FTK_REF_PUSH_ALL"] = "1"
     if mode == "resident_streaming":
         env["FTK_REF_STREAMING"] = "1"
+    if mode == "resident_reset_rerun":
+        env["FTK_REF_RESET_RERUN"] = "1"
     return env
 
 
-def _run_shim_driver(name, mode, tmp_path):
+def _run_shim_driver(name, mode, tmp_path, driver=SHIM_DRIVER):
     import json
     from refdump import read_dump, write_input
     g = load_golden(name)
-    inp, out = tmp_path / "in.bin", tmp_path / "o.bin"
+    inp, out = tmp_path / "in.bin", tmp_path / (os.path.basename(driver) + ".o.bin")
     write_input(str(inp), g["steps"], g["nd"], g["nv"])
-    r = subprocess.run([SHIM_DRIVER, "file", str(inp), str(out)], capture_output=True, text=True, timeout=600, env=_driver_env(name, g, mode))
+    r = subprocess.run([driver, "file", str(inp), str(out)], capture_output=True, text=True, timeout=600, env=_driver_env(name, g, mode))
     assert r.returncode == 0, r.stderr[-2000:]
     info = json.loads(r.stdout.strip().splitlines()[-1])
-    assert info["hip_resident"] == (mode != "oneshot")
+    assert info["hip_resident"] == (mode != "oneshot" and driver == SHIM_DRIVER)
     return g, read_dump(str(out)), info
 
 
@@ -185,6 +188,36 @@ def test_patched_reference_tracker_one_shot_mode(name, tmp_path):
         pytest.skip("oracle/_ref/ftk_shim_driver not built (needs the build container: make -C oracle ref)")
     g, d, _ = _run_shim_driver(name, "oneshot", tmp_path)
     _assert_dump_equals_fixture(d, g)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["woven_31x37x32", "random_2d_scalar_29x24x6_saddles", "random_3d_scalar_13x12x11x4"])
+def test_patched_reference_tracker_reset_and_second_run(name, tmp_path):
+    """FTK_REF_RESET_RERUN: the driver runs the series, calls the tracker's reset() and runs it again -- what the reference's ParaView filter
+    does after every run -- and dumps the second run.  The patched tracker must give what the reference's CPU path gives in the same mode
+    (oracle/_ref/ftk_ref_driver), not what the fixture holds, because reset() does not start the reference over:
+      * vector_field_resolution, the sticky minimum behind the scaling factor, survives reset() in 2D and 3D: every step of the second run is
+        swept under the first run's LAST factor;
+      * critical_point_tracker_2d_regular::reset sets current_timestep = 0 and clears the discrete points; the patch's hip_reset() closes the
+        device context there, and the next push opens a new one, which must be given the options again (tag mode, type filter);
+      * the 3D tracker has no reset() of its own: critical_point_tracker::reset clears the snapshots only, current_timestep goes on counting
+        and the first run's points stay, so the second run's points join them; the patch notices the emptied deque at the next push and
+        clears the resident slices (resident_sweep::clear), the context stays."""
+    if not (os.path.exists(SHIM_DRIVER) and os.path.exists(REF_DRIVER)):
+        pytest.skip("oracle/_ref/ftk_shim_driver and ftk_ref_driver not built (needs the build container: make -C oracle ref)")
+    g, d, info = _run_shim_driver(name, "resident_reset_rerun", tmp_path)
+    _, ref, ref_info = _run_shim_driver(name, "resident_reset_rerun", tmp_path, driver=REF_DRIVER)
+    # a driver made from an older oracle/ref_driver.cpp ignores the mode and answers with the first run: it is not the driver this test needs
+    # (oracle/Makefile makes both again when their sources changed; tests/test_reference_patch.py fails where one was left behind)
+    if info.get("runs") != 2 or ref_info.get("runs") != 2:
+        pytest.skip("oracle/_ref drivers were built before FTK_REF_RESET_RERUN existed (needs the build container: make -C oracle ref)")
+    assert info["hip_resident"] is True                                            # (of the second run: the driver asks again after reset())
+    assert np.all(ref["factors"] == g["factors"][-1]), (ref["factors"], g["factors"])        # the reference's own second run: the sticky minimum
+    if g["nd"] == 2:
+        assert g["factors"][0] < g["factors"][-1]                                            # ... which is not the fixture's run
+    assert len(ref["records"]) > (len(g["records"]) if g["nd"] == 3 else 0)                 # 3D: the first run's points are still there
+    _assert_dump_equals_fixture(d, dict(factors=ref["factors"], records=ref["records"]))
+    assert sorted((tuple(t.tolist()), l) for l, t in d["curves"]) == sorted((tuple(t.tolist()), l) for l, t in ref["curves"])
 
 
 @pytest.mark.gpu
