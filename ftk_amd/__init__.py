@@ -122,6 +122,7 @@ class Context:
         self._h = C.c_void_p()
         _lib.check(self._L.ftkx_create(C.byref(self._h), nd, device_id))
         self._keep = {}
+        self._keep_aux = {}
         self._smoothing = False
         self._perturbing = False
         self._clamping = False
@@ -164,6 +165,8 @@ class Context:
         for st, sz in (domain, core, ext):
             args += [_lib.ll(st), _lib.ll(sz, fill=1)]
         self._ck(self._L.ftkx_set_mesh(self._h, *args))
+        self._n_vertices = int(np.prod([int(v) for v in ext[1]][:self.nd], dtype=np.int64))
+        self._keep_aux = {}
 
     def set_spatial_smoothing(self, sigma, ksize=3):
         """ftkx_set_spatial_smoothing: scalar slices pushed from now on are conv_gaussian(S, sigma, ksize, ksize // 2); ksize 0: off"""
@@ -305,6 +308,45 @@ class Context:
     def drop_slice(self, t):
         self._ck(self._L.ftkx_drop_slice(self._h, t))
         self._keep.pop(t, None)
+        for slot in (1, 2):
+            getattr(self, "_keep_aux", {}).pop((t, slot), None)
+
+    # auxiliary scalar fields sampled at critical points (sample_kernels.hip)
+    def push_aux_slice(self, t, slot, A, on_device=None):
+        """ftkx_push_aux_slice / _f32: A -- one value per vertex of the array extent, float64 or float32 -- becomes the field that slot 1 or 2
+        of the records is sampled from at timestep t.  on_device as for push_scalar_slice: None = 0 for a host array, 1 (lent: read where it
+        lies) for a device tensor; 2: a device tensor, copied.  Smoothing, perturbation and clamp never apply"""
+        pa, ka, da, f32 = _ptr(A)
+        if on_device is not None:
+            if int(on_device) not in (0, 1, 2) or (int(on_device) != 0) != bool(da):
+                raise ValueError("on_device: 0 for a host array, 1 or 2 for a device tensor")
+            da = int(on_device)
+        n = getattr(self, "_n_vertices", None)
+        if n is not None and ka is not None and int(ka.numel() if hasattr(ka, "numel") else ka.size) != n:
+            raise FtkxError(_lib.E_INVALID, f"push_aux_slice: {int(ka.numel() if hasattr(ka, 'numel') else ka.size)} values for an array extent of {n} vertices")
+        self._ck((self._L.ftkx_push_aux_slice_f32 if f32 else self._L.ftkx_push_aux_slice)(self._h, int(t), int(slot), pa, da))
+        self._keep_aux[(int(t), int(slot))] = ka if da == 1 and not f32 else None      # (lent: alive until the slice is dropped)
+
+    def sample_aux(self, records):
+        """ftkx_sample_aux: scalar[1] / scalar[2] of every record, for the slots that have an aux array at all timesteps the records read, in
+        place on a contiguous CP_DTYPE array (as a sweep returned it: the aux word says which element a record is); returns it"""
+        if not (isinstance(records, np.ndarray) and records.dtype == CP_DTYPE and records.flags.c_contiguous and records.flags.writeable):
+            raise TypeError("sample_aux: a contiguous, writeable CP_DTYPE array")
+        self._ck(self._L.ftkx_sample_aux(self._h, records.ctypes.data, len(records)))
+        return records
+
+    def sample_counts(self):
+        """(launches, records): launches of the sample kernel by sample_aux on this context so far, and the records they took"""
+        a = C.c_ulonglong(0); b = C.c_ulonglong(0)
+        self._ck(self._L.ftkx_debug_sample_counts(self._h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
+    def debug_sample_relaunch(self, records, reps):
+        """profiling aid: the sample kernel over `records` `reps` times back to back -> device ms per launch (HIP events); nothing is written"""
+        r = np.ascontiguousarray(records, dtype=CP_DTYPE)
+        ms = (C.c_double * int(reps))()
+        self._ck(self._L.ftkx_debug_sample_relaunch(self._h, r.ctypes.data, len(r), int(reps), ms))
+        return list(ms)
 
     def slice_resolution(self, t):
         r, m = C.c_double(), C.c_double()
@@ -1077,11 +1119,33 @@ class _TrackerRegular:
         self._ck(self._L.ftkx_tracker_set_flags(self._h, f["robust"], f["use_type_filter"], f["type_filter"], f["compute_degrees"], f["exact_only"], f["tag_mode"]))
         self._ck(self._L.ftkx_tracker_initialize(self._h))
 
-    def push_scalar_field_snapshot(self, s):
+    def set_scalar_components(self, names):
+        """critical_point_tracker::set_scalar_components: one to three names; the first names scalar[0] (the tracker's own scalar field), the
+        others the extra fields every push then brings as components=[...], sampled at the critical points into scalar[1] and scalar[2]"""
+        names = [str(n).encode() for n in names]
+        self._ck(self._L.ftkx_tracker_set_scalar_components(self._h, (C.c_char_p * max(1, len(names)))(*names), len(names)))
+
+    def _push_extra(self, kind, s, v, j, components):
+        """a push_* call with the snapshot's extra scalar fields (all arrays of one call: one dtype, one place)"""
+        got = [_ptr(a) for a in (s, v, j)] + [_ptr(a) for a in components]
+        given = [g for g in got if g[0] is not None]
+        f32 = _same_type(*[g[3] for g in given])
+        if len({g[2] for g in given}) > 1:
+            raise ValueError("the arrays of one push must all be host arrays or all device tensors")
+        dev = given[0][2] if given else 0
+        extra = (C.c_void_p * max(1, len(components)))(*[g[0] for g in got[3:]])
+        self._keep.append(None if f32 else tuple(g[1] for g in got))
+        self._ck(self._L.ftkx_tracker_push_snapshot_extra(self._h, kind, got[0][0], got[1][0], got[2][0], extra, len(components), dev, int(f32)))
+
+    def push_scalar_field_snapshot(self, s, components=None):
+        if components is not None:
+            return self._push_extra(0, s, None, None, list(components))
         p, k, d, f32 = _ptr(s); self._keep.append(None if f32 else k)      # (float32: read before the call returns, never borrowed)
         self._ck((self._L.ftkx_tracker_push_scalar_field_snapshot_f32 if f32 else self._L.ftkx_tracker_push_scalar_field_snapshot)(self._h, p, d))
 
-    def push_vector_field_snapshot(self, v):
+    def push_vector_field_snapshot(self, v, components=None):
+        if components is not None:
+            return self._push_extra(1, None, v, None, list(components))
         p, k, d, f32 = _ptr(v); self._keep.append(None if f32 else k)
         self._ck((self._L.ftkx_tracker_push_vector_field_snapshot_f32 if f32 else self._L.ftkx_tracker_push_vector_field_snapshot)(self._h, p, d))
 
@@ -1091,7 +1155,9 @@ class _TrackerRegular:
         ptrs, nc, keep, dev, f32 = _planes(planes); self._keep.append(None)
         self._ck((self._L.ftkx_tracker_push_vector_field_components_f32 if f32 else self._L.ftkx_tracker_push_vector_field_components)(self._h, ptrs, nc, dev))
 
-    def push_field_data_snapshot(self, s, v, j):
+    def push_field_data_snapshot(self, s, v, j, components=None):
+        if components is not None:
+            return self._push_extra(2, s, v, j, list(components))
         ps, ks, ds, fs = _ptr(s); pv, kv, dv, fv = _ptr(v); pj, kj, dj, fj = _ptr(j)
         f32 = _same_type(*[f for p, f in ((ps, fs), (pv, fv), (pj, fj)) if p is not None])
         self._keep.append(None if f32 else (ks, kv, kj))
@@ -1130,6 +1196,17 @@ class _TrackerRegular:
         offs = np.zeros(nc.value + 1, dtype=np.int64); tags = np.zeros(max(1, npts.value), dtype=np.uint64); loop = np.zeros(max(1, nc.value), dtype=np.int32)
         self._ck(self._L.ftkx_tracker_get_curves(self._h, offs.ctypes.data, tags.ctypes.data, loop.ctypes.data))
         return [tags[offs[i]:offs[i + 1]] for i in range(nc.value)], loop[:nc.value]
+
+    def get_traced_scalars(self):
+        """after finalize(): per curve an array (points, 3) of scalar[0 .. 2], in the order of get_traced_critical_points()"""
+        curves, _ = self.get_traced_critical_points()
+        npts = sum(len(c) for c in curves)
+        sc = np.zeros((max(1, npts), 3), dtype=np.float64)
+        self._ck(self._L.ftkx_tracker_get_curve_scalars(self._h, sc.ctypes.data))
+        out, k = [], 0
+        for c in curves:
+            out.append(sc[k:k + len(c)]); k += len(c)
+        return out
 
     def post_process(self):
         """json_interface::post_process with its default options, on the traced curves"""

@@ -92,6 +92,8 @@ EXPORTS = [
     "ftkx_tracker_push_vector_field_components", "ftkx_tracker_push_vector_field_components_f32",
     "ftkx_debug_series_order", "ftkx_debug_sort_records",
     "ftkx_set_perturbation", "ftkx_set_clamp", "ftkx_adjust", "ftkx_adjust_f32", "ftkx_debug_adjust_relaunch", "ftkx_debug_adjust_counts", "ftkx_tracker_set_perturbation", "ftkx_tracker_set_clamp",
+    "ftkx_push_aux_slice", "ftkx_push_aux_slice_f32", "ftkx_sample_aux", "ftkx_debug_sample_relaunch", "ftkx_debug_sample_counts",
+    "ftkx_tracker_set_scalar_components", "ftkx_tracker_push_snapshot_extra", "ftkx_tracker_get_curve_scalars",
     "ftkx_tracker_push_scalar_field_snapshot_f32", "ftkx_tracker_push_vector_field_snapshot_f32", "ftkx_tracker_push_field_data_snapshot_f32",
     "ftkx_tracker_post_process", "ftkx_tracker_get_curve_points", "ftkx_tracker_write", "ftkx_tracker_read_critical_points",
     "ftkx_tracker_create", "ftkx_tracker_create_multi", "ftkx_tracker_sync", "ftkx_tracker_destroy", "ftkx_tracker_last_error", "ftkx_tracker_set_domain", "ftkx_tracker_set_array_domain",
@@ -211,6 +213,14 @@ def load():
     L.ftkx_adjust_f32.argtypes = [vp, vp, C.c_size_t, C.c_double, C.c_ulonglong, C.c_int, C.c_int, C.c_double, C.c_double, dbl]
     L.ftkx_debug_adjust_relaunch.argtypes = [vp, vp, C.c_int, C.c_size_t, C.c_double, C.c_ulonglong, C.c_int, C.c_int, C.c_double, C.c_double, dbl, C.c_int, C.POINTER(C.c_double)]
     L.ftkx_debug_adjust_counts.argtypes = [vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
+    L.ftkx_push_aux_slice.argtypes = [vp, C.c_int, C.c_int, dbl, C.c_int]
+    L.ftkx_push_aux_slice_f32.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int]
+    L.ftkx_sample_aux.argtypes = [vp, vp, C.c_size_t]
+    L.ftkx_debug_sample_relaunch.argtypes = [vp, vp, C.c_size_t, C.c_int, C.POINTER(C.c_double)]
+    L.ftkx_debug_sample_counts.argtypes = [vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
+    L.ftkx_tracker_set_scalar_components.argtypes = [vp, C.POINTER(C.c_char_p), C.c_int]
+    L.ftkx_tracker_push_snapshot_extra.argtypes = [vp, C.c_int, vp, vp, vp, C.POINTER(vp), C.c_int, C.c_int, C.c_int]
+    L.ftkx_tracker_get_curve_scalars.argtypes = [vp, dbl]
     L.ftkx_tracker_set_perturbation.argtypes = [vp, C.c_double, C.c_ulonglong]
     L.ftkx_tracker_set_clamp.argtypes = [vp, C.c_int, C.c_double, C.c_double]
     L.ftkx_tracker_push_scalar_field_snapshot_f32.argtypes = [vp, vp, C.c_int]

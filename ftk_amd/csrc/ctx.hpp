@@ -24,6 +24,7 @@
 #include "ctx_block.hpp"
 #include "temporal_steps.hpp"
 #include "adjust_steps.hpp"
+#include "sample_steps.hpp"
 
 struct ftkx_phase_clock;
 
@@ -59,6 +60,7 @@ void launch_widen(const float *src, size_t count, double *dst, hipStream_t st); 
 template <class T> void launch_adjust(const T *src, size_t count, bool perturb, bool clamp, const AdjustArgs &a, double *dst, hipStream_t st);   // adjust_kernels.hip: T double or float; src == dst allowed
 template <class T> bool launch_concat(const T *const *planes, int nc, size_t count, double *dst, hipStream_t st);   // concat_kernels.hip: T double or float; whether the 16-byte body ran
 void launch_temporal(const double *const *arrays, int ksize, const double *weights, size_t count, double *out, hipStream_t st);   // temporal_kernels.hip
+void launch_sample(int nd, const SampleMesh &m, const SampleIn *in, size_t n, const SampleSlice *tab, int t_min, unsigned slots, double *out, hipStream_t st);   // sample_kernels.hip
 void launch_calib_read(const void *p, size_t bytes, double *scratch, hipStream_t stream);
 const char *last_mask_kernel();
 void launch_cull_coarse(const Mesh &m, const Fields *d_steps, int nsteps, u64 *d_refine, u64 refine_cap, hipStream_t stream, const FactorJob *job = nullptr);
@@ -336,6 +338,15 @@ struct ftkx_ctx {
   // launches of the concat kernel by its path -- ftkx_debug_planar_counts.  Host planes are staged like every other source: floats in
   // f32_stage (each plane at a multiple of 16 bytes), doubles in a pooled array.
   unsigned long long planar_vec = 0, planar_scalar = 0;
+  // auxiliary scalar fields (ftkx_push_aux_slice, ftkx_sample_aux; sample_steps.hpp): per timestep the arrays that record slots 1 and 2 are
+  // sampled from -- field-class arrays out of `arrays`, or lent by the caller -- next to the slices, not in them: no sweep reads them, and a
+  // slice that is pushed again keeps them.  They leave with ftkx_drop_slice(t).  Only the sample kernel reads them, on the context's stream,
+  // and ftkx_sample_aux waits for it: a dropped array goes straight back to the pool.  sm_*: what a call sends up (16 bytes per record,
+  // the table of slice pointers) and brings down (8 bytes per record and slot), kept between calls.
+  struct AuxSlice { ftkx_block A[2]; };
+  std::map<int, AuxSlice> aux;
+  ftkx_block sm_h_in{FTKX_BLOCK_PINNED}, sm_d_in, sm_d_out, sm_h_out{FTKX_BLOCK_PINNED_NONCOHERENT}, sm_d_tab;
+  unsigned long long sm_launches = 0, sm_records = 0;      // ftkx_debug_sample_counts
   std::vector<ftkxh::Request> pending;
   // Cull-ahead: the sweeps the caller announced (ftkx_sweep_announce) for the slices of the next ftkx_slices_prepare, and -- once that
   // call has queued their cull right behind the mask kernel -- the survivor list it left on the device.  The cull needs the masks

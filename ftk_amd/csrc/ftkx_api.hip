@@ -3,11 +3,13 @@
 // (src/filters/critical_point_tracer_2d_regular.cu:168-272, ..._3d_regular.cu:144-250), which re-allocates, re-uploads and
 // frees everything on every call and synchronises the whole device; here slices stay resident, launches go to a stream,
 // and the hit buffer is persistent (grown and the batch replayed if a launch overflows it).
+#include <atomic>
 #include <map>
 #include <mutex>
 #include <type_traits>
 #include "ctx.hpp"
 #include "cp_device.hpp"
+#include "host_sort.hpp"
 #include <sched.h>
 
 using namespace ftkxh;
@@ -481,6 +483,7 @@ int ftkx_set_mesh(ftkx_ctx *c, const long long dst[3], const long long dsz[3], c
   HIP_TRY(c, sync_tails(c));
   for (ftkx_series_pending &P : c->sr_pend) release_retired(c, P);
   temporal_release(c);                    // a temporal series that was open starts afresh: its raw snapshots have the old lattice's size
+  c->aux.clear();                         // (aux arrays left behind by slices that were never dropped: the old lattice's, too)
   c->arrays.clear();
   for (int d = 0; d < c->nd; d ++) {
     if (dsz[d] < 0 || csz[d] < 0 || esz[d] <= 0) return fail(c, FTKX_E_INVALID, "ftkx_set_mesh: negative size on axis %d", d);
@@ -569,10 +572,11 @@ template <class T> static void queue_adjust(ftkx_ctx *c, const T *from, size_t c
   else c->adj_out_of_place ++;
 }
 
-template <class T> static int stage_into(ftkx_ctx *c, const T *src, size_t count, int on_device, bool smooth, double *dst, int t)
+// raw: the array is no snapshot of the stream's (an aux array, ftkx_push_aux_slice): perturbation and clamp pass it by.
+template <class T> static int stage_into(ftkx_ctx *c, const T *src, size_t count, int on_device, bool smooth, double *dst, int t, bool raw = false)
 {
   constexpr bool f32 = std::is_same<T, float>::value;
-  const bool adjust = c->adj.on();
+  const bool adjust = !raw && c->adj.on();
   if constexpr (!f32) if (!smooth && adjust) {
     const bool here = on_device != 0 && ftkx_pointer_device(src) == c->device;
     if (on_device == 0) { if (int rc = upload_from_host(c, dst, src, count * sizeof(T))) return rc; }
@@ -777,6 +781,222 @@ int ftkx_push_slice_planar(ftkx_ctx *c, int t, const double *const *Vc, int nc, 
 int ftkx_push_slice_planar_f32(ftkx_ctx *c, int t, const float *const *Vc, int nc, const float *J, const float *S, int on_device)
 { return push_planar_common<float>(c, t, Vc, nc, J, S, on_device); }
 
+// ---- auxiliary scalar fields sampled at critical points (sample_steps.hpp, sample_kernels.hip) -------------------------------------------
+// the aux arrays of timestep t leave: owned ones to the pool (only the sample kernel reads them, and ftkx_sample_aux has waited for it)
+static void drop_aux(ftkx_ctx *c, int t)
+{
+  auto it = c->aux.find(t);
+  if (it == c->aux.end()) return;
+  for (ftkx_block &b : it->second.A) if (b.p) give_pooled(c, std::move(b));
+  c->aux.erase(it);
+}
+
+extern "C++" {
+template <class T> static int push_aux_common(ftkx_ctx *c, int t, int slot, const T *A, int on_device)
+{
+  constexpr bool f32 = std::is_same<T, float>::value;
+  if (!c) return fail(nullptr, FTKX_E_INVALID, "null context");
+  if (!c->mesh_set) return fail(c, FTKX_E_INVALID, "ftkx_push_aux_slice: call ftkx_set_mesh first");
+  if (t < 0) return fail(c, FTKX_E_INVALID, "ftkx_push_aux_slice: negative timestep");
+  if (slot != 1 && slot != 2) return fail(c, FTKX_E_INVALID, "ftkx_push_aux_slice: slot must be 1 or 2, not %d (slot 0 is the scalar field of the sweep)", slot);
+  if (on_device < 0 || on_device > 2) return fail(c, FTKX_E_INVALID, "ftkx_push_aux_slice: on_device must be 0, 1 or 2");
+  if (!A || ((size_t)A & (sizeof(T) - 1))) return fail(c, FTKX_E_INVALID, "ftkx_push_aux_slice: the array is null or not a multiple of its element's size");
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t n = n_vertices(c);
+  ftkx_block b;
+  if (!f32 && on_device == 1) b = ftkx_block::lent(const_cast<T *>(A), n * sizeof(double));
+  else {
+    if (int rc = take_pooled(c, n, b)) return rc;
+    if (int rc = stage_into<T>(c, A, n, on_device, false, b.as<double>(), t, true)) return rc;      // (b is freed, not pooled)
+    // a device source is read by a copy or by the widen kernel and never adopted: the call returns once it has been read
+    if (on_device != 0) HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  ftkx_block &dst = c->aux[t].A[slot - 1];
+  if (dst.p) give_pooled(c, std::move(dst));
+  dst = std::move(b);
+  return FTKX_OK;
+}
+}  // extern "C++"
+
+int ftkx_push_aux_slice(ftkx_ctx *c, int t, int slot, const double *A, int on_device) { return push_aux_common<double>(c, t, slot, A, on_device); }
+int ftkx_push_aux_slice_f32(ftkx_ctx *c, int t, int slot, const float *A, int on_device) { return push_aux_common<float>(c, t, slot, A, on_device); }
+
+// What a launch of the sample kernel needs, on the device when this returns FTKX_OK with slots != 0: the records' (tag, aux word) pairs and
+// behind them the table of slice pointers in sm_d_in, room for the results in sm_d_out and sm_h_out.  Every check of ftkx_sample_aux is
+// made here, before anything is written anywhere.
+// f(begin, end) over the records of a call: on a few host threads from 2^18 records (below that starting the threads costs more than the
+// loops: 62 181 records of bench.py's C2 take 0.5 ms on one thread, 0.76 ms on eight)
+extern "C++" {
+template <class F> static void sample_ranges(size_t n, F f)
+{
+  if (n < ((size_t)1 << 18)) f((size_t)0, n);
+  else ftkx::for_ranges_on_threads(n, f);
+}
+}  // extern "C++"
+
+struct SamplePlan {
+  ftkx::SampleMesh m;
+  int t_min = 0, ntab = 0;
+  unsigned slots = 0;
+  int nslots = 0;
+  const ftkx::SampleIn *d_in = nullptr;
+  const ftkx::SampleSlice *d_tab = nullptr;
+};
+
+static int sample_prepare(ftkx_ctx *c, const char *who, const ftkx_cp_t *recs, size_t n, SamplePlan &P)
+{
+  if (!c) return fail(nullptr, FTKX_E_INVALID, "null context");
+  if (!c->mesh_set) return fail(c, FTKX_E_INVALID, "%s: call ftkx_set_mesh first", who);
+  if (n == 0) return FTKX_OK;
+  if (!recs) return fail(c, FTKX_E_INVALID, "%s: null records", who);
+  HIP_TRY(c, hipSetDevice(c->device));
+  const int nd = c->nd;
+  ftkx::SampleMesh &m = P.m;
+  m.tag_mode = c->opt.tag_mode;
+  m.scalar_mode = c->scalar_mode == 1;
+  for (int d = 0; d < 3; d ++) {
+    m.dom_lb[d] = (int)c->dom_st[d]; m.dom_sz[d] = (int)c->dom_sz[d];
+    m.core_st[d] = (int)c->core_st[d]; m.core_sz[d] = (int)c->core_sz[d];
+    m.ext_st[d] = (int)c->ext_st[d]; m.ext_sz[d] = (int)c->ext_sz[d];
+  }
+  // ONE pass over the records (72 bytes each: at 10^6 of them every pass is a walk through memory), on a few host threads where there are
+  // many (sample_ranges): tag and aux word into the pinned block that goes up, the range of the timesteps beside it.  Everything behind reads the
+  // 16-byte pairs.  The table of slice pointers travels behind the pairs; the block has room for 2 048 timesteps from the start.
+  const size_t in_bytes = n * sizeof(ftkx::SampleIn);
+  size_t tab_room = 2048 * sizeof(ftkx::SampleSlice);
+  if (int rc = c->sm_h_in.reserve(c, in_bytes + tab_room, in_bytes + in_bytes / 4 + tab_room, c->stream)) return rc;
+  ftkx::SampleIn *h_in = c->sm_h_in.as<ftkx::SampleIn>();
+  std::atomic<int> lo(2147483647), hi(-1);
+  auto pack = [&]() {
+    sample_ranges(n, [&](size_t b, size_t e) {
+      int mn = 2147483647, mx = -1;
+      for (size_t i = b; i < e; i ++) {
+        h_in[i] = ftkx::SampleIn{recs[i].tag, ftkx_cp_aux(&recs[i]), 0u};
+        const int t = (int)(h_in[i].aux >> 1);
+        mn = std::min(mn, t); mx = std::max(mx, t);
+      }
+      for (int seen = lo.load(); mn < seen && !lo.compare_exchange_weak(seen, mn); ) {}
+      for (int seen = hi.load(); mx > seen && !hi.compare_exchange_weak(seen, mx); ) {}
+    });
+  };
+  pack();
+  const int t_min = lo.load(), t_max = hi.load();
+  if (t_max >= 2147483646 || (long long)t_max - (long long)t_min > (1ll << 22)) return fail(c, FTKX_E_NOSLICE, "%s: the records' timesteps span %d .. %d, which cannot all be resident", who, t_min, t_max);
+  if (m.tag_mode == FTKX_TAG_REFERENCE && !ftkx::sample_reference_tags_exact(nd, c->dom_sz, t_max))
+    return fail(c, FTKX_E_UNSUPPORTED, "%s: FTKX_TAG_REFERENCE tags may have wrapped at timestep %d of this mesh and cannot be decoded (use FTKX_TAG_EXACT64)", who, t_max);
+  const int ntab = t_max - t_min + 2;                                    // (an interval record of t_max reads t_max + 1)
+  const size_t tab_bytes = (size_t)ntab * sizeof(ftkx::SampleSlice);
+  if (tab_bytes > tab_room) {                                            // (more than 2 048 timesteps: the pairs are packed again into the larger block)
+    if (int rc = c->sm_h_in.reserve(c, in_bytes + tab_bytes, in_bytes + in_bytes / 4 + tab_bytes, c->stream)) return rc;
+    h_in = c->sm_h_in.as<ftkx::SampleIn>();
+    pack();
+  }
+  // which timesteps are read, and that every record decodes to a simplex inside the arrays: nothing else reaches the kernel
+  std::vector<unsigned char> need((size_t)ntab, 0);
+  std::mutex need_lock;
+  std::atomic<size_t> first_bad(n);
+  sample_ranges(n, [&](size_t b, size_t e) {
+    std::vector<unsigned char> mine((size_t)ntab, 0);
+    for (size_t i = b; i < e; i ++) {
+      const ftkx::SampleIn in = h_in[i];
+      const size_t at = (size_t)((int)(in.aux >> 1) - t_min);
+      mine[at] = 1;
+      if (!(in.aux & 1u)) mine[at + 1] = 1;
+      int corner[4], type = 0;
+      const bool ok = nd == 2 ? ftkx::sample_element<2>(m, ftkx::k_fan3, in.tag, in.aux, corner, type) : ftkx::sample_element<3>(m, ftkx::k_fan4, in.tag, in.aux, corner, type);
+      if (!ok) { size_t seen = first_bad.load(); while (i < seen && !first_bad.compare_exchange_weak(seen, i)) {} }
+    }
+    std::lock_guard<std::mutex> g(need_lock);
+    for (int k = 0; k < ntab; k ++) need[(size_t)k] |= mine[(size_t)k];
+  });
+  std::vector<ftkx::SampleSlice> tab((size_t)ntab, ftkx::SampleSlice{nullptr, nullptr, {nullptr, nullptr}});
+  int needed = 0, have[2] = {0, 0};
+  for (int k = 0; k < ntab; k ++) {
+    if (!need[(size_t)k]) continue;
+    const int t = t_min + k;
+    auto it = c->slices.find(t);
+    if (it == c->slices.end()) return fail(c, FTKX_E_NOSLICE, "%s: slice %d not resident", who, t);
+    const Slice &s = it->second;
+    if (s.sparse) return fail(c, FTKX_E_UNSUPPORTED, "%s: slice %d exists as masks and patches only", who, t);
+    if (m.scalar_mode ? !s.S.p : !s.V.p) return fail(c, FTKX_E_INVALID, "%s: slice %d has no field array", who, t);
+    tab[(size_t)k].S = s.S.as<double>(); tab[(size_t)k].V = s.V.as<double>();
+    needed ++;
+    auto ia = c->aux.find(t);
+    for (int a = 0; a < 2; a ++)
+      if (ia != c->aux.end() && ia->second.A[a].p) { tab[(size_t)k].A[a] = ia->second.A[a].as<double>(); have[a] ++; }
+  }
+  for (int a = 0; a < 2; a ++) {
+    if (have[a] != 0 && have[a] != needed) return fail(c, FTKX_E_NOSLICE, "%s: slot %d has an aux array at %d of the %d timesteps the records read", who, a + 1, have[a], needed);
+    if (have[a]) { P.slots |= 1u << a; P.nslots ++; }
+  }
+  if (const size_t i = first_bad.load(); i < n)
+    return fail(c, FTKX_E_INVALID, "%s: record %zu (tag %llu, timestep %d) is not an element of this context's mesh under its tag mode", who, i, recs[i].tag, ftkx_cp_timestep(&recs[i]));
+  if (!P.slots) return FTKX_OK;
+  memcpy(h_in + n, tab.data(), tab_bytes);
+  if (int rc = c->sm_d_in.reserve(c, in_bytes + tab_bytes, in_bytes + in_bytes / 4 + tab_bytes + 4096, c->stream)) return rc;
+  const size_t out_bytes = n * (size_t)P.nslots * sizeof(double);
+  if (int rc = c->sm_d_out.reserve(c, out_bytes, out_bytes + out_bytes / 4, c->stream)) return rc;
+  if (int rc = c->sm_h_out.reserve(c, out_bytes, out_bytes + out_bytes / 4, c->stream)) return rc;
+  HIP_TRY(c, hipMemcpyAsync(c->sm_d_in.p, c->sm_h_in.p, in_bytes + tab_bytes, hipMemcpyHostToDevice, c->stream));
+  P.t_min = t_min; P.ntab = ntab;
+  P.d_in = c->sm_d_in.as<ftkx::SampleIn>();
+  P.d_tab = reinterpret_cast<const ftkx::SampleSlice *>(P.d_in + n);
+  return FTKX_OK;
+}
+
+int ftkx_sample_aux(ftkx_ctx *c, ftkx_cp_t *recs, size_t n)
+{
+  SamplePlan P;
+  if (int rc = sample_prepare(c, "ftkx_sample_aux", recs, n, P)) return rc;
+  if (n == 0 || !P.slots) return FTKX_OK;
+  ftkx::launch_sample(c->nd, P.m, P.d_in, n, P.d_tab, P.t_min, P.slots, c->sm_d_out.as<double>(), c->stream);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(c->sm_h_out.p, c->sm_d_out.p, n * (size_t)P.nslots * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  c->sm_launches ++; c->sm_records += n;
+  const double *o = c->sm_h_out.as<double>();
+  const double *o1 = (P.slots & 1u) ? o : nullptr, *o2 = (P.slots & 2u) ? o + ((P.slots & 1u) ? n : 0) : nullptr;
+  sample_ranges(n, [&](size_t b, size_t e) {      // (one walk through the records for both slots)
+    for (size_t i = b; i < e; i ++) { if (o1) recs[i].scalar[1] = o1[i]; if (o2) recs[i].scalar[2] = o2[i]; }
+  });
+  return FTKX_OK;
+}
+
+// profiling aid (tools/sample_time.py): the sample kernel `reps` times back to back, a pair of events around every launch; the records are
+// not written
+int ftkx_debug_sample_relaunch(ftkx_ctx *c, const ftkx_cp_t *recs, size_t n, int reps, double *ms)
+{
+  if (c && (!ms || reps < 1 || n == 0)) return fail(c, FTKX_E_INVALID, "ftkx_debug_sample_relaunch: bad argument");
+  SamplePlan P;
+  if (int rc = sample_prepare(c, "ftkx_debug_sample_relaunch", recs, n, P)) return rc;
+  if (!P.slots) return fail(c, FTKX_E_NOSLICE, "ftkx_debug_sample_relaunch: no aux array is resident");
+  std::vector<hipEvent_t> ev(2 * (size_t)reps, nullptr);
+  auto run = [&]() -> int {
+    for (hipEvent_t &e : ev) HIP_TRY(c, hipEventCreate(&e));
+    for (int i = 0; i < reps; i ++) {
+      HIP_TRY(c, hipEventRecord(ev[2 * (size_t)i], c->stream));
+      ftkx::launch_sample(c->nd, P.m, P.d_in, n, P.d_tab, P.t_min, P.slots, c->sm_d_out.as<double>(), c->stream);
+      HIP_TRY(c, hipEventRecord(ev[2 * (size_t)i + 1], c->stream));
+    }
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (int i = 0; i < reps; i ++) { float t = 0; HIP_TRY(c, hipEventElapsedTime(&t, ev[2 * (size_t)i], ev[2 * (size_t)i + 1])); ms[i] = t; }
+    return FTKX_OK;
+  };
+  const int rc = run();
+  if (rc) (void)hipStreamSynchronize(c->stream);
+  for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+  return rc;
+}
+
+int ftkx_debug_sample_counts(const ftkx_ctx *c, unsigned long long *launches, unsigned long long *records)
+{
+  if (!c) return fail(nullptr, FTKX_E_INVALID, "null context");
+  if (launches) *launches = c->sm_launches;
+  if (records) *records = c->sm_records;
+  return FTKX_OK;
+}
+
 int ftkx_debug_planar_counts(const ftkx_ctx *c, unsigned long long *vec_launches, unsigned long long *scalar_launches)
 {
   if (!c) return fail(nullptr, FTKX_E_INVALID, "null context");
@@ -810,6 +1030,7 @@ int ftkx_drop_slice(ftkx_ctx *c, int t)
   (void)hipSetDevice(c->device);
   free_slice(it->second, c);
   c->slices.erase(it);
+  drop_aux(c, t);
   return FTKX_OK;
 }
 

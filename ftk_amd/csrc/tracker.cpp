@@ -511,6 +511,8 @@ void critical_point_tracker_regular::initialize()
   if ((int)domain.nd() != nd || (int)array_domain.nd() != nd) throw ftkx_error(FTKX_E_INVALID, "initialize: set_domain / set_array_domain first");
   if (temporal_smoothing_ksize && (multi || slab))
     throw ftkx_error(FTKX_E_UNSUPPORTED, "initialize: temporal smoothing with one device and no slab mode only (a slab needs raw halo snapshots of its neighbours)");
+  if (n_extra_expected() > 0 && (multi || slab || temporal_smoothing_ksize))
+    throw ftkx_error(FTKX_E_UNSUPPORTED, "initialize: extra scalar components with one device, no slab mode and no temporal smoothing only (its emissions lag the pushes)");
   sync();
   if (multi) { for (auto &W : multi->w) apply_configuration(W->ctx); }
   else apply_configuration(ctx);
@@ -552,6 +554,11 @@ void critical_point_tracker_regular::push_snapshot(int kind, const void *s, cons
 {
   if (planes && multi) throw ftkx_error(FTKX_E_UNSUPPORTED, "push: component planes with one device only (a multi-device tracker takes the interleaved FP64 array)");
   if (f32 && multi) throw ftkx_error(FTKX_E_UNSUPPORTED, "push: float32 snapshots with one device only (a multi-device tracker takes FP64 arrays)");
+  if (extras_in_push != n_extra_expected())
+    throw ftkx_error(FTKX_E_INVALID, "push: " + std::to_string(scalar_components.size()) + " scalar components take " + std::to_string(n_extra_expected()) + " extra arrays with every snapshot, not " +
+                                     std::to_string(extras_in_push));
+  if (extras_in_push > 0 && (multi || slab || temporal_smoothing_ksize || deferred_collection))
+    throw ftkx_error(FTKX_E_UNSUPPORTED, "push: extra scalar components not with deferred collection, several devices, slab mode or temporal smoothing");
   if (temporal_smoothing_ksize) {
     // the raw snapshot feeds the filter; what the filter emits is the snapshot the tracker sees (a device source is read, not adopted)
     if (kind == 2) throw ftkx_error(FTKX_E_UNSUPPORTED, "push_field_data_snapshot: temporal smoothing takes a scalar or a vector snapshot alone");
@@ -621,6 +628,54 @@ void critical_point_tracker_regular::push_field_data_snapshot(const double *s, c
 void critical_point_tracker_regular::push_scalar_field_snapshot(const float *s, bool device) { push_scalar(s, device, true); }
 void critical_point_tracker_regular::push_vector_field_snapshot(const float *v, bool device) { push_vector(v, device, true); }
 void critical_point_tracker_regular::push_field_data_snapshot(const float *s, const float *v, const float *j, bool device) { push_field_data(s, v, j, device, true); }
+
+// ---- extra scalar components (set_scalar_components) ------------------------------------------------------------------------------------
+void critical_point_tracker_regular::set_scalar_components(const std::vector<std::string> &names)
+{
+  if (names.empty() || names.size() > 3) throw ftkx_error(FTKX_E_INVALID, "set_scalar_components: one to three names (FTK_CP_MAX_NUM_VARS = 3)");
+  scalar_components = names;
+}
+
+// a snapshot and its extras: the snapshot as ever, then extra[k] as the aux array of slot k + 1 at the snapshot's timestep.  The extras are
+// checked first: a push that fails leaves no snapshot behind.
+void critical_point_tracker_regular::push_with_extras(int kind, const void *s, const void *v, const void *j, const void *const *extra, int n_extra, bool device, bool f32)
+{
+  if (n_extra < 0 || n_extra > 2 || (n_extra > 0 && !extra)) throw ftkx_error(FTKX_E_INVALID, "push: zero to two extra arrays");
+  for (int k = 0; k < n_extra; k ++) if (!extra[k]) throw ftkx_error(FTKX_E_INVALID, "push: extra array " + std::to_string(k) + " is null");
+  const int t = next_push_timestep;
+  extras_in_push = n_extra;
+  try {
+    if (kind == 0) push_scalar(s, device, f32);
+    else if (kind == 1) push_vector(v, device, f32);
+    else push_field_data(s, v, j, device, f32);
+  } catch (...) { extras_in_push = 0; throw; }
+  extras_in_push = 0;
+  for (int k = 0; k < n_extra; k ++)
+    check(f32 ? ftkx_push_aux_slice_f32(ctx, t, k + 1, static_cast<const float *>(extra[k]), device ? 1 : 0)
+              : ftkx_push_aux_slice(ctx, t, k + 1, static_cast<const double *>(extra[k]), device ? 1 : 0));
+}
+
+void critical_point_tracker_regular::push_scalar_field_snapshot(const double *s, const double *const *extra, int n_extra, bool device)
+{ push_with_extras(0, s, nullptr, nullptr, reinterpret_cast<const void *const *>(extra), n_extra, device, false); }
+void critical_point_tracker_regular::push_vector_field_snapshot(const double *v, const double *const *extra, int n_extra, bool device)
+{ push_with_extras(1, nullptr, v, nullptr, reinterpret_cast<const void *const *>(extra), n_extra, device, false); }
+void critical_point_tracker_regular::push_field_data_snapshot(const double *s, const double *v, const double *j, const double *const *extra, int n_extra, bool device)
+{ push_with_extras(2, s, v, j, reinterpret_cast<const void *const *>(extra), n_extra, device, false); }
+void critical_point_tracker_regular::push_scalar_field_snapshot(const float *s, const float *const *extra, int n_extra, bool device)
+{ push_with_extras(0, s, nullptr, nullptr, reinterpret_cast<const void *const *>(extra), n_extra, device, true); }
+void critical_point_tracker_regular::push_vector_field_snapshot(const float *v, const float *const *extra, int n_extra, bool device)
+{ push_with_extras(1, nullptr, v, nullptr, reinterpret_cast<const void *const *>(extra), n_extra, device, true); }
+void critical_point_tracker_regular::push_field_data_snapshot(const float *s, const float *v, const float *j, const float *const *extra, int n_extra, bool device)
+{ push_with_extras(2, s, v, j, reinterpret_cast<const void *const *>(extra), n_extra, device, true); }
+
+// The sampling point: behind the step's sweep, in front of the pop of its snapshots.  The context's record buffer stays as the sweep left it.
+void critical_point_tracker_regular::sample_step_records(const ftkx_cp_t *&recs, size_t n, std::vector<ftkx_cp_t> &store)
+{
+  if (n_extra_expected() == 0 || n == 0) return;
+  store.assign(recs, recs + n);
+  check(ftkx_sample_aux(ctx, store.data(), n));
+  recs = store.data();
+}
 
 // nc < 1 never reaches push_snapshot, where 0 means "no planes"; whether nc is the tracker's dimension is the context's check
 void critical_point_tracker_regular::push_vector_field_components(const double *const *comps, int nc, bool device)
@@ -695,6 +750,7 @@ void critical_point_tracker_regular::update_timestep()
 // still out), then collect the step before it
 void critical_point_tracker_regular::step_deferred(int scope)
 {
+  if (n_extra_expected() > 0) throw ftkx_error(FTKX_E_UNSUPPORTED, "update_timestep: extra scalar components not with deferred collection (a step's snapshots are popped before its records arrive)");
   if (deferred_depth > 1) {                 // batches: recorded; queued with the batch's last step (submit_batch)
     batch_ts.push_back(current_timestep); batch_scopes.push_back(scope);
     if ((int)batch_ts.size() >= deferred_depth) submit_batch();
@@ -726,6 +782,8 @@ void critical_point_tracker_regular::step_now(int scope)
     update_vector_field_scaling_factor();
     check(ftkx_sweep(ctx, current_timestep, scope, vector_field_scaling_factor, &recs, &n));
   }
+  std::vector<ftkx_cp_t> sampled;
+  sample_step_records(recs, n, sampled);
   take_records(recs, n, current_timestep);
   check(ftkx_get_stats(ctx, &last_stats));
   if (enable_streaming_trajectories && scope == FTKX_SCOPE_BOTH) grow();      // 2d:326-330, 3d:197-201: only after an interval sweep
@@ -912,7 +970,10 @@ void critical_point_tracker_regular::write_discrete(const std::string &filename,
   recs.reserve(points.size());
   for (const feature_point_t &cp : points) recs.push_back(record_of(cp));
   // text labels: the reference's scalar_components default to {"scalar"} whether or not a scalar field exists
-  check_on(nullptr, ftkx_write_critical_points(filename.c_str(), format, recs.data(), recs.size(), nullptr, nullptr, nullptr, -1));     // (the i/o calls leave their message with the calling thread)
+  std::vector<const char *> names;
+  for (const std::string &s : scalar_components) names.push_back(s.c_str());
+  check_on(nullptr, ftkx_write_critical_points(filename.c_str(), format, recs.data(), recs.size(), nullptr, nullptr, names.empty() ? nullptr : names.data(),
+                                               names.empty() ? -1 : (int)names.size()));     // (the i/o calls leave their message with the calling thread)
 }
 void critical_point_tracker_regular::write_critical_points_json(const std::string &f) const { write_discrete(f, FTKX_FORMAT_JSON); }
 void critical_point_tracker_regular::write_critical_points_binary(const std::string &f) const { write_discrete(f, FTKX_FORMAT_BINARY); }
@@ -954,7 +1015,10 @@ void critical_point_tracker_regular::write_traced(const std::string &filename, i
   std::memset(&tr, 0, sizeof(tr));
   tr.n_curves = num_traced_curves(); tr.n_points = f.recs.size();
   tr.offsets = offsets.data(); tr.indices = f.indices.data(); tr.loop = loop.data(); tr.type = type.data(); tr.t = t.data(); tr.id = ids.data();
-  check_on(nullptr, ftkx_write_traced_critical_points(filename.c_str(), format, f.recs.data(), f.recs.size(), &tr, nullptr, -1));     // (the i/o calls leave their message with the calling thread)
+  std::vector<const char *> names;
+  for (const std::string &s : scalar_components) names.push_back(s.c_str());
+  check_on(nullptr, ftkx_write_traced_critical_points(filename.c_str(), format, f.recs.data(), f.recs.size(), &tr, names.empty() ? nullptr : names.data(),
+                                                      names.empty() ? -1 : (int)names.size()));     // (the i/o calls leave their message with the calling thread)
 }
 void critical_point_tracker_regular::write_traced_critical_points_json(const std::string &f) const { write_traced(f, FTKX_FORMAT_JSON); }
 void critical_point_tracker_regular::write_traced_critical_points_binary(const std::string &f) const { write_traced(f, FTKX_FORMAT_BINARY); }
@@ -1151,6 +1215,43 @@ int ftkx_tracker_get_curve_points(const ftkx_tracker *h, unsigned int *type, dou
   for (size_t k = 0; k < pts.size(); k ++) { if (type) type[k] = pts[k].type; if (t) t[k] = pts[k].t; }
   if (ids) for (size_t i = 0; i < h->t->num_traced_curves(); i ++) ids[i] = h->t->get_traced_ids()[i];
   return FTKX_OK;
+}
+
+int ftkx_tracker_get_curve_scalars(const ftkx_tracker *h, double *scalars)
+{
+  if (!h || !h->t || !scalars) return FTKX_E_INVALID;
+  const auto &pts = h->t->get_traced_points();
+  for (size_t k = 0; k < pts.size(); k ++) for (int s = 0; s < 3; s ++) scalars[3 * k + s] = pts[k].scalar[s];
+  return FTKX_OK;
+}
+
+int ftkx_tracker_set_scalar_components(ftkx_tracker *h, const char *const *names, int n)
+{
+  return guarded(h, [&] {
+    if (!names || n < 1 || n > 3) throw ftkx::ftkx_error(FTKX_E_INVALID, "ftkx_tracker_set_scalar_components: one to three names");
+    std::vector<std::string> v;
+    for (int i = 0; i < n; i ++) { if (!names[i]) throw ftkx::ftkx_error(FTKX_E_INVALID, "ftkx_tracker_set_scalar_components: null name"); v.push_back(names[i]); }
+    h->t->set_scalar_components(v);
+  });
+}
+
+int ftkx_tracker_push_snapshot_extra(ftkx_tracker *h, int kind, const void *s, const void *v, const void *j, const void *const *extra, int n_extra, int dev, int f32)
+{
+  return guarded(h, [&] {
+    ftkx::critical_point_tracker_regular &t = *h->t;
+    if (kind < 0 || kind > 2) throw ftkx::ftkx_error(FTKX_E_INVALID, "ftkx_tracker_push_snapshot_extra: kind 0, 1 or 2");
+    if (f32) {
+      const float *const *e = reinterpret_cast<const float *const *>(extra);
+      if (kind == 0) t.push_scalar_field_snapshot(static_cast<const float *>(s), e, n_extra, dev != 0);
+      else if (kind == 1) t.push_vector_field_snapshot(static_cast<const float *>(v), e, n_extra, dev != 0);
+      else t.push_field_data_snapshot(static_cast<const float *>(s), static_cast<const float *>(v), static_cast<const float *>(j), e, n_extra, dev != 0);
+    } else {
+      const double *const *e = reinterpret_cast<const double *const *>(extra);
+      if (kind == 0) t.push_scalar_field_snapshot(static_cast<const double *>(s), e, n_extra, dev != 0);
+      else if (kind == 1) t.push_vector_field_snapshot(static_cast<const double *>(v), e, n_extra, dev != 0);
+      else t.push_field_data_snapshot(static_cast<const double *>(s), static_cast<const double *>(v), static_cast<const double *>(j), e, n_extra, dev != 0);
+    }
+  });
 }
 
 int ftkx_tracker_write(const ftkx_tracker *h, const char *path, int format, int traced)

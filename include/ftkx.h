@@ -31,7 +31,7 @@ extern "C" {
 typedef struct ftkx_cp_t {
   double x[3];              /* lattice coordinates (REGULAR_COORDS_SIMPLE); 2D: x[2] = 0 */
   double t;
-  double scalar[3];         /* scalar[0] filled iff a scalar field was given (FTK_CP_MAX_NUM_VARS = 3) */
+  double scalar[3];         /* scalar[0] filled iff a scalar field was given (FTK_CP_MAX_NUM_VARS = 3); [1], [2]: 0 unless ftkx_sample_aux filled them */
   unsigned int type;        /* include/ftk/numeric/critical_point_type.hh:10-36 */
   unsigned long long tag;   /* see ftkx_options.tag_mode */
 } ftkx_cp_t;
@@ -588,6 +588,39 @@ int ftkx_debug_adjust_relaunch(ftkx_ctx *ctx, const void *src, int src_is_f32, s
                                double *dst, int reps, double *ms);
 /* how many snapshots this context was pushed went through the adjust kernel: from a float32 source, FP64 in place, FP64 out of place */
 int ftkx_debug_adjust_counts(const ftkx_ctx *ctx, unsigned long long *from_float, unsigned long long *in_place, unsigned long long *out_of_place);
+
+/* ---- auxiliary scalar fields sampled at critical points (critical_point_tracker::set_scalar_components, filters/critical_point_tracker.hh:50-51) ---- */
+/* A record has three scalar slots (FTK_CP_MAX_NUM_VARS); the sweep fills scalar[0] from the slice's own S.  Slots 1 and 2 take other fields
+ * of the same lattice -- pressure at the critical points of a velocity field, two more variables along an extremum's trajectory -- read at
+ * the critical point with the very barycentric weights scalar[0] is read with: mu from the simplex's field values exactly as the record
+ * kernels form it (2D: the solve, clamped only where it failed; 3D: the solve, always clamped), then a[0] * mu[0] + a[1] * mu[1] + ... left
+ * to right.  Pushing a slice's own S as an aux array gives scalar[0] back bit for bit.  It is ONE pass over finished records, behind any
+ * sweep (ftkx_sweep, _collect, _series, the one-shot calls' records with a context of the same mesh): the sweeps, their kernels and their
+ * records are not changed by it, and records whose slots nobody asks for keep zeros there.
+ * ftkx_push_aux_slice: A holds one value per vertex of the mesh's array extent (the layout of S) and becomes the aux array of slot 1 or 2
+ * at timestep t, replacing one that was there.  on_device as for ftkx_push_scalar_slice: 0 host memory, copied; 2 device memory of any
+ * device, copied; 1 device memory of this context's device, LENT -- read where it lies, never written, never freed by the library, the
+ * caller's until ftkx_drop_slice(t) or ftkx_destroy.  _f32: widened on the device into an array of the context's own (on_device 1: read
+ * where it lies, the call returns once it has been read).  Aux arrays come out of and go back to the pool of the slices' field arrays
+ * (ftkx_debug_array_counts, class 0).  They belong to timestep t, not to the slice object: they may be pushed before or after the field
+ * slice, stay when it is pushed again, and leave with ftkx_drop_slice(t).  Spatial and temporal smoothing, perturbation and clamp NEVER
+ * apply to them: an aux array is read as it was pushed.  FTKX_E_INVALID: slot not 1 or 2, a null or misaligned array, no mesh.
+ * ftkx_sample_aux: recs are n host records of this context's mesh and options, with the aux word the sweep wrote (they may be the
+ * context's own record buffer).  For every slot that has an aux array at ALL timesteps the records read -- a record's own, and the one
+ * behind it for an interval record -- scalar[slot] of every record is overwritten; no other byte of a record changes.  Everything is
+ * checked before anything is written (all or nothing): a timestep without a resident field slice, or a slot with arrays at some of the
+ * timesteps but not all: FTKX_E_NOSLICE; a slice that exists as masks only: FTKX_E_UNSUPPORTED; FTKX_TAG_REFERENCE tags on a mesh and at
+ * timesteps where their int32 products may have wrapped (the tag no longer says which element it is): FTKX_E_UNSUPPORTED; a record that is
+ * no element of the mesh: FTKX_E_INVALID.  No slot with arrays, or n == 0: FTKX_OK, nothing is done.  16 bytes per record go up, 8 per
+ * record and slot come down, through buffers the context keeps; the call waits for its kernel on the context's stream. */
+int ftkx_push_aux_slice(ftkx_ctx *ctx, int t, int slot /* 1 | 2 */, const double *A, int on_device);
+int ftkx_push_aux_slice_f32(ftkx_ctx *ctx, int t, int slot /* 1 | 2 */, const float *A, int on_device);
+int ftkx_sample_aux(ftkx_ctx *ctx, ftkx_cp_t *recs, size_t n);
+/* profiling aid (tools/sample_time.py): the kernel of ftkx_sample_aux launched `reps` times back to back on the context's stream, a pair of
+ * events around every launch; ms: reps device times.  The records are not written. */
+int ftkx_debug_sample_relaunch(ftkx_ctx *ctx, const ftkx_cp_t *recs, size_t n, int reps, double *ms);
+/* launches of the sample kernel by ftkx_sample_aux on this context so far, and the records they took.  Either may be null. */
+int ftkx_debug_sample_counts(const ftkx_ctx *ctx, unsigned long long *launches, unsigned long long *records);
 
 /* test aid: the ordering step of the device-driven pass completed last on this context (ftkx_sweep_series, ftkx_sweep_series_complete), as
  * it ran: out[0] the number of buckets, out[1] the shift that takes an order key to its bucket, out[2] the fullest bucket, out[3] the

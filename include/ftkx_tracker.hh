@@ -179,6 +179,16 @@ public:
   void set_perturbation(double sigma, unsigned long long seed = 0) { perturbation_sigma = sigma; perturbation_seed = seed; }
   void set_clamp(double lo, double hi) { clamp_on = true; clamp_lo = lo; clamp_hi = hi; }
   void unset_clamp() { clamp_on = false; }
+  // critical_point_tracker::set_scalar_components (critical_point_tracker.hh:50-51): one to three names; the first names scalar[0], the
+  // tracker's own scalar field (which stays 0 where there is none, whatever it is called), the others name fields of the same lattice that
+  // are sampled at every critical point with its barycentric weights (ftkx.h: ftkx_push_aux_slice, ftkx_sample_aux) and land in scalar[1]
+  // and scalar[2].  With more than one name every snapshot is pushed with its extra arrays (the push_* overloads that take `extra`), and
+  // update_timestep() samples the step's records before the step's snapshots are popped: get_critical_points(), the traced and the
+  // streaming trajectories and the writers see the filled slots; the text writers print the names.  Smoothing, perturbation and clamp never
+  // touch the extra arrays.  Not covered, FTKX_E_UNSUPPORTED at initialize() or at the push: deferred collection, multi-device trackers,
+  // slab mode, temporal smoothing (its emissions lag the pushes).
+  void set_scalar_components(const std::vector<std::string> &names);
+  const std::vector<std::string> &get_scalar_components() const { return scalar_components; }
   int snapshots_from_last_push() const { return last_push_snapshots; }      // 0 or 1; always 1 with the filter off
   bool flush_temporal_smoothing();
   // Several RANKS behind the tracker -- one process per GPU, or one tracker per device and thread in one process.  The reference keeps an
@@ -211,6 +221,15 @@ public:
   void push_scalar_field_snapshot(const float *scalar, bool device = false);
   void push_vector_field_snapshot(const float *vector, bool device = false);
   void push_field_data_snapshot(const float *scalar, const float *vector, const float *jacobian, bool device = false);
+  // the same with the snapshot's extra scalar fields (set_scalar_components): extra[0 .. n_extra - 1], one value per vertex each, for
+  // scalar[1] (and scalar[2]); n_extra must be the number of names minus one, and a tracker with more than one name takes these forms
+  // only.  device = true: FP64 extras are borrowed like the snapshot, until it is popped; float32 extras are read before the call returns.
+  void push_scalar_field_snapshot(const double *scalar, const double *const *extra, int n_extra, bool device = false);
+  void push_vector_field_snapshot(const double *vector, const double *const *extra, int n_extra, bool device = false);
+  void push_field_data_snapshot(const double *scalar, const double *vector, const double *jacobian, const double *const *extra, int n_extra, bool device = false);
+  void push_scalar_field_snapshot(const float *scalar, const float *const *extra, int n_extra, bool device = false);
+  void push_vector_field_snapshot(const float *vector, const float *const *extra, int n_extra, bool device = false);
+  void push_field_data_snapshot(const float *scalar, const float *vector, const float *jacobian, const float *const *extra, int n_extra, bool device = false);
   // a vector snapshot as one array per component (u, v, w in separate variables of a file): comps[0 .. nc - 1], nc the tracker's dimension,
   // each a host (device = true: device) array of one value per vertex.  They are interleaved -- and widened where they are floats -- on
   // the device (ftkx.h: ftkx_push_slice_planar); the tracker gives what push_vector_field_snapshot gives for the interleaved array.  Device
@@ -291,6 +310,12 @@ protected:
   void push_scalar(const void *s, bool device, bool f32);                                          // the push_* methods' checks, in front of push_snapshot
   void push_vector(const void *v, bool device, bool f32, int planes = 0);
   void push_field_data(const void *s, const void *v, const void *j, bool device, bool f32);
+  // extra scalar fields (set_scalar_components)
+  std::vector<std::string> scalar_components;               // empty: never set (the writers' default label, no extras)
+  int n_extra_expected() const { return scalar_components.empty() ? 0 : (int)scalar_components.size() - 1; }
+  int extras_in_push = 0;                                   // how many extras the push_* call in hand brings (push_snapshot holds it to the names)
+  void push_with_extras(int kind, const void *s, const void *v, const void *j, const void *const *extra, int n_extra, bool device, bool f32);
+  void sample_step_records(const ftkx_cp_t *&recs, size_t n, std::vector<ftkx_cp_t> &store);   // the step's records with slots 1, 2 filled (a copy in `store`)
   double vector_field_resolution = std::numeric_limits<double>::max();   // sticky running minimum (never reset)
   unsigned long long vector_field_scaling_factor = 1;
   ftkx_stats last_stats;
@@ -425,6 +450,13 @@ int  ftkx_tracker_push_vector_field_snapshot_f32(ftkx_tracker *, const float *v,
 int  ftkx_tracker_push_field_data_snapshot_f32(ftkx_tracker *, const float *s, const float *v, const float *j, int on_device);
 int  ftkx_tracker_push_vector_field_components(ftkx_tracker *, const double *const *comps, int nc, int on_device);   /* one array per component, interleaved on the device */
 int  ftkx_tracker_push_vector_field_components_f32(ftkx_tracker *, const float *const *comps, int nc, int on_device);
+/* critical_point_tracker_regular::set_scalar_components: n (1 .. 3) names; and the push_* overloads that bring a snapshot's extra scalar
+ * fields: kind 0 push_scalar_field_snapshot (s), 1 push_vector_field_snapshot (v), 2 push_field_data_snapshot (s, v, j); f32 != 0: every
+ * array of the call is float32.  ftkx_tracker_get_curve_scalars: after finalize, scalar[0 .. 2] of every curve point, 3 doubles per point
+ * in the order of ftkx_tracker_get_curves */
+int  ftkx_tracker_set_scalar_components(ftkx_tracker *, const char *const *names, int n);
+int  ftkx_tracker_push_snapshot_extra(ftkx_tracker *, int kind, const void *s, const void *v, const void *j, const void *const *extra, int n_extra, int on_device, int f32);
+int  ftkx_tracker_get_curve_scalars(const ftkx_tracker *, double *scalars);
 int  ftkx_tracker_advance_timestep(ftkx_tracker *);
 int  ftkx_tracker_update_timestep(ftkx_tracker *);
 int  ftkx_tracker_num_critical_points(const ftkx_tracker *, size_t *n);

@@ -1,0 +1,178 @@
+"""ftk_amd/csrc/sample_steps.hpp WITHOUT a GPU, through tests/hostcheck/sample_host.cpp: sampling a fixture's own S at the fixture's records
+gives the scalar[0] the reference's CPU path wrote (tag decode, vertices, mu and the lerp order pinned at once), a foreign field gives what
+the pinned oracle gives with that field as S, the three tag modes decode the same elements, FTKX_TAG_REFERENCE is refused exactly where
+its bound says the tags may have wrapped, and the same file runs as a program of its own under AddressSanitizer + UBSan.
+All comparisons of doubles are on bit patterns (a NaN equal to any NaN)."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import sample_cases as SC
+from common import load_golden, wrap_golden_names
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+NEW = ["ftkx_push_aux_slice", "ftkx_push_aux_slice_f32", "ftkx_sample_aux", "ftkx_debug_sample_relaunch", "ftkx_debug_sample_counts", "ftkx_tracker_set_scalar_components",
+       "ftkx_tracker_push_snapshot_extra", "ftkx_tracker_get_curve_scalars"]
+
+
+def _runtime(name):
+    p = subprocess.run(["g++", "-print-file-name=" + name], capture_output=True, text=True).stdout.strip()
+    return p if os.path.isabs(p) and os.path.exists(p) else None
+
+
+@pytest.fixture(scope="module")
+def hs(tmp_path_factory):
+    return SC.host(tmp_path_factory.mktemp("hostcheck"))
+
+
+# ---- 1. self-sampling against the real reference ---------------------------------------------------------------------------------------------
+def test_self_sampling_covers_the_named_fixtures():
+    names = SC.scalar_golden_names()
+    for want in ("moving_extremum_3d_21x21x21x4_overflow", "moving_extremum_2d_21x21x9_aligned", "moving_extremum_3d_12x10x9x5_aligned", "adversarial_2d_scalar_17x13x6",
+                 "adversarial_3d_scalar_9x9x9x4", "huge_nan_3d_scalar_10x9x9x3", "random_3d_scalar_13x12x11x4_norobust"):
+        assert want in names
+    assert all(load_golden(n)["nv"] == 1 for n in names) and len(names) >= 25
+
+
+@pytest.mark.parametrize("name", SC.scalar_golden_names())
+def test_own_scalar_field_sampled_is_the_references_scalar0(hs, name):
+    g = load_golden(name)
+    r = g["records"]
+    assert len(r) > 0
+    aux = SC.aux_words(r)
+    # (the fixtures' tags are the reference's: int32 products that did not wrap on these meshes, so the 64-bit decode applies)
+    assert hs.hs_reference_ok(g["nd"], (C.c_longlong * 3)(*(SC.domain_of(g)[1] + [1] * (3 - g["nd"]))), int(r["timestep"].max())) == 1
+    o1, o2, ok, bad = SC.host_sample(g, SC.TAG_REFERENCE, r["tag"], aux, A1=g["steps"], A2=g["steps"])
+    assert bad == 0 and ok.all()
+    assert SC.same_doubles(o1, r["scalar"]), f"{name}: {int((o1.view(np.uint64) != r['scalar'].view(np.uint64)).sum())} of {len(r)} values differ from the reference's scalar[0]"
+    assert SC.same_doubles(o2, r["scalar"])
+
+
+# ---- 2. a foreign field against the pinned oracle ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", SC.FOREIGN)
+def test_foreign_field_is_what_the_oracle_gives_with_it_as_S(hs, oracle, name):
+    g = load_golden(name)
+    r = g["records"]
+    assert len(r) >= 20 and r["ordinal"].any() and not r["ordinal"].all(), "a case needs 20 records, ordinal and interval ones"
+    B = [SC.foreign_field(name, t, 0) for t in range(g["DT"])]
+    Cf = [SC.foreign_field(name, t, 1) for t in range(g["DT"])]
+    for b in B:
+        f = b.reshape(-1)
+        assert np.abs(f[np.arange(f.size) % 17 != 0]).max() <= 1e3 and set(np.abs(f[::17]).tolist()) <= {0.0, 5e-324, 1e300}
+    o1, o2, ok, bad = SC.host_sample(g, SC.TAG_EXACT64, r["tag"], SC.aux_words(r), A1=B, A2=Cf)
+    assert bad == 0 and ok.all()
+    e1 = SC.expected_for(r["tag"], SC.foreign_expectation(oracle, name, 0))
+    e2 = SC.expected_for(r["tag"], SC.foreign_expectation(oracle, name, 1))
+    assert SC.same_doubles(o1, e1), f"{name}: {int((o1.view(np.uint64) != e1.view(np.uint64)).sum())} of {len(r)} values differ from the oracle's"
+    assert SC.same_doubles(o2, e2)
+    assert not SC.same_doubles(o1, o2)
+
+
+# ---- 3. tag modes -----------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["random_2d_scalar_29x24x6", "random_3d_scalar_13x12x11x4"])
+def test_tag_modes_name_the_same_elements(hs, name):
+    g = load_golden(name)
+    r = g["records"]
+    aux = SC.aux_words(r)
+    B = [SC.foreign_field(name, t, 0) for t in range(g["DT"])]
+    ref = SC.host_sample(g, SC.TAG_EXACT64, r["tag"], aux, A1=B)
+    assert ref[3] == 0
+    same = SC.host_sample(g, SC.TAG_REFERENCE, r["tag"], aux, A1=B)
+    assert same[3] == 0 and SC.same_doubles(same[0], ref[0])
+    wi = SC.work_index_tags(g, r["tag"], aux)
+    assert not np.array_equal(wi, r["tag"])
+    work = SC.host_sample(g, SC.TAG_WORK_INDEX, wi, aux, A1=B)
+    assert work[3] == 0 and SC.same_doubles(work[0], ref[0])
+    # the decode itself, element by element, against the tag formula
+    nd = g["nd"]
+    st, sz = SC.domain_of(g)
+    mesh = SC.mesh_ints(g, SC.TAG_EXACT64)
+    corner = (C.c_int * 4)(); typ = C.c_int()
+    for i in range(0, len(r), max(1, len(r) // 200)):
+        assert hs.hs_element(nd, mesh.ctypes.data, int(r["tag"][i]), int(aux[i]), corner, C.byref(typ)) == 1
+        lin = 0
+        for d in reversed(range(nd)):
+            lin = lin * sz[d] + (corner[d] - st[d])
+        lin += int(r["timestep"][i]) * int(np.prod(sz))
+        assert lin * (12 if nd == 2 else 60) + typ.value == int(r["tag"][i]) and corner[nd] == int(r["timestep"][i])
+
+
+def test_a_tag_of_another_mesh_is_refused_not_read(hs):
+    g = load_golden("random_2d_scalar_29x24x6")
+    r = g["records"]
+    aux = SC.aux_words(r)
+    tags = r["tag"].copy()
+    tags[0] = np.uint64(2 ** 62)                       # a corner index far outside the domain
+    aux2 = aux.copy(); aux2[1] ^= 1                    # a type that is not of the scope the aux word names
+    o1, _, ok, bad = SC.host_sample(g, SC.TAG_EXACT64, tags, aux2, A1=g["steps"])
+    assert bad == 2 and not ok[0] and not ok[1] and ok[2:].all() and o1[0] == 0.0 and o1[1] == 0.0
+
+
+@pytest.mark.parametrize("name", wrap_golden_names())
+def test_wrapped_reference_tags_are_refused_exact64_decodes(hs, oracle, name):
+    g = load_golden(name)
+    nd, t0 = g["nd"], g["t0"]
+    sz = (C.c_longlong * 3)(*(SC.domain_of(g)[1] + [1] * (3 - nd)))
+    bound = (12 if nd == 2 else 60) * int(np.prod(SC.domain_of(g)[1]))
+    # unsupported exactly when the bound says the int32 products may have wrapped
+    for t_max in (0, 1, t0, t0 + g["DT"], (2 ** 31 - 1) // bound - 2, (2 ** 31 - 1) // bound - 1, (2 ** 31 - 1) // bound):
+        if 0 <= t_max < 2 ** 31 - 2:
+            assert hs.hs_reference_ok(nd, sz, int(t_max)) == (1 if bound * (t_max + 2) < 2 ** 31 else 0), t_max
+    assert hs.hs_reference_ok(nd, sz, t0) == 0                       # these series start where the tags wrap
+    exact, _, _ = oracle.track(g["steps"], nd, g["nv"], tag_mode=oracle.TAG_EXACT64, nthreads=4, t0=t0)
+    assert len(exact) == len(g["records"])
+    fields = g["steps"]
+    A = fields if g["nv"] == 1 else [np.ascontiguousarray(f[..., 0]) for f in fields]      # (vector input: its first component as the aux field)
+    o1, _, ok, bad = SC.host_sample(g, SC.TAG_EXACT64, exact["tag"], SC.aux_words(exact), A1=A, t0=t0)
+    assert bad == 0 and ok.all()
+    if g["nv"] == 1:
+        assert SC.same_doubles(o1, exact["scalar"][:, 0])            # the oracle's scalar[0] of the same elements
+    # the reference's (wrapped) tags of the same records do not name these elements any more
+    _, _, ok_ref, bad_ref = SC.host_sample(g, SC.TAG_EXACT64, g["records"]["tag"], SC.aux_words(g["records"]), A1=A, t0=t0)
+    assert bad_ref > 0
+
+
+def test_steps_are_clean_under_asan_ubsan(tmp_path):
+    """(no skip where the runtimes are missing: the bounds of the arrays are then unchecked, which is a failure)"""
+    assert _runtime("libasan.so") and _runtime("libubsan.so"), "g++ finds no libasan / libubsan: the sanitizer run of sample_steps.hpp cannot be made"
+    exe = str(tmp_path / "sample_host_san")
+    r = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-DSAMPLE_HOST_MAIN", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                        "-fno-omit-frame-pointer", "-pthread", "-o", exe, SC.SRC], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    env = dict(os.environ, ASAN_OPTIONS="abort_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
+    r = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=600)
+    assert r.returncode == 0 and "sample_host run complete" in r.stdout and "Sanitizer" not in r.stderr, (r.stdout[-2000:], r.stderr[-4000:])
+
+
+# ---- the entries, without a GPU --------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def lib():
+    from ftk_amd import build, _lib
+    build.build()
+    return _lib.load()
+
+
+def test_entries_are_declared_exported_and_bound(lib):
+    from ftk_amd import _lib, build
+    import ftk_amd
+    hdr = open(os.path.join(ROOT, "include", "ftkx.h")).read() + open(os.path.join(ROOT, "include", "ftkx_tracker.hh")).read()
+    for name in NEW:
+        assert name + "(" in hdr and hasattr(lib, name) and name in _lib.EXPORTS, name
+    for n in ("push_aux_slice", "sample_aux", "sample_counts", "debug_sample_relaunch"):
+        assert callable(getattr(ftk_amd.Context, n)), n
+    for cls in (ftk_amd.CriticalPointTracker2DRegular, ftk_amd.CriticalPointTracker3DRegular):
+        assert callable(cls.set_scalar_components) and callable(cls.get_traced_scalars)
+    assert "sample_kernels.hip" in [os.path.basename(s) for s in build.SRC]
+
+
+def test_null_context_is_refused(lib):
+    from ftk_amd import _lib
+    E = _lib.E_INVALID
+    assert lib.ftkx_push_aux_slice(None, 0, 1, None, 0) == E and lib.ftkx_push_aux_slice_f32(None, 0, 1, None, 0) == E
+    assert lib.ftkx_sample_aux(None, None, 0) == E and lib.ftkx_debug_sample_relaunch(None, None, 1, 1, None) == E
+    assert lib.ftkx_debug_sample_counts(None, None, None) == E
+    assert lib.ftkx_tracker_set_scalar_components(None, None, 1) == E and lib.ftkx_tracker_get_curve_scalars(None, None) == E
