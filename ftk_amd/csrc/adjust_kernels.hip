@@ -25,7 +25,7 @@ __global__ __launch_bounds__(kAdjustThreads) void adjust_kernel(const T *src, Ad
 }
 
 // src: `count` elements at a multiple of sizeof(T) bytes, dst: `count` doubles at a multiple of 8, equal to src or not overlapping it,
-// count >= 1, perturb || clamp: checked by the callers (ftkx_api.hip)
+// count >= 1, perturb || clamp: checked by the callers (ingest.hip)
 template <class T> void launch_adjust(const T *src, size_t count, bool perturb, bool clamp, const AdjustArgs &a, double *dst, hipStream_t st)
 {
   const AdjustPlan p = adjust_plan<T>(src, count, dst);

@@ -187,7 +187,7 @@ struct AdjustPlan {
   bool vec;          // a pair is one aligned access on either side
 };
 
-// src: a multiple of sizeof(T) bytes, dst: a multiple of 8; src == dst or no overlap (checked by the callers, ftkx_api.hip)
+// src: a multiple of sizeof(T) bytes, dst: a multiple of 8; src == dst or no overlap (checked by the callers, ingest.hip)
 template <class T> inline AdjustPlan adjust_plan(const T *src, size_t count, const double *dst)
 {
   AdjustPlan p;

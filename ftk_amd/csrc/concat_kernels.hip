@@ -54,7 +54,7 @@ template <class T, int NC> static bool launch_concat_nc(const T *const *planes, 
 }
 
 // planes: nc (2 or 3) arrays of `count` elements each at a multiple of sizeof(T) bytes, dst: count * nc doubles at a multiple of 8 that
-// overlap no plane, count >= 1: checked by the callers (ftkx_api.hip).  Returns whether the 16-byte body was launched.
+// overlap no plane, count >= 1: checked by the callers (ingest.hip).  Returns whether the 16-byte body was launched.
 template <class T> bool launch_concat(const T *const *planes, int nc, size_t count, double *dst, hipStream_t st)
 {
   return nc == 2 ? launch_concat_nc<T, 2>(planes, count, dst, st) : launch_concat_nc<T, 3>(planes, count, dst, st);

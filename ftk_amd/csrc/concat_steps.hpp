@@ -13,7 +13,7 @@
 // dst + head * NC is a multiple of 16 as well.  Then the head's vertices go one by one to lanes 0 .. G - 1 of workgroup 0 and the up to
 // G - 1 vertices behind the last whole group to its lanes G .. 2G - 1.  Otherwise every vertex goes on its own (NC narrow loads, NC 8-byte
 // stores): head 0, nvec = count, no tail.  Planes start at any multiple of sizeof(T), dst at any multiple of 8, dst overlaps no plane (the
-// callers check, ftkx_api.hip); planes may be one another.
+// callers check, ingest.hip); planes may be one another.
 //
 // How the body's doubles reach memory was decided by measurement (NOTES, "Planar vector snapshots"), per element type:
 //   double planes: DIRECT.  The lane that loaded a group stores its run itself, as 16-byte stores; groups are dealt to the lanes of a capped

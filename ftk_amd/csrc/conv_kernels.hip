@@ -54,7 +54,7 @@ template <int ND, int K, class SRC> static void launch_conv_k(const SRC *S, cons
   hipLaunchKernelGGL((conv_kernel<ND, K, SRC>), dim3(grid), dim3(kConvThreads), 0, st, S, d, d_weights, out);
 }
 
-// nd 2 or 3 (2D: DD == 1), ksize odd in [1, 9], extents >= 1: checked by the callers (ftkx_api.hip).  d_weights: ksize^nd doubles on the device.
+// nd 2 or 3 (2D: DD == 1), ksize odd in [1, 9], extents >= 1: checked by the callers (ingest.hip).  d_weights: ksize^nd doubles on the device.
 // SRC double or float: a float32 source is widened where the tile is staged, so no widened copy of it is written and read back.
 template <class SRC> void launch_conv(int nd, const SRC *S, int DW, int DH, int DD, const double *d_weights, int ksize, double *out, hipStream_t st)
 {

@@ -1,5 +1,5 @@
 // Shared between the translation units of libftkx.so that implement the C ABI of include/ftkx.h (ftkx_api.hip: context, slices,
-// options, one-shot calls; prepare.hip: the one-pass mask + reduction pre-pass; collect.hip: the batched sweep; halo.hip: the compact
+// options, one-shot calls; ingest.hip: how snapshots come in -- pushes, smoothing, perturbation and clamp, the temporal ring; prepare.hip: the one-pass mask + reduction pre-pass; collect.hip: the batched sweep; halo.hip: the compact
 // t-slab halo; series.hip: the device-driven pass over a resident series).  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -318,7 +318,7 @@ struct ftkx_ctx {
   // here as it came, 4 bytes per value, until the widen kernel or the convolution has made the FP64 slice of it.  Reserved by the bytes of
   // that very array (count * sizeof(float)), drained by the stream that read it last.  Written by the upload's DMAs or a copy on the
   // context's stream, read by one kernel on the context's stream: how the next push's writes are ordered behind that kernel is said where
-  // it is filled (ftkx_api.hip, stage_into).
+  // it is filled (ingest.hip, ingest).
   ftkx_block f32_stage;
   hipStream_t f32_stage_reader = nullptr;      // the stream of the kernel that read it last
   unsigned long long f32_widened = 0, f32_direct = 0;   // ftkx_debug_f32_counts: float32 arrays through the widen kernel / straight through the convolution
@@ -432,7 +432,16 @@ int fail(ftkx_ctx *c, int code, const char *fmt, ...);
                                       "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
   } while (0)
 
+// what the one-shot calls on device pointers open with
+#define DERIVE_PROLOGUE(c) do { if (!(c)) return fail(nullptr, FTKX_E_INVALID, "null context"); HIP_TRY((c), hipSetDevice((c)->device)); } while (0)
+
+// ingest.hip
+void temporal_release(ftkx_ctx *c);                             // the temporal ring's arrays back to the pool, the filter as it was constructed
+void drop_aux(ftkx_ctx *c, int t);                              // the aux arrays of timestep t leave
+int adopt_resident_slice(ftkx_ctx *c, int t, const double *full);   // the library's own borrowing push of an array that has been processed already (slab.cpp)
 // ftkx_api.hip
+const std::string &global_error();                              // what fail(nullptr, ...) said last on this thread
+int settings_not_now(ftkx_ctx *c, const char *who);             // a setting must not change under sweeps pending or series passes open: 0, or fail()'s code
 size_t n_vertices(const ftkx_ctx *c);
 int mask_pitch(const ftkx_ctx *c);
 int u_pitch(const ftkx_ctx *c);

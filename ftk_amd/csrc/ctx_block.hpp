@@ -62,7 +62,7 @@ private:
 
 // The slice arrays of a context that no slice holds right now (a streaming tracker pushes and pops one slice per step: an allocation and a
 // free per step cost more than the sweep itself).  An array is taken out for exactly the class and the bytes it was allocated with, so one
-// of another lattice is never handed out.  WHEN an array may come back depends on stream order and stays with the callers (ftkx_api.hip:
+// of another lattice is never handed out.  WHEN an array may come back depends on stream order and stays with the callers (ftkx_api.hip, ingest.hip:
 // free_slice, release_retired, give_pooled); whatever takes it out next is ordered behind its last reader by the context's stream,
 // whichever array it is: every class is searched newest first (what was given back last is what the caches may still hold).
 enum ftkx_array_class { FTKX_ARRAY_FIELD = 0, FTKX_ARRAY_MASK, FTKX_ARRAY_SUMMARY, FTKX_ARRAY_CLASSES };

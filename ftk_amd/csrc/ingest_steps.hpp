@@ -1,0 +1,64 @@
+// How a caller's array becomes a resident FP64 array of the context: ONE pure function from the case to the steps, free of the device.
+// ingest.hip executes the plan (every push, the temporal ring, the aux arrays); tests/test_ingest_plan_host.py walks every case without a
+// GPU through tests/hostcheck/ingest_plan.cpp, and tests/test_gpu_ingest_paths.py holds the executor's counters to it.
+//
+// The case: the source's element type (f32: float, else double), its form (planar: one array per component, else one interleaved array),
+// whether the spatial smoothing applies (smooth), whether perturbation or clamp applies (adjust: false for a raw array -- an aux array),
+// where the caller says it lies (on_device 0 host, 1 this device and borrowable, 2 device memory of any device) and whether every source
+// pointer IS device memory of the context's device (on_this_device).  planar && smooth is refused by every caller before the plan is asked.
+#pragma once
+
+namespace ftkx {
+
+enum IngestStage { INGEST_STAGE_NONE = 0, INGEST_STAGE_F32, INGEST_STAGE_POOLED };       // the context's f32_stage block / a pooled field array
+enum IngestCopy { INGEST_COPY_NONE = 0, INGEST_COPY_TO_DST, INGEST_COPY_TO_STAGE };      // where the source is copied to
+// the first kernel of the chain: it writes dst.  INGEST_ADJUST is adjust_kernel<T> on the source's own type (float: in place of the widen kernel)
+enum IngestKernel { INGEST_NO_KERNEL = 0, INGEST_CONCAT, INGEST_CONV, INGEST_ADJUST, INGEST_WIDEN };
+// which of the context's debug counters the chain moves, as bits (planar: planar_vec or planar_scalar, by what launch_concat returns)
+enum IngestCounter { INGEST_CNT_FROM_FLOAT = 1, INGEST_CNT_IN_PLACE = 2, INGEST_CNT_OUT_OF_PLACE = 4, INGEST_CNT_F32_WIDENED = 8, INGEST_CNT_F32_DIRECT = 16, INGEST_CNT_PLANAR = 32 };
+
+struct IngestPlan {
+  bool reads_here;        // a kernel may read the caller's pointers where they lie
+  bool adopt;             // the array is lent to the context as it is: nothing is taken, nothing is queued
+  bool caller_waits;      // the call returns only once the source has been read (a host source has been staged completely by the upload)
+  IngestStage stage;
+  IngestCopy copy;
+  IngestKernel first;     // reads the stage where there is one, dst after a copy into dst, the caller's pointers otherwise
+  bool then_adjust;       // adjust_kernel<double> in place on dst behind the first kernel (or behind the copy): the LAST kernel of the chain
+  unsigned counters;
+};
+
+// Whether the plan depends on on_this_device at all: where it does not, the executor does not ask the runtime where the pointers lie.
+inline bool ingest_asks_where(bool f32, bool planar, bool smooth, bool adjust, int on_device)
+{
+  return (planar ? on_device == 1 : on_device != 0) && (f32 || planar || smooth || adjust);
+}
+
+// must_own: the caller keeps the array for itself (the temporal ring owns its slots) and never adopts.
+inline IngestPlan ingest_plan(bool f32, bool planar, bool smooth, bool adjust, int on_device, bool on_this_device, bool must_own = false)
+{
+  IngestPlan p{false, false, false, INGEST_STAGE_NONE, INGEST_COPY_NONE, INGEST_NO_KERNEL, false, 0u};
+  // THE TWO DIFFER: planes handed over as "device memory of any device" (2) are always staged, an interleaved array of 2 that lies on this
+  // device is read where it lies.  Kept as it was found; making planes read in place is a change of behaviour and speed of its own.
+  p.reads_here = (planar ? on_device == 1 : on_device != 0) && on_this_device;
+  p.adopt = !must_own && !f32 && !planar && on_device == 1 && !smooth && !adjust;      // (the pointer is not examined)
+  p.caller_waits = on_device != 0 && !p.adopt;
+  if (p.adopt) return p;
+  if (!f32 && !planar && !smooth) {
+    // FP64, interleaved, no smoothing: no staging array.  Brought straight into dst (and adjusted there), or -- on this device, with
+    // something to compute -- read where it lies and written adjusted into dst
+    if (adjust && p.reads_here) { p.first = INGEST_ADJUST; p.counters = INGEST_CNT_OUT_OF_PLACE; }
+    else { p.copy = INGEST_COPY_TO_DST; p.then_adjust = adjust; p.counters = adjust ? INGEST_CNT_IN_PLACE : 0u; }
+    return p;
+  }
+  // everything a kernel reads: it reads this device's memory only
+  if (!p.reads_here) { p.stage = f32 ? INGEST_STAGE_F32 : INGEST_STAGE_POOLED; p.copy = INGEST_COPY_TO_STAGE; }
+  p.first = planar ? INGEST_CONCAT : smooth ? INGEST_CONV : adjust ? INGEST_ADJUST : INGEST_WIDEN;      // (the last two: float by elimination)
+  p.then_adjust = adjust && p.first != INGEST_ADJUST;
+  p.counters = p.first == INGEST_CONCAT ? INGEST_CNT_PLANAR : p.first == INGEST_CONV ? (f32 ? INGEST_CNT_F32_DIRECT : 0u)
+             : p.first == INGEST_ADJUST ? INGEST_CNT_FROM_FLOAT : INGEST_CNT_F32_WIDENED;
+  if (p.then_adjust) p.counters |= INGEST_CNT_IN_PLACE;
+  return p;
+}
+
+}  // namespace ftkx

@@ -115,14 +115,7 @@ int rb_recover(void *u, int t_halo, const void *full, const int *ts, const int *
   // (`full` is the upper neighbour's RESIDENT first slice: where spatial smoothing is set it has been smoothed by its owner's push and
   // must not be convolved again, and where perturbation or clamp is set it has been adjusted there -- this push is the library's own, and
   // borrows the array as it is)
-  const int smoothing = c->smooth_ksize;
-  const ftkx_ctx::Adjust adjust = c->adj;
-  c->smooth_ksize = 0;
-  c->adj = ftkx_ctx::Adjust();
-  rc = c->scalar_mode == 1 ? ftkx_push_scalar_slice(c, t_halo, (const double *)full, 1) : ftkx_push_slice(c, t_halo, (const double *)full, nullptr, nullptr, 1);
-  c->smooth_ksize = smoothing;
-  c->adj = adjust;
-  if (rc) return rc;
+  if ((rc = ftkxh::adopt_resident_slice(c, t_halo, (const double *)full))) return rc;
   rc = ftkx_sweep_series(c, ts, scopes, n, running, factors, out, n_out);
   const int rc2 = ftkx_drop_slice(c, t_halo);                // (the next pass starts compact again)
   return rc ? rc : rc2;

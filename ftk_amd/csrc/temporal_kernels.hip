@@ -39,7 +39,7 @@ template <int K, int NSRC> struct TemporalDispatch {
 template <int K> struct TemporalDispatch<K, 0> { static void go(int, const TemporalArgs &, size_t, double *, hipStream_t) {} };
 
 // arrays: ksize device pointers of `count` doubles, repeats allowed; weights: ksize doubles on the host; ksize odd in [1, 9] and count >= 1:
-// checked by the callers (ftkx_api.hip)
+// checked by the callers (ingest.hip)
 void launch_temporal(const double *const *arrays, int ksize, const double *weights, size_t count, double *out, hipStream_t st)
 {
   TemporalArgs a;

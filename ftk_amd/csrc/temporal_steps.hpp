@@ -1,5 +1,5 @@
 // Temporal Gaussian smoothing of a series of snapshots: the state machine that says which snapshots an emission adds up, and what one
-// element's sum is, for temporal_kernels.hip and ftkx_api.hip.
+// element's sum is, for temporal_kernels.hip and ingest.hip.
 //
 // Reference (host): include/ftk/filters/streaming_filter.hh, driven by ndarray_stream::modified_callback with
 // --temporal-smoothing-kernel[-size] (include/ftk/ndarray/stream.hh); its weights: gaussian_kernel, include/ftk/ndarray/conv.hh:50-72.

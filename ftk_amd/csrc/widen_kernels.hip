@@ -20,7 +20,7 @@ __global__ __launch_bounds__(kWidenThreads) void widen_kernel(const float *__res
   widen_lane<VEC>(src, p, dst, (size_t)blockIdx.x, (size_t)gridDim.x, (int)threadIdx.x);
 }
 
-// src: `count` floats at a multiple of 4 bytes, dst: `count` doubles at a multiple of 8, not overlapping, count >= 1: checked by the callers (ftkx_api.hip)
+// src: `count` floats at a multiple of 4 bytes, dst: `count` doubles at a multiple of 8, not overlapping, count >= 1: checked by the callers (ingest.hip)
 void launch_widen(const float *src, size_t count, double *dst, hipStream_t st)
 {
   const WidenPlan p = widen_plan(src, count, dst);

@@ -40,7 +40,7 @@ struct WidenPlan {
   WIDEN_HD size_t tail_at() const { return vec ? head + nvec * (size_t)kWidenGroup : count; }     // [tail_at, count): one by one, lanes 4 .. 6 of workgroup 0
 };
 
-// src: a multiple of 4 bytes, dst: a multiple of 8 (checked by the callers, ftkx_api.hip)
+// src: a multiple of 4 bytes, dst: a multiple of 8 (checked by the callers, ingest.hip)
 inline WidenPlan widen_plan(const float *src, size_t count, const double *dst)
 {
   WidenPlan p;
