@@ -179,7 +179,7 @@ def synthetic(name, dims, k, DT, x0=None, dirv=None):
 
 
 def sweep(nd, scope, t, domain, core, ext, V, J, S, factor, jacobian_symmetric=True, robust=True,
-          type_filter=None, compute_degrees=False, tag_mode=TAG_EXACT64, nthreads=1, explicit=None, rectilinear=None):
+          type_filter=None, compute_degrees=False, tag_mode=TAG_EXACT64, nthreads=1, explicit=None, rectilinear=None, bounds=None):
     """domain/core/ext = (starts, sizes) spatial.  V/J/S = (cur, next) numpy arrays or None.
     explicit: REGULAR_COORDS_EXPLICIT array of shape (n1, n0, ncomp).  rectilinear: REGULAR_COORDS_RECTILINEAR, one 1-D array per axis."""
     a = SweepArgs()
@@ -200,6 +200,10 @@ def sweep(nd, scope, t, domain, core, ext, V, J, S, factor, jacobian_symmetric=T
     a.jacobian_symmetric, a.robust = int(jacobian_symmetric), int(robust)
     a.use_type_filter, a.type_filter = int(type_filter is not None), int(type_filter or 0)
     a.compute_degrees, a.tag_mode, a.nthreads = int(compute_degrees), tag_mode, nthreads
+    if bounds is not None:            # REGULAR_COORDS_BOUNDS, as track(bounds=...) sets it
+        a.coords_mode = 1
+        for i, b in enumerate(bounds):
+            a.bounds[i] = float(b)
     if explicit is not None:
         e = _f64(explicit); keep.append(e)
         a.coords_mode, a.expl, a.expl_ncomp, a.expl_n0 = 3, e.ctypes.data, e.shape[-1], e.shape[-2]
