@@ -174,143 +174,248 @@ void ev_harvest(ftkx_ctx *c, bool all)
   c->events.swap(later);
 }
 
-// launches everything the pending requests need; counters must have been zeroed.
-// Fast-path requests are grouped into sub-batches (one mask / cull / exact launch each); a new sub-batch starts whenever a
-// slice's masks would be needed under a second quantisation factor (the factor is a running minimum, so it changes a few
-// times at the start of a series and then stays put).
-int run_batch(ftkx_ctx *c, const double *sparse_field, bool cull_done)
+void ev_drop(ftkx_ctx *c) { for (auto &e : c->events) { ev_give(c, e.second.first); ev_give(c, e.second.second); } c->events.clear(); }
+
+int read_counters(ftkx_ctx *c)
 {
-  const bool cull_only = sparse_field != nullptr;   // ftkx_sweep_cull: stop after the cull and list the survivors that read `sparse_field`
-  Mesh m;
-  fill_mesh(c, m);
-  const int nd = c->nd;
-  struct Sub { std::vector<MaskJob> jobs; std::vector<Fields> steps; };
-  std::vector<Sub> subs(1);
-  const bool two_level = ftkx::masks_have_summary(m);
-  // the tile requests: one launch per run of consecutive requests with the same cull setting -- a workgroup walks the run's steps in time
-  // order with its tile staged in LDS (tile_kernels.hip) -- under the smallest form any of them asks for (every form is correct everywhere)
-  std::vector<TileParams> tiles;
-  std::vector<Fields> tile_fields;
-  const bool tile_walk = !(getenv("FTKX_TILE_WALK") && atoi(getenv("FTKX_TILE_WALK")) == 0);      // (test hook: 0 = a launch per step)
+  HIP_TRY(c, hipMemcpyAsync(c->h_counters.p, c->sr_tail[0].counters.as<u64>(), ftkx::CNT_N * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return FTKX_OK;
+}
+
+// ---- the host-driven batch: gather -> plan_batch (batch_plan.hpp) -> stage -> queue -> commit -------------------------------------------
+namespace {
+// the slices the pending requests read, each once, and the requests in terms of them
+struct BatchInput { std::vector<Slice *> slice; std::vector<SliceFacts> facts; std::vector<BatchRequest> requests; };
+
+void gather_batch(ftkx_ctx *c, BatchInput &in)
+{
+  std::map<int, int> index;
+  auto at = [&](int t) {
+    const auto ins = index.emplace(t, (int)in.slice.size());
+    if (ins.second) { Slice &s = c->slices[t]; in.slice.push_back(&s); in.facts.push_back(slice_facts(s)); }
+    return ins.first->second;
+  };
   for (const Request &r : c->pending) {
-    Slice &s0 = c->slices[r.t];
-    Slice *s1 = (r.scope & FTKX_SCOPE_INTERVAL) ? &c->slices[r.t + 1] : nullptr;
+    const int s0 = at(r.t);
+    in.requests.push_back(BatchRequest{r.mode, s0, (r.scope & FTKX_SCOPE_INTERVAL) ? at(r.t + 1) : -1, r.factor});
+  }
+}
+
+// everything the plan needs in memory: mask arrays of the slices it builds, the descriptor block, filled, the tile kernels' statistics
+int stage_batch(ftkx_ctx *c, const Mesh &m, bool two_level, const BatchInput &in, const BatchPlan &P)
+{
+  for (const BatchSub &sb : P.subs)
+    for (const BatchMaskJob &j : sb.jobs)
+      if (const int rc = ensure_mask_arrays(c, *in.slice[j.slice], two_level)) return rc;
+  if (!P.runs.empty()) {
+    bool fresh = false;
+    if (const int rc = c->d_tile_stats.reserve(c, 512 * sizeof(u64), 0, nullptr, &fresh)) return rc;
+    if (fresh) HIP_TRY(c, hipMemsetAsync(c->d_tile_stats.p, 0, 512 * sizeof(u64), c->stream));
+  }
+  if (!P.bytes) return FTKX_OK;
+  if (const int rc = ensure_desc(c, P.bytes)) return rc;
+  auto fields_of = [&](int i, bool fast) {
+    const Request &r = c->pending[i];
+    const int of[2] = {in.requests[i].s0, in.requests[i].s1};
     Fields f;
     memset(&f, 0, sizeof(f));
-    f.S[0] = s0.S.as<double>(); f.V[0] = s0.V.as<double>(); f.J[0] = s0.J.as<double>();
-    if (s1) { f.S[1] = s1->S.as<double>(); f.V[1] = s1->V.as<double>(); f.J[1] = s1->J.as<double>(); }
     f.factor = (double)r.factor; f.t = r.t; f.scope_mask = r.scope;
-    if (r.mode == MODE_FAST) {
-      for (Slice *s : {&s0, s1}) {
-        if (!s) continue;
-        if (masks_valid(c, *s, r.factor, two_level, m.u_rows)) continue;     // e.g. built by ftkx_slices_prepare, or by an earlier step
-        if (s->sparse) return fail(c, FTKX_E_NOSLICE, "sweep: the masks of halo slice (masks only) do not serve factor %llu: send the slice itself", r.factor);
-        int rc = ensure_mask_arrays(c, *s, two_level);
-        if (rc) return rc;
-        // masks of this slice already (re)built or used in the current sub-batch under another factor -> close it
-        bool touched = false;
-        for (const MaskJob &j : subs.back().jobs) touched = touched || j.M == s->M.p;
-        for (const Fields &g : subs.back().steps) touched = touched || g.M[0] == s->M.p || g.M[1] == s->M.p;
-        if (touched) subs.emplace_back();
-        bool rule_on;
-        const double big = job_big(c, *s, r.factor, &rule_on);
-        subs.back().jobs.push_back(with_lean_thresholds(MaskJob{s->S.as<double>(), s->V.as<double>(), s->M.as<unsigned char>(), two_level ? s->U.as<unsigned char>() : nullptr, nullptr, 1.0 / (double)r.factor, big}, m));
-        s->mask_factor = r.factor; s->mask_big = rule_on; s->u_rows = m.u_rows;
-      }
-      f.M[0] = s0.M.as<unsigned char>(); f.M[1] = s1 ? s1->M.as<unsigned char>() : nullptr;
-      f.U[0] = two_level ? s0.U.as<unsigned char>() : nullptr; f.U[1] = (two_level && s1) ? s1->U.as<unsigned char>() : nullptr;
-      subs.back().steps.push_back(f);
-    } else {
-      TileParams p;
-      p.m = m; p.steps = nullptr; p.nsteps = 1; p.repeat = c->tile_repeat; p.cull = r.mode == MODE_TILE_CULL ? 1 : 0; p.step = (int)tile_fields.size();
-      tile_fields.push_back(f);
-      { const char *e = getenv("FTKX_TILE_FAN"); p.fan = e ? atoi(e) : 2; }
-      {
-        // largest |quantised component| the request can meet, where the slices' maxima are known (the kernel checks every tile anyway)
-        double bound = -1.0;
-        if (s0.max_known() && (!s1 || s1->max_known())) bound = std::max(s0.maxabs, s1 ? s1->maxabs : 0.0) * (double)r.factor;
-        const double fp_bound = nd == 3 ? 524287.0 : 33554431.0;     // below 2^19 (3D: error-bounded fp64) / 2^25 (2D: exact fp64)
-        p.form = (nd == 3 && !m.robust) ? 0 : bound < 0 ? 1 : bound < fp_bound ? 2 : bound < 2147483647.0 ? 1 : 0;
-        p.form = std::min(p.form, p.fan == 9 ? 2 : p.fan);
-      }
-      int tile[3];
-      ftkx::tile_dims(nd, tile);
-      for (int d = 0; d < 3; d ++) p.ntiles[d] = d < nd ? (int)((c->core_sz[d] + tile[d] - 1) / tile[d]) : 1;
-      if (tile_walk && !tiles.empty() && tiles.back().cull == p.cull && tiles.back().fan == p.fan && tiles.back().step + tiles.back().nsteps == p.step) {
-        tiles.back().nsteps ++;
-        tiles.back().form = std::min(tiles.back().form, p.form);
-      } else tiles.push_back(p);
+    for (int k = 0; k < 2; k ++) {
+      if (of[k] < 0) continue;
+      const Slice &s = *in.slice[of[k]];
+      f.S[k] = s.S.as<double>(); f.V[k] = s.V.as<double>(); f.J[k] = s.J.as<double>();
+      if (fast) { f.M[k] = s.M.as<unsigned char>(); f.U[k] = two_level ? s.U.as<unsigned char>() : nullptr; }
     }
-  }
-  // one upload for all descriptors: the mask jobs of each sub-batch, then ONE array of Fields for the whole batch -- the steps of
-  // sub-batch 0, 1, ... back to back (each cull / exact launch gets its slice of it) and the tile requests behind them; the
-  // record kernel looks a simplex's request up in that array by the index its pass descriptor carries
-  size_t total = 0;
-  std::vector<size_t> job_off, step_base;
-  for (const Sub &sb : subs) { job_off.push_back(total); total += (sb.jobs.size() * sizeof(MaskJob) + 255) / 256 * 256; }
-  const size_t fields_off = total;
-  size_t nfields = 0;
-  for (const Sub &sb : subs) { step_base.push_back(nfields); nfields += sb.steps.size(); }
-  const size_t tile_base = nfields;
-  nfields += tile_fields.size();
-  total += (nfields * sizeof(Fields) + 255) / 256 * 256;
-  if ((nfields >> (64 - ftkx::kPassStepShift)) != 0) return fail(c, FTKX_E_INVALID, "sweep: too many requests in one batch (%zu)", nfields);
-  if (total) {
-    int rc = ensure_desc(c, total);
-    if (rc) return rc;
-    Fields *hf = (Fields *)((char *)c->h_desc.p + fields_off);
-    for (size_t i = 0; i < subs.size(); i ++) {
-      if (!subs[i].jobs.empty()) memcpy((char *)c->h_desc.p + job_off[i], subs[i].jobs.data(), subs[i].jobs.size() * sizeof(MaskJob));
-      if (!subs[i].steps.empty()) memcpy(hf + step_base[i], subs[i].steps.data(), subs[i].steps.size() * sizeof(Fields));
+    return f;
+  };
+  char *h = (char *)c->h_desc.p;
+  Fields *hf = (Fields *)(h + P.fields_off);
+  for (size_t i = 0; i < P.subs.size(); i ++) {
+    MaskJob *hj = (MaskJob *)(h + P.job_off[i]);
+    for (const BatchMaskJob &j : P.subs[i].jobs) {
+      const Slice &s = *in.slice[j.slice];
+      *hj ++ = with_lean_thresholds(MaskJob{s.S.as<double>(), s.V.as<double>(), s.M.as<unsigned char>(), two_level ? s.U.as<unsigned char>() : nullptr, nullptr, 1.0 / (double)j.factor, j.big}, m);
     }
-    for (size_t i = 0; i < tile_fields.size(); i ++) hf[tile_base + i] = tile_fields[i];
-    HIP_TRY(c, hipMemcpyAsync(c->d_desc.p, c->h_desc.p, total, hipMemcpyHostToDevice, c->stream));
+    Fields *hs = hf + P.step_base[i];
+    for (int r : P.subs[i].steps) *hs ++ = fields_of(r, true);
   }
-  const Fields *d_fields = (const Fields *)((char *)c->d_desc.p + fields_off);
-  for (TileParams &p : tiles) { p.step += (int)tile_base; p.steps = d_fields + p.step; }
-  if (cull_only && (subs.size() > 1 || !tiles.empty()))
-    return fail(c, FTKX_E_UNSUPPORTED, "ftkx_sweep_cull: the batch needs masks under two factors or the tile path (send the slice itself)");
-  for (size_t i = 0; i < subs.size(); i ++) {
-    const Sub &sb = subs[i];
+  for (size_t k = 0; k < P.tile_steps.size(); k ++) hf[P.tile_base + k] = fields_of(P.tile_steps[k], false);
+  return FTKX_OK;
+}
+
+// the whole batch onto the context's stream, in one go; counters must have been zeroed
+int queue_batch(ftkx_ctx *c, const Mesh &m, bool two_level, const BatchPlan &P, const double *sparse_field, bool cull_done)
+{
+  const bool cull_only = sparse_field != nullptr;
+  ftkx_tail_set &T = c->sr_tail[0];
+  if (P.bytes) HIP_TRY(c, hipMemcpyAsync(c->d_desc.p, c->h_desc.p, P.bytes, hipMemcpyHostToDevice, c->stream));
+  const Fields *d_fields = (const Fields *)((char *)c->d_desc.p + P.fields_off);
+  for (size_t i = 0; i < P.subs.size(); i ++) {
+    const BatchSub &sb = P.subs[i];
     if (sb.steps.empty()) continue;
-    const MaskJob *d_jobs = (const MaskJob *)((char *)c->d_desc.p + job_off[i]);
-    const Fields *d_steps = d_fields + step_base[i];
+    const MaskJob *d_jobs = (const MaskJob *)((char *)c->d_desc.p + P.job_off[i]);
+    const Fields *d_steps = d_fields + P.step_base[i];
     if (!sb.jobs.empty()) { ev_begin(c, K_MASK); ftkx::launch_masks(m, d_jobs, (int)sb.jobs.size(), c->stream); ev_end(c); }
     // the survivor list is shared by the sub-batches of one collect: the exact kernel of sub-batch i must not re-test the
     // survivors of sub-batch i-1, so each sub-batch gets its own list segment by resetting the list counter in between
     if (i > 0) {
-      HIP_TRY(c, hipMemsetAsync(c->sr_tail[0].counters.as<u64>() + ftkx::CNT_SURVIVOR_LIST, 0, sizeof(u64), c->stream));
-      HIP_TRY(c, hipMemsetAsync(c->sr_tail[0].counters.as<u64>() + ftkx::CNT_REFINE_LIST, 0, sizeof(u64), c->stream));
+      HIP_TRY(c, hipMemsetAsync(T.counters.as<u64>() + ftkx::CNT_SURVIVOR_LIST, 0, sizeof(u64), c->stream));
+      HIP_TRY(c, hipMemsetAsync(T.counters.as<u64>() + ftkx::CNT_REFINE_LIST, 0, sizeof(u64), c->stream));
     }
-    if (cull_done) {    // the survivor list of exactly these steps is on the device already (cull-ahead, see ftkx_ctx::ahead)
-      if (subs.size() != 1 || !sb.jobs.empty()) return fail(c, FTKX_E_DEVICE, "internal: cull-ahead taken over by a batch that rebuilds masks");
-    } else {
+    if (!cull_done) {    // (cull-ahead, see ftkx_ctx::ahead: the survivor list of exactly these steps is on the device already)
       ev_begin(c, K_CULL);
-      if (two_level) ftkx::launch_cull_two_level(m, d_steps, (int)sb.steps.size(), c->sr_tail[0].refine.as<u64>(), c->sr_tail[0].refine_capacity, c->sr_tail[0].list.as<u64>(), c->sr_tail[0].list_capacity, c->stream);
-      else ftkx::launch_cull(m, d_steps, (int)sb.steps.size(), c->sr_tail[0].list.as<u64>(), c->sr_tail[0].list_capacity, c->stream);
+      if (two_level) ftkx::launch_cull_two_level(m, d_steps, (int)sb.steps.size(), T.refine.as<u64>(), T.refine_capacity, T.list.as<u64>(), T.list_capacity, c->stream);
+      else ftkx::launch_cull(m, d_steps, (int)sb.steps.size(), T.list.as<u64>(), T.list_capacity, c->stream);
       ev_end(c);
     }
     if (cull_only) {
       // (the exact kernel is what publishes the list peak; without it the host reads the list counter itself)
-      ftkx::launch_sparse_cells(m, d_steps, c->sr_tail[0].list.as<u64>(), c->sr_tail[0].list_capacity, sparse_field, c->d_cells.as<u64>(), c->d_cells.count<u64>(), c->stream);
+      ftkx::launch_sparse_cells(m, d_steps, T.list.as<u64>(), T.list_capacity, sparse_field, c->d_cells.as<u64>(), c->d_cells.count<u64>(), c->stream);
       continue;
     }
-    ev_begin(c, K_EXACT); ftkx::launch_exact(m, d_steps, (int)step_base[i], c->sr_tail[0].list.as<u64>(), c->sr_tail[0].list_capacity, c->stream); ev_end(c);
+    ev_begin(c, K_EXACT); ftkx::launch_exact(m, d_steps, (int)P.step_base[i], T.list.as<u64>(), T.list_capacity, c->stream); ev_end(c);
   }
   if (cull_only) { HIP_TRY(c, hipGetLastError()); return FTKX_OK; }
-  if (!tiles.empty()) {
-    bool fresh = false;
-    if (const int rc = c->d_tile_stats.reserve(c, 512 * sizeof(u64), 0, nullptr, &fresh)) return rc;
-    if (fresh) HIP_TRY(c, hipMemsetAsync(c->d_tile_stats.p, 0, 512 * sizeof(u64), c->stream));
-    for (TileParams &p : tiles) { p.stats = c->d_tile_stats.as<u64>(); ev_begin(c, K_TILE); ftkx::launch_tile(p, c->stream); ev_end(c); }
+  if (!P.runs.empty()) {
+    TileParams p;
+    p.m = m; p.repeat = c->tile_repeat; p.stats = c->d_tile_stats.as<u64>();
+    int tile[3];
+    ftkx::tile_dims(c->nd, tile);
+    for (int d = 0; d < 3; d ++) p.ntiles[d] = d < c->nd ? (int)((c->core_sz[d] + tile[d] - 1) / tile[d]) : 1;
+    for (const BatchTileRun &run : P.runs) {
+      p.step = (int)P.tile_base + run.first; p.steps = d_fields + p.step; p.nsteps = run.nsteps;
+      p.cull = run.cull; p.fan = run.fan; p.form = run.form;
+      ev_begin(c, K_TILE); ftkx::launch_tile(p, c->stream); ev_end(c);
+    }
     ftkx::launch_tile_stats_fold(c->d_tile_stats.as<u64>(), m.counters, c->stream);
   }
   // the FP64 half, once for the whole batch: records of every simplex that passed (timed with the kernel family that fed it)
   // (K_EXACT also behind tile requests: K_TILE is the integer test of every simplex and nothing else -- bench.py's int-VALU figure)
-  if (nfields) { ev_begin(c, K_EXACT); ftkx::launch_records(m, d_fields, c->stream); ev_end(c); }
+  if (P.nfields) { ev_begin(c, K_EXACT); ftkx::launch_records(m, d_fields, c->stream); ev_end(c); }
   HIP_TRY(c, hipGetLastError());
   return FTKX_OK;
 }
+}  // namespace
+
+// Launches everything the pending requests need.  What the slices say of their masks changes once the whole batch has been queued --
+// one uninterrupted sequence on one stream, so "built" then holds for everything queued later -- and not before: a batch that is
+// refused, or cannot get its memory, leaves every slice as it was; one that fails between launches leaves the masks it meant to
+// build marked as not built.
+int run_batch(ftkx_ctx *c, const double *sparse_field, bool cull_done)
+{
+  Mesh m;
+  fill_mesh(c, m);
+  const bool two_level = ftkx::masks_have_summary(m);
+  BatchInput in;
+  gather_batch(c, in);
+  // (test hooks, read per batch: 0 = a tile launch per step; the tile kernel's fan)
+  const char *walk = getenv("FTKX_TILE_WALK"), *fan = getenv("FTKX_TILE_FAN");
+  const BatchPlan P = plan_batch(BatchMesh{c->nd, m.robust != 0, two_level, m.u_rows}, in.requests, in.facts, BatchKnobs{!(walk && atoi(walk) == 0), fan ? atoi(fan) : 2});
+  if (P.status == BATCH_SPARSE_CANNOT_SERVE)
+    return fail(c, FTKX_E_NOSLICE, "sweep: the masks of halo slice (masks only) do not serve factor %llu: send the slice itself", c->pending[P.refused].factor);
+  if (P.status == BATCH_TOO_MANY) return fail(c, FTKX_E_INVALID, "sweep: too many requests in one batch (%zu)", P.nfields);
+  if (sparse_field && (P.subs.size() > 1 || !P.runs.empty()))      // ftkx_sweep_cull: one cull, whose survivors that read `sparse_field` are listed
+    return fail(c, FTKX_E_UNSUPPORTED, "ftkx_sweep_cull: the batch needs masks under two factors or the tile path (send the slice itself)");
+  if (cull_done && (P.subs.size() != 1 || !P.subs[0].jobs.empty())) return fail(c, FTKX_E_DEVICE, "internal: cull-ahead taken over by a batch that rebuilds masks");
+  if (const int rc = stage_batch(c, m, two_level, in, P)) return rc;
+  const int rc = queue_batch(c, m, two_level, P, sparse_field, cull_done);
+  for (const BatchSub &sb : P.subs)
+    for (const BatchMaskJob &j : sb.jobs) {
+      Slice &s = *in.slice[j.slice];
+      const SliceFacts &f = P.facts[j.slice];
+      if (rc) s.mask_factor = 0;
+      else { s.mask_factor = f.mask_factor; s.mask_big = f.mask_big; s.u_rows = f.u_rows; }
+    }
+  return rc;
+}
+
+// ---- ftkx_sweep_collect's stages --------------------------------------------------------------------------------------------------------
+namespace {
+// the buffers a batch writes: at their first sizes, or as earlier batches left them
+int collect_reserve(ftkx_ctx *c, bool any_fast)
+{
+  ftkx_tail_set &T = c->sr_tail[0];
+  int rc;
+  if ((rc = ensure_hit_buffer(c, std::max<u64>(c->capacity, 1u << 16)))) return rc;
+  if (c->nd == 3 && (rc = ensure_fragile(c, T, std::max<u64>(T.fragile_capacity, 1u << 12)))) return rc;
+  if (any_fast && (rc = ensure_list(c, T, std::max<u64>(T.list_capacity, 1u << 20)))) return rc;
+  if (any_fast && (rc = ensure_refine(c, T, std::max<u64>(T.refine_capacity, 1u << 20)))) return rc;
+  return FTKX_OK;
+}
+
+// the batch, and again while a buffer was too small (overflow_verdict, batch_plan.hpp); afterwards h_counters holds the counters of the run that fitted
+int collect_attempts(ftkx_ctx *c, bool any_fast, u64 fast_cells, bool use_ahead)
+{
+  ftkx_tail_set &T = c->sr_tail[0];
+  const u64 *hc = c->h_counters.as<u64>();
+  for (int attempt = 0; ; attempt ++) {
+    int rc;
+    // (cull-ahead: the counters were zeroed before that cull and hold its list counts)
+    if (!use_ahead) HIP_TRY(c, hipMemsetAsync(T.counters.as<u64>(), 0, ftkx::CNT_N * sizeof(u64), c->stream));
+    if ((rc = run_batch(c, nullptr, use_ahead))) return rc;
+    use_ahead = false;                                         // a replay culls afresh
+    if ((rc = read_counters(c))) return rc;
+    c->ahead_staged = false;
+    // (records <= simplices that passed: the 2D type filter may drop some; the pass list shares the hit buffer's capacity)
+    const BatchSizes n{std::max(hc[ftkx::CNT_HITS], hc[ftkx::CNT_PASS]), hc[ftkx::CNT_LIST_PEAK], hc[ftkx::CNT_REFINE_PEAK], hc[ftkx::CNT_FRAGILE]};
+    const BatchSizes cap{c->capacity, T.list_capacity, T.refine_capacity, T.fragile_capacity};
+    const BatchVerdict v = overflow_verdict(n, cap, any_fast, fast_cells, attempt);
+    if (v.what == BATCH_DONE) { ev_harvest(c); return FTKX_OK; }
+    ev_drop(c);
+    if (v.what == BATCH_GIVE_UP) return fail(c, FTKX_E_DEVICE, "buffer overflow persisted after regrowing four times");
+    if (v.what == BATCH_REPLAY_DENSE) {
+      for (const Request &r : c->pending) {
+        auto a = c->slices.find(r.t), b = c->slices.find(r.t + 1);
+        if ((a != c->slices.end() && a->second.sparse) || ((r.scope & FTKX_SCOPE_INTERVAL) && b != c->slices.end() && b->second.sparse))
+          return fail(c, FTKX_E_UNSUPPORTED, "sweep: most cells survive the cull and a masked halo slice is involved (send the slice itself)");
+      }
+      for (Request &r : c->pending) if (r.mode == MODE_FAST) r.mode = MODE_TILE_CULL;
+      any_fast = false;
+      c->dense_collects = 16;
+    }
+    if (v.want.fragile > cap.fragile && (rc = ensure_fragile(c, T, v.want.fragile))) return rc;
+    if (v.want.refined > cap.refined && (rc = ensure_refine(c, T, v.want.refined))) return rc;
+    if (v.want.listed > cap.listed && (rc = ensure_list(c, T, v.want.listed))) return rc;
+    if (v.want.hits > cap.hits && (rc = ensure_hit_buffer(c, v.want.hits))) return rc;
+  }
+}
+
+// 3D records whose class hangs on the last bits of pow / acos / cos (an eigenvalue of the Hessian that is zero up to rounding):
+// classified again here, with the libm the reference itself runs on, and written back before the records are sorted.  Rare -- an
+// exactly singular Hessian takes plateaus or lattice-aligned data -- and then one small round trip.
+int reclassify_fragile(ftkx_ctx *c, u64 nf)
+{
+  std::vector<u64> frag((size_t)nf * 10), pairs((size_t)nf * 2);
+  HIP_TRY(c, hipMemcpyAsync(frag.data(), c->sr_tail[0].fragile.as<u64>(), frag.size() * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  for (size_t i = 0; i < (size_t)nf; i ++) {
+    double A[3][3];
+    memcpy(A, &frag[i * 10 + 1], sizeof(A));
+    pairs[2 * i] = frag[i * 10];
+    pairs[2 * i + 1] = (u64)ftkx::classify3(A, c->opt.jacobian_symmetric != 0);
+  }
+  if (const int rc = ensure_desc(c, pairs.size() * sizeof(u64))) return rc;
+  memcpy(c->h_desc.p, pairs.data(), pairs.size() * sizeof(u64));
+  HIP_TRY(c, hipMemcpyAsync(c->d_desc.p, c->h_desc.p, pairs.size() * sizeof(u64), hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(patch_types_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, c->stream, c->d_hits.as<ftkx_cp_t>(), (const u64 *)c->d_desc.p, (size_t)nf);
+  HIP_TRY(c, hipGetLastError());
+  c->stats.reclassified = nf;
+  return FTKX_OK;
+}
+
+// the records into h_hits in tag order: sorted on the device where there are enough of them, by the host otherwise
+int order_and_download(ftkx_ctx *c, size_t n, int key_bits)
+{
+  if (!n) return FTKX_OK;
+  const bool on_device = n >= 4096 && n < (1ull << 31);
+  if (on_device) { if (const int rc = sort_hits_on_device(c, n, key_bits)) return rc; }
+  HIP_TRY(c, hipMemcpyAsync(c->h_hits.as<ftkx_cp_t>(), (on_device ? c->d_sorted : c->d_hits).as<ftkx_cp_t>(), n * sizeof(ftkx_cp_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (!on_device) std::sort(c->h_hits.as<ftkx_cp_t>(), c->h_hits.as<ftkx_cp_t>() + n, [](const ftkx_cp_t &a, const ftkx_cp_t &b) { return a.tag < b.tag; });
+  return FTKX_OK;
+}
+}  // namespace
 
 // may ftkx_sweep_collect take the cull-ahead's survivor list over?
 bool ahead_serves_pending(const ftkx_ctx *c, const Mesh &m, bool two_level)
@@ -364,16 +469,12 @@ int ftkx_sweep_enqueue(ftkx_ctx *c, int t, int scope, unsigned long long factor)
     if (c->core_sz[d] == 0) return FTKX_OK;    // empty core: nothing to enumerate
   HIP_TRY(c, hipSetDevice(c->device));
   const int nd = c->nd;
-
-  // Is the strict-sign cull usable?  Only with the robust integer test (the FP64 test of the non-robust 3D mode has no such
-  // property) and a power-of-two factor: the masks test v >= 1/factor on doubles, which equals trunc(v * factor) >= 1 only then
-  // (the tracker always passes 1 << nbits); any other factor a direct caller hands over takes the tile path, which quantises like
-  // the reference.  Determinants that could leave int64 are dealt with per vertex (MaskJob::big), not per request.
-  const bool fast = !c->opt.exact_only && pow2_factor(factor) && (nd == 2 || c->opt.robust);
-  if ((s0->sparse || (s1 && s1->sparse)) && (!fast || c->dense_collects > 0))
+  const int mode = request_mode(c->opt.exact_only != 0, factor, nd, c->opt.robust != 0, c->dense_collects);
+  const bool fast = mode != MODE_TILE;          // the strict-sign cull is usable (as masks, or inside the tile kernel)
+  if ((s0->sparse || (s1 && s1->sparse)) && sparse_slice_refuses(mode))
     return fail(c, FTKX_E_UNSUPPORTED, "sweep: a masked halo slice only serves sweeps that use the cull (send the slice itself)");
   if (c->pending.empty()) memset(&c->stats, 0, sizeof(c->stats));
-  c->pending.push_back(Request{t, scope, factor, fast ? (c->dense_collects > 0 ? MODE_TILE_CULL : MODE_FAST) : MODE_TILE});
+  c->pending.push_back(Request{t, scope, factor, mode});
 
   u64 cells = 1;
   for (int d = 0; d < nd; d ++) cells *= (u64)c->core_sz[d];
@@ -391,115 +492,37 @@ int ftkx_sweep_collect(ftkx_ctx *c, const ftkx_cp_t **out, size_t *n_out)
   if (out) *out = nullptr;
   if (n_out) *n_out = 0;
   if (c->pending.empty()) return FTKX_OK;
-  int rc;
-  if ((rc = ensure_hit_buffer(c, std::max<u64>(c->capacity, 1u << 16)))) { c->pending.clear(); return rc; }
-  if (c->nd == 3 && (rc = ensure_fragile(c, c->sr_tail[0], std::max<u64>(c->sr_tail[0].fragile_capacity, 1u << 12)))) { c->pending.clear(); return rc; }
+  struct Forget { ftkx_ctx *c; ~Forget() { c->pending.clear(); } } forget{c};      // whichever way out: the batch is not pending afterwards
   bool any_fast = false;
   u64 fast_cells = 0;
+  int t_max = 0;
   {
     u64 cells = 1;
     for (int d = 0; d < c->nd; d ++) cells *= (u64)c->core_sz[d];
-    for (const Request &r : c->pending) if (r.mode == MODE_FAST) { any_fast = true; fast_cells += cells; }
+    for (const Request &r : c->pending) {
+      if (r.mode == MODE_FAST) { any_fast = true; fast_cells += cells; }
+      t_max = std::max(t_max, r.t);
+    }
   }
+  int rc;
+  if ((rc = collect_reserve(c, any_fast))) return rc;
   if (c->dense_collects > 0) c->dense_collects --;          // the fast path is probed again after a while
-  if (any_fast && (rc = ensure_list(c, c->sr_tail[0], std::max<u64>(c->sr_tail[0].list_capacity, 1u << 20)))) { c->pending.clear(); return rc; }
-  if (any_fast && (rc = ensure_refine(c, c->sr_tail[0], std::max<u64>(c->sr_tail[0].refine_capacity, 1u << 20)))) { c->pending.clear(); return rc; }
-  // upper bound of the tags this batch can emit -> number of key bits for the device sort
-  int key_bits = 64;
-  if (c->opt.tag_mode != FTKX_TAG_REFERENCE) {            // REFERENCE tags go through int32 products and may wrap to anything
-    int t_max = 0;
-    for (const Request &r : c->pending) t_max = std::max(t_max, r.t);
-    long double bound = c->nd == 2 ? 12.0L : 60.0L;
-    const bool work_index = c->opt.tag_mode == FTKX_TAG_WORK_INDEX;
-    for (int d = 0; d < c->nd; d ++) bound *= (long double)(work_index ? c->core_sz[d] : c->dom_sz[d]);
-    if (!work_index) bound *= (long double)(t_max + 2);
-    int b = 1;
-    while (b < 64 && ldexpl(1.0L, b) <= bound) b ++;
-    key_bits = b;
-  }
+  const int sort_bits = key_bits(c->opt.tag_mode, c->nd, c->core_sz, c->dom_sz, t_max);
   bool use_ahead = false;
   if (!c->ahead.empty()) {
     Mesh m; fill_mesh(c, m);
     use_ahead = ahead_serves_pending(c, m, ftkx::masks_have_summary(m));
-    c->ahead.clear();                                        // one use; and a replay below culls afresh
+    c->ahead.clear();                                        // one use
   }
+  if ((rc = collect_attempts(c, any_fast, fast_cells, use_ahead))) return rc;
   const u64 *hc = c->h_counters.as<u64>();
-  for (int attempt = 0; ; attempt ++) {
-    // (cull-ahead: the counters were zeroed before that cull and hold its list counts)
-    if (!use_ahead) HIP_TRY(c, hipMemsetAsync(c->sr_tail[0].counters.as<u64>(), 0, ftkx::CNT_N * sizeof(u64), c->stream));
-    if ((rc = run_batch(c, nullptr, use_ahead))) { c->pending.clear(); return rc; }
-    use_ahead = false;
-    HIP_TRY(c, hipMemcpyAsync(c->h_counters.p, c->sr_tail[0].counters.as<u64>(), ftkx::CNT_N * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->ahead_staged = false;
-    // (records <= simplices that passed: the 2D type filter may drop some; the pass list shares the hit buffer's capacity)
-    const u64 hits = std::max(hc[ftkx::CNT_HITS], hc[ftkx::CNT_PASS]);
-    const u64 listed = hc[ftkx::CNT_LIST_PEAK], refined = hc[ftkx::CNT_REFINE_PEAK];
-    const u64 fragile = hc[ftkx::CNT_FRAGILE];
-    if (hits <= c->capacity && listed <= c->sr_tail[0].list_capacity && refined <= c->sr_tail[0].refine_capacity && fragile <= c->sr_tail[0].fragile_capacity) { ev_harvest(c); break; }
-    // a buffer was too small (records / survivors beyond capacity were only counted): grow to what this batch needs, replay it
-    for (auto &e : c->events) { ev_give(c, e.second.first); ev_give(c, e.second.second); }
-    c->events.clear();
-    if (attempt == 4) { c->pending.clear(); return fail(c, FTKX_E_DEVICE, "buffer overflow persisted after regrowing four times"); }
-    // Most cells survive the cull (data whose quantised magnitudes can overflow the determinants almost everywhere):
-    // a survivor list would be as large as the input.  Such a batch goes through the tile kernel instead, which stages each
-    // tile's vertices once and applies the same cull rule in LDS.
-    if (any_fast && (listed > c->sr_tail[0].list_capacity || refined > c->sr_tail[0].refine_capacity) && (listed > fast_cells / 8 || refined * 8 > fast_cells / 8)) {
-      for (const Request &r : c->pending) {
-        auto a = c->slices.find(r.t), b = c->slices.find(r.t + 1);
-        if ((a != c->slices.end() && a->second.sparse) || ((r.scope & FTKX_SCOPE_INTERVAL) && b != c->slices.end() && b->second.sparse)) {
-          c->pending.clear();
-          return fail(c, FTKX_E_UNSUPPORTED, "sweep: most cells survive the cull and a masked halo slice is involved (send the slice itself)");
-        }
-      }
-      for (Request &r : c->pending) if (r.mode == MODE_FAST) r.mode = MODE_TILE_CULL;
-      any_fast = false;
-      c->dense_collects = 16;
-      if (hits > c->capacity && (rc = ensure_hit_buffer(c, 2 * hits + 1024))) { c->pending.clear(); return rc; }
-      continue;
-    }
-    if (fragile > c->sr_tail[0].fragile_capacity && (rc = ensure_fragile(c, c->sr_tail[0], fragile + fragile / 8 + 1024))) { c->pending.clear(); return rc; }
-    if (refined > c->sr_tail[0].refine_capacity && (rc = ensure_refine(c, c->sr_tail[0], refined + refined / 8 + 1024))) { c->pending.clear(); return rc; }
-    if (listed > c->sr_tail[0].list_capacity && (rc = ensure_list(c, c->sr_tail[0], listed + listed / 8 + 1024))) { c->pending.clear(); return rc; }
-    // with a truncated survivor list the hit count is a lower bound: leave generous room
-    const u64 want_hits = std::max<u64>(hits + hits / 8 + 1024, (listed > c->sr_tail[0].list_capacity || refined > c->sr_tail[0].refine_capacity) ? 2 * hits + 1024 : 0);
-    if (want_hits > c->capacity && (rc = ensure_hit_buffer(c, want_hits))) { c->pending.clear(); return rc; }
-  }
-  c->pending.clear();
   const size_t n = (size_t)hc[ftkx::CNT_HITS];
   c->stats.hits = n;
   c->stats.cells_survived = hc[ftkx::CNT_CELLS_SURVIVED];
   c->stats.simplices_tested = hc[ftkx::CNT_SIMPLICES_TESTED];
   if ((rc = ensure_host_buffer(c, n))) return rc;
-  // 3D records whose class hangs on the last bits of pow / acos / cos (an eigenvalue of the Hessian that is zero up to rounding):
-  // classified again here, with the libm the reference itself runs on, and written back before the records are sorted.  Rare -- an
-  // exactly singular Hessian takes plateaus or lattice-aligned data -- and then one small round trip.
-  if (const u64 nf = hc[ftkx::CNT_FRAGILE]) {
-    std::vector<u64> frag((size_t)nf * 10), pairs((size_t)nf * 2);
-    HIP_TRY(c, hipMemcpyAsync(frag.data(), c->sr_tail[0].fragile.as<u64>(), frag.size() * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    for (size_t i = 0; i < (size_t)nf; i ++) {
-      double A[3][3];
-      memcpy(A, &frag[i * 10 + 1], sizeof(A));
-      pairs[2 * i] = frag[i * 10];
-      pairs[2 * i + 1] = (u64)ftkx::classify3(A, c->opt.jacobian_symmetric != 0);
-    }
-    if ((rc = ensure_desc(c, pairs.size() * sizeof(u64)))) return rc;
-    memcpy(c->h_desc.p, pairs.data(), pairs.size() * sizeof(u64));
-    HIP_TRY(c, hipMemcpyAsync(c->d_desc.p, c->h_desc.p, pairs.size() * sizeof(u64), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(patch_types_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, c->stream, c->d_hits.as<ftkx_cp_t>(), (const u64 *)c->d_desc.p, (size_t)nf);
-    HIP_TRY(c, hipGetLastError());
-    c->stats.reclassified = nf;
-  }
-  if (n >= 4096 && n < (1ull << 31)) {
-    if ((rc = sort_hits_on_device(c, n, key_bits))) return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->h_hits.as<ftkx_cp_t>(), c->d_sorted.as<ftkx_cp_t>(), n * sizeof(ftkx_cp_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-  } else if (n) {
-    HIP_TRY(c, hipMemcpyAsync(c->h_hits.as<ftkx_cp_t>(), c->d_hits.as<ftkx_cp_t>(), n * sizeof(ftkx_cp_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    std::sort(c->h_hits.as<ftkx_cp_t>(), c->h_hits.as<ftkx_cp_t>() + n, [](const ftkx_cp_t &a, const ftkx_cp_t &b) { return a.tag < b.tag; });
-  }
+  if (hc[ftkx::CNT_FRAGILE] && (rc = reclassify_fragile(c, hc[ftkx::CNT_FRAGILE]))) return rc;
+  if ((rc = order_and_download(c, n, sort_bits))) return rc;
   if (out) *out = c->h_hits.as<ftkx_cp_t>();
   if (n_out) *n_out = n;
   return FTKX_OK;

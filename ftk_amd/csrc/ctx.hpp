@@ -19,6 +19,7 @@
 
 #include "sweep_params.hpp"
 #include "split_policy.hpp"
+#include "batch_plan.hpp"
 #include "internal.hpp"
 #include "pass2_layout.hpp"
 #include "ctx_block.hpp"
@@ -166,11 +167,10 @@ struct Slice {                      // move-only: it owns its arrays
   bool max_known() const { return have_res || have_fused || sparse; }
 };
 
-// how a request is swept: MODE_TILE tests every simplex (exact_only, non-robust 3D, odd factors); MODE_FAST = masks -> cull ->
-// survivor list -> exact kernel; MODE_TILE_CULL = the tile kernel with its in-tile cull (same per-vertex legality rule), for
-// data on which most cells survive the cull anyway (the int64-overflow regime: a survivor list would be as large as the input)
-enum { MODE_TILE = 0, MODE_FAST = 1, MODE_TILE_CULL = 2 };
-struct Request { int t, scope; unsigned long long factor; int mode; };
+// what the batch plan (batch_plan.hpp) is told of a slice
+inline SliceFacts slice_facts(const Slice &s) { return SliceFacts{s.M.p != nullptr, s.U.p != nullptr, s.sparse, s.mask_factor, s.mask_big, s.u_rows, s.max_known(), s.maxabs}; }
+
+struct Request { int t, scope; unsigned long long factor; int mode; };      // mode: MODE_* (batch_plan.hpp, request_mode)
 
 enum { K_MASK = 0, K_CULL = 1, K_EXACT = 2, K_TILE = 3, K_N = 4 };
 
@@ -465,10 +465,7 @@ int ensure_red(ftkx_ctx *c, size_t nslices);                    // d_red: 128 wo
 int ensure_host_buffer(ftkx_ctx *c, size_t want);
 void fill_mesh(const ftkx_ctx *c, Mesh &m);
 int slice_resolution(ftkx_ctx *c, Slice &s);
-bool overflow_free(int nd, double maxabs, u64 factor);
-double big_threshold(int nd, u64 factor);
-bool pow2_factor(u64 factor);
-bool masks_valid(const ftkx_ctx *c, const Slice &s, u64 factor, bool two_level, int u_rows);
+bool masks_valid(const ftkx_ctx *c, const Slice &s, u64 factor, bool two_level, int u_rows);   // these two: batch_plan.hpp's, of a slice of this context
 double job_big(const ftkx_ctx *c, const Slice &s, u64 factor, bool *rule_on);
 int ensure_mask_arrays(ftkx_ctx *c, Slice &s, bool two_level);
 int upload_from_host(ftkx_ctx *c, void *dst, const void *src, size_t bytes);       // upload.cpp
@@ -488,9 +485,10 @@ void ev_give(ftkx_ctx *c, hipEvent_t e);
 void ev_begin(ftkx_ctx *c, int kind);
 void ev_end(ftkx_ctx *c);
 void ev_harvest(ftkx_ctx *c, bool all = true);   // all: after a stream synchronise; otherwise only the pairs that have completed
+void ev_drop(ftkx_ctx *c);                       // the pairs of a batch that is replayed: back to the pool, unread
 int run_batch(ftkx_ctx *c, const double *sparse_field = nullptr, bool cull_done = false);
+int read_counters(ftkx_ctx *c);                  // set 0's CNT_* words into h_counters; waits for the stream
 bool ahead_serves_pending(const ftkx_ctx *c, const Mesh &m, bool two_level);
 int sort_hits_on_device(ftkx_ctx *c, size_t n, int key_bits);
-int finish_records(ftkx_ctx *c, size_t n, int key_bits);
 
 }  // namespace ftkxh

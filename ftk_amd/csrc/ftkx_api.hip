@@ -228,36 +228,9 @@ int slice_resolution(ftkx_ctx *c, Slice &s)
   return FTKX_OK;
 }
 
-// the strict-sign cull is exact only while no determinant of the predicate can leave int64:
-// |det4| <= 24 M^3 (3D), |det3| <= 6 M^2 (2D) with M = max |quantised component|   
-bool overflow_free(int nd, double maxabs, u64 factor)
-{
-  const long double M = floorl((long double)maxabs * (long double)factor) + 1.0L;
-  const long double lim = 9223372036854775807.0L;
-  return nd == 3 ? 24.0L * M * M * M < lim : 6.0L * M * M < lim;
-}
-
-double big_threshold(int nd, u64 factor) { return (double)(nd == 3 ? ftkx::kSafeM3 : ftkx::kSafeM2) / (double)factor; }
-bool pow2_factor(u64 factor) { return factor != 0 && (factor & (factor - 1)) == 0 && factor <= (1ull << 53); }
-
-// Masks built under mask_factor serve a sweep under `factor` when they can only cull less than masks built under `factor`
-// itself: the sign thresholds need mask_factor <= factor; the per-vertex overflow rule (MaskJob::big) is factor-specific, so a
-// larger factor is accepted only when the slice's max |v| shows that no vertex is big under it either.
-bool masks_valid(const ftkx_ctx *c, const Slice &s, u64 factor, bool two_level, int u_rows)
-{
-  if (!s.M.p || (two_level && !s.U.p) || s.mask_factor == 0 || s.mask_factor > factor) return false;
-  if (two_level && s.u_rows != u_rows) return false;           // summaries of another geometry (FTKX_MASK_* changed since)
-  if (s.mask_big && s.mask_factor == factor) return true;
-  return s.max_known() && overflow_free(c->nd, s.maxabs, factor);   // no vertex is big under `factor`: the rule would change nothing
-}
-
-// the per-vertex rule costs the marching kernels a few instructions per row: it is switched on only when it can matter
-double job_big(const ftkx_ctx *c, const Slice &s, u64 factor, bool *rule_on)
-{
-  const bool off = s.max_known() && overflow_free(c->nd, s.maxabs, factor);
-  *rule_on = !off;
-  return off ? HUGE_VAL : big_threshold(c->nd, factor);
-}
+// (what masks serve and which jobs need the per-vertex rule: batch_plan.hpp)
+bool masks_valid(const ftkx_ctx *c, const Slice &s, u64 factor, bool two_level, int u_rows) { return masks_valid(c->nd, slice_facts(s), factor, two_level, u_rows); }
+double job_big(const ftkx_ctx *c, const Slice &s, u64 factor, bool *rule_on) { return job_big(c->nd, slice_facts(s), factor, rule_on); }
 
 // (host memory -> HBM: upload.cpp)
 

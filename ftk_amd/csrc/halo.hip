@@ -281,27 +281,27 @@ int ftkx_sweep_cull(ftkx_ctx *c, int t_sparse, size_t *n_cells)
   int rc;
   if ((rc = ensure_hit_buffer(c, std::max<u64>(c->capacity, 1u << 16)))) return rc;
   if ((rc = ensure_list(c, c->sr_tail[0], std::max<u64>(c->sr_tail[0].list_capacity, 1u << 20))) || (rc = ensure_refine(c, c->sr_tail[0], std::max<u64>(c->sr_tail[0].refine_capacity, 1u << 20)))) return rc;
-  for (int attempt = 0; attempt < 4; attempt ++) {
-    if ((rc = c->d_cells.reserve(c, c->sr_tail[0].list_capacity * sizeof(u64)))) return rc;      // (run_batch hands launch_sparse_cells its count)
-    HIP_TRY(c, hipMemsetAsync(c->sr_tail[0].counters.as<u64>(), 0, ftkx::CNT_N * sizeof(u64), c->stream));
+  ftkx_tail_set &T = c->sr_tail[0];
+  const u64 *hc = c->h_counters.as<u64>();
+  for (int attempt = 0; ; attempt ++) {
+    if ((rc = c->d_cells.reserve(c, T.list_capacity * sizeof(u64)))) return rc;      // (run_batch hands launch_sparse_cells its count)
+    HIP_TRY(c, hipMemsetAsync(T.counters.as<u64>(), 0, ftkx::CNT_N * sizeof(u64), c->stream));
     if ((rc = run_batch(c, field))) return rc;
-    const u64 *hc = c->h_counters.as<u64>();
-    HIP_TRY(c, hipMemcpyAsync(c->h_counters.p, c->sr_tail[0].counters.as<u64>(), ftkx::CNT_N * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
     u64 halo_bad = 0;
     HIP_TRY(c, hipMemcpyAsync(&halo_bad, halo_bad_flag(c), sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if ((rc = read_counters(c))) return rc;
     if (halo_bad) {      // the packed mask message of this slice did not fit (more words than it holds, or another geometry): its masks are incomplete
       HIP_TRY(c, hipMemsetAsync(halo_bad_flag(c), 0, sizeof(u64), c->stream));
       return fail(c, FTKX_E_NOSLICE, "ftkx_sweep_cull: the packed masks of halo slice %d were incomplete (send the slice itself)", t_sparse);
     }
-    for (auto &e : c->events) { ev_give(c, e.second.first); ev_give(c, e.second.second); }
-    c->events.clear();
-    const u64 listed = hc[ftkx::CNT_SURVIVOR_LIST], refined = std::max(hc[ftkx::CNT_REFINE_LIST], hc[ftkx::CNT_REFINE_PEAK]);
-    if (listed <= c->sr_tail[0].list_capacity && refined <= c->sr_tail[0].refine_capacity) { c->n_cells = (size_t)hc[ftkx::CNT_SPARSE]; *n_cells = c->n_cells; return FTKX_OK; }
-    if (refined > c->sr_tail[0].refine_capacity && (rc = ensure_refine(c, c->sr_tail[0], refined + refined / 8 + 1024))) return rc;
-    if (listed > c->sr_tail[0].list_capacity && (rc = ensure_list(c, c->sr_tail[0], 2 * listed + 1024))) return rc;
+    ev_drop(c);
+    // (no exact kernel has published the lists' peaks: the counters themselves)
+    const BatchVerdict v = cull_verdict(hc[ftkx::CNT_SURVIVOR_LIST], std::max(hc[ftkx::CNT_REFINE_LIST], hc[ftkx::CNT_REFINE_PEAK]), T.list_capacity, T.refine_capacity, attempt);
+    if (v.what == BATCH_DONE) { c->n_cells = (size_t)hc[ftkx::CNT_SPARSE]; *n_cells = c->n_cells; return FTKX_OK; }
+    if (v.what == BATCH_GIVE_UP) return fail(c, FTKX_E_DEVICE, "ftkx_sweep_cull: survivor lists kept overflowing");
+    if (v.want.refined > T.refine_capacity && (rc = ensure_refine(c, T, v.want.refined))) return rc;
+    if (v.want.listed > T.list_capacity && (rc = ensure_list(c, T, v.want.listed))) return rc;
   }
-  return fail(c, FTKX_E_DEVICE, "ftkx_sweep_cull: survivor lists kept overflowing");
 }
 
 int ftkx_get_sparse_cells(ftkx_ctx *c, unsigned long long *dst, int dst_on_device)

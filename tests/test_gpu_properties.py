@@ -622,6 +622,53 @@ def test_announced_x_masked_halo_x_factor_change(gpu, kind, halo, announce):
         c.close()
 
 
+def test_cull_only_refusal_leaves_the_context_sound(gpu):
+    """ftkx_sweep_cull on a pending batch that needs masks under two factors (slices without masks and with unknown maxima, factors
+    256, 1024, 1024: slice 1 would be built twice) is refused with FTKX_E_UNSUPPORTED before anything is queued -- and no slice may say
+    afterwards that it has the masks the refused plan had in mind.  The protocol's answer (cancel, the halo slice itself, the same steps
+    again) must give the records of a sweep that tests every simplex."""
+    import torch
+    dims, nt, split = (72, 40, 24), 5, 3
+    grids = np.meshgrid(*[np.linspace(-1.0, 1.0, n) for n in reversed(dims)], indexing="ij")
+    steps = [np.ascontiguousarray(np.exp(-3.0 * sum((g - 0.07 * k) ** 2 for g in grids)) + 0.2 * np.sin(3.0 * grids[-1] + 0.3 * k)) for k in range(nt)]
+    dom = ([2] * 3, [d - 3 for d in dims])
+    dev = torch.device("cuda", 0)
+    own, scopes, factors = list(range(split)), [gpu.SCOPE_BOTH] * split, [256, 1024, 1024]
+
+    def make(**opts):
+        c = gpu.Context(3)
+        c.set_mesh(dom, dom, ([0] * 3, list(dims)))
+        c.set_options(jacobian_symmetric=1, derive_jacobian=1, tag_mode=gpu.TAG_EXACT64, **opts)
+        return c
+    whole = make(exact_only=1)
+    for t in range(split + 1):
+        whole.push_scalar_slice(t, steps[t])
+    whole.sweep_enqueue_many(own, scopes, factors)
+    ref = np.array(whole.sweep_collect())
+    assert len(ref) > 0
+    A, B = make(), make()
+    for t in own:
+        A.push_scalar_slice(t, steps[t])                       # no slices_prepare: no masks, maxima unknown
+    B.push_scalar_slice(split, steps[split])
+    rmB = B.slices_prepare([split], 0)
+    nbytes, _cap = B.packed_masks_bytes()
+    buf = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    B.export_masks_packed(split, buf)
+    A.push_masked_slice_packed(split, True, buf, 256, rmB[split][1])
+    A.sweep_enqueue_many(own, scopes, factors)
+    with pytest.raises(gpu.FtkxError) as e:
+        A.sweep_cull(split, torch, dev)
+    assert e.value.code == gpu._lib.E_UNSUPPORTED, e.value
+    A.sweep_cancel()
+    A.push_scalar_slice(split, steps[split])
+    A.sweep_enqueue_many(own, scopes, factors)
+    got = np.array(A.sweep_collect())
+    assert A.stats()["cull_enabled"] == 1
+    assert got.tobytes() == ref.tobytes(), (len(got), len(ref))
+    for c in (whole, A, B):
+        c.close()
+
+
 def _vector_field(rng, dims, kind):
     """a vector field (components last) with what the vector mask kernels treat specially"""
     nd = len(dims)
