@@ -309,7 +309,14 @@ class Context:
         self._ck(self._L.ftkx_drop_slice(self._h, t))
         self._keep.pop(t, None)
         for slot in (1, 2):
-            getattr(self, "_keep_aux", {}).pop((t, slot), None)
+            self._let_go_aux(getattr(self, "_keep_aux", {}).pop((t, slot), None))
+
+    def _let_go_aux(self, lent):
+        """a lent aux tensor leaves its timestep: an armed series pass that is still open may read it (set_series_sampling) -- kept until the
+        open passes have been completed"""
+        if lent is not None and getattr(self, "_open_series", None):
+            self._lent_under_passes = getattr(self, "_lent_under_passes", [])
+            self._lent_under_passes.append(lent)
 
     # auxiliary scalar fields sampled at critical points (sample_kernels.hip)
     def push_aux_slice(self, t, slot, A, on_device=None):
@@ -325,6 +332,7 @@ class Context:
         if n is not None and ka is not None and int(ka.numel() if hasattr(ka, "numel") else ka.size) != n:
             raise FtkxError(_lib.E_INVALID, f"push_aux_slice: {int(ka.numel() if hasattr(ka, 'numel') else ka.size)} values for an array extent of {n} vertices")
         self._ck((self._L.ftkx_push_aux_slice_f32 if f32 else self._L.ftkx_push_aux_slice)(self._h, int(t), int(slot), pa, da))
+        self._let_go_aux(self._keep_aux.get((int(t), int(slot))))      # (one that this push replaces)
         self._keep_aux[(int(t), int(slot))] = ka if da == 1 and not f32 else None      # (lent: alive until the slice is dropped)
 
     def sample_aux(self, records):
@@ -340,6 +348,26 @@ class Context:
         a = C.c_ulonglong(0); b = C.c_ulonglong(0)
         self._ck(self._L.ftkx_debug_sample_counts(self._h, C.byref(a), C.byref(b)))
         return int(a.value), int(b.value)
+
+    def set_series_sampling(self, on=True):
+        """ftkx_set_series_sampling: while on, sweep_series and sweep_series_submit / _complete return their records with scalar[1] /
+        scalar[2] filled from the aux arrays, sampled on the device inside the pass (slots with an array at every slice the pass reads; a
+        slot with arrays at some but not all: FtkxError -4 at submit).  Not while a pass is open (-1).  A lent aux tensor (on_device=1) that is
+        dropped or replaced under open passes is kept referenced here until they have been completed"""
+        self._ck(self._L.ftkx_set_series_sampling(self._h, 1 if on else 0))
+
+    def series_sampled(self):
+        """(slots, where) of the series pass completed last: the set of slots filled (bit 0: scalar[1], bit 1: scalar[2]); 0 not filled, 1 by
+        the kernel inside the pass, 2 behind the host-driven batch inside the call"""
+        s = C.c_uint(0); w = C.c_int(0)
+        self._ck(self._L.ftkx_series_sampled(self._h, C.byref(s), C.byref(w)))
+        return int(s.value), int(w.value)
+
+    def series_sample_counts(self):
+        """(launches, records, workgroups of the last launch) of the in-pass sample kernel on this context so far"""
+        a = C.c_ulonglong(0); b = C.c_ulonglong(0); g = C.c_uint(0)
+        self._ck(self._L.ftkx_debug_series_sample_counts(self._h, C.byref(a), C.byref(b), C.byref(g)))
+        return int(a.value), int(b.value), int(g.value)
 
     def debug_sample_relaunch(self, records, reps):
         """profiling aid: the sample kernel over `records` `reps` times back to back -> device ms per launch (HIP events); nothing is written"""
@@ -464,6 +492,8 @@ class Context:
         f = np.empty((max(1, n),), dtype=np.uint64)
         out, cnt = C.c_void_p(), C.c_size_t()
         self._ck(self._L.ftkx_sweep_series_complete(self._h, C.byref(run), f.ctypes.data, C.byref(out), C.byref(cnt)))
+        if not self._open_series:
+            self._lent_under_passes = []      # (no pass is left that could read a lent aux tensor dropped meanwhile)
         return _lib.records_from(out.value, cnt.value, copy), f[:n], run.value
 
     # ---- the slab pass (ftkx_series_dist_*): one rank's device-driven pass, queued in stages; ftk_amd/tslab.py drives it ----
@@ -504,6 +534,7 @@ class Context:
         """ftkx_sweep_series_abort: discard the open passes (after a failed submit / complete, or to give up)"""
         self._open_series = []
         self._ck(self._L.ftkx_sweep_series_abort(self._h))
+        self._lent_under_passes = []
 
     def series_last_path(self):
         """(path, status bits) of the last sweep_series: 1 device-driven (kernel chain), 2 finished by the fused tail, 4 one launch, 5 split (the
@@ -1056,6 +1087,12 @@ class _TrackerRegular:
         if on and (lo is None or hi is None):
             raise ValueError("set_clamp: both bounds, or none")
         self._ck(self._L.ftkx_tracker_set_clamp(self._h, int(on), float(lo) if on else 0.0, float(hi) if on else 0.0))
+
+    def set_sampling_in_pass(self, b=True):
+        """before initialize(): with components named (set_scalar_components), every step's device-driven pass fills scalar[1] / scalar[2]
+        itself (Context.set_series_sampling) instead of a pass over the finished records -- which allows deferred collection, single steps
+        and batches, with components.  Same points and curves, bit for bit.  Default off"""
+        self._ck(self._L.ftkx_tracker_set_sampling_in_pass(self._h, int(bool(b))))
 
     def set_temporal_smoothing(self, sigma, ksize=5):
         """before initialize(): the pushed snapshots are raw and feed the reference stream's temporal filter on the device; the tracker sees

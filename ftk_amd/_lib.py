@@ -93,6 +93,7 @@ EXPORTS = [
     "ftkx_debug_series_order", "ftkx_debug_sort_records",
     "ftkx_set_perturbation", "ftkx_set_clamp", "ftkx_adjust", "ftkx_adjust_f32", "ftkx_debug_adjust_relaunch", "ftkx_debug_adjust_counts", "ftkx_tracker_set_perturbation", "ftkx_tracker_set_clamp",
     "ftkx_push_aux_slice", "ftkx_push_aux_slice_f32", "ftkx_sample_aux", "ftkx_debug_sample_relaunch", "ftkx_debug_sample_counts",
+    "ftkx_set_series_sampling", "ftkx_series_sampled", "ftkx_debug_series_sample_counts", "ftkx_tracker_set_sampling_in_pass",
     "ftkx_tracker_set_scalar_components", "ftkx_tracker_push_snapshot_extra", "ftkx_tracker_get_curve_scalars",
     "ftkx_tracker_push_scalar_field_snapshot_f32", "ftkx_tracker_push_vector_field_snapshot_f32", "ftkx_tracker_push_field_data_snapshot_f32",
     "ftkx_tracker_post_process", "ftkx_tracker_get_curve_points", "ftkx_tracker_write", "ftkx_tracker_read_critical_points",
@@ -218,6 +219,9 @@ def load():
     L.ftkx_sample_aux.argtypes = [vp, vp, C.c_size_t]
     L.ftkx_debug_sample_relaunch.argtypes = [vp, vp, C.c_size_t, C.c_int, C.POINTER(C.c_double)]
     L.ftkx_debug_sample_counts.argtypes = [vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
+    L.ftkx_set_series_sampling.argtypes = [vp, C.c_int]
+    L.ftkx_series_sampled.argtypes = [vp, C.POINTER(C.c_uint), C.POINTER(C.c_int)]
+    L.ftkx_debug_series_sample_counts.argtypes = [vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), C.POINTER(C.c_uint)]
     L.ftkx_tracker_set_scalar_components.argtypes = [vp, C.POINTER(C.c_char_p), C.c_int]
     L.ftkx_tracker_push_snapshot_extra.argtypes = [vp, C.c_int, vp, vp, vp, C.POINTER(vp), C.c_int, C.c_int, C.c_int]
     L.ftkx_tracker_get_curve_scalars.argtypes = [vp, dbl]
@@ -243,6 +247,7 @@ def load():
     L.ftkx_tracker_set_current_timestep.argtypes = [vp, C.c_int]
     L.ftkx_tracker_set_enable_streaming_trajectories.argtypes = [vp, C.c_int]
     L.ftkx_tracker_set_deferred_collection.argtypes = [vp, C.c_int]
+    L.ftkx_tracker_set_sampling_in_pass.argtypes = [vp, C.c_int]
     L.ftkx_tracker_set_trace_on_device.argtypes = [vp, C.c_int]
     L.ftkx_tracker_trace_last_path.argtypes = [vp]
     L.ftkx_tracker_set_post_process_on_device.argtypes = [vp, C.c_int]

@@ -62,6 +62,8 @@ template <class T> void launch_adjust(const T *src, size_t count, bool perturb, 
 template <class T> bool launch_concat(const T *const *planes, int nc, size_t count, double *dst, hipStream_t st);   // concat_kernels.hip: T double or float; whether the 16-byte body ran
 void launch_temporal(const double *const *arrays, int ksize, const double *weights, size_t count, double *out, hipStream_t st);   // temporal_kernels.hip
 void launch_sample(int nd, const SampleMesh &m, const SampleIn *in, size_t n, const SampleSlice *tab, int t_min, unsigned slots, double *out, hipStream_t st);   // sample_kernels.hip
+void launch_series_sample(int nd, const SampleMesh &m, ftkx_cp_t *recs, const u64 *counters, u64 capacity, const SampleSlice *tab, int t_min, int ntab, unsigned slots,
+                          unsigned workgroups, hipStream_t st);   // sample_kernels.hip: in place over the records of a series pass
 void launch_calib_read(const void *p, size_t bytes, double *scratch, hipStream_t stream);
 const char *last_mask_kernel();
 void launch_cull_coarse(const Mesh &m, const Fields *d_steps, int nsteps, u64 *d_refine, u64 refine_cap, hipStream_t stream, const FactorJob *job = nullptr);
@@ -211,6 +213,11 @@ struct ftkx_series_pending {
   std::vector<std::pair<ftkx_block, ftkx_block>> retired;   // (M, U) arrays this pass still reads, replaced in their slices by the pass queued behind it
   std::vector<ftkxh::Slice> parked;        // slices dropped (or replaced) while this split pass was the newest one open: its tail -- on a stream of its own -- may still read
                                     // their arrays, which go back to the pools when it has been completed (release_retired)
+  std::vector<ftkx_block> parked_aux;      // aux arrays dropped or replaced meanwhile: the same decision (ingest.hip, retire_aux), the same release
+  // an armed pass (ftkx_set_series_sampling) that has a slot to fill: the sample kernel runs behind its record kernel, in place over B.d_out
+  unsigned sample_slots = 0;        // bit s: slot s + 1 is sampled (the slot rule, decided when the pass was planned); 0: planned as an unarmed pass
+  size_t off_sample = 0;            // its slice table in the descriptor block: SampleSlice per timestep sample_t_min .. + sample_ntab
+  int sample_t_min = 0, sample_ntab = 0;
   // slab pass (ftkx_series_dist_*): one rank's part of a series cut into timestep slabs, queued in stages with the caller's collectives between them
   bool dist = false;
   int dist_stage = 0;               // 1 begun (masks, contribution, outgoing masks), 2 culled (request written), 3 served (reply written), 4 finished = open
@@ -340,13 +347,25 @@ struct ftkx_ctx {
   unsigned long long planar_vec = 0, planar_scalar = 0;
   // auxiliary scalar fields (ftkx_push_aux_slice, ftkx_sample_aux; sample_steps.hpp): per timestep the arrays that record slots 1 and 2 are
   // sampled from -- field-class arrays out of `arrays`, or lent by the caller -- next to the slices, not in them: no sweep reads them, and a
-  // slice that is pushed again keeps them.  They leave with ftkx_drop_slice(t).  Only the sample kernel reads them, on the context's stream,
-  // and ftkx_sample_aux waits for it: a dropped array goes straight back to the pool.  sm_*: what a call sends up (16 bytes per record,
-  // the table of slice pointers) and brings down (8 bytes per record and slot), kept between calls.
+  // slice that is pushed again keeps them.  They leave with ftkx_drop_slice(t).  Two kernels read them: the sample kernel of
+  // ftkx_sample_aux on the context's stream, which the call waits for, and the sample kernel of an armed series pass
+  // (ftkx_set_series_sampling), which runs where the pass's tail runs -- on the context's stream, or for a split pass on a tail stream that
+  // is in no order with whatever takes the array out of the pool next.  So a dropped or replaced array takes the way a dropped slice's
+  // arrays take (free_slice): parked with the newest open pass where that one is split (ftkx_series_pending::parked_aux, released by
+  // release_retired), straight back to the pool otherwise.  sm_*: what a call sends up (16 bytes per record, the table of slice pointers)
+  // and brings down (8 bytes per record and slot), kept between calls.
   struct AuxSlice { ftkx_block A[2]; };
   std::map<int, AuxSlice> aux;
   ftkx_block sm_h_in{FTKX_BLOCK_PINNED}, sm_d_in, sm_d_out, sm_h_out{FTKX_BLOCK_PINNED_NONCOHERENT}, sm_d_tab;
   unsigned long long sm_launches = 0, sm_records = 0;      // ftkx_debug_sample_counts
+  // ftkx_set_series_sampling: series passes fill scalar[1] / scalar[2] themselves (series.hip).  sr_sampled_*: ftkx_series_sampled, of the
+  // pass completed last; ss_*: ftkx_debug_series_sample_counts, the in-pass launches, the records of the passes they belonged to (known
+  // when a pass completes) and the grid of the last launch
+  bool sr_sampling = false;
+  unsigned sr_sampled_slots = 0;
+  int sr_sampled_where = 0;
+  unsigned long long ss_launches = 0, ss_records = 0;
+  unsigned ss_last_wgs = 0;
   std::vector<ftkxh::Request> pending;
   // Cull-ahead: the sweeps the caller announced (ftkx_sweep_announce) for the slices of the next ftkx_slices_prepare, and -- once that
   // call has queued their cull right behind the mask kernel -- the survivor list it left on the device.  The cull needs the masks
@@ -437,12 +456,25 @@ int fail(ftkx_ctx *c, int code, const char *fmt, ...);
 
 // ingest.hip
 void temporal_release(ftkx_ctx *c);                             // the temporal ring's arrays back to the pool, the filter as it was constructed
-void drop_aux(ftkx_ctx *c, int t);                              // the aux arrays of timestep t leave
+void drop_aux(ftkx_ctx *c, int t);                              // the aux arrays of timestep t leave (parked with the newest open split pass, or to the pool)
 int adopt_resident_slice(ftkx_ctx *c, int t, const double *full);   // the library's own borrowing push of an array that has been processed already (slab.cpp)
 // ftkx_api.hip
 const std::string &global_error();                              // what fail(nullptr, ...) said last on this thread
 int settings_not_now(ftkx_ctx *c, const char *who);             // a setting must not change under sweeps pending or series passes open: 0, or fail()'s code
 size_t n_vertices(const ftkx_ctx *c);
+// the part of the context's mesh and options the samplers read (sample_steps.hpp)
+inline ftkx::SampleMesh sample_mesh_of(const ftkx_ctx *c)
+{
+  ftkx::SampleMesh m;
+  m.tag_mode = c->opt.tag_mode;
+  m.scalar_mode = c->scalar_mode == 1;
+  for (int d = 0; d < 3; d ++) {
+    m.dom_lb[d] = (int)c->dom_st[d]; m.dom_sz[d] = (int)c->dom_sz[d];
+    m.core_st[d] = (int)c->core_st[d]; m.core_sz[d] = (int)c->core_sz[d];
+    m.ext_st[d] = (int)c->ext_st[d]; m.ext_sz[d] = (int)c->ext_sz[d];
+  }
+  return m;
+}
 int mask_pitch(const ftkx_ctx *c);
 int u_pitch(const ftkx_ctx *c);
 size_t u_bytes(const ftkx_ctx *c);

@@ -111,6 +111,8 @@ void release_retired(ftkx_ctx *c, ftkx_series_pending &P)
   // (slices dropped while this pass was the newest one open: its tail is through, a pass queued behind it was planned after the drop)
   for (Slice &sl : P.parked) release_slice(sl, c);
   P.parked.clear();
+  for (ftkx_block &b : P.parked_aux) c->arrays.give(FTKX_ARRAY_FIELD, std::move(b), kPoolCap);      // (the pass's sample kernel was on that tail)
+  P.parked_aux.clear();
 }
 
 // ---- the tail sets (ctx.hpp) ---------------------------------------------------------------------------------------------------------
@@ -464,7 +466,7 @@ int ftkx_set_mesh(ftkx_ctx *c, const long long dst[3], const long long dsz[3], c
   if (!c) return fail(nullptr, FTKX_E_INVALID, "null context");
   if (!c->slices.empty()) return fail(c, FTKX_E_INVALID, "ftkx_set_mesh: drop all slices first");
   HIP_TRY(c, hipSetDevice(c->device));
-  // nothing of the old lattice stays: slices dropped under an open split pass are parked with it, not in `slices` -- its tail is waited for
+  // nothing of the old lattice stays: slices and aux arrays dropped under an open split pass are parked with it, not in `slices` / `aux` -- its tail is waited for
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   HIP_TRY(c, sync_tails(c));
   for (ftkx_series_pending &P : c->sr_pend) release_retired(c, P);
@@ -509,13 +511,7 @@ static int sample_prepare(ftkx_ctx *c, const char *who, const ftkx_cp_t *recs, s
   HIP_TRY(c, hipSetDevice(c->device));
   const int nd = c->nd;
   ftkx::SampleMesh &m = P.m;
-  m.tag_mode = c->opt.tag_mode;
-  m.scalar_mode = c->scalar_mode == 1;
-  for (int d = 0; d < 3; d ++) {
-    m.dom_lb[d] = (int)c->dom_st[d]; m.dom_sz[d] = (int)c->dom_sz[d];
-    m.core_st[d] = (int)c->core_st[d]; m.core_sz[d] = (int)c->core_sz[d];
-    m.ext_st[d] = (int)c->ext_st[d]; m.ext_sz[d] = (int)c->ext_sz[d];
-  }
+  m = sample_mesh_of(c);
   // ONE pass over the records (72 bytes each: at 10^6 of them every pass is a walk through memory), on a few host threads where there are
   // many (sample_ranges): tag and aux word into the pinned block that goes up, the range of the timesteps beside it.  Everything behind reads the
   // 16-byte pairs.  The table of slice pointers travels behind the pairs; the block has room for 2 048 timesteps from the start.

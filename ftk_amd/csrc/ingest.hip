@@ -244,12 +244,25 @@ int adopt_resident_slice(ftkx_ctx *c, int t, const double *full)
 }
 
 // ---- auxiliary scalar fields sampled at critical points (sample_steps.hpp, sample_kernels.hip) -------------------------------------------
-// the aux arrays of timestep t leave: owned ones to the pool (only the sample kernel reads them, and ftkx_sample_aux has waited for it)
+// An aux array leaves its timestep (dropped, or replaced by a push).  ftkx_sample_aux has waited for its kernel; the sample kernel of an armed
+// series pass (ftkx_set_series_sampling) may still be queued.  The decision is free_slice's (ftkx_api.hip): the newest open pass is a SPLIT
+// pass -- its tail, on a stream of its own, is in no order with whatever takes the array out of the pool next -- and the array is parked with
+// that pass until it has been completed (release_retired); otherwise it goes to the pool, behind the context's stream.
+static void retire_aux(ftkx_ctx *c, ftkx_block &&b)
+{
+  if (c->sr_open > 0) {
+    ftkx_series_pending &N = c->sr_pend[c->sr_place(c->sr_open - 1)];
+    if (N.open && N.split) { N.parked_aux.push_back(std::move(b)); return; }
+  }
+  give_pooled(c, std::move(b));
+}
+
+// the aux arrays of timestep t leave
 void drop_aux(ftkx_ctx *c, int t)
 {
   auto it = c->aux.find(t);
   if (it == c->aux.end()) return;
-  for (ftkx_block &b : it->second.A) if (b.p) give_pooled(c, std::move(b));
+  for (ftkx_block &b : it->second.A) if (b.p) retire_aux(c, std::move(b));
   c->aux.erase(it);
 }
 
@@ -279,7 +292,7 @@ template <class T> static int push_aux_common(ftkx_ctx *c, int t, int slot, cons
   // a device source that was not adopted is read by a copy or by the widen kernel: the call returns once it has been read
   if (waits) HIP_TRY(c, hipStreamSynchronize(c->stream));
   ftkx_block &dst = c->aux[t].A[slot - 1];
-  if (dst.p) give_pooled(c, std::move(dst));
+  if (dst.p) retire_aux(c, std::move(dst));
   dst = std::move(b);
   return FTKX_OK;
 }

@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include "sample_steps.hpp"
+#include "sweep_params.hpp"   // CNT_PASS
 
 namespace ftkx {
 
@@ -40,6 +41,32 @@ void launch_sample(int nd, const SampleMesh &m, const SampleIn *in, size_t n, co
   const dim3 grid((unsigned)((n + (size_t)kSampleThreads - 1) / (size_t)kSampleThreads));
   if (nd == 2) hipLaunchKernelGGL((sample_kernel<2>), grid, dim3(kSampleThreads), 0, st, m, in, n, tab, t_min, slots, out);
   else hipLaunchKernelGGL((sample_kernel<3>), grid, dim3(kSampleThreads), 0, st, m, in, n, tab, t_min, slots, out);
+}
+
+// ---- the series pass samples its own records (ftkx_set_series_sampling) ------------------------------------------------------------------
+// In place over the records a pass left in device memory (series.hip queues it between the record kernel and the finish kernel): how many
+// there are is read on the device, the grid is whatever the host chose without knowing -- a stride loop, one lane per record.  The loop
+// body is series_sample_lane (sample_steps.hpp), which the CPU build runs as this kernel's oracle.  The two doubles of a record are stored
+// the way the record kernel stores the record (series_kernels.hip): relaxed, system scope -- they go through to memory, where the copy
+// kernel, which may be resident on another XCD and polling already, finds them once its acquire has let it past.  No LDS, no scratch, no
+// atomic read-modify-write.
+template <int ND>
+__global__ __launch_bounds__(kSampleThreads) void series_sample_kernel(SampleMesh m, ftkx_cp_t *recs, const u64 *__restrict__ counters, u64 capacity,
+                                                                        const SampleSlice *__restrict__ tab, int t_min, int ntab, unsigned slots)
+{
+  u64 n = counters[CNT_PASS];
+  if (n > capacity) n = capacity;
+  const size_t first = (size_t)blockIdx.x * (size_t)kSampleThreads + (size_t)threadIdx.x, stride = (size_t)gridDim.x * (size_t)kSampleThreads;
+  series_sample_lane<ND>(m, sample_fan<ND>(), recs, (size_t)n, tab, t_min, ntab, slots, first, stride,
+                         [](double *at, double v) { __hip_atomic_store(at, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); });
+}
+
+void launch_series_sample(int nd, const SampleMesh &m, ftkx_cp_t *recs, const u64 *counters, u64 capacity, const SampleSlice *tab, int t_min, int ntab, unsigned slots,
+                          unsigned workgroups, hipStream_t st)
+{
+  const dim3 grid(workgroups < 1u ? 1u : workgroups);
+  if (nd == 2) hipLaunchKernelGGL((series_sample_kernel<2>), grid, dim3(kSampleThreads), 0, st, m, recs, counters, capacity, tab, t_min, ntab, slots);
+  else hipLaunchKernelGGL((series_sample_kernel<3>), grid, dim3(kSampleThreads), 0, st, m, recs, counters, capacity, tab, t_min, ntab, slots);
 }
 
 }  // namespace ftkx

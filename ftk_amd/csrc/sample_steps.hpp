@@ -21,6 +21,7 @@
 // plain C++ compiler (tests/hostcheck/sample_host.cpp).
 #pragma once
 #include <cstddef>
+#include <vector>
 
 #include "../../include/ftkx.h"
 #include "cp_device.hpp"
@@ -184,6 +185,55 @@ FTKX_HD inline bool sample_record(const SampleMesh &m, const fan_table<ND + 1> &
   const SampleSlice s1 = fan.ordinal[type] ? s0 : tab[at + 1];
   sample_simplex<ND>(m, fan, corner, type, s0, s1, slots, out);
   return true;
+}
+
+// ---- the series pass samples its own records (ftkx_set_series_sampling; series_sample_kernel in sample_kernels.hip, queued by series.hip) ----
+// One lane of the kernel's grid-stride loop, in place over the records the pass left in device memory: records first, first + stride, ...
+// below n.  A lane loads the tag and word 15 (the aux word) of its record, samples it (sample_record: every gather before the solve) and
+// hands the armed slots to `store(address, value)` -- the kernel stores with the scope the record kernel's stores have, the host build
+// (tests/hostcheck/series_sample_host.cpp) plainly.  No other byte of a record is written.  A record that is no element of the mesh, or
+// whose timestep has no entry in the table (tab[0 .. ntab): timestep t_min + k, null arrays where the pass reads no slice), is left as it
+// is: the records of a pass are its own steps', so this is a guard against reading outside the table, not a path that is taken.
+template <int ND, class Store>
+FTKX_HD inline void series_sample_lane(const SampleMesh &m, const fan_table<ND + 1> &fan, ftkx_cp_t *recs, size_t n, const SampleSlice *tab, int t_min, int ntab,
+                                       unsigned slots, size_t first, size_t stride, Store store)
+{
+  for (size_t i = first; i < n; i += stride) {
+    const SampleIn in{recs[i].tag, reinterpret_cast<const unsigned *>(recs + i)[15], 0u};
+    const long long at = (long long)(in.aux >> 1) - (long long)t_min, last = (in.aux & 1u) ? at : at + 1;
+    if (at < 0 || last >= (long long)ntab) continue;
+    if (m.scalar_mode ? (!tab[at].S || !tab[last].S) : (!tab[at].V || !tab[last].V)) continue;
+    double r[2];
+    if (!sample_record<ND>(m, fan, in, tab, t_min, slots, r)) continue;
+    if (slots & 1u) store(&recs[i].scalar[1], r[0]);
+    if (slots & 2u) store(&recs[i].scalar[2], r[1]);
+  }
+}
+
+// the slices the steps of a pass read, in time order: a step's own, and the one behind it for an interval sweep (series.hip: P.slice_ts)
+inline void series_slice_timesteps(const int *ts, const int *scopes, int n, std::vector<int> &slice_ts)
+{
+  for (int i = 0; i < n; i ++) {
+    if (slice_ts.empty() || slice_ts.back() != ts[i]) slice_ts.push_back(ts[i]);
+    if (scopes[i] & FTKX_SCOPE_INTERVAL) slice_ts.push_back(ts[i] + 1);
+  }
+}
+
+// The slot rule of an armed pass, decided when it is submitted.  have[j]: bit s set = slot s + 1 has an aux array at the j-th of the k
+// slices the pass reads.  A slot with an array at every one of them is sampled (bit s of *slots), one with none is left zero.  Returns 0,
+// or the slot (1 | 2) that has an array at some of the slices but not all: the pass is refused (FTKX_E_NOSLICE) and *slots is 0.
+inline int series_sample_slots(const unsigned char *have, size_t k, unsigned *slots)
+{
+  *slots = 0;
+  unsigned all = 0;
+  for (int s = 0; s < 2; s ++) {
+    size_t with = 0;
+    for (size_t j = 0; j < k; j ++) with += (have[j] >> s) & 1u;
+    if (with != 0 && with != k) { *slots = 0; return s + 1; }
+    if (with != 0) all |= 1u << s;
+  }
+  *slots = all;
+  return 0;
 }
 
 }  // namespace ftkx

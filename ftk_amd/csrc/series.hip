@@ -82,9 +82,8 @@ int series_steps(ftkx_ctx *c, const int *ts, const int *scopes, int n, std::vect
   for (int i = 0; i < n; i ++) {
     if (scopes[i] < FTKX_SCOPE_ORDINAL || scopes[i] > FTKX_SCOPE_BOTH) return fail(c, FTKX_E_INVALID, "ftkx_sweep_series: bad scope %d", scopes[i]);
     if (i > 0 && ts[i] <= ts[i - 1]) return fail(c, FTKX_E_INVALID, "ftkx_sweep_series: timesteps must be strictly ascending");
-    if (slice_ts.empty() || slice_ts.back() != ts[i]) slice_ts.push_back(ts[i]);
-    if (scopes[i] & FTKX_SCOPE_INTERVAL) slice_ts.push_back(ts[i] + 1);
   }
+  ftkx::series_slice_timesteps(ts, scopes, n, slice_ts);      // (sample_steps.hpp: the slot rule of an armed pass runs over the same list)
   for (size_t j = 0; j < slice_ts.size(); j ++)
     if (c->slices.find(slice_ts[j]) == c->slices.end()) return fail(c, FTKX_E_NOSLICE, "ftkx_sweep_series: slice %d not resident", slice_ts[j]);
   return FTKX_OK;
@@ -116,6 +115,74 @@ bool series_applicable(ftkx_ctx *c, const int *ts, const int *scopes, int n, con
   }
   if (ok && (c->opt.coords_mode == 2 || c->opt.coords_mode == 3)) ok = false;     // (their bounds checks live in ftkx_sweep_enqueue)
   return ok;
+}
+
+// ---- an armed pass (ftkx_set_series_sampling): its records leave the device with scalar[1] / scalar[2] filled ---------------------------------
+// The sample kernel (sample_kernels.hip, series_sample_kernel) works in place on the records the record kernel left in device memory, in
+// stream order behind it and in front of the finish kernel; the copy kernel takes the filled records over PCIe.  So a pass with a slot to
+// fill leaves its records on the device (P.to_device) and takes the kernel chain: the fused tail and the one-launch pass write into pinned
+// memory themselves.  Its slice table lies in the pass's descriptor block, behind the step table.
+constexpr int kSeriesSampleMaxTab = 4096;      // timesteps the table spans at most; a pass over a wider span is left to the host-driven batch
+
+// The slot rule, at submit, over the slices the pass's steps read (sample_steps.hpp, series_sample_slots), and whatever ftkx_sample_aux would
+// refuse for the records of these steps, with its code.  Nothing has been queued or allocated yet.  P.sample_slots = 0: planned as an unarmed pass.
+int series_sample_plan(ftkx_ctx *c, ftkx_series_pending &P, const std::vector<Slice *> &sl)
+{
+  P.sample_slots = 0;
+  if (!c->sr_sampling || c->aux.empty()) return FTKX_OK;
+  std::vector<unsigned char> have(P.k, 0);
+  for (size_t j = 0; j < P.k; j ++) {
+    const auto ia = c->aux.find(P.slice_ts[j]);
+    if (ia != c->aux.end()) have[j] = (unsigned char)((ia->second.A[0].p ? 1 : 0) | (ia->second.A[1].p ? 2 : 0));
+  }
+  unsigned slots = 0;
+  if (const int partial = ftkx::series_sample_slots(have.data(), P.k, &slots))
+    return fail(c, FTKX_E_NOSLICE, "ftkx_sweep_series: slot %d has an aux array at some of the %zu timesteps the pass reads, not at all of them", partial, P.k);
+  if (!slots) return FTKX_OK;
+  for (size_t j = 0; j < P.k; j ++) {
+    if (sl[j]->sparse) return fail(c, FTKX_E_UNSUPPORTED, "ftkx_sweep_series: slice %d exists as masks and patches only", P.slice_ts[j]);
+    if (c->scalar_mode == 1 ? !sl[j]->S.p : !sl[j]->V.p) return fail(c, FTKX_E_INVALID, "ftkx_sweep_series: slice %d has no field array", P.slice_ts[j]);
+  }
+  if (c->opt.tag_mode == FTKX_TAG_REFERENCE && !ftkx::sample_reference_tags_exact(c->nd, c->dom_sz, P.ts.back()))
+    return fail(c, FTKX_E_UNSUPPORTED, "ftkx_sweep_series: FTKX_TAG_REFERENCE tags may have wrapped at timestep %d of this mesh and cannot be decoded (use FTKX_TAG_EXACT64)", P.ts.back());
+  P.sample_slots = slots;
+  P.sample_t_min = P.slice_ts.front();
+  const long long span = (long long)P.slice_ts.back() - (long long)P.slice_ts.front() + 1;
+  P.sample_ntab = span <= kSeriesSampleMaxTab ? (int)span : 0;      // (0: no table -- the host-driven batch, which samples behind itself)
+  return FTKX_OK;
+}
+
+// the table: per timestep of the span the slice's field arrays and the aux arrays of the slots sampled; null where the pass reads no slice
+void series_write_sample_table(ftkx_ctx *c, const ftkx_series_pending &P, const std::vector<Slice *> &sl)
+{
+  ftkx::SampleSlice *tab = (ftkx::SampleSlice *)((char *)c->sr_buf[P.buf].h_desc.p + P.off_sample);
+  for (int k = 0; k < P.sample_ntab; k ++) tab[k] = ftkx::SampleSlice{nullptr, nullptr, {nullptr, nullptr}};
+  for (size_t j = 0; j < P.k; j ++) {
+    ftkx::SampleSlice &e = tab[P.slice_ts[j] - P.sample_t_min];
+    e.S = sl[j]->S.as<double>(); e.V = sl[j]->V.as<double>();
+    const ftkx_ctx::AuxSlice &a = c->aux.find(P.slice_ts[j])->second;      // (there: the slot rule)
+    for (int s = 0; s < 2; s ++) e.A[s] = ((P.sample_slots >> s) & 1u) ? a.A[s].as<double>() : nullptr;
+  }
+}
+
+// the sampler of an armed pass, on the stream of its tail behind the record kernel
+void series_queue_sample(ftkx_ctx *c, const ftkx_series_pending &P, hipStream_t st)
+{
+  ftkx_series_buffers &B = c->sr_buf[P.buf];
+  const ftkx_tail_set &T = c->sr_tail[P.tail_set];
+  // The grid is fixed here, where the number of records is not known: from the hit count of the pass completed last, as P.to_device is decided --
+  // a lane per record of a pass like that one, between 4 workgroups and 4 per CU; the stride loop takes whatever the pass has beyond.  In a
+  // split-sparse pass: the few workgroups its neighbours in series_queue_rest get, next to a mask kernel.
+  const unsigned long long by_hits = ((unsigned long long)c->stats.hits + ftkx::kSampleThreads - 1) / ftkx::kSampleThreads;
+  const unsigned wgs = P.split_sparse ? 16u : (unsigned)std::max<unsigned long long>(4, std::min<unsigned long long>(by_hits, 1024));
+  // VISIBILITY.  The copy kernel that takes these records to the host may be resident already, on another stream and another XCD, polling the
+  // word the next pass's begin kernel stores (or it is ordered by an event).  The sampler's stores therefore have the scope the record
+  // kernel's have -- relaxed, SYSTEM scope: written through to memory, not left in this XCD's L2 -- and the copy kernel reads them behind
+  // its acquire, exactly as it reads the rest of the record.  The sampler's own loads of tag and aux word are ordered behind the record
+  // kernel by the kernel boundary on this stream.
+  ftkx::launch_series_sample(c->nd, sample_mesh_of(c), B.d_out.as<ftkx_cp_t>(), T.counters.as<u64>(), std::min<u64>(c->capacity, (u64)B.d_out.count<ftkx_cp_t>()),
+                             (const ftkx::SampleSlice *)((const char *)B.d_desc.p + P.off_sample), P.sample_t_min, P.sample_ntab, P.sample_slots, wgs, st);
+  c->ss_launches ++; c->ss_last_wgs = wgs;
 }
 
 // a slab pass's block of DB_N words, zeroed on the context's stream when it is made
@@ -229,6 +296,7 @@ void series_queue_rest(ftkx_ctx *c, const ftkx_series_pending &P, const Mesh &m,
   B.rank_max = ftkx::launch_bucket_rank(m, T.bucketed.as<u64>(), T.boff.as<unsigned>(), T.sorted.as<u64>(), B.results.as<u64>(), st, few ? 16 : 0);
   if (B.copy_out) { (void)hipStreamWaitEvent(st, B.ev_copied, 0); B.copy_out = false; }   // (the copy of the pass that used these buffers last: long through)
   ftkx::launch_series_records(m, d_steps, T.sorted.as<u64>(), P.to_device ? B.d_out.as<ftkx_cp_t>() : B.out.as<ftkx_cp_t>(), st, P.split);
+  if (P.sample_slots) series_queue_sample(c, P, st);      // (an armed pass: to_device, the records are filled where they lie)
   if (!P.split) ev_end(c);
   ftkx::launch_series_finish(m, B.results.as<u64>(), P.nwords, T.list_capacity, T.refine_capacity, B.h_results.as<u64>(), flag, seq, st);
 }
@@ -603,6 +671,7 @@ int series_plan(ftkx_ctx *c, ftkx_series_pending &P, const int *ts, const int *s
   P.k = k;
   std::vector<Slice *> sl(k);
   for (size_t j = 0; j < k; j ++) sl[j] = &c->slices.find(P.slice_ts[j])->second;
+  if ((rc = series_sample_plan(c, P, sl))) return rc;         // (an armed context: which slots this pass fills, or why it is refused)
 
   // ---- is the device-driven form applicable? ---------------------------------------------------------------------------------------
   Mesh m; fill_mesh(c, m);
@@ -612,10 +681,12 @@ int series_plan(ftkx_ctx *c, ftkx_series_pending &P, const int *ts, const int *s
   bool ok = series_applicable(c, ts, scopes, n, P.slice_ts, sl, P.cells, dist ? dist->t_halo : -1);
   if (prev && prev->by_host) ok = false;                     // (its running minimum will not be on the device)
   if (dist && !P.two_level) ok = false;                      // (the halo's masks travel as summaries + the words they do not describe)
+  if (P.sample_slots && P.sample_ntab == 0) ok = false;      // (a span of timesteps too wide for the slice table)
   P.hint = std::max<unsigned long long>(factor_of(running_in), 256ull);
   P.u_rows = m.u_rows;
   if (!ok) { P.by_host = true; P.open = true; return FTKX_OK; }
-  if (series_one_eligible(c, n, k, P.cells, dist != nullptr)) return series_plan_one(c, P, ts, scopes, n, sl, prev, before);
+  // (a pass with a slot to fill declines the one-launch form here, as it declines the fused tail below: both write their records into pinned memory)
+  if (!P.sample_slots && series_one_eligible(c, n, k, P.cells, dist != nullptr)) return series_plan_one(c, P, ts, scopes, n, sl, prev, before);
   std::vector<const u64 *> from_res, from_max;
   series_slice_readiness(c, P, sl, before, dist, from_res, from_max);
 
@@ -626,6 +697,7 @@ int series_plan(ftkx_ctx *c, ftkx_series_pending &P, const int *ts, const int *s
   if ((rc = ensure_list(c, S0, std::max<u64>(S0.list_capacity, 1u << 20))) || (rc = ensure_refine(c, S0, std::max<u64>(S0.refine_capacity, 1u << 20)))) return rc;
   const unsigned long long mask_bytes = (unsigned long long)P.ntodo * (unsigned long long)n_vertices(c) * 8ull * (c->scalar_mode == 1 ? 1ull : (unsigned long long)nd);
   series_decide_split(c, P, pipelined, dist != nullptr, mask_bytes);
+  if (P.sample_slots) P.to_device = true;                    // (split or not is decided as for an unarmed pass; where the records are written is not)
   if (before && before->open && before->split) series_retire_masks(P, sl, *before);
   for (size_t j = 0; j < k; j ++) if (P.red_index[j] >= 0 && (rc = ensure_mask_arrays(c, *sl[j], P.two_level))) return rc;
   series_bucket_geometry(P);
@@ -633,7 +705,8 @@ int series_plan(ftkx_ctx *c, ftkx_series_pending &P, const int *ts, const int *s
   P.nwords = (size_t)ftkx::SR_HEAD + (size_t)n + 2 * k + (dist ? (size_t)ftkx::kDistContrib * (size_t)dist->nranks : 0);
   // descriptors: mask jobs | steps | slice table | step table, one pinned block fetched by a kernel
   P.off_steps = align256(P.ntodo * sizeof(MaskJob)); P.off_slices = P.off_steps + align256((size_t)n * sizeof(Fields)); P.off_sinfo = P.off_slices + align256(k * sizeof(ftkx::SeriesSlice));
-  const size_t desc_bytes = P.off_sinfo + align256((size_t)n * sizeof(ftkx::SeriesStep));
+  P.off_sample = P.off_sinfo + align256((size_t)n * sizeof(ftkx::SeriesStep));      // (an armed pass: | the sampler's slice table)
+  const size_t desc_bytes = P.off_sample + (P.sample_slots ? align256((size_t)P.sample_ntab * sizeof(ftkx::SampleSlice)) : 0);
   // A pass with many records, queued while another is still out: the record kernel leaves them in device memory and a small kernel on a
   // stream of its own takes them over PCIe -- next to the mask kernel of the pass queued behind.  (A record kernel that writes through
   // PCIe itself holds its stream for the transfer: 106 us of woven 1024^2 x 64's 363.)
@@ -645,6 +718,7 @@ int series_plan(ftkx_ctx *c, ftkx_series_pending &P, const int *ts, const int *s
   if ((rc = series_tail_resources(c, P, before, mask_bytes))) return rc;
   series_mesh(c, P, m);                                      // (the buffers may have moved)
   series_write_desc(c, P, m, sl, from_res, from_max);
+  if (P.sample_slots) series_write_sample_table(c, P, sl);
 
   // ---- the whole pass, queued ------------------------------------------------------------------------------------------------------
   P.seq = ++ B.seq;
@@ -742,6 +816,32 @@ int series_submit(ftkx_ctx *c, ftkx_series_pending &P, const int *ts, const int 
   return FTKX_OK;
 }
 
+// Every way from a pass to the host-driven batch -- P.by_host up front (FTKX_SERIES=0 among its reasons), the flags a kernel raised, a fused
+// tail that declined with the lists gone -- ends here: the batch sweeps the steps and, where the pass was to fill slots, the existing sample
+// pass (ftkx_sample_aux: sample_prepare + launch_sample) runs over the batch's records before they are returned (ftkx_series_sampled: where =
+// 2).  A failure there fails the call with its code.  The aux arrays are looked up again NOW: one that has been dropped since the pass was
+// submitted fails the call as a dropped slice does.
+int series_by_host_sampled(ftkx_ctx *c, ftkx_series_pending &P, double *running, unsigned long long *factors, const ftkx_cp_t **out, size_t *n_out)
+{
+  const ftkx_cp_t *recs = nullptr;
+  size_t nrec = 0;
+  int rc = series_by_host(c, P.ts.data(), P.scopes.data(), P.n, P.slice_ts, running, factors, &recs, &nrec);
+  if (rc) return rc;
+  if (P.sample_slots) {
+    for (int t : P.slice_ts) {
+      const auto ia = c->aux.find(t);
+      for (int s = 0; s < 2; s ++)
+        if (((P.sample_slots >> s) & 1u) && (ia == c->aux.end() || !ia->second.A[s].p))
+          return fail(c, FTKX_E_NOSLICE, "ftkx_sweep_series: the aux array of slot %d at timestep %d was dropped before the pass was completed", s + 1, t);
+    }
+    if ((rc = ftkx_sample_aux(c, const_cast<ftkx_cp_t *>(recs), nrec))) return rc;      // (the context's own record buffer: ftkx.h allows it)
+    c->sr_sampled_slots = P.sample_slots; c->sr_sampled_where = 2;
+  }
+  if (out) *out = recs;
+  if (n_out) *n_out = nrec;
+  return FTKX_OK;
+}
+
 // Second half: the host waits (once) for the pass, marks the slices, patches what has to be patched on the host, or has the host-driven
 // batch sweep the steps again where a kernel raised a flag.
 int series_complete(ftkx_ctx *c, ftkx_series_pending &P, double *running_resolution, unsigned long long *factors, const ftkx_cp_t **out, size_t *n_out)
@@ -750,13 +850,14 @@ int series_complete(ftkx_ctx *c, ftkx_series_pending &P, double *running_resolut
   const size_t k = P.k;
   P.open = false;
   memset(c->sr_last_order, 0, sizeof(c->sr_last_order));      // (ftkx_debug_series_order: zero unless this pass's records came through the bucket chain)
+  c->sr_sampled_slots = 0; c->sr_sampled_where = 0;           // (ftkx_series_sampled: set where this pass's records were filled)
   double running = *running_resolution;                       // (what the pass started from: the host-driven batch, if it comes to that, starts there too)
   // (the split pass's self-check samples the time between two completions by the plain way out of this function: any other way out breaks the chain)
   const double last_complete_s = c->sr_last_complete_s;
   const int last_complete_kind = c->sr_last_complete_kind;
   c->sr_last_complete_s = 0; c->sr_last_complete_kind = 0;
   if (P.by_host) {
-    int rc = series_by_host(c, P.ts.data(), P.scopes.data(), n, P.slice_ts, &running, factors, out, n_out);
+    int rc = series_by_host_sampled(c, P, &running, factors, out, n_out);
     if (rc == FTKX_OK) *running_resolution = running;
     return rc;
   }
@@ -823,7 +924,7 @@ int series_complete(ftkx_ctx *c, ftkx_series_pending &P, double *running_resolut
       // running minimum the lower ranks' contributions give, over a halo slice that has its patches -- both settled above)
       c->sr_short_chain = false;
       if (!P.split) ev_end(c);
-      int rc = series_by_host(c, P.ts.data(), P.scopes.data(), n, P.slice_ts, &running, factors, out, n_out);
+      int rc = series_by_host_sampled(c, P, &running, factors, out, n_out);
       if (rc == FTKX_OK) *running_resolution = running;
       return rc;
     }
@@ -856,7 +957,7 @@ int series_complete(ftkx_ctx *c, ftkx_series_pending &P, double *running_resolut
       if (refined > S0.refine_capacity && (rc = ensure_refine(c, S0, refined + refined / 8 + 1024))) return rc;
       if (fragile > S0.fragile_capacity && (rc = ensure_fragile(c, S0, fragile + fragile / 8 + 1024))) return rc;
     }
-    rc = series_by_host(c, P.ts.data(), P.scopes.data(), n, P.slice_ts, &running, factors, out, n_out);
+    rc = series_by_host_sampled(c, P, &running, factors, out, n_out);
     if (rc == FTKX_OK) *running_resolution = running;
     return rc;
   }
@@ -916,6 +1017,7 @@ int series_complete(ftkx_ctx *c, ftkx_series_pending &P, double *running_resolut
     if (e[0] < nrec) H[e[0]].type = (unsigned)ftkx::classify3(A, c->opt.jacobian_symmetric != 0);
   }
   c->stats.reclassified = nf;
+  if (P.sample_slots) { c->sr_sampled_slots = P.sample_slots; c->sr_sampled_where = 1; c->ss_records += nrec; }      // (the in-pass kernel filled them on the device)
   // (a bucket too full to rank on the device: its records are unordered among themselves -- series_order.hpp)
   if (status & ftkx::SERIES_FIX_ORDER) ftkxh::series_fix_order(H, nrec);
   double run;
@@ -1014,6 +1116,7 @@ int ftkx_series_dist_begin(ftkx_ctx *c, const int *ts, const int *scopes, int n,
   // (upper <= rank: a series that is periodic in time -- the slice behind the last slab is the first slab's first, include/ftkx_slab.h)
   if (halo && (upper >= nranks || !(scopes[n - 1] & FTKX_SCOPE_INTERVAL))) return fail(c, FTKX_E_INVALID, "ftkx_series_dist_begin: the upper neighbour must be a rank of the series, and the last step an interval sweep");
   if (c->scalar_mode < 0) return fail(c, FTKX_E_INVALID, "ftkx_series_dist_begin: push this rank's slices first");
+  if (c->sr_sampling) return fail(c, FTKX_E_UNSUPPORTED, "ftkx_series_dist_begin: slab passes do not sample (ftkx_set_series_sampling is on: sample the gathered records with ftkx_sample_aux)");
   c->ahead.clear(); c->announced.clear();
   HIP_TRY(c, hipSetDevice(c->device));
   ftkx_series_pending &Q = c->sr_pend[c->sr_place(c->sr_open)];
@@ -1226,6 +1329,32 @@ int ftkx_series_last_path(const ftkx_ctx *c, unsigned long long *status)
   if (!c) return -1;
   if (status) *status = c->sr_last_status;
   return c->sr_last_path;
+}
+
+int ftkx_set_series_sampling(ftkx_ctx *c, int on)
+{
+  if (!c) return fail(nullptr, FTKX_E_INVALID, "null context");
+  const bool want = on != 0;
+  if (want != c->sr_sampling && (c->sr_open > 0 || slab_half_queued(c))) return fail(c, FTKX_E_INVALID, "ftkx_set_series_sampling: series passes are open, complete them first");
+  c->sr_sampling = want;
+  return FTKX_OK;
+}
+
+int ftkx_series_sampled(const ftkx_ctx *c, unsigned *slots, int *where)
+{
+  if (!c) return fail(nullptr, FTKX_E_INVALID, "null context");
+  if (slots) *slots = c->sr_sampled_slots;
+  if (where) *where = c->sr_sampled_where;
+  return FTKX_OK;
+}
+
+int ftkx_debug_series_sample_counts(const ftkx_ctx *c, unsigned long long *launches, unsigned long long *records, unsigned *workgroups_of_last_launch)
+{
+  if (!c) return fail(nullptr, FTKX_E_INVALID, "null context");
+  if (launches) *launches = c->ss_launches;
+  if (records) *records = c->ss_records;
+  if (workgroups_of_last_launch) *workgroups_of_last_launch = c->ss_last_wgs;
+  return FTKX_OK;
 }
 
 }  // extern "C"

@@ -504,6 +504,7 @@ void critical_point_tracker_regular::apply_configuration(ftkx_ctx *c)
   check_on(c, ftkx_set_perturbation(c, perturbation_sigma, perturbation_seed));
   check_on(c, ftkx_set_clamp(c, clamp_on ? 1 : 0, clamp_lo, clamp_hi));
   check_on(c, ftkx_set_temporal_smoothing(c, temporal_smoothing_sigma, temporal_smoothing_ksize, next_push_timestep));
+  check_on(c, ftkx_set_series_sampling(c, samples_in_pass() ? 1 : 0));      // (set_sampling_in_pass with components: the passes fill slots 1, 2)
 }
 
 void critical_point_tracker_regular::initialize()
@@ -557,7 +558,7 @@ void critical_point_tracker_regular::push_snapshot(int kind, const void *s, cons
   if (extras_in_push != n_extra_expected())
     throw ftkx_error(FTKX_E_INVALID, "push: " + std::to_string(scalar_components.size()) + " scalar components take " + std::to_string(n_extra_expected()) + " extra arrays with every snapshot, not " +
                                      std::to_string(extras_in_push));
-  if (extras_in_push > 0 && (multi || slab || temporal_smoothing_ksize || deferred_collection))
+  if (extras_in_push > 0 && (multi || slab || temporal_smoothing_ksize || (deferred_collection && !samples_in_pass())))
     throw ftkx_error(FTKX_E_UNSUPPORTED, "push: extra scalar components not with deferred collection, several devices, slab mode or temporal smoothing");
   if (temporal_smoothing_ksize) {
     // the raw snapshot feeds the filter; what the filter emits is the snapshot the tracker sees (a device source is read, not adopted)
@@ -750,7 +751,9 @@ void critical_point_tracker_regular::update_timestep()
 // still out), then collect the step before it
 void critical_point_tracker_regular::step_deferred(int scope)
 {
-  if (n_extra_expected() > 0) throw ftkx_error(FTKX_E_UNSUPPORTED, "update_timestep: extra scalar components not with deferred collection (a step's snapshots are popped before its records arrive)");
+  // (components: only where the pass samples its own records -- in stream order, in front of whatever reuses the popped snapshots' arrays)
+  if (n_extra_expected() > 0 && !samples_in_pass())
+    throw ftkx_error(FTKX_E_UNSUPPORTED, "update_timestep: extra scalar components not with deferred collection (a step's snapshots are popped before its records arrive; set_sampling_in_pass(true) lifts this)");
   if (deferred_depth > 1) {                 // batches: recorded; queued with the batch's last step (submit_batch)
     batch_ts.push_back(current_timestep); batch_scopes.push_back(scope);
     if ((int)batch_ts.size() >= deferred_depth) submit_batch();
@@ -770,12 +773,14 @@ void critical_point_tracker_regular::step_now(int scope)
   const ftkx_cp_t *recs = nullptr;
   size_t n = 0;
   collect_deferred();
+  bool filled = false;      // the pass filled slots 1, 2 itself (set_sampling_in_pass)
   if (window_is_the_step()) {
     // The device-driven pass (ftkx_sweep_series): the newly arrived snapshot's masks and reduction, the sticky factor (formed on the
     // device from the running minimum handed in), cull, exact test and records are queued at once and waited for once.
     unsigned long long f = 0;
     check(ftkx_sweep_series(ctx, &current_timestep, &scope, 1, &vector_field_resolution, &f, &recs, &n));
     vector_field_scaling_factor = f;
+    filled = samples_in_pass();
   } else {
     // (more than two snapshots queued: the reference's factor takes every queued snapshot into account, critical_point_tracker.hh:853)
     check(ftkx_sweep_announce(ctx, &current_timestep, &scope, 1));
@@ -783,7 +788,7 @@ void critical_point_tracker_regular::step_now(int scope)
     check(ftkx_sweep(ctx, current_timestep, scope, vector_field_scaling_factor, &recs, &n));
   }
   std::vector<ftkx_cp_t> sampled;
-  sample_step_records(recs, n, sampled);
+  if (!filled) sample_step_records(recs, n, sampled);
   take_records(recs, n, current_timestep);
   check(ftkx_get_stats(ctx, &last_stats));
   if (enable_streaming_trajectories && scope == FTKX_SCOPE_BOTH) grow();      // 2d:326-330, 3d:197-201: only after an interval sweep
@@ -1115,6 +1120,7 @@ int ftkx_tracker_flush_temporal_smoothing(ftkx_tracker *h, int *appended)
 { return guarded(h, [&] { const bool b = h->t->flush_temporal_smoothing(); if (appended) *appended = b ? 1 : 0; }); }
 int ftkx_tracker_set_trace_on_device(ftkx_tracker *h, int on) { return guarded(h, [&] { h->t->set_trace_on_device(on != 0); }); }
 int ftkx_tracker_set_post_process_on_device(ftkx_tracker *h, int on) { return guarded(h, [&] { h->t->set_post_process_on_device(on != 0); }); }
+int ftkx_tracker_set_sampling_in_pass(ftkx_tracker *h, int on) { return guarded(h, [&] { h->t->set_sampling_in_pass(on != 0); }); }
 int ftkx_tracker_set_deferred_collection(ftkx_tracker *h, int on) { return guarded(h, [&] { h->t->set_deferred_collection(on != 0, on); }); }
 int ftkx_tracker_set_communicator(ftkx_tracker *h, void *comm, int rank, int nranks, int nt) { return guarded(h, [&] { h->t->set_communicator(comm, rank, nranks, nt); }); }
 int ftkx_tracker_set_slab_transport(ftkx_tracker *h, const ftkx_slab_transport *tr, int rank, int nranks, int nt)

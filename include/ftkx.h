@@ -31,7 +31,7 @@ extern "C" {
 typedef struct ftkx_cp_t {
   double x[3];              /* lattice coordinates (REGULAR_COORDS_SIMPLE); 2D: x[2] = 0 */
   double t;
-  double scalar[3];         /* scalar[0] filled iff a scalar field was given (FTK_CP_MAX_NUM_VARS = 3); [1], [2]: 0 unless ftkx_sample_aux filled them */
+  double scalar[3];         /* scalar[0] filled iff a scalar field was given (FTK_CP_MAX_NUM_VARS = 3); [1], [2]: 0 unless ftkx_sample_aux or an armed series pass (ftkx_set_series_sampling) filled them */
   unsigned int type;        /* include/ftk/numeric/critical_point_type.hh:10-36 */
   unsigned long long tag;   /* see ftkx_options.tag_mode */
 } ftkx_cp_t;
@@ -621,6 +621,32 @@ int ftkx_sample_aux(ftkx_ctx *ctx, ftkx_cp_t *recs, size_t n);
 int ftkx_debug_sample_relaunch(ftkx_ctx *ctx, const ftkx_cp_t *recs, size_t n, int reps, double *ms);
 /* launches of the sample kernel by ftkx_sample_aux on this context so far, and the records they took.  Either may be null. */
 int ftkx_debug_sample_counts(const ftkx_ctx *ctx, unsigned long long *launches, unsigned long long *records);
+
+/* ---- the series pass samples its own records: they leave the device filled ----
+ * ftkx_set_series_sampling(ctx, on), default off.  While it is on, the records of ftkx_sweep_series and of ftkx_sweep_series_submit /
+ * _complete come back with scalar[1] / scalar[2] filled -- the values ftkx_sample_aux gives, bit for bit; no other byte of a record differs
+ * from the pass of a context that is not armed.  The sampling runs in stream order inside the pass, on the records in device memory in
+ * front of their copy to the host: nothing goes up, nothing is decoded on the host, and the slices and aux arrays may be dropped as soon
+ * as the pass has been submitted.  Which slots are filled is decided at submit, over the slices the pass's steps read (a step's own, and
+ * the one behind it for an interval sweep): a slot with an aux array at every one of them is sampled; one with none is left zero; one
+ * with an array at some but not all: FTKX_E_NOSLICE, nothing is queued and the context stays usable.  With no aux array at any of them
+ * the pass is planned, queued and run exactly as without the switch.  Whatever ftkx_sample_aux refuses for those records and arrays is
+ * refused at submit with the same code.  A pass with a slot to fill keeps its records in device memory, takes the kernel chain (not the
+ * fused tail, not the one-launch pass: ftkx_series_last_path 1 or 5) and has the copy kernel bring them over; where the host-driven batch
+ * takes the pass over (ftkx_series_last_path 0) the batch's records are sampled inside the call before they are returned, and a failure
+ * there -- an aux array dropped meanwhile: FTKX_E_NOSLICE -- fails the call.  Slab passes (ftkx_series_dist_*) on an armed context:
+ * FTKX_E_UNSUPPORTED.  Changing the switch while a pass is open: FTKX_E_INVALID.
+ * Lifetime: an aux array of the context's own that is dropped or replaced under an open pass is kept for as long as that pass may read it
+ * (as a dropped slice's arrays are).  A LENT array (on_device = 1) is the caller's to keep alive until every pass submitted while it was
+ * resident has been completed.
+ * ftkx_series_sampled: of the pass completed last -- *slots the set of slots filled (bit 0: scalar[1], bit 1: scalar[2]), *where 0 not
+ * filled, 1 by the kernel inside the pass, 2 behind the host-driven batch inside the call.  Either may be null.
+ * ftkx_debug_series_sample_counts: launches of the in-pass kernel on this context so far, the records of the passes they belonged to
+ * (counted when a pass completes), and the workgroups of the last launch.  Each may be null.  ftkx_debug_sample_counts keeps its meaning:
+ * launches on behalf of ftkx_sample_aux, and of `where` = 2. */
+int ftkx_set_series_sampling(ftkx_ctx *ctx, int on);
+int ftkx_series_sampled(const ftkx_ctx *ctx, unsigned *slots, int *where);
+int ftkx_debug_series_sample_counts(const ftkx_ctx *ctx, unsigned long long *launches, unsigned long long *records, unsigned *workgroups_of_last_launch);
 
 /* test aid: the ordering step of the device-driven pass completed last on this context (ftkx_sweep_series, ftkx_sweep_series_complete), as
  * it ran: out[0] the number of buckets, out[1] the shift that takes an order key to its bucket, out[2] the fullest bucket, out[3] the

@@ -185,9 +185,16 @@ public:
   // and scalar[2].  With more than one name every snapshot is pushed with its extra arrays (the push_* overloads that take `extra`), and
   // update_timestep() samples the step's records before the step's snapshots are popped: get_critical_points(), the traced and the
   // streaming trajectories and the writers see the filled slots; the text writers print the names.  Smoothing, perturbation and clamp never
-  // touch the extra arrays.  Not covered, FTKX_E_UNSUPPORTED at initialize() or at the push: deferred collection, multi-device trackers,
+  // touch the extra arrays.  Not covered, FTKX_E_UNSUPPORTED at initialize() or at the push: deferred collection (unless set_sampling_in_pass), multi-device trackers,
   // slab mode, temporal smoothing (its emissions lag the pushes).
   void set_scalar_components(const std::vector<std::string> &names);
+  // not in the reference: with set_sampling_in_pass(true) (before initialize(); default false: nothing changes) and more than one component
+  // named, the tracker's context is armed (ftkx.h: ftkx_set_series_sampling) -- a step's device-driven pass fills scalar[1] / scalar[2] itself,
+  // in stream order in front of the pop of the step's snapshots.  update_timestep() then takes those records as they come instead of
+  // sampling them in a pass of its own (with more than two snapshots queued it keeps that pass), and deferred collection
+  // (set_deferred_collection, single steps and batches) is allowed with components.  Same points, same curves, bit for bit.  Multi-device
+  // trackers, slab mode and temporal smoothing stay FTKX_E_UNSUPPORTED with components.
+  void set_sampling_in_pass(bool b) { sampling_in_pass = b; }
   const std::vector<std::string> &get_scalar_components() const { return scalar_components; }
   int snapshots_from_last_push() const { return last_push_snapshots; }      // 0 or 1; always 1 with the filter off
   bool flush_temporal_smoothing();
@@ -313,7 +320,9 @@ protected:
   // extra scalar fields (set_scalar_components)
   std::vector<std::string> scalar_components;               // empty: never set (the writers' default label, no extras)
   int n_extra_expected() const { return scalar_components.empty() ? 0 : (int)scalar_components.size() - 1; }
-  int extras_in_push = 0;                                   // how many extras the push_* call in hand brings (push_snapshot holds it to the names)
+  bool sampling_in_pass = false;                            // set_sampling_in_pass
+  bool samples_in_pass() const { return sampling_in_pass && n_extra_expected() > 0; }      // the context is armed (apply_configuration)
+  int extras_in_push = 0;                                 // how many extras the push_* call in hand brings (push_snapshot holds it to the names)
   void push_with_extras(int kind, const void *s, const void *v, const void *j, const void *const *extra, int n_extra, bool device, bool f32);
   void sample_step_records(const ftkx_cp_t *&recs, size_t n, std::vector<ftkx_cp_t> &store);   // the step's records with slots 1, 2 filled (a copy in `store`)
   double vector_field_resolution = std::numeric_limits<double>::max();   // sticky running minimum (never reset)
@@ -455,6 +464,7 @@ int  ftkx_tracker_push_vector_field_components_f32(ftkx_tracker *, const float *
  * array of the call is float32.  ftkx_tracker_get_curve_scalars: after finalize, scalar[0 .. 2] of every curve point, 3 doubles per point
  * in the order of ftkx_tracker_get_curves */
 int  ftkx_tracker_set_scalar_components(ftkx_tracker *, const char *const *names, int n);
+int  ftkx_tracker_set_sampling_in_pass(ftkx_tracker *, int on);      /* not in the reference: see critical_point_tracker_regular::set_sampling_in_pass */
 int  ftkx_tracker_push_snapshot_extra(ftkx_tracker *, int kind, const void *s, const void *v, const void *j, const void *const *extra, int n_extra, int on_device, int f32);
 int  ftkx_tracker_get_curve_scalars(const ftkx_tracker *, double *scalars);
 int  ftkx_tracker_advance_timestep(ftkx_tracker *);
