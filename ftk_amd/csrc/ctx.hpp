@@ -20,6 +20,7 @@
 #include "sweep_params.hpp"
 #include "split_policy.hpp"
 #include "batch_plan.hpp"
+#include "series_verdict.hpp"
 #include "internal.hpp"
 #include "pass2_layout.hpp"
 #include "ctx_block.hpp"
@@ -406,17 +407,13 @@ struct ftkx_ctx {
   double sr_last_complete_s = 0;        // host clock of the last completion (0: the pipeline ran empty since)
   int sr_last_complete_kind = 0;        // 1 in order / 2 split, of a calibration pass; 0 otherwise
   unsigned sr_split_seq = 0;          // split passes queued so far: their parity picks the set
-  int sr_one_off = 0;                  // passes for which the one-launch form is not tried (it declined a moment ago)
   ftkx_block sr_one_scratch;           // u64: the one-launch pass's barrier counters, partial reductions and per-workgroup counts (ONE_WORDS)
   ftkx_block sr_fetch_flag;            // unsigned, device: [0] the number of the last pass whose descriptors have been fetched (series_begin_kernel), [1] its arrival counter
   unsigned sr_fetch_seq = 0;
   hipEvent_t sr_ev_fetched = nullptr;  // slab passes: recorded behind the begin kernel, waited for by the copy of the pass before (no spin-wait there)
   unsigned long long mask_epoch = 0;  // source of Slice::mask_gen values
   double sr_last_running = 0;         // the running minimum the host knew when it last collected a pass (hint of a chained pass)
-  int sr_skip_small = 0;             // passes for which the fused tail kernel is not launched (the data was hit-dense a moment ago)
-  int sr_late_streak = 0;            // consecutive passes the fused tail declined late
-  bool sr_short_chain = false;       // the last pass was finished by the fused tail kernel: the next one is queued without the kernels behind it
-  bool sr_sparse = false;            // the last pass had few survivors and records (the fused tail's range): a pass whose mask kernel is long enough is split
+  ftkxh::tail_policy sr_policy;     // what the passes completed so far say about the form of the next one (series_verdict.hpp)
   int sr_last_buf = 0;               // the buffers of the pass completed last (ftkx_series_dist_status reads its results block)
   size_t sr_last_gathered_off = 0; int sr_last_nranks = 0;   // where its gathered contributions sit in that block (0 ranks: not a slab pass)
   int sr_last_path = 0;              // which way the last ftkx_sweep_series went: 0 the host-driven batch, 1 device-driven (the kernel chain), 2 early single-workgroup tail,

@@ -271,14 +271,6 @@ int ensure_set1(ftkx_ctx *c)
   return FTKX_OK;
 }
 
-bool short_chain_now(const ftkx_ctx *c, bool to_device, bool *small_now)
-{
-  const bool small_on = ftkx::env_hook("FTKX_SERIES_HOOKS", "small", 1) != 0, short_on = ftkx::env_hook("FTKX_SERIES_HOOKS", "short", 1) != 0;
-  const bool sn = small_on && c->sr_skip_small == 0 && !to_device;
-  if (small_now) *small_now = sn;
-  return sn && short_on && c->sr_short_chain;
-}
-
 // the kernels behind the fused tail: refine, exact test, ordering, records, finish
 void series_queue_rest(ftkx_ctx *c, const ftkx_series_pending &P, const Mesh &m, unsigned seq)
 {
@@ -359,9 +351,8 @@ ftkx::SeriesStep series_step(const std::vector<int> &slice_ts, int t, int scope,
 // ---- the one-launch pass for small series (one_kernel.hip) --------------------------------------------------------------------------------
 bool series_one_eligible(ftkx_ctx *c, int n, size_t k, u64 cells, bool dist)
 {
-  const bool one_on = ftkx::env_hook("FTKX_SERIES_HOOKS", "one", 1) != 0;
-  if (!one_on || dist || c->sr_one_off > 0) { if (c->sr_one_off > 0 && !dist) c->sr_one_off --; return false; }
-  return ftkx::one_eligible_by_size(c->nd, n, k, cells, (u64)n_vertices(c), (u64)c->stats.hits);      // (the sizes' part: one_plan.hpp)
+  return ftkxh::tail_one_allowed(c->sr_policy, ftkx::env_hook("FTKX_SERIES_HOOKS", "one", 1) != 0, dist) &&      // (asked first: an ask counts whatever the sizes say)
+         ftkx::one_eligible_by_size(c->nd, n, k, cells, (u64)n_vertices(c), (u64)c->stats.hits);      // (the sizes' part: one_plan.hpp)
 }
 
 int series_plan_one(ftkx_ctx *c, ftkx_series_pending &P, const int *ts, const int *scopes, int n, const std::vector<Slice *> &sl, const ftkx_series_pending *prev,
@@ -488,7 +479,7 @@ void series_decide_split(ftkx_ctx *c, ftkx_series_pending &P, bool pipelined, bo
   // streams kept for the process) measures 0.764-0.774 alone, behind three other configurations and inside the driver's full line
   // (tools/dense_split.py) -- and auto's self-check keeps a context in order where it is not so.  Smaller hit-dense passes lose: woven
   // 1024^2 x 64, tail = mask kernel = 100 us, 0.205 -> 0.279 split.
-  const bool sparse_now = c->sr_sparse && !P.to_device;
+  const bool sparse_now = ftkxh::tail_sparse(c->sr_policy) && !P.to_device;
   // (a hit-dense chain is ~550 us next to a mask kernel -- double_gyre's 56 766 records --: only mask launches of 4 GB and more hide it.)
   // The decision, and in "auto" the self-check behind it: split_policy.hpp
   ftkxh::split_inputs in;
@@ -497,7 +488,7 @@ void series_decide_split(ftkx_ctx *c, ftkx_series_pending &P, bool pipelined, bo
   in.signature = ((unsigned long long)P.n << 48) ^ ((unsigned long long)P.ntodo << 32) ^ (unsigned long long)P.cells;
   const ftkxh::split_verdict v = ftkxh::split_decide(c->sr_cal, in);
   P.split = v.split; P.cal_kind = v.cal_kind; c->sr_split_forced = v.forced;
-  P.split_sparse = P.split && c->sr_sparse && !P.to_device;
+  P.split_sparse = P.split && sparse_now;
 }
 
 // a slice whose masks this pass rebuilds while the tail of the (split) pass before it -- on its own stream -- still reads them: fresh arrays here,
@@ -784,18 +775,14 @@ int series_queue_tail(ftkx_ctx *c, ftkx_series_pending &P)
   unsigned *flag = series_flag(B);
   hipStream_t st = tail_stream(c, P);
   if (!P.split) ev_begin(c, K_EXACT);
-  // sparse data: one kernel does the rest of the pass (and the kernels below leave at once).  (A pass that has just found far more
-  // survivors than the fused kernel takes does not launch it for a while: finding nothing to do costs its 256 workgroups of 256-VGPR
-  // wavefronts ~15 us.)  The fused tail finished the last pass too: this one is queued WITHOUT the seven kernels behind it -- each of them
-  // costs a few us just to find out that it has nothing to do.  Should the fused tail decline this time, it says so itself and the rest is
-  // queued then (or, with another pass queued behind already, the host-driven batch sweeps the steps).
-  bool small_now = false;
-  P.short_chain = short_chain_now(c, P.to_device, &small_now);
-  if (P.split) { small_now = false; P.short_chain = false; }      // (the fused tail does not fit next to a mask kernel: the chain)
-  if (c->sr_skip_small > 0) c->sr_skip_small --;
-  P.small_now = small_now;
+  // sparse data: one kernel does the rest of the pass (and the kernels below leave at once).  The fused tail finished the last pass too:
+  // this one is queued WITHOUT the seven kernels behind it -- each of them costs a few us just to find out that it has nothing to do.
+  // Should the fused tail decline this time, it says so itself and the rest is queued then (or, with another pass queued behind already,
+  // the host-driven batch sweeps the steps).  When the fused tail sits out, and what a split pass gets: the tail policy, series_verdict.hpp
+  const ftkxh::tail_plan tp = ftkxh::tail_plan_next(c->sr_policy, ftkx::env_hook("FTKX_SERIES_HOOKS", "small", 1) != 0, ftkx::env_hook("FTKX_SERIES_HOOKS", "short", 1) != 0, P.to_device, P.split);
+  P.small_now = tp.small_now; P.short_chain = tp.short_chain;
   const ftkx_tail_set &T = tail_of(c, P);
-  if (small_now) ftkx::launch_series_small(m, P.two_level ? ftkx::coarse_view(m) : m, d_steps, P.two_level, T.refine.as<u64>(), T.list.as<u64>(), B.out.as<ftkx_cp_t>(), B.results.as<u64>(), P.nwords,
+  if (P.small_now) ftkx::launch_series_small(m, P.two_level ? ftkx::coarse_view(m) : m, d_steps, P.two_level, T.refine.as<u64>(), T.list.as<u64>(), B.out.as<ftkx_cp_t>(), B.results.as<u64>(), P.nwords,
                                           B.h_results.as<u64>(), flag, P.seq, reinterpret_cast<unsigned *>(T.counters.as<u64>() + ftkx::CNT_SMALL_DONE), P.short_chain, st);
   if (!P.short_chain) series_queue_rest(c, P, m, P.seq);
   if (P.split) HIP_TRY(c, hipEventRecord(B.ev_tail, st));
@@ -842,156 +829,117 @@ int series_by_host_sampled(ftkx_ctx *c, ftkx_series_pending &P, double *running,
   return FTKX_OK;
 }
 
-// Second half: the host waits (once) for the pass, marks the slices, patches what has to be patched on the host, or has the host-driven
-// batch sweep the steps again where a kernel raised a flag.
-int series_complete(ftkx_ctx *c, ftkx_series_pending &P, double *running_resolution, unsigned long long *factors, const ftkx_cp_t **out, size_t *n_out)
+// ---- the second half, stage by stage (series_complete) ----------------------------------------------------------------------------------
+// The masks and reductions of a pass stand whichever way its records are made: the slices are marked like ftkx_slices_prepare marks
+// them -- slice by slice, unless something has rebuilt or dropped its masks, or replaced it, since the pass was queued
+void series_mark_slices(ftkx_ctx *c, const ftkx_series_pending &P, const u64 *R)
+{
+  for (size_t j = 0; j < P.k; j ++) {
+    if (P.red_index[j] < 0) continue;
+    auto it = c->slices.find(P.slice_ts[j]);
+    if (it == c->slices.end() || it->second.mask_gen != P.gen[j]) continue;
+    Slice &s = it->second;
+    double r, x;
+    memcpy(&r, &R[ftkx::SR_HEAD + P.n + j], 8); memcpy(&x, &R[ftkx::SR_HEAD + P.n + P.k + j], 8);
+    if (std::isinf(x)) { s.mask_factor = 0; s.have_fused = false; continue; }     // the fused max is not the max FINITE |v|: the host-driven path reduces it exactly
+    s.res_below = r; s.fused_factor = P.hint; s.have_fused = true;
+    if (!s.have_res) s.maxabs = x;
+    s.mask_factor = overflow_free(c->nd, s.maxabs, P.hint) ? P.hint : 0;
+    s.mask_big = false; s.u_rows = P.u_rows;
+  }
+}
+
+// its counterpart (ftkx_sweep_series_abort): the masks an abandoned pass was building are nobody's -- built, but never marked
+void series_unmark_slices(ftkx_ctx *c, const ftkx_series_pending &P)
+{
+  for (size_t j = 0; j < P.k && j < P.red_index.size(); j ++) {
+    auto it = c->slices.find(P.slice_ts[j]);
+    if (P.red_index[j] >= 0 && it != c->slices.end() && it->second.mask_gen == P.gen[j]) { it->second.mask_factor = 0; it->second.have_fused = false; }
+  }
+}
+
+// What came back.  Whoever stored the flag -- the fused tail, finishing or declining, or the finish kernel -- copied the whole results block
+// first: the reductions, the status, a slab pass's gathered contributions.  Everything that does not depend on HOW the records get made is
+// read here, so that every way out of series_complete has done it.
+void series_read_back(ftkx_ctx *c, const ftkx_series_pending &P, ftkxh::pass_facts &seen, double *running)
+{
+  const u64 *R = c->sr_buf[P.buf].h_results.as<u64>();
+  c->sr_last_status = ftkxh::pass_read(seen, R);
+  series_mark_slices(c, P, R);
+  c->sr_last_buf = P.buf; c->sr_last_nranks = 0;
+  if (!P.dist) return;
+  // a slab pass: what the other ranks contributed came back with the results -- the running minimum before this slab and the halo
+  // slice's reduction are what the host-driven batch needs, should it have to take the pass over
+  c->sr_last_nranks = P.dist_nranks; c->sr_last_gathered_off = (size_t)ftkx::SR_HEAD + (size_t)P.n + 2 * P.k;
+  const u64 *G = R + c->sr_last_gathered_off;
+  for (int r = 0; r < P.dist_rank; r ++) { double v; memcpy(&v, &G[(size_t)ftkx::kDistContrib * r], 8); *running = std::min(*running, v); }
+  auto it = P.t_halo >= 0 ? c->slices.find(P.t_halo) : c->slices.end();
+  if (it != c->slices.end() && it->second.sparse && P.dist_upper >= 0 && P.dist_upper < P.dist_nranks) {
+    Slice &h = it->second;
+    double r, x;
+    memcpy(&r, &G[(size_t)ftkx::kDistContrib * P.dist_upper + 2], 8); memcpy(&x, &G[(size_t)ftkx::kDistContrib * P.dist_upper + 3], 8);
+    h.have_res = true; h.res = r; h.maxabs = x; h.res_below = r;
+  }
+}
+
+// PASS_QUEUE_REST: the rest of the chain behind a fused tail that declined, waited for; the status is the finish kernel's then (its copy of
+// the block: the same reductions, the final counters)
+int series_requeue_rest(ftkx_ctx *c, ftkx_series_pending &P, ftkxh::pass_facts &seen)
+{
+  ftkx_series_buffers &B = c->sr_buf[P.buf];
+  Mesh m; series_mesh(c, P, m);
+  const unsigned seq2 = ++ B.seq;
+  series_queue_rest(c, P, m, seq2);
+  HIP_TRY(c, hipGetLastError());                              // (no event for the tail stream: a pass queued in its short form is never split)
+  if (const char *why = ftkx::wait_flag(series_flag(B), seq2, tail_stream(c, P))) return fail(c, FTKX_E_DEVICE, "ftkx_sweep_series: %s", why);
+  c->sr_last_status = ftkxh::pass_read(seen, B.h_results.as<u64>());
+  return FTKX_OK;
+}
+
+// SERIES_OVERFLOW: what was too small is grown (series_growth) before the host-driven batch sweeps
+int series_grow(ftkx_ctx *c, const ftkx_series_pending &P)
+{
+  const u64 *cnt = c->sr_buf[P.buf].h_results.as<u64>() + ftkx::SR_COUNTERS;
+  ftkx_tail_set &S0 = c->sr_tail[0];                          // (the other set follows when a pass is planned on it)
+  const BatchSizes cap{c->capacity, S0.list_capacity, S0.refine_capacity, S0.fragile_capacity};
+  const BatchSizes want = series_growth(BatchSizes{cnt[ftkx::CNT_PASS], cnt[ftkx::CNT_LIST_PEAK], cnt[ftkx::CNT_REFINE_PEAK], cnt[ftkx::CNT_FRAGILE]}, cap);
+  if (c->sr_open > 0) { HIP_TRY(c, hipStreamSynchronize(c->stream)); HIP_TRY(c, sync_tails(c)); }      // (a pass queued behind this one still uses the buffers)
+  int rc;
+  if (want.hits > cap.hits && (rc = ensure_hit_buffer(c, want.hits))) return rc;
+  if (want.listed > cap.listed && (rc = ensure_list(c, S0, want.listed))) return rc;
+  if (want.refined > cap.refined && (rc = ensure_refine(c, S0, want.refined))) return rc;
+  return want.fragile > cap.fragile ? ensure_fragile(c, S0, want.fragile) : FTKX_OK;
+}
+
+// The pass's own records: what is reported of it, the records in host memory, and what the host patches in them.  `last_s`, `last_kind`: the
+// completion before this one, as series_complete found it.
+int series_records(ftkx_ctx *c, ftkx_series_pending &P, unsigned long long status, double last_s, int last_kind, double *running_resolution,
+                   unsigned long long *factors, const ftkx_cp_t **out, size_t *n_out)
 {
   const int nd = c->nd, n = P.n;
-  const size_t k = P.k;
-  P.open = false;
-  memset(c->sr_last_order, 0, sizeof(c->sr_last_order));      // (ftkx_debug_series_order: zero unless this pass's records came through the bucket chain)
-  c->sr_sampled_slots = 0; c->sr_sampled_where = 0;           // (ftkx_series_sampled: set where this pass's records were filled)
-  double running = *running_resolution;                       // (what the pass started from: the host-driven batch, if it comes to that, starts there too)
-  // (the split pass's self-check samples the time between two completions by the plain way out of this function: any other way out breaks the chain)
-  const double last_complete_s = c->sr_last_complete_s;
-  const int last_complete_kind = c->sr_last_complete_kind;
-  c->sr_last_complete_s = 0; c->sr_last_complete_kind = 0;
-  if (P.by_host) {
-    int rc = series_by_host_sampled(c, P, &running, factors, out, n_out);
-    if (rc == FTKX_OK) *running_resolution = running;
-    return rc;
-  }
   ftkx_series_buffers &B = c->sr_buf[P.buf];
+  const u64 *R = B.h_results.as<u64>(), *cnt = R + ftkx::SR_COUNTERS;
   unsigned *flag = series_flag(B);
-  Mesh m; series_mesh(c, P, m);
-  if (const char *why = ftkx::wait_flag(flag, P.seq, tail_stream(c, P))) return fail(c, FTKX_E_DEVICE, "ftkx_sweep_series: %s", why);
-  release_retired(c, P);                                     // (the tail that read them is through)
-  // (with no pass left open the tail stream is at its end: waited for, so that whatever the caller does next on the context's stream --
-  // a host-driven batch, a pass that is not split -- finds the counters and lists idle)
-  if (P.split && c->sr_open == 0) HIP_TRY(c, sync_tails(c));
-
-  // ---- what came back ----------------------------------------------------------------------------------------------------------------
-  // (whoever stored the flag -- the fused tail, finishing or declining, or the finish kernel -- copied the whole results block first: the
-  // reductions, the status, a slab pass's gathered contributions.  Everything below that does not depend on HOW the records get made comes
-  // first, so that every way out of this function has done it.)
-  const u64 *R = B.h_results.as<u64>();
-  unsigned long long status = R[ftkx::SR_STATUS];
-  c->sr_last_status = status;
-  // the masks and reductions of this pass stand whichever way the records are made: the slices are marked like ftkx_slices_prepare marks
-  // them -- slice by slice, unless something has rebuilt or dropped its masks, or replaced it, since the pass was queued
-  {
-    for (size_t j = 0; j < k; j ++) {
-      if (P.red_index[j] < 0) continue;
-      auto it = c->slices.find(P.slice_ts[j]);
-      if (it == c->slices.end() || it->second.mask_gen != P.gen[j]) continue;
-      Slice &s = it->second;
-      double r, x;
-      memcpy(&r, &R[ftkx::SR_HEAD + n + j], 8); memcpy(&x, &R[ftkx::SR_HEAD + n + k + j], 8);
-      if (std::isinf(x)) { s.mask_factor = 0; s.have_fused = false; continue; }     // the fused max is not the max FINITE |v|: the host-driven path reduces it exactly
-      s.res_below = r; s.fused_factor = P.hint; s.have_fused = true;
-      if (!s.have_res) s.maxabs = x;
-      s.mask_factor = overflow_free(nd, s.maxabs, P.hint) ? P.hint : 0;
-      s.mask_big = false; s.u_rows = P.u_rows;
-    }
-  }
-  c->sr_last_buf = P.buf; c->sr_last_nranks = 0;
-  if (P.dist) {
-    // a slab pass: what the other ranks contributed came back with the results -- the running minimum before this slab and the halo
-    // slice's reduction are what the host-driven batch needs, should it have to take the pass over
-    c->sr_last_nranks = P.dist_nranks; c->sr_last_gathered_off = (size_t)ftkx::SR_HEAD + (size_t)n + 2 * k;
-    const u64 *G = R + c->sr_last_gathered_off;
-    for (int r = 0; r < P.dist_rank; r ++) { double v; memcpy(&v, &G[(size_t)ftkx::kDistContrib * r], 8); running = std::min(running, v); }
-    auto it = P.t_halo >= 0 ? c->slices.find(P.t_halo) : c->slices.end();
-    if (it != c->slices.end() && it->second.sparse && P.dist_upper >= 0 && P.dist_upper < P.dist_nranks) {
-      Slice &h = it->second;
-      double r, x;
-      memcpy(&r, &G[(size_t)ftkx::kDistContrib * P.dist_upper + 2], 8); memcpy(&x, &G[(size_t)ftkx::kDistContrib * P.dist_upper + 3], 8);
-      h.have_res = true; h.res = r; h.maxabs = x; h.res_below = r;
-    }
-    if (status & ftkx::SERIES_HALO_FULL) {
-      c->sr_short_chain = false;
-      if (P.short_chain && !P.split) ev_end(c);
-      ev_harvest(c, false);
-      *running_resolution = running;
-      return fail(c, FTKX_E_NOSLICE, "slab pass: the halo slice %d is needed as a whole (request -1: too many surviving cells, a mask message that did not fit, or masks the host rebuilds): nothing was swept", P.t_halo);
-    }
-  }
-  if (P.short_chain) {
-    if ((status & ftkx::SERIES_TAIL_PENDING) && (c->sr_open > 0 || c->sr_lists_owner != P.uid)) {
-      // (the rest of this pass cannot be queued: the counters and lists are not this pass's any more -- the pass queued behind it has them
-      // now, or the host-driven batch took them when the pass BEFORE this one fell back (two short-chain passes that both declined,
-      // completed back to back).  The host-driven batch sweeps the steps; it happens when sparse data turns dense.  A slab pass: from the
-      // running minimum the lower ranks' contributions give, over a halo slice that has its patches -- both settled above)
-      c->sr_short_chain = false;
-      if (!P.split) ev_end(c);
-      int rc = series_by_host_sampled(c, P, &running, factors, out, n_out);
-      if (rc == FTKX_OK) *running_resolution = running;
-      return rc;
-    }
-    if (status & ftkx::SERIES_TAIL_PENDING) {
-      const unsigned seq2 = ++ B.seq;
-      series_queue_rest(c, P, m, seq2);
-      if (P.split) HIP_TRY(c, hipEventRecord(B.ev_tail, tail_stream(c, P)));
-      HIP_TRY(c, hipGetLastError());
-      if (const char *why = ftkx::wait_flag(flag, seq2, tail_stream(c, P))) return fail(c, FTKX_E_DEVICE, "ftkx_sweep_series: %s", why);
-      status = R[ftkx::SR_STATUS];                           // (the finish kernel's copy of the block: the same reductions, the final counters)
-      c->sr_last_status = status;
-    } else if (!P.split) ev_end(c);
-  }
-  ev_harvest(c, false);
-  const unsigned long long redo = ftkx::SERIES_AMBIGUOUS | ftkx::SERIES_MASKS_INVALID | ftkx::SERIES_INF | ftkx::SERIES_OVERFLOW;
-  if (status & redo) {
-    c->sr_short_chain = false; c->sr_sparse = false;
-    if (P.one) c->sr_one_off = 16;                           // (more hits than a workgroup parks, or the device was not this kernel's alone: the usual way for a while)
-    int rc;
-    if (status & ftkx::SERIES_OVERFLOW) {                    // grow what was too small (the host-driven batch would find out the same way, one replay later)
-      const u64 *cnt = R + ftkx::SR_COUNTERS;
-      const u64 hits = cnt[ftkx::CNT_PASS], listed = cnt[ftkx::CNT_LIST_PEAK], refined = cnt[ftkx::CNT_REFINE_PEAK], fragile = cnt[ftkx::CNT_FRAGILE];
-      if (c->sr_open > 0) {                                  // (a pass queued behind this one still uses the buffers)
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        HIP_TRY(c, sync_tails(c));
-      }
-      if (hits > c->capacity && (rc = ensure_hit_buffer(c, hits + hits / 8 + 1024))) return rc;
-      ftkx_tail_set &S0 = c->sr_tail[0];                      // (the other set follows when a pass is planned on it)
-      if (listed > S0.list_capacity && (rc = ensure_list(c, S0, listed + listed / 8 + 1024))) return rc;
-      if (refined > S0.refine_capacity && (rc = ensure_refine(c, S0, refined + refined / 8 + 1024))) return rc;
-      if (fragile > S0.fragile_capacity && (rc = ensure_fragile(c, S0, fragile + fragile / 8 + 1024))) return rc;
-    }
-    rc = series_by_host_sampled(c, P, &running, factors, out, n_out);
-    if (rc == FTKX_OK) *running_resolution = running;
-    return rc;
-  }
-  c->sr_last_path = (status & ftkx::SERIES_ONE) ? 4 : P.split ? 5 : (status & ftkx::SERIES_EARLY) ? 2 : 1;
-  if (!(status & (ftkx::SERIES_ONE | ftkx::SERIES_EARLY))) {
-    const unsigned long long order[4] = {(unsigned long long)P.nbins, (unsigned long long)P.shift, R[ftkx::SR_COUNTERS + ftkx::CNT_BUCKET_MAX], B.rank_max};
+  const ftkxh::series_path path = ftkxh::series_path_of(status, P.split);
+  c->sr_last_path = path.path;
+  if (path.order_filled) {
+    const unsigned long long order[4] = {(unsigned long long)P.nbins, (unsigned long long)P.shift, cnt[ftkx::CNT_BUCKET_MAX], B.rank_max};
     memcpy(c->sr_last_order, order, sizeof(order));
   }
-  {
-    // the split pass's self-check: the time since the last completion is a sample of this pass's form if the pipeline was full all the while
-    // (another pass is open now and one was when the last one completed) and the last completion was of the same form
-    const double now = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-    ftkxh::split_sample(c->sr_cal, P.cal_kind, now, last_complete_s, last_complete_kind, c->sr_open > 0);
-    c->sr_last_complete_kind = P.cal_kind;
-    c->sr_last_complete_s = c->sr_open > 0 ? now : 0.0;
-  }
-  if (!P.one && !P.split) c->sr_short_chain = (status & ftkx::SERIES_EARLY) != 0;      // (a split pass says nothing about the fused tail)
-  if (!P.one) {
-    const u64 *cn = R + ftkx::SR_COUNTERS;
-    c->sr_sparse = (status & ftkx::SERIES_EARLY) != 0 || (R[ftkx::SR_NHITS] <= 1024 && (P.two_level ? cn[ftkx::CNT_REFINE_PEAK] : cn[ftkx::CNT_LIST_PEAK]) <= 4 * 2048ull);
-  }
-  const u64 *cnt = R + ftkx::SR_COUNTERS;
-  if (!(status & ftkx::SERIES_EARLY) && (P.two_level ? cnt[ftkx::CNT_REFINE_PEAK] : cnt[ftkx::CNT_LIST_PEAK]) > 4 * 2048ull) c->sr_skip_small = 16;
-  // (few coarse cells, many records in them: the fused tail declined late, tens of microseconds lost.  Twice in a row: the series is like that)
-  c->sr_late_streak = (status & ftkx::SERIES_LATE_DECLINE) ? c->sr_late_streak + 1 : 0;
-  if (c->sr_late_streak >= 2) c->sr_skip_small = 16;
+  // the split pass's self-check: the time since the last completion is a sample of this pass's form if the pipeline was full all the while
+  // (another pass is open now and one was when the last one completed) and the last completion was of the same form
+  const double now = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+  ftkxh::split_sample(c->sr_cal, P.cal_kind, now, last_s, last_kind, c->sr_open > 0);
+  c->sr_last_complete_kind = P.cal_kind;
+  c->sr_last_complete_s = c->sr_open > 0 ? now : 0.0;
   const size_t nrec = (size_t)R[ftkx::SR_NHITS];
   ftkx_cp_t *H = B.out.as<ftkx_cp_t>();
   if (P.to_device) {                                         // (the copy kernel; the mask kernel of the pass queued behind this one is running meanwhile)
     if (P.copy_pending) series_queue_copy(c, P, nullptr, 0);    // (no pass was queued behind this one)
     if (const char *why = ftkx::wait_flag(flag + 2, P.seq, c->sr_copy_stream)) {
       // the copy stream drained without the flag: the copy kernel gave up waiting for the begin kernel of the pass queued behind this one (a
-      // caller that took seconds to submit it).  This pass itself is through -- its own flag was waited for above --, so the copy needs no
-      // wait now: once more, unconditionally
+      // caller that took seconds to submit it).  This pass itself is through -- its own flag was waited for --, so the copy needs no wait
+      // now: once more, unconditionally
       if (hipStreamQuery(c->sr_copy_stream) != hipSuccess) return fail(c, FTKX_E_DEVICE, "ftkx_sweep_series: %s", why);
       series_queue_copy(c, P, nullptr, 0);
       if (const char *why2 = ftkx::wait_flag(flag + 2, P.seq, c->sr_copy_stream)) return fail(c, FTKX_E_DEVICE, "ftkx_sweep_series: %s", why2);
@@ -999,10 +947,8 @@ int series_complete(ftkx_ctx *c, ftkx_series_pending &P, double *running_resolut
     B.copy_out = false;                                      // (the copy is through: the pass that takes these buffers next need not wait for its event)
   }
   memset(&c->stats, 0, sizeof(c->stats));
-  {
-    const u64 n_ord = nd == 2 ? 2 : 6, n_int = nd == 2 ? 10 : 54;
-    for (int i = 0; i < n; i ++) { c->stats.cells += P.cells; c->stats.work_items += P.cells * (((P.scopes[i] & 1) ? n_ord : 0) + ((P.scopes[i] & 2) ? n_int : 0)); }
-  }
+  const u64 n_ord = nd == 2 ? 2 : 6, n_int = nd == 2 ? 10 : 54;
+  for (int i = 0; i < n; i ++) { c->stats.cells += P.cells; c->stats.work_items += P.cells * (((P.scopes[i] & 1) ? n_ord : 0) + ((P.scopes[i] & 2) ? n_int : 0)); }
   c->stats.cull_enabled = 1;
   c->stats.hits = nrec;
   c->stats.cells_survived = cnt[ftkx::CNT_CELLS_SURVIVED];
@@ -1027,6 +973,55 @@ int series_complete(ftkx_ctx *c, ftkx_series_pending &P, double *running_resolut
   if (out) *out = H;
   if (n_out) *n_out = nrec;
   return FTKX_OK;
+}
+
+// Second half: the host waits (once) for the pass, reads back what stands whichever way the records get made, and leaves the way the
+// verdict names (series_verdict.hpp): with the pass's own records, through the host-driven batch, or -- a slab pass -- failing for its halo.
+int series_complete(ftkx_ctx *c, ftkx_series_pending &P, double *running_resolution, unsigned long long *factors, const ftkx_cp_t **out, size_t *n_out)
+{
+  int rc;
+  // ---- prelude: what the last pass reported is reset
+  P.open = false;
+  memset(c->sr_last_order, 0, sizeof(c->sr_last_order));      // (ftkx_debug_series_order: zero unless this pass's records came through the bucket chain)
+  c->sr_sampled_slots = 0; c->sr_sampled_where = 0;           // (ftkx_series_sampled: set where this pass's records were filled)
+  double running = *running_resolution;                       // (what the pass started from: the host-driven batch, if it comes to that, starts there too)
+  // (the split pass's self-check samples the time between two completions by the plain way out of this function: any other way out breaks the chain)
+  const double last_s = c->sr_last_complete_s;
+  const int last_kind = c->sr_last_complete_kind;
+  c->sr_last_complete_s = 0; c->sr_last_complete_kind = 0;
+  ftkxh::pass_facts seen{0, P.one, P.split, P.two_level, 0, 0, 0};
+  if (!P.by_host) {
+    // ---- the one wait, and what came back
+    if (const char *why = ftkx::wait_flag(series_flag(c->sr_buf[P.buf]), P.seq, tail_stream(c, P))) return fail(c, FTKX_E_DEVICE, "ftkx_sweep_series: %s", why);
+    release_retired(c, P);                                   // (the tail that read them is through)
+    // (with no pass left open the tail stream is at its end: waited for, so that whatever the caller does next on the context's stream --
+    // a host-driven batch, a pass that is not split -- finds the counters and lists idle)
+    if (P.split && c->sr_open == 0) HIP_TRY(c, sync_tails(c));
+    series_read_back(c, P, seen, &running);
+  }
+  // ---- the verdict, with at most one re-queue of the rest of the chain
+  const ftkxh::pass_form form{P.by_host, P.dist, P.short_chain};
+  const bool open_behind = c->sr_open > 0, lists_own = c->sr_lists_owner == P.uid;
+  ftkxh::pass_verdict v = ftkxh::series_verdict(seen.status, form, open_behind, lists_own);
+  const bool rest_queued = v.end == PASS_QUEUE_REST;
+  if (rest_queued) {
+    if ((rc = series_requeue_rest(c, P, seen))) return rc;
+    v = ftkxh::series_verdict(seen.status & ~(unsigned long long)ftkx::SERIES_TAIL_PENDING, form, open_behind, lists_own);
+  }
+  // (a pass queued in its short form left the event pair of its tail open: series_queue_rest closes it, behind the record kernel)
+  if (P.short_chain && !P.split && !rest_queued) ev_end(c);
+  if (!P.by_host) ev_harvest(c, false);
+  ftkxh::tail_learn(c->sr_policy, v.end, seen);
+  if (v.end == PASS_RECORDS) return series_records(c, P, seen.status, last_s, last_kind, running_resolution, factors, out, n_out);
+  // ---- the one way out without the pass's own records.  The host-driven batch sweeps the steps from `running`: what the pass started from; a
+  // slab pass: what the lower ranks' contributions give, over a halo slice that has its patches (both settled by series_read_back)
+  if (v.end == PASS_HALO_FULL) {
+    *running_resolution = running;
+    return fail(c, FTKX_E_NOSLICE, "slab pass: the halo slice %d is needed as a whole (request -1: too many surviving cells, a mask message that did not fit, or masks the host rebuilds): nothing was swept", P.t_halo);
+  }
+  if (v.grow && (rc = series_grow(c, P))) return rc;
+  if ((rc = series_by_host_sampled(c, P, &running, factors, out, n_out)) == FTKX_OK) *running_resolution = running;
+  return rc;
 }
 
 }  // namespace
@@ -1264,17 +1259,14 @@ int ftkx_sweep_series_abort(ftkx_ctx *c)
   for (ftkx_series_pending &P : c->sr_pend) {
     if (P.dist && P.dist_stage > 0 && P.dist_stage < 4) { P.open = true; }      // (a slab pass that was never finished: its masks are nobody's either)
     if (!P.open) continue;
-    // the masks this pass was building are nobody's: built, but never marked
-    for (size_t j = 0; j < P.k && j < P.red_index.size(); j ++) {
-      auto it = c->slices.find(P.slice_ts[j]);
-      if (P.red_index[j] >= 0 && it != c->slices.end() && it->second.mask_gen == P.gen[j]) { it->second.mask_factor = 0; it->second.have_fused = false; }
-    }
+    series_unmark_slices(c, P);
     release_retired(c, P);
     P.open = false; P.copy_pending = false; P.dist_stage = 0;
   }
   for (ftkx_series_buffers &B : c->sr_buf) B.copy_out = false;
   c->sr_open = 0; c->sr_head = 0;
-  c->sr_short_chain = false; c->sr_sparse = false; c->sr_lists_owner = 0; c->sr_last_running = 0;
+  ftkxh::tail_abort(c->sr_policy);
+  c->sr_lists_owner = 0; c->sr_last_running = 0;
   c->ahead.clear(); c->announced.clear();
   if (e != hipSuccess) return fail(c, FTKX_E_DEVICE, "ftkx_sweep_series_abort: %s", hipGetErrorString(e));
   return FTKX_OK;
