@@ -10,6 +10,7 @@ import numpy as np
 from . import _lib
 from ._lib import (CP_DTYPE, FORMAT_BINARY, FORMAT_JSON, FORMAT_TEXT, SCOPE_BOTH, SCOPE_INTERVAL, SCOPE_ORDINAL, SOURCE_DERIVED, SOURCE_GIVEN, SOURCE_NONE,  # noqa: F401
                    TAG_EXACT64, TAG_REFERENCE, TAG_WORK_INDEX, FtkxError, Options, Stats)
+from ._lib import DTYPE_BF16, DTYPE_F16, DTYPE_F32, DTYPE_F64, DTYPE_I8, DTYPE_I16, DTYPE_I32, DTYPE_U8, DTYPE_U16, DTYPE_U32  # noqa: F401
 
 __all__ = ["trace_curves", "pass2", "trace_and_post_process", "post_process", "post_process_curves", "TrajectorySet", "write_critical_points", "read_critical_points",
            "write_traced_critical_points", "read_traced_critical_points", "Context", "CriticalPointTracker2DRegular", "CriticalPointTracker3DRegular", "extract_cp2dt", "extract_cp3dt",
@@ -33,6 +34,54 @@ def _ptr(a):
         return a.ctypes.data, a, 0, True
     a = np.ascontiguousarray(a, dtype=np.float64)
     return a.ctypes.data, a, 0, False
+
+
+_NUMPY_DTYPES = {np.dtype(np.float64): DTYPE_F64, np.dtype(np.float32): DTYPE_F32, np.dtype(np.float16): DTYPE_F16, np.dtype(np.uint8): DTYPE_U8, np.dtype(np.int8): DTYPE_I8,
+                 np.dtype(np.uint16): DTYPE_U16, np.dtype(np.int16): DTYPE_I16, np.dtype(np.uint32): DTYPE_U32, np.dtype(np.int32): DTYPE_I32}
+_TORCH_DTYPES = {"torch.float64": DTYPE_F64, "torch.float32": DTYPE_F32, "torch.float16": DTYPE_F16, "torch.bfloat16": DTYPE_BF16, "torch.uint8": DTYPE_U8, "torch.int8": DTYPE_I8,
+                 "torch.uint16": DTYPE_U16, "torch.int16": DTYPE_I16, "torch.uint32": DTYPE_U32, "torch.int32": DTYPE_I32}
+
+
+def _ptr_typed(a):
+    """keep_dtype=True: host numpy array / torch tensor / raw int -> (address, the array itself, on_device, DTYPE_*).  The array goes to the
+    library's typed entries with the element type it has -- float16, bfloat16 (torch), 8- / 16- / 32-bit integers, float32, float64 -- and
+    is widened on the device; nothing is converted on the host.  Any other element type (64-bit integers, bool, complex, a byte order that
+    is not the machine's) raises TypeError before the library is called.  A raw int is taken for float64"""
+    if a is None:
+        return None, None, 0, None
+    if isinstance(a, int):
+        return a, None, 1, DTYPE_F64
+    if hasattr(a, "data_ptr"):
+        dt = _TORCH_DTYPES.get(str(a.dtype))
+        if dt is None:
+            raise TypeError(f"keep_dtype: {a.dtype} is not taken (float64, float32, float16, bfloat16, and integers of 8, 16 or 32 bits)")
+        a = a.contiguous()
+        return a.data_ptr(), a, 1 if a.is_cuda else 0, dt
+    if not isinstance(a, np.ndarray):
+        raise TypeError("keep_dtype: a numpy array or a torch tensor")
+    dt = _NUMPY_DTYPES.get(a.dtype) if a.dtype.isnative else None
+    if dt is None:
+        raise TypeError(f"keep_dtype: {a.dtype} is not taken (float64, float32, float16, and integers of 8, 16 or 32 bits)")
+    a = np.ascontiguousarray(a)
+    return a.ctypes.data, a, 0, dt
+
+
+def _ptr_any(a, keep_dtype):
+    """_ptr, or _ptr_typed where keep_dtype is set -> (address, keepalive, on_device, DTYPE_*)"""
+    if keep_dtype:
+        return _ptr_typed(a)
+    p, k, d, f32 = _ptr(a)
+    return p, k, d, None if p is None else DTYPE_F32 if f32 else DTYPE_F64
+
+
+def _one_dtype(*dtypes):
+    """the arrays of one push (those that are given) share one element type -> which"""
+    kinds = {d for d in dtypes if d is not None}
+    if len(kinds) > 1:
+        if kinds <= {DTYPE_F32, DTYPE_F64}:
+            raise TypeError("the arrays of one push must all be float32 or all float64")
+        raise TypeError("the arrays of one push must share one element type")
+    return kinds.pop() if kinds else DTYPE_F64
 
 
 def _same_type(*f32):
@@ -212,16 +261,20 @@ class Context:
         """ftkx_set_temporal_smoothing: a series of raw snapshots for temporal_push starts, its first emission being timestep t0; ksize 0: off"""
         self._ck(self._L.ftkx_set_temporal_smoothing(self._h, float(sigma), int(ksize), int(t0)))
 
-    def temporal_push(self, A, is_vector=False, on_device=None):
+    def temporal_push(self, A, is_vector=False, on_device=None, keep_dtype=False):
         """ftkx_temporal_push: one raw snapshot (host array or device tensor; always copied) -> the timestep of the smoothed slice that became
-        resident, or -1.  on_device as in push_scalar_slice"""
-        p, k, d, f32 = _ptr(A)
+        resident, or -1.  on_device and keep_dtype as in push_scalar_slice"""
+        p, k, d, dt = _ptr_any(A, keep_dtype)
+        f32 = dt == DTYPE_F32
         if on_device is not None:
             if int(on_device) not in (0, 1, 2) or (int(on_device) != 0) != bool(d):
                 raise ValueError("on_device: 0 for a host array, 1 or 2 for a device tensor")
             d = int(on_device)
         t = C.c_int(-1)
-        self._ck((self._L.ftkx_temporal_push_f32 if f32 else self._L.ftkx_temporal_push)(self._h, p, int(bool(is_vector)), d, C.byref(t)))
+        if dt is not None and dt > DTYPE_F32:
+            self._ck(self._L.ftkx_temporal_push_typed(self._h, p, dt, int(bool(is_vector)), d, C.byref(t)))
+        else:
+            self._ck((self._L.ftkx_temporal_push_f32 if f32 else self._L.ftkx_temporal_push)(self._h, p, int(bool(is_vector)), d, C.byref(t)))
         if t.value >= 0:
             self._keep[t.value] = None
         return t.value
@@ -252,15 +305,20 @@ class Context:
         self._ck(self._L.ftkx_debug_temporal_relaunch(self._h, ptrs, w.size, w.ctypes.data, int(count), out_ptr, int(reps), ms))
         return list(ms)
 
-    def push_slice(self, t, V, J=None, S=None):
-        pv, kv, dv, fv = _ptr(V); pj, kj, dj, fj = _ptr(J); ps, ks, ds, fs = _ptr(S)
+    def push_slice(self, t, V, J=None, S=None, keep_dtype=False):
+        """keep_dtype as in push_scalar_slice; V, J and S share one element type"""
+        pv, kv, dv, fv = _ptr_any(V, keep_dtype); pj, kj, dj, fj = _ptr_any(J, keep_dtype); ps, ks, ds, fs = _ptr_any(S, keep_dtype)
         devs = {d for p, d in ((pv, dv), (pj, dj), (ps, ds)) if p is not None}
         if len(devs) != 1:
             raise ValueError("V, J, S must all be host arrays or all device tensors")
         on_dev = devs.pop()
-        f32 = _same_type(*[f for p, f in ((pv, fv), (pj, fj), (ps, fs)) if p is not None])
-        self._ck((self._L.ftkx_push_slice_f32 if f32 else self._L.ftkx_push_slice)(self._h, t, pv, pj, ps, on_dev))
-        owned = f32 or self._perturbing or self._clamping
+        dt = _one_dtype(fv, fj, fs)
+        f32 = dt == DTYPE_F32
+        if dt > DTYPE_F32:
+            self._ck(self._L.ftkx_push_slice_typed(self._h, t, pv, pj, ps, dt, on_dev))
+        else:
+            self._ck((self._L.ftkx_push_slice_f32 if f32 else self._L.ftkx_push_slice)(self._h, t, pv, pj, ps, on_dev))
+        owned = dt != DTYPE_F64 or self._perturbing or self._clamping
         self._keep[t] = (kv, kj, ks) if on_dev and not owned else None       # (float32, perturbation, clamp: read before the call returned, the context owns FP64 copies)
 
     def push_slice_planar(self, t, planes, J=None, S=None, on_device=None):
@@ -294,15 +352,22 @@ class Context:
             self._keep[t.value] = None
         return t.value
 
-    def push_scalar_slice(self, t, S, on_device=None):
-        """on_device: None = 0 for a host array, 1 (borrowed) for a device tensor; 2: a device tensor, copied"""
-        ps, ks, ds, f32 = _ptr(S)
+    def push_scalar_slice(self, t, S, on_device=None, keep_dtype=False):
+        """on_device: None = 0 for a host array, 1 (borrowed) for a device tensor; 2: a device tensor, copied.
+        keep_dtype=True: a float16 / bfloat16 / 8-, 16- or 32-bit integer array or tensor goes to the device with the element type it has
+        (ftkx_push_scalar_slice_typed) and is widened there, exactly; it is read before the call returns and never borrowed.  float32 and
+        float64 go where they go without it; any other element type raises TypeError"""
+        ps, ks, ds, dt = _ptr_any(S, keep_dtype)
+        f32 = dt == DTYPE_F32
         if on_device is not None:
             if int(on_device) not in (0, 1, 2) or (int(on_device) != 0) != bool(ds):
                 raise ValueError("on_device: 0 for a host array, 1 or 2 for a device tensor")
             ds = int(on_device)
-        self._ck((self._L.ftkx_push_scalar_slice_f32 if f32 else self._L.ftkx_push_scalar_slice)(self._h, t, ps, ds))
-        owned = self._smoothing or self._perturbing or self._clamping or f32
+        if dt is not None and dt > DTYPE_F32:
+            self._ck(self._L.ftkx_push_scalar_slice_typed(self._h, t, ps, dt, ds))
+        else:
+            self._ck((self._L.ftkx_push_scalar_slice_f32 if f32 else self._L.ftkx_push_scalar_slice)(self._h, t, ps, ds))
+        owned = self._smoothing or self._perturbing or self._clamping or (dt is not None and dt != DTYPE_F64)
         self._keep[t] = ks if ds == 1 and not owned else None     # (2, smoothing, perturbation, clamp, float32: the context owns a copy)
 
     def drop_slice(self, t):
@@ -660,6 +725,22 @@ class Context:
     def widen_f32(self, src_ptr, count, dst_ptr):
         """ftkx_widen_f32: dst[e] = double(src[e]) for `count` floats"""
         self._ck(self._L.ftkx_widen_f32(self._h, src_ptr, int(count), dst_ptr))
+
+    def widen_typed(self, src_ptr, dtype, count, dst_ptr):
+        """ftkx_widen_typed on device pointers: dst[e] = double(src[e]) for `count` elements of type `dtype` (DTYPE_F32 .. DTYPE_I32)"""
+        self._ck(self._L.ftkx_widen_typed(self._h, src_ptr, int(dtype), int(count), dst_ptr))
+
+    def debug_narrow_relaunch(self, src_ptr, dtype, count, dst_ptr, reps):
+        """profiling aid: the narrow kernel `reps` times back to back -> device ms per launch (HIP events)"""
+        ms = (C.c_double * int(reps))()
+        self._ck(self._L.ftkx_debug_narrow_relaunch(self._h, src_ptr, int(dtype), int(count), dst_ptr, int(reps), ms))
+        return list(ms)
+
+    def narrow_counts(self):
+        """launches of the narrow kernel by this context's pushes, a tuple indexed by DTYPE_* ([DTYPE_F64] and [DTYPE_F32] stay 0)"""
+        n = (C.c_ulonglong * 10)()
+        self._ck(self._L.ftkx_debug_narrow_counts(self._h, n))
+        return tuple(int(v) for v in n)
 
     def debug_widen_relaunch(self, src_ptr, count, dst_ptr, reps):
         """profiling aid: the widen kernel `reps` times back to back -> device ms per launch (HIP events)"""
@@ -1174,13 +1255,42 @@ class _TrackerRegular:
         self._keep.append(None if f32 else tuple(g[1] for g in got))
         self._ck(self._L.ftkx_tracker_push_snapshot_extra(self._h, kind, got[0][0], got[1][0], got[2][0], extra, len(components), dev, int(f32)))
 
-    def push_scalar_field_snapshot(self, s, components=None):
+    def _narrow(self, keep_dtype, components, *arrays):
+        """keep_dtype=True: the one element type of the arrays of a push where it is narrower than float32 (they then go to the typed
+        entries as they are: (addresses, on_device, DTYPE_*, keepalives)), else None: the push goes the way it goes without keep_dtype.
+        The keepalives are the arrays the addresses point into -- the contiguous copies of views that were not contiguous among them --
+        and the caller holds the tuple until the library has read them (it reads before it returns).  Raises TypeError for an element
+        type the library does not take; narrow snapshots come without extra components"""
+        if not keep_dtype:
+            return None
+        got = [_ptr_typed(a) for a in arrays] + [_ptr_typed(a) for a in (components or [])]
+        dt = _one_dtype(*[g[3] for g in got])
+        if dt <= DTYPE_F32:
+            return None
+        if components is not None:
+            raise TypeError("keep_dtype: extra scalar components are float32 or float64")
+        if len({g[2] for g in got if g[0] is not None}) > 1:
+            raise ValueError("the arrays of one push must all be host arrays or all device tensors")
+        self._keep.append(None)                                            # (read before the call returns, never borrowed)
+        return [g[0] for g in got], next(g[2] for g in got if g[0] is not None), dt, [g[1] for g in got]
+
+    def push_scalar_field_snapshot(self, s, components=None, keep_dtype=False):
+        """keep_dtype=True: a float16 / bfloat16 / 8-, 16- or 32-bit integer snapshot goes to the device with the element type it has and is
+        widened there (Context.push_scalar_slice); any element type the library does not take raises TypeError"""
+        narrow = self._narrow(keep_dtype, components, s)
+        if narrow:
+            rc = self._L.ftkx_tracker_push_scalar_field_snapshot_typed(self._h, narrow[0][0], narrow[2], narrow[1])      # (`narrow` holds the arrays until here)
+            return self._ck(rc)
         if components is not None:
             return self._push_extra(0, s, None, None, list(components))
         p, k, d, f32 = _ptr(s); self._keep.append(None if f32 else k)      # (float32: read before the call returns, never borrowed)
         self._ck((self._L.ftkx_tracker_push_scalar_field_snapshot_f32 if f32 else self._L.ftkx_tracker_push_scalar_field_snapshot)(self._h, p, d))
 
-    def push_vector_field_snapshot(self, v, components=None):
+    def push_vector_field_snapshot(self, v, components=None, keep_dtype=False):
+        narrow = self._narrow(keep_dtype, components, v)
+        if narrow:
+            rc = self._L.ftkx_tracker_push_vector_field_snapshot_typed(self._h, narrow[0][0], narrow[2], narrow[1])
+            return self._ck(rc)
         if components is not None:
             return self._push_extra(1, None, v, None, list(components))
         p, k, d, f32 = _ptr(v); self._keep.append(None if f32 else k)
@@ -1192,7 +1302,11 @@ class _TrackerRegular:
         ptrs, nc, keep, dev, f32 = _planes(planes); self._keep.append(None)
         self._ck((self._L.ftkx_tracker_push_vector_field_components_f32 if f32 else self._L.ftkx_tracker_push_vector_field_components)(self._h, ptrs, nc, dev))
 
-    def push_field_data_snapshot(self, s, v, j, components=None):
+    def push_field_data_snapshot(self, s, v, j, components=None, keep_dtype=False):
+        narrow = self._narrow(keep_dtype, components, s, v, j)
+        if narrow:
+            rc = self._L.ftkx_tracker_push_field_data_snapshot_typed(self._h, narrow[0][0], narrow[0][1], narrow[0][2], narrow[2], narrow[1])
+            return self._ck(rc)
         if components is not None:
             return self._push_extra(2, s, v, j, list(components))
         ps, ks, ds, fs = _ptr(s); pv, kv, dv, fv = _ptr(v); pj, kj, dj, fj = _ptr(j)

@@ -17,6 +17,8 @@ SCOPE_ORDINAL, SCOPE_INTERVAL, SCOPE_BOTH = 1, 2, 3
 TAG_WORK_INDEX, TAG_REFERENCE, TAG_EXACT64 = 0, 1, 2
 FORMAT_BINARY, FORMAT_JSON, FORMAT_TEXT = 0, 1, 2
 SOURCE_NONE, SOURCE_GIVEN, SOURCE_DERIVED = 0, 1, 2
+# element types of the typed entries (FTKX_DTYPE_* of include/ftkx.h)
+DTYPE_F64, DTYPE_F32, DTYPE_F16, DTYPE_BF16, DTYPE_U8, DTYPE_I8, DTYPE_U16, DTYPE_I16, DTYPE_U32, DTYPE_I32 = range(10)
 
 
 class Options(C.Structure):
@@ -88,6 +90,8 @@ EXPORTS = [
     "ftkx_sweep", "ftkx_sweep_series", "ftkx_sweep_series_submit", "ftkx_sweep_series_complete", "ftkx_sweep_series_abort", "ftkx_series_dist_cells", "ftkx_series_dist_begin", "ftkx_series_dist_cull", "ftkx_series_dist_serve", "ftkx_series_dist_finish", "ftkx_series_dist_status", "ftkx_series_last_path", "ftkx_series_split_decision", "ftkx_sweep_enqueue", "ftkx_sweep_enqueue_many", "ftkx_sweep_collect", "ftkx_sweep_cancel", "ftkx_get_stats", "ftkx_invalidate_masks", "ftkx_debug_stream_read", "ftkx_debug_tile_repeat", "ftkx_set_profiling", "ftkx_get_kernel_times", "ftkx_extract_cp2dt", "ftkx_extract_cp3dt", "ftkx_free",
     "ftkx_trace_curves", "ftkx_trace_curves_ctx", "ftkx_trace_curves_tags_ctx", "ftkx_trace_curves_device", "ftkx_trace_last_path", "ftkx_free_curves", "ftkx_post_process_curves", "ftkx_post_process_curves_device", "ftkx_pass2_device", "ftkx_post_process_last_path", "ftkx_free_trajectories", "ftkx_format_from_path", "ftkx_write_critical_points", "ftkx_read_critical_points", "ftkx_write_traced_critical_points", "ftkx_read_traced_critical_points", "ftkx_gradient2D", "ftkx_jacobian2D", "ftkx_gradient3D", "ftkx_jacobian3D", "ftkx_gaussian_kernel", "ftkx_conv2D", "ftkx_conv3D", "ftkx_set_spatial_smoothing", "ftkx_tracker_set_spatial_smoothing", "ftkx_debug_conv_relaunch", "ftkx_gaussian_kernel1d", "ftkx_temporal_combine", "ftkx_set_temporal_smoothing", "ftkx_temporal_push", "ftkx_temporal_flush", "ftkx_debug_temporal_relaunch", "ftkx_tracker_set_temporal_smoothing", "ftkx_tracker_snapshots_from_last_push", "ftkx_tracker_flush_temporal_smoothing", "ftkx_tracker_reset", "ftkx_version", "ftkx_device_count", "ftkx_pointer_device", "ftkx_context_device", "ftkx_last_mask_kernel", "ftkx_debug_mask_kernel_launches", "ftkx_debug_upload_counts", "ftkx_debug_mask_relaunch",
     "ftkx_push_scalar_slice_f32", "ftkx_push_slice_f32", "ftkx_temporal_push_f32", "ftkx_widen_f32", "ftkx_conv2D_f32", "ftkx_conv3D_f32", "ftkx_debug_widen_relaunch", "ftkx_debug_f32_counts", "ftkx_debug_array_counts",
+    "ftkx_dtype_size", "ftkx_push_scalar_slice_typed", "ftkx_push_slice_typed", "ftkx_temporal_push_typed", "ftkx_widen_typed", "ftkx_debug_narrow_relaunch", "ftkx_debug_narrow_counts",
+    "ftkx_tracker_push_scalar_field_snapshot_typed", "ftkx_tracker_push_vector_field_snapshot_typed", "ftkx_tracker_push_field_data_snapshot_typed",
     "ftkx_push_slice_planar", "ftkx_push_slice_planar_f32", "ftkx_temporal_push_planar", "ftkx_temporal_push_planar_f32", "ftkx_concat", "ftkx_concat_f32", "ftkx_debug_concat_relaunch", "ftkx_debug_planar_counts",
     "ftkx_tracker_push_vector_field_components", "ftkx_tracker_push_vector_field_components_f32",
     "ftkx_debug_series_order", "ftkx_debug_sort_records",
@@ -197,6 +201,16 @@ def load():
     L.ftkx_conv3D_f32.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, dbl, C.c_int, dbl]
     L.ftkx_debug_widen_relaunch.argtypes = [vp, vp, C.c_size_t, dbl, C.c_int, C.POINTER(C.c_double)]
     L.ftkx_debug_f32_counts.argtypes = [vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
+    L.ftkx_dtype_size.argtypes = [C.c_int]; L.ftkx_dtype_size.restype = C.c_size_t
+    L.ftkx_push_scalar_slice_typed.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int]
+    L.ftkx_push_slice_typed.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, C.c_int]
+    L.ftkx_temporal_push_typed.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
+    L.ftkx_widen_typed.argtypes = [vp, vp, C.c_int, C.c_size_t, dbl]
+    L.ftkx_debug_narrow_relaunch.argtypes = [vp, vp, C.c_int, C.c_size_t, dbl, C.c_int, C.POINTER(C.c_double)]
+    L.ftkx_debug_narrow_counts.argtypes = [vp, C.POINTER(C.c_ulonglong)]
+    L.ftkx_tracker_push_scalar_field_snapshot_typed.argtypes = [vp, vp, C.c_int, C.c_int]
+    L.ftkx_tracker_push_vector_field_snapshot_typed.argtypes = [vp, vp, C.c_int, C.c_int]
+    L.ftkx_tracker_push_field_data_snapshot_typed.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int]
     L.ftkx_debug_array_counts.argtypes = [vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
     for f in (L.ftkx_push_slice_planar, L.ftkx_push_slice_planar_f32):
         f.argtypes = [vp, C.c_int, C.POINTER(vp), C.c_int, vp, vp, C.c_int]

@@ -59,6 +59,7 @@ void launch_jacobian3d(const double *V, int DW, int DH, int DD, double *J, hipSt
 void launch_resolution(const double *p, size_t n, u64 *out2, hipStream_t st);
 template <class SRC> void launch_conv(int nd, const SRC *S, int DW, int DH, int DD, const double *d_weights, int ksize, double *out, hipStream_t st);   // conv_kernels.hip: SRC double or float
 void launch_widen(const float *src, size_t count, double *dst, hipStream_t st);   // widen_kernels.hip
+void launch_narrow(int dtype, const void *src, size_t count, double *dst, hipStream_t st);   // narrow_kernels.hip: dtype FTKX_DTYPE_F16 .. _I32
 template <class T> void launch_adjust(const T *src, size_t count, bool perturb, bool clamp, const AdjustArgs &a, double *dst, hipStream_t st);   // adjust_kernels.hip: T double or float; src == dst allowed
 template <class T> bool launch_concat(const T *const *planes, int nc, size_t count, double *dst, hipStream_t st);   // concat_kernels.hip: T double or float; whether the 16-byte body ran
 void launch_temporal(const double *const *arrays, int ksize, const double *weights, size_t count, double *out, hipStream_t st);   // temporal_kernels.hip
@@ -330,6 +331,9 @@ struct ftkx_ctx {
   ftkx_block f32_stage;
   hipStream_t f32_stage_reader = nullptr;      // the stream of the kernel that read it last
   unsigned long long f32_widened = 0, f32_direct = 0;   // ftkx_debug_f32_counts: float32 arrays through the widen kernel / straight through the convolution
+  // narrow sources (ftkx_push_*_typed, ftkx_temporal_push_typed: half, bfloat16, 8- / 16- / 32-bit integers): staged in f32_stage as they
+  // came, count * the element's size bytes, under the same ordering; the narrow kernel's launches by FTKX_DTYPE_* (ftkx_debug_narrow_counts)
+  unsigned long long narrow_launches[10] = {0};
   // perturbation and clamp (ftkx_set_perturbation, ftkx_set_clamp; adjust_steps.hpp): both off by default.  While either is on, every
   // snapshot pushed is adjusted by ONE kernel on the context's stream behind the widening and the spatial smoothing and in front of the
   // temporal ring (the stream's order), with its timestep as the noise's snapshot number.  The counters: ftkx_debug_adjust_counts.

@@ -4,11 +4,15 @@
 #include <type_traits>
 #include "ctx.hpp"
 #include "ingest_steps.hpp"
+#include "narrow_steps.hpp"
 #include "relaunch.hpp"
 
 using namespace ftkxh;
 
 constexpr size_t kSmoothWeights = 729;      // ftkx_ctx::d_conv_w: where the smoothing's weights start
+static_assert(ftkx::NARROW_F64 == FTKX_DTYPE_F64 && ftkx::NARROW_F32 == FTKX_DTYPE_F32 && ftkx::NARROW_F16 == FTKX_DTYPE_F16 && ftkx::NARROW_BF16 == FTKX_DTYPE_BF16 &&
+              ftkx::NARROW_U8 == FTKX_DTYPE_U8 && ftkx::NARROW_I8 == FTKX_DTYPE_I8 && ftkx::NARROW_U16 == FTKX_DTYPE_U16 && ftkx::NARROW_I16 == FTKX_DTYPE_I16 &&
+              ftkx::NARROW_U32 == FTKX_DTYPE_U32 && ftkx::NARROW_I32 == FTKX_DTYPE_I32 && ftkx::NARROW_DTYPES == 10, "narrow_steps.hpp and ftkx.h number the element types alike");
 
 // ---- what every way of making a slice resident shares -----------------------------------------------------------------------------------
 // the checks in front of a push of timestep t
@@ -162,6 +166,50 @@ template <class T> static int ingest(ftkx_ctx *c, const T *const *planes, int nc
   return FTKX_OK;
 }
 
+// ---- narrow sources: half, bfloat16, 8- / 16- / 32-bit integers (narrow_kernels.hip) ----------------------------------------------------------
+// dst becomes the FP64 array of the `count` elements of type `dtype` (ftkx::narrow_dtype_ok) at src, by ftkx::narrow_ingest_plan: the narrow
+// kernel in FRONT of the chain an FP64 source takes.  It reads this device's memory only: a host source, one handed over as "device memory
+// of any device" (2) and a pointer of another device go through the context's f32_stage block as they came, count * the element's size
+// bytes, under the ordering said above (ingest).  It writes dst -- or, where smoothing is set, a pooled array that conv_kernel<double> reads
+// into dst and that goes back to the pool in stream order; adjust_kernel<double> follows in place.  Never adopted.
+static int ingest_narrow(ftkx_ctx *c, const void *src, int dtype, size_t count, const Ingest &how, ftkx_block &dst, bool *waits)
+{
+  const bool on_this_device = ftkx::narrow_ingest_asks_where(how.on_device) && ftkx_pointer_device(src) == c->device;
+  const ftkx::NarrowIngestPlan p = ftkx::narrow_ingest_plan(how.smooth, how.adjust, how.on_device, on_this_device);
+  if (p.caller_waits) *waits = true;
+  if (int rc = take_pooled(c, count, dst)) return rc;
+  double *const out = dst.as<double>();
+  const void *from = src;
+  if (p.staged) {
+    const size_t bytes = count * ftkx::narrow_dtype_size(dtype);
+    if (c->f32_stage_reader && c->f32_stage_reader != c->stream) HIP_TRY(c, hipStreamSynchronize(c->f32_stage_reader));
+    c->f32_stage_reader = nullptr;
+    if (int rc = c->f32_stage.reserve(c, bytes, 0, c->stream)) return rc;
+    if (how.on_device == 0) { if (int rc = upload_from_host(c, c->f32_stage.p, src, bytes)) return rc; }
+    else if (hipMemcpyAsync(c->f32_stage.p, src, bytes, hipMemcpyDefault, c->stream) != hipSuccess) return fail(c, FTKX_E_DEVICE, "push: copy of the source failed");
+    from = c->f32_stage.p;
+    c->f32_stage_reader = c->stream;
+  }
+  ftkx_block tmp;
+  if (p.to_pooled) { if (int rc = take_pooled(c, count, tmp)) return rc; }
+  ftkx::launch_narrow(dtype, from, count, p.to_pooled ? tmp.as<double>() : out, c->stream);
+  c->narrow_launches[dtype] ++;
+  if (p.to_pooled)
+    ftkx::launch_conv<double>(c->nd, tmp.as<double>(), (int)c->ext_sz[0], (int)c->ext_sz[1], (int)c->ext_sz[2], c->d_conv_w.as<double>() + kSmoothWeights, c->smooth_ksize, out, c->stream);
+  if (p.then_adjust) queue_adjust<double>(c, out, count, how.t, out);
+  const hipError_t e = hipGetLastError();
+  if (tmp.p) give_pooled(c, std::move(tmp));
+  HIP_TRY(c, e);
+  return FTKX_OK;
+}
+
+// one interleaved array by the element type of the push: T double or float -> ingest<T>; T void -> narrow elements of type `dtype`
+template <class T> static int ingest_array(ftkx_ctx *c, const T *src, int dtype, size_t count, const Ingest &how, ftkx_block &dst, bool *waits)
+{
+  if constexpr (std::is_void<T>::value) return ingest_narrow(c, src, dtype, count, how, dst, waits);
+  else return ingest<T>(c, &src, 1, count, how, dst, waits);
+}
+
 // ---- vector snapshots given as one array per component (concat_kernels.hip) --------------------------------------------------------------
 // what every launch of the concat kernel asks of its arguments (dst null: an array of the context's own, not taken yet); nothing is queued
 template <class T> static int planar_args(ftkx_ctx *c, const char *who, const T *const *planes, int nc, size_t count, const double *dst)
@@ -182,16 +230,18 @@ template <class T> static int planar_args(ftkx_ctx *c, const char *who, const T 
 }
 
 // ---- the slice pushes -------------------------------------------------------------------------------------------------------------------
-// T: the element type of the caller's arrays (double, or float: ftkx_push_*_f32).  The resident slice is FP64 either way.
+// T: the element type of the caller's arrays (double, or float: ftkx_push_*_f32; void: narrow elements of type `dtype`, ftkx_push_*_typed,
+// never planar).  The resident slice is FP64 either way.
 // Vc (ftkx_push_slice_planar*; V is null then): V arrives as nc planes; J and S keep their interleaved layout
-template <class T> static int push_common(ftkx_ctx *c, int t, const T *V, const T *J, const T *S, int on_device, bool scalar_only, const T *const *Vc = nullptr, int nc = 0, bool planar = false)
+template <class T> static int push_common(ftkx_ctx *c, int t, const T *V, const T *J, const T *S, int on_device, bool scalar_only, const T *const *Vc = nullptr, int nc = 0, bool planar = false,
+                                          int dtype = -1)
 {
   if (c) c->ahead.clear();
   if (!c) return fail(nullptr, FTKX_E_INVALID, "null context");
   if (int rc = push_checks(c, t, on_device, scalar_only, scalar_only ? S != nullptr : planar ? Vc != nullptr : V != nullptr)) return rc;
   const size_t n = n_vertices(c);
   const int nd = c->nd;
-  if (planar) {
+  if constexpr (!std::is_void<T>::value) if (planar) {
     if (nc != nd) return fail(c, FTKX_E_INVALID, "push: %d planes for a context of %d dimensions", nc, nd);
     if (int rc = planar_args<T>(c, "push", Vc, nc, n, nullptr)) return rc;
   }
@@ -206,11 +256,15 @@ template <class T> static int push_common(ftkx_ctx *c, int t, const T *V, const 
   bool waits = false;
   // one interleaved array of the push (null: none); smoothing applies to S alone: vector pushes were refused above
   auto take = [&](const T *src, size_t count, bool smooth, ftkx_block &dst) -> int {
-    return src ? ingest<T>(c, &src, 1, count, Ingest{on_device, t, smooth, adjust, false}, dst, &waits) : FTKX_OK;
+    return src ? ingest_array<T>(c, src, dtype, count, Ingest{on_device, t, smooth, adjust, false}, dst, &waits) : FTKX_OK;
+  };
+  auto take_planes = [&]() -> int {
+    if constexpr (std::is_void<T>::value) return fail(c, FTKX_E_INVALID, "push: planes of narrow elements are not taken");
+    else return ingest<T>(c, Vc, nc, n, Ingest{on_device, t, false, adjust, false}, s.V, &waits);
   };
   if (int rc = take(S, n, c->smooth_ksize != 0, s.S)) return rc;
   if (!scalar_only) {
-    if (int rc = planar ? ingest<T>(c, Vc, nc, n, Ingest{on_device, t, false, adjust, false}, s.V, &waits) : take(V, n * nd, false, s.V)) return rc;
+    if (int rc = planar ? take_planes() : take(V, n * nd, false, s.V)) return rc;
     if (int rc = take(J, n * nd * nd, false, s.J)) return rc;
   }
   // scalar input: V = gradient2D/3D(S) is never materialised -- every kernel evaluates it where it needs it, with the
@@ -330,8 +384,9 @@ static int temporal_emit(ftkx_ctx *c, const ftkx::TemporalSeries &next, bool pop
 }
 
 // T: the element type of the caller's snapshot (double, or float: ftkx_temporal_push_f32); the ring holds FP64 arrays either way.
+// (void: narrow elements of type `dtype`, ftkx_temporal_push_typed, never planar: widened into the slot, adjusted there)
 // planes (ftkx_temporal_push_planar*; A is null then): a vector snapshot as nc arrays, one per component
-template <class T> static int temporal_push_common(ftkx_ctx *c, const T *A, int is_vector, int on_device, int *t_emitted, const T *const *planes = nullptr, int nc = 0)
+template <class T> static int temporal_push_common(ftkx_ctx *c, const T *A, int is_vector, int on_device, int *t_emitted, const T *const *planes = nullptr, int nc = 0, int dtype = -1)
 {
   if (c) c->ahead.clear();
   if (!c) return fail(nullptr, FTKX_E_INVALID, "null context");
@@ -345,7 +400,7 @@ template <class T> static int temporal_push_common(ftkx_ctx *c, const T *A, int 
   }
   const bool scalar = !is_vector;
   if (int rc = push_checks(c, c->tm_next, on_device, scalar, A != nullptr || planes != nullptr)) return rc;
-  if (planes) {
+  if constexpr (!std::is_void<T>::value) if (planes) {
     if (nc != c->nd) return fail(c, FTKX_E_INVALID, "ftkx_temporal_push: %d planes for a context of %d dimensions", nc, c->nd);
     if (int rc = planar_args<T>(c, "ftkx_temporal_push", planes, nc, n_vertices(c), nullptr)) return rc;
   }
@@ -361,7 +416,11 @@ template <class T> static int temporal_push_common(ftkx_ctx *c, const T *A, int 
   if (c->tm.kind < 0 && c->tm.size == 0) { c->tm_t0 = c->tm_next; c->tm_pushed = 0; }      // the series' first snapshot
   const Ingest how{on_device, c->tm_t0 + (int)c->tm_pushed, c->smooth_ksize != 0, c->adj.on(), true};
   bool waits = false;
-  if (int rc = planes ? ingest<T>(c, planes, nc, n_vertices(c), how, slot, &waits) : ingest<T>(c, &A, 1, count, how, slot, &waits)) return rc;
+  auto take_planes = [&]() -> int {
+    if constexpr (std::is_void<T>::value) return fail(c, FTKX_E_INVALID, "ftkx_temporal_push: planes of narrow elements are not taken");
+    else return ingest<T>(c, planes, nc, n_vertices(c), how, slot, &waits);
+  };
+  if (int rc = planes ? take_planes() : ingest_array<T>(c, A, dtype, count, how, slot, &waits)) return rc;
   // A device source has to be read before the caller may overwrite it (a host source has been staged completely by upload_from_host):
   // the call ends by waiting for THIS point of the stream, not for the stream -- sweeps queued before the push (deferred collection) and
   // the emission queued behind it run on.
@@ -452,6 +511,31 @@ template <class T> static int adjust_common(ftkx_ctx *c, const char *who, const 
   if (int rc = adjust_args<T>(c, who, src, count, sigma, clamp_on, lo, hi, dst)) return rc;
   const ftkx::AdjustArgs a{sigma, seed, t, lo, hi};
   return timed_relaunch(c, reps, ms, [&] { ftkx::launch_adjust<T>(src, count, sigma > 0, clamp_on != 0, a, dst, c->stream); });
+}
+
+// the bare narrow kernel's arguments: a dtype it has (float32 is handed to the widen kernel by the callers; FP64 has no kernel: a copy is
+// not a conversion), the rest as widen_args
+static int narrow_args(ftkx_ctx *c, const char *who, const void *src, int dtype, size_t count, const double *dst)
+{
+  if (!ftkx::narrow_dtype_ok(dtype)) return fail(c, FTKX_E_INVALID, "%s: dtype %d is not one of FTKX_DTYPE_F16 .. FTKX_DTYPE_I32", who, dtype);
+  const size_t esize = ftkx::narrow_dtype_size(dtype);
+  if (!src || !dst) return fail(c, FTKX_E_INVALID, "%s: null argument", who);
+  if (count < 1) return fail(c, FTKX_E_INVALID, "%s: count must be positive", who);
+  if (((size_t)src & (esize - 1)) || ((size_t)dst & 7)) return fail(c, FTKX_E_INVALID, "%s: src must be a multiple of its element's size and dst a multiple of 8", who);
+  if ((const char *)src < (const char *)(dst + count) && (const char *)dst < (const char *)src + count * esize) return fail(c, FTKX_E_INVALID, "%s: input and output overlap", who);
+  return FTKX_OK;
+}
+
+// what a typed push asks of its arrays before the checks of its FP64 counterpart: a narrow dtype, every given pointer a multiple of its size.
+// Like every push, refused or not, it ends what was announced ahead (c->ahead).
+static int typed_args(ftkx_ctx *c, const char *who, int dtype, const void *const *arrays, int n)
+{
+  if (c) c->ahead.clear();
+  if (!c) return fail(nullptr, FTKX_E_INVALID, "null context");
+  if (!ftkx::narrow_dtype_ok(dtype)) return fail(c, FTKX_E_INVALID, "%s: dtype %d is not one of FTKX_DTYPE_*", who, dtype);
+  for (int k = 0; k < n; k ++)
+    if ((size_t)arrays[k] & (ftkx::narrow_dtype_size(dtype) - 1)) return fail(c, FTKX_E_INVALID, "%s: an array is not a multiple of its element's size", who);
+  return FTKX_OK;
 }
 
 static int temporal_combine_args(ftkx_ctx *c, const char *who, const double *const *arrays, int ksize, const double *weights, size_t count, const double *out)
@@ -593,6 +677,65 @@ int ftkx_debug_widen_relaunch(ftkx_ctx *c, const float *src, size_t count, doubl
   if (!ms || reps < 1) return fail(c, FTKX_E_INVALID, "ftkx_debug_widen_relaunch: bad argument");
   if (int rc = widen_args(c, "ftkx_debug_widen_relaunch", src, count, dst)) return rc;
   return timed_relaunch(c, reps, ms, [&] { ftkx::launch_widen(src, count, dst, c->stream); });
+}
+
+// ---- half, bfloat16, integers -> FP64 (narrow_kernels.hip) -----------------------------------------------------------------------------------
+size_t ftkx_dtype_size(int dtype) { return ftkx::narrow_dtype_size(dtype); }
+
+int ftkx_push_scalar_slice_typed(ftkx_ctx *c, int t, const void *S, int dtype, int on_device)
+{
+  if (dtype == FTKX_DTYPE_F64) return ftkx_push_scalar_slice(c, t, static_cast<const double *>(S), on_device);
+  if (dtype == FTKX_DTYPE_F32) return ftkx_push_scalar_slice_f32(c, t, static_cast<const float *>(S), on_device);
+  const void *a[1] = {S};
+  if (int rc = typed_args(c, "ftkx_push_scalar_slice_typed", dtype, a, 1)) return rc;
+  return push_common<void>(c, t, nullptr, nullptr, S, on_device, true, nullptr, 0, false, dtype);
+}
+
+int ftkx_push_slice_typed(ftkx_ctx *c, int t, const void *V, const void *J, const void *S, int dtype, int on_device)
+{
+  if (dtype == FTKX_DTYPE_F64) return ftkx_push_slice(c, t, static_cast<const double *>(V), static_cast<const double *>(J), static_cast<const double *>(S), on_device);
+  if (dtype == FTKX_DTYPE_F32) return ftkx_push_slice_f32(c, t, static_cast<const float *>(V), static_cast<const float *>(J), static_cast<const float *>(S), on_device);
+  const void *a[3] = {V, J, S};
+  if (int rc = typed_args(c, "ftkx_push_slice_typed", dtype, a, 3)) return rc;
+  return push_common<void>(c, t, V, J, S, on_device, false, nullptr, 0, false, dtype);
+}
+
+int ftkx_temporal_push_typed(ftkx_ctx *c, const void *A, int dtype, int is_vector, int on_device, int *t_emitted)
+{
+  if (dtype == FTKX_DTYPE_F64) return ftkx_temporal_push(c, static_cast<const double *>(A), is_vector, on_device, t_emitted);
+  if (dtype == FTKX_DTYPE_F32) return ftkx_temporal_push_f32(c, static_cast<const float *>(A), is_vector, on_device, t_emitted);
+  const void *a[1] = {A};
+  if (int rc = typed_args(c, "ftkx_temporal_push_typed", dtype, a, 1)) return rc;
+  return temporal_push_common<void>(c, A, is_vector, on_device, t_emitted, nullptr, 0, dtype);
+}
+
+int ftkx_widen_typed(ftkx_ctx *c, const void *src, int dtype, size_t count, double *dst)
+{
+  if (dtype == FTKX_DTYPE_F32) return ftkx_widen_f32(c, static_cast<const float *>(src), count, dst);
+  DERIVE_PROLOGUE(c);
+  if (int rc = narrow_args(c, "ftkx_widen_typed", src, dtype, count, dst)) return rc;
+  ftkx::launch_narrow(dtype, src, count, dst, c->stream);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipStreamSynchronize(c->stream));      // (the caller may read `dst`)
+  return FTKX_OK;
+}
+
+// profiling aid (tools/push_narrow_time.py): the narrow kernel `reps` times back to back
+int ftkx_debug_narrow_relaunch(ftkx_ctx *c, const void *src, int dtype, size_t count, double *dst, int reps, double *ms)
+{
+  if (dtype == FTKX_DTYPE_F32) return ftkx_debug_widen_relaunch(c, static_cast<const float *>(src), count, dst, reps, ms);
+  DERIVE_PROLOGUE(c);
+  if (!ms || reps < 1) return fail(c, FTKX_E_INVALID, "ftkx_debug_narrow_relaunch: bad argument");
+  if (int rc = narrow_args(c, "ftkx_debug_narrow_relaunch", src, dtype, count, dst)) return rc;
+  return timed_relaunch(c, reps, ms, [&] { ftkx::launch_narrow(dtype, src, count, dst, c->stream); });
+}
+
+int ftkx_debug_narrow_counts(const ftkx_ctx *c, unsigned long long per_dtype[10])
+{
+  if (!c) return fail(nullptr, FTKX_E_INVALID, "null context");
+  if (!per_dtype) return fail(nullptr, FTKX_E_INVALID, "ftkx_debug_narrow_counts: null argument");
+  for (int i = 0; i < 10; i ++) per_dtype[i] = c->narrow_launches[i];
+  return FTKX_OK;
 }
 
 // ---- component planes -> interleaved FP64 (concat_kernels.hip) ------------------------------------------------------------------------------

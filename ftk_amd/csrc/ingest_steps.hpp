@@ -6,6 +6,7 @@
 // whether the spatial smoothing applies (smooth), whether perturbation or clamp applies (adjust: false for a raw array -- an aux array),
 // where the caller says it lies (on_device 0 host, 1 this device and borrowable, 2 device memory of any device) and whether every source
 // pointer IS device memory of the context's device (on_this_device).  planar && smooth is refused by every caller before the plan is asked.
+// Sources narrower than a float have a plan of their own, narrow_ingest_plan below (tests/test_narrow_plan_host.py).
 #pragma once
 
 namespace ftkx {
@@ -58,6 +59,36 @@ inline IngestPlan ingest_plan(bool f32, bool planar, bool smooth, bool adjust, i
   p.counters = p.first == INGEST_CONCAT ? INGEST_CNT_PLANAR : p.first == INGEST_CONV ? (f32 ? INGEST_CNT_F32_DIRECT : 0u)
              : p.first == INGEST_ADJUST ? INGEST_CNT_FROM_FLOAT : INGEST_CNT_F32_WIDENED;
   if (p.then_adjust) p.counters |= INGEST_CNT_IN_PLACE;
+  return p;
+}
+
+// ---- narrow sources: half, bfloat16, 8- / 16- / 32-bit integers (narrow_steps.hpp) ----------------------------------------------------------
+// They go IN FRONT of the chain above, not into it: the narrow kernel writes the FP64 array, and what follows is what follows an FP64 source
+// that was copied into the slice -- conv_kernel<double> out of a pooled array where smoothing is set, adjust_kernel<double> in place.  Neither
+// kernel gets an instantiation per narrow type.  The case: smooth, adjust, on_device and on_this_device as above (always one interleaved
+// array; planes of narrow elements are not taken).
+struct NarrowIngestPlan {
+  bool reads_here;        // the narrow kernel reads the caller's pointer where it lies: on_device 1 and memory of this device, nothing else
+  bool staged;            // otherwise the source's bytes (count * the element's size) go into the context's f32_stage block first
+  bool adopt;             // never: the resident array is FP64
+  bool caller_waits;      // a device source has been read when the call returns (a host source has been staged completely by the upload)
+  bool to_pooled;         // the narrow kernel writes a pooled field array, which conv_kernel<double> reads into dst (smoothing); else it writes dst
+  bool then_adjust;       // adjust_kernel<double> in place on dst: the LAST kernel of the chain
+  unsigned counters;      // INGEST_CNT_IN_PLACE where then_adjust; the float32 and planar counters never move
+};
+
+// whether the plan depends on on_this_device at all
+inline bool narrow_ingest_asks_where(int on_device) { return on_device == 1; }
+
+inline NarrowIngestPlan narrow_ingest_plan(bool smooth, bool adjust, int on_device, bool on_this_device)
+{
+  NarrowIngestPlan p{false, false, false, false, false, false, 0u};
+  p.reads_here = on_device == 1 && on_this_device;
+  p.staged = !p.reads_here;
+  p.caller_waits = on_device != 0;
+  p.to_pooled = smooth;
+  p.then_adjust = adjust;
+  p.counters = adjust ? INGEST_CNT_IN_PLACE : 0u;
   return p;
 }
 

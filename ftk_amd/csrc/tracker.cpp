@@ -57,24 +57,18 @@ unsigned long long factor_of(double resolution, int minbits, int maxbits)
   return 1ull << std::max(minbits, std::min(nbits, maxbits));
 }
 
-// one snapshot -> one context.  kind: 0 scalar (V derived), 1 vector, 2 all three given; f32: the arrays are floats (widened on the device);
-// planes (kind 1): v is an array of that many pointers, one per component (interleaved on the device)
-int push_to(ftkx_ctx *c, int kind, int t, const void *s, const void *v, const void *j, int on_device, bool f32 = false, int planes = 0)
+// one snapshot -> one context.  kind: 0 scalar (V derived), 1 vector, 2 all three given; dtype: the arrays' element type, FTKX_DTYPE_*
+// (everything but FP64 is widened on the device; the typed entries hand FP64 and float32 to the entries they always took);
+// planes (kind 1; FP64 or float32): v is an array of that many pointers, one per component (interleaved on the device)
+int push_to(ftkx_ctx *c, int kind, int t, const void *s, const void *v, const void *j, int on_device, int dtype = FTKX_DTYPE_F64, int planes = 0)
 {
   if (planes) {
-    if (f32) return ftkx_push_slice_planar_f32(c, t, static_cast<const float *const *>(v), planes, nullptr, nullptr, on_device);
+    if (dtype == FTKX_DTYPE_F32) return ftkx_push_slice_planar_f32(c, t, static_cast<const float *const *>(v), planes, nullptr, nullptr, on_device);
     return ftkx_push_slice_planar(c, t, static_cast<const double *const *>(v), planes, nullptr, nullptr, on_device);
   }
-  if (f32) {
-    const float *fs = static_cast<const float *>(s), *fv = static_cast<const float *>(v), *fj = static_cast<const float *>(j);
-    if (kind == 0) return ftkx_push_scalar_slice_f32(c, t, fs, on_device);
-    if (kind == 1) return ftkx_push_slice_f32(c, t, fv, nullptr, nullptr, on_device);
-    return ftkx_push_slice_f32(c, t, fv, fj, fs, on_device);
-  }
-  const double *ds = static_cast<const double *>(s), *dv = static_cast<const double *>(v), *dj = static_cast<const double *>(j);
-  if (kind == 0) return ftkx_push_scalar_slice(c, t, ds, on_device);
-  if (kind == 1) return ftkx_push_slice(c, t, dv, nullptr, nullptr, on_device);
-  return ftkx_push_slice(c, t, dv, dj, ds, on_device);
+  if (kind == 0) return ftkx_push_scalar_slice_typed(c, t, s, dtype, on_device);
+  if (kind == 1) return ftkx_push_slice_typed(c, t, v, nullptr, nullptr, dtype, on_device);
+  return ftkx_push_slice_typed(c, t, v, j, s, dtype, on_device);
 }
 }  // namespace
 
@@ -551,10 +545,14 @@ void critical_point_tracker_regular::reset()
 }
 
 // one snapshot -> the context(s) whose steps read it (kind: see push_to)
-void critical_point_tracker_regular::push_snapshot(int kind, const void *s, const void *v, const void *j, bool device, bool f32, int planes)
+void critical_point_tracker_regular::push_snapshot(int kind, const void *s, const void *v, const void *j, bool device, int dtype, int planes)
 {
+  const bool f32 = dtype == FTKX_DTYPE_F32;
+  if (ftkx_dtype_size(dtype) == 0) throw ftkx_error(FTKX_E_INVALID, "push: element type " + std::to_string(dtype) + " is not one of FTKX_DTYPE_*");
+  if (planes && dtype != FTKX_DTYPE_F64 && !f32) throw ftkx_error(FTKX_E_UNSUPPORTED, "push: component planes are FP64 or float32");
   if (planes && multi) throw ftkx_error(FTKX_E_UNSUPPORTED, "push: component planes with one device only (a multi-device tracker takes the interleaved FP64 array)");
   if (f32 && multi) throw ftkx_error(FTKX_E_UNSUPPORTED, "push: float32 snapshots with one device only (a multi-device tracker takes FP64 arrays)");
+  if (dtype != FTKX_DTYPE_F64 && multi) throw ftkx_error(FTKX_E_UNSUPPORTED, "push: half, bfloat16 and integer snapshots with one device only (a multi-device tracker takes FP64 arrays)");
   if (extras_in_push != n_extra_expected())
     throw ftkx_error(FTKX_E_INVALID, "push: " + std::to_string(scalar_components.size()) + " scalar components take " + std::to_string(n_extra_expected()) + " extra arrays with every snapshot, not " +
                                      std::to_string(extras_in_push));
@@ -568,8 +566,7 @@ void critical_point_tracker_regular::push_snapshot(int kind, const void *s, cons
     const void *a = kind == 0 ? s : v;
     if (planes) check(f32 ? ftkx_temporal_push_planar_f32(ctx, static_cast<const float *const *>(v), planes, device ? 1 : 0, &t_emitted)
                           : ftkx_temporal_push_planar(ctx, static_cast<const double *const *>(v), planes, device ? 1 : 0, &t_emitted));
-    else check(f32 ? ftkx_temporal_push_f32(ctx, static_cast<const float *>(a), kind, device ? 1 : 0, &t_emitted)
-                   : ftkx_temporal_push(ctx, static_cast<const double *>(a), kind, device ? 1 : 0, &t_emitted));
+    else check(ftkx_temporal_push_typed(ctx, a, dtype, kind, device ? 1 : 0, &t_emitted));
     take_emitted(t_emitted);
     return;
   }
@@ -577,7 +574,7 @@ void critical_point_tracker_regular::push_snapshot(int kind, const void *s, cons
   const int t = next_push_timestep;
   if (slab && (t < slab_t0 || t >= slab_t1)) throw ftkx_error(FTKX_E_INVALID, "slab mode: timestep " + std::to_string(t) + " is not in this rank's slab [" + std::to_string(slab_t0) + ", " + std::to_string(slab_t1) + ")");
   if (multi) multi->push(kind, t, static_cast<const double *>(s), static_cast<const double *>(v), static_cast<const double *>(j), device);
-  else check(push_to(ctx, kind, t, s, v, j, device ? 1 : 0, f32, planes));
+  else check(push_to(ctx, kind, t, s, v, j, device ? 1 : 0, dtype, planes));
   field_data_snapshots.push_back(t);
   next_push_timestep ++;
 }
@@ -601,34 +598,37 @@ bool critical_point_tracker_regular::flush_temporal_smoothing()
   return t_emitted >= 0;
 }
 
-void critical_point_tracker_regular::push_scalar(const void *s, bool device, bool f32)
+void critical_point_tracker_regular::push_scalar(const void *s, bool device, int dtype)
 {
   if (!initialized) throw ftkx_error(FTKX_E_INVALID, "push: initialize() first");
   if (vector_field_source != SOURCE_DERIVED) throw ftkx_error(FTKX_E_INVALID, "push_scalar_field_snapshot: vector_field_source must be SOURCE_DERIVED");
-  push_snapshot(0, s, nullptr, nullptr, device, f32);       // V = gradientND(s) on the device
+  push_snapshot(0, s, nullptr, nullptr, device, dtype);       // V = gradientND(s) on the device
 }
 
-void critical_point_tracker_regular::push_vector(const void *v, bool device, bool f32, int planes)
+void critical_point_tracker_regular::push_vector(const void *v, bool device, int dtype, int planes)
 {
   if (!initialized) throw ftkx_error(FTKX_E_INVALID, "push: initialize() first");
   if (spatial_smoothing_ksize) throw ftkx_error(FTKX_E_UNSUPPORTED, "push_vector_field_snapshot: spatial smoothing takes scalar snapshots only");
-  push_snapshot(1, nullptr, v, nullptr, device, f32, planes);       // J derived at hits when jacobian_field_source == SOURCE_DERIVED
+  push_snapshot(1, nullptr, v, nullptr, device, dtype, planes);       // J derived at hits when jacobian_field_source == SOURCE_DERIVED
 }
 
-void critical_point_tracker_regular::push_field_data(const void *s, const void *v, const void *j, bool device, bool f32)
+void critical_point_tracker_regular::push_field_data(const void *s, const void *v, const void *j, bool device, int dtype)
 {
   if (!initialized) throw ftkx_error(FTKX_E_INVALID, "push: initialize() first");
   if (spatial_smoothing_ksize) throw ftkx_error(FTKX_E_UNSUPPORTED, "push_field_data_snapshot: spatial smoothing takes scalar snapshots only");
   if (perturbation_sigma > 0 || clamp_on) throw ftkx_error(FTKX_E_UNSUPPORTED, "push_field_data_snapshot: perturbation and clamp take a scalar or a vector snapshot alone");
-  push_snapshot(2, s, v, j, device, f32);
+  push_snapshot(2, s, v, j, device, dtype);
 }
 
-void critical_point_tracker_regular::push_scalar_field_snapshot(const double *s, bool device) { push_scalar(s, device, false); }
-void critical_point_tracker_regular::push_vector_field_snapshot(const double *v, bool device) { push_vector(v, device, false); }
-void critical_point_tracker_regular::push_field_data_snapshot(const double *s, const double *v, const double *j, bool device) { push_field_data(s, v, j, device, false); }
-void critical_point_tracker_regular::push_scalar_field_snapshot(const float *s, bool device) { push_scalar(s, device, true); }
-void critical_point_tracker_regular::push_vector_field_snapshot(const float *v, bool device) { push_vector(v, device, true); }
-void critical_point_tracker_regular::push_field_data_snapshot(const float *s, const float *v, const float *j, bool device) { push_field_data(s, v, j, device, true); }
+void critical_point_tracker_regular::push_scalar_field_snapshot(const double *s, bool device) { push_scalar(s, device, FTKX_DTYPE_F64); }
+void critical_point_tracker_regular::push_vector_field_snapshot(const double *v, bool device) { push_vector(v, device, FTKX_DTYPE_F64); }
+void critical_point_tracker_regular::push_field_data_snapshot(const double *s, const double *v, const double *j, bool device) { push_field_data(s, v, j, device, FTKX_DTYPE_F64); }
+void critical_point_tracker_regular::push_scalar_field_snapshot(const float *s, bool device) { push_scalar(s, device, FTKX_DTYPE_F32); }
+void critical_point_tracker_regular::push_vector_field_snapshot(const float *v, bool device) { push_vector(v, device, FTKX_DTYPE_F32); }
+void critical_point_tracker_regular::push_field_data_snapshot(const float *s, const float *v, const float *j, bool device) { push_field_data(s, v, j, device, FTKX_DTYPE_F32); }
+void critical_point_tracker_regular::push_scalar_field_snapshot(const void *s, int dtype, bool device) { push_scalar(s, device, dtype); }
+void critical_point_tracker_regular::push_vector_field_snapshot(const void *v, int dtype, bool device) { push_vector(v, device, dtype); }
+void critical_point_tracker_regular::push_field_data_snapshot(const void *s, const void *v, const void *j, int dtype, bool device) { push_field_data(s, v, j, device, dtype); }
 
 // ---- extra scalar components (set_scalar_components) ------------------------------------------------------------------------------------
 void critical_point_tracker_regular::set_scalar_components(const std::vector<std::string> &names)
@@ -646,9 +646,10 @@ void critical_point_tracker_regular::push_with_extras(int kind, const void *s, c
   const int t = next_push_timestep;
   extras_in_push = n_extra;
   try {
-    if (kind == 0) push_scalar(s, device, f32);
-    else if (kind == 1) push_vector(v, device, f32);
-    else push_field_data(s, v, j, device, f32);
+    const int dtype = f32 ? FTKX_DTYPE_F32 : FTKX_DTYPE_F64;
+    if (kind == 0) push_scalar(s, device, dtype);
+    else if (kind == 1) push_vector(v, device, dtype);
+    else push_field_data(s, v, j, device, dtype);
   } catch (...) { extras_in_push = 0; throw; }
   extras_in_push = 0;
   for (int k = 0; k < n_extra; k ++)
@@ -682,12 +683,12 @@ void critical_point_tracker_regular::sample_step_records(const ftkx_cp_t *&recs,
 void critical_point_tracker_regular::push_vector_field_components(const double *const *comps, int nc, bool device)
 {
   if (!comps || nc < 1) throw ftkx_error(FTKX_E_INVALID, "push_vector_field_components: no components");
-  push_vector(comps, device, false, nc);
+  push_vector(comps, device, FTKX_DTYPE_F64, nc);
 }
 void critical_point_tracker_regular::push_vector_field_components(const float *const *comps, int nc, bool device)
 {
   if (!comps || nc < 1) throw ftkx_error(FTKX_E_INVALID, "push_vector_field_components: no components");
-  push_vector(comps, device, true, nc);
+  push_vector(comps, device, FTKX_DTYPE_F32, nc);
 }
 
 bool critical_point_tracker_regular::pop_field_data_snapshot()
@@ -1150,6 +1151,10 @@ int ftkx_tracker_push_scalar_field_snapshot_f32(ftkx_tracker *h, const float *s,
 int ftkx_tracker_push_vector_field_snapshot_f32(ftkx_tracker *h, const float *v, int dev) { return guarded(h, [&] { h->t->push_vector_field_snapshot(v, dev != 0); }); }
 int ftkx_tracker_push_field_data_snapshot_f32(ftkx_tracker *h, const float *s, const float *v, const float *j, int dev)
 { return guarded(h, [&] { h->t->push_field_data_snapshot(s, v, j, dev != 0); }); }
+int ftkx_tracker_push_scalar_field_snapshot_typed(ftkx_tracker *h, const void *s, int dtype, int dev) { return guarded(h, [&] { h->t->push_scalar_field_snapshot(s, dtype, dev != 0); }); }
+int ftkx_tracker_push_vector_field_snapshot_typed(ftkx_tracker *h, const void *v, int dtype, int dev) { return guarded(h, [&] { h->t->push_vector_field_snapshot(v, dtype, dev != 0); }); }
+int ftkx_tracker_push_field_data_snapshot_typed(ftkx_tracker *h, const void *s, const void *v, const void *j, int dtype, int dev)
+{ return guarded(h, [&] { h->t->push_field_data_snapshot(s, v, j, dtype, dev != 0); }); }
 int ftkx_tracker_push_vector_field_components(ftkx_tracker *h, const double *const *comps, int nc, int dev)
 { return guarded(h, [&] { h->t->push_vector_field_components(comps, nc, dev != 0); }); }
 int ftkx_tracker_push_vector_field_components_f32(ftkx_tracker *h, const float *const *comps, int nc, int dev)

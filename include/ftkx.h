@@ -17,6 +17,9 @@
  *   V[c + nd*(x + DW*(y + DH*z))]            vector field, nd components
  *   J[k + nd*j + nd*nd*(x + DW*(y + DH*z))]  jacobian; the tracker reads Js[j][k] = J(k, j, ...)  (2d:566-582, 3d:405-422)
  *   S[x + DW*(y + DH*z)]                     scalar
+ * Resident arrays are FP64.  A caller's array is FP64 too unless the entry says otherwise: the *_f32 entries take float32, the *_typed
+ * entries take any element type of FTKX_DTYPE_* -- FP64, float32, IEEE half, bfloat16, 8- / 16- / 32-bit integers -- as it is, at its own
+ * bytes per value over the link, and widen it to FP64 on the device, exactly (ndarray<T>::from_array<T1>, include/ftk/ndarray.hh:401-410).
  */
 #ifndef FTKX_H
 #define FTKX_H
@@ -520,6 +523,50 @@ int ftkx_debug_f32_counts(const ftkx_ctx *ctx, unsigned long long *widened, unsi
  * pool is not counted; neither is one the caller lent with on_device = 1); pooled: how many lie in the pool right now, held by no slice.
  * Either may be null.  Reads the context, changes nothing. */
 int ftkx_debug_array_counts(const ftkx_ctx *ctx, unsigned long long allocated[3], unsigned long long pooled[3]);
+
+/* ---- half, bfloat16 and integer snapshots (ndarray<T>::from_array<T1>, ndarray.hh:401-410) ---- */
+/* Image sequences and .vti image data of unsigned char / short, NetCDF variables of NC_BYTE / NC_SHORT / NC_INT, half or bfloat16 fields
+ * of an ML surrogate: the reference widens all of them on one host thread, p[i] = static_cast<double>(a[i]).  Here the elements go to the
+ * device as they are -- 1, 2 or 4 bytes per value over PCIe -- and ONE kernel widens them there, in front of everything else.  Every value
+ * of every type below is a double, so widening is exact (a subnormal half becomes a normal double, a NaN stays a NaN with its sign): each
+ * typed entry gives, byte for byte, the resident slice its FP64 counterpart gives for the widened array, and spatial smoothing,
+ * perturbation, clamp, the temporal filter and the sweep behind it are that push's.  Checks, error codes and refusals are the
+ * counterpart's.  64-bit integers are not exact in FP64 and are not taken. */
+enum {
+  FTKX_DTYPE_F64 = 0,      /* FP64: a typed entry hands it to the FP64 entry unchanged */
+  FTKX_DTYPE_F32 = 1,      /* float32: handed to the _f32 entry unchanged */
+  FTKX_DTYPE_F16 = 2,      /* IEEE half */
+  FTKX_DTYPE_BF16 = 3,     /* bfloat16: the upper 16 bits of a float32 */
+  FTKX_DTYPE_U8 = 4, FTKX_DTYPE_I8 = 5,
+  FTKX_DTYPE_U16 = 6, FTKX_DTYPE_I16 = 7,
+  FTKX_DTYPE_U32 = 8, FTKX_DTYPE_I32 = 9
+};
+/* bytes of one element; 0 for a dtype that is none of the above */
+size_t ftkx_dtype_size(int dtype);
+/* One entry point for every element type.  dtype: FTKX_DTYPE_*, anything else FTKX_E_INVALID; a pointer that is not a multiple of
+ * ftkx_dtype_size(dtype) is FTKX_E_INVALID.  ftkx_push_slice_typed: V, J and S (those given) share the one type.
+ * on_device: 0 host memory, uploaded as it is; 2 device memory of any device, copied as it is; 1 device memory of this context's device,
+ * READ where it lies.  A narrow array is never adopted: the call returns once the source has been read and the caller may overwrite it.
+ * A host source, a source given with 2 and a pointer of another device are staged in the context's byte block for narrow sources,
+ * count * ftkx_dtype_size(dtype) bytes.  The narrow kernel writes straight into the slice's own array; where spatial smoothing is set it
+ * writes a pooled array that the FP64 convolution reads into the slice's array; perturbation and clamp follow in place.
+ * ftkx_debug_f32_counts and ftkx_debug_planar_counts do not move for a narrow push; ftkx_debug_adjust_counts moves as for a copied FP64
+ * source (in_place).  Narrow and float32 and FP64 pushes may be mixed in one context. */
+int ftkx_push_scalar_slice_typed(ftkx_ctx *ctx, int t, const void *S, int dtype, int on_device);
+int ftkx_push_slice_typed(ftkx_ctx *ctx, int t, const void *V, const void *J, const void *S, int dtype, int on_device);
+int ftkx_temporal_push_typed(ftkx_ctx *ctx, const void *A, int dtype, int is_vector, int on_device, int *t_emitted);
+/* src: `count` elements of `dtype`, dst: `count` doubles, DEVICE pointers that do not overlap; src a multiple of its element's size, dst of
+ * 8.  A lane takes 4 elements with one load and stores 2 x 16 bytes where source and destination can be brought to 4 elements' bytes and
+ * to 16 by the same 0-3 leading elements, and goes element by element otherwise.  The call returns when `dst` is complete.  dtype:
+ * FTKX_DTYPE_F16 .. FTKX_DTYPE_I32; FTKX_DTYPE_F32 is handed to ftkx_widen_f32 (below: to ftkx_debug_widen_relaunch); FP64 has nothing to
+ * widen and is FTKX_E_INVALID like an unknown code. */
+int ftkx_widen_typed(ftkx_ctx *ctx, const void *src, int dtype, size_t count, double *dst);
+/* profiling aid (tools/push_narrow_time.py): the kernel of ftkx_widen_typed launched `reps` times back to back on the context's stream, a
+ * pair of events around every launch; ms: reps device times. */
+int ftkx_debug_narrow_relaunch(ftkx_ctx *ctx, const void *src, int dtype, size_t count, double *dst, int reps, double *ms);
+/* per_dtype[FTKX_DTYPE_*]: launches of the narrow kernel by this context's pushes so far, by element type ([0] and [1] stay 0: FP64 and
+ * float32 never take it) */
+int ftkx_debug_narrow_counts(const ftkx_ctx *ctx, unsigned long long per_dtype[10]);
 
 /* ---- vector snapshots given as one array per component (the stream's "u, v, w in separate variables"; ndarray::concat, ndarray.hh:1157-1172) ---- */
 /* The reference reads a vector field that a file keeps as one variable per component into nv arrays and interleaves them on the host,

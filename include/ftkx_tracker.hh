@@ -228,6 +228,14 @@ public:
   void push_scalar_field_snapshot(const float *scalar, bool device = false);
   void push_vector_field_snapshot(const float *vector, bool device = false);
   void push_field_data_snapshot(const float *scalar, const float *vector, const float *jacobian, bool device = false);
+  // snapshots of any element type the library takes (dtype: FTKX_DTYPE_* of ftkx.h -- half, bfloat16, 8- / 16- / 32-bit integers beside
+  // float32 and FP64): the elements go to the device as they are, 1, 2 or 4 bytes per value, and are widened there, exactly
+  // (ftkx_push_scalar_slice_typed); the tracker gives what it gives for the widened arrays.  The arrays of one push share one type.  A
+  // device pointer of a narrow type is read before the call returns, never borrowed.  One device (slab ranks included); a multi-device
+  // tracker throws FTKX_E_UNSUPPORTED for everything but FP64.
+  void push_scalar_field_snapshot(const void *scalar, int dtype, bool device);
+  void push_vector_field_snapshot(const void *vector, int dtype, bool device);
+  void push_field_data_snapshot(const void *scalar, const void *vector, const void *jacobian, int dtype, bool device);
   // the same with the snapshot's extra scalar fields (set_scalar_components): extra[0 .. n_extra - 1], one value per vertex each, for
   // scalar[1] (and scalar[2]); n_extra must be the number of names minus one, and a tracker with more than one name takes these forms
   // only.  device = true: FP64 extras are borrowed like the snapshot, until it is popped; float32 extras are read before the call returns.
@@ -313,10 +321,10 @@ protected:
   std::vector<int> field_data_snapshots;                    // timesteps resident on the device (<= 2, a deque in the reference)
   int next_push_timestep = 0;
   void take_emitted(int t);                                 // temporal smoothing: the filter's emission t (-1: none) joins field_data_snapshots
-  void push_snapshot(int kind, const void *s, const void *v, const void *j, bool device, bool f32, int planes = 0);   // behind the push_* methods: one snapshot (f32: of floats; planes: v is that many component pointers) -> the context(s) that read it
-  void push_scalar(const void *s, bool device, bool f32);                                          // the push_* methods' checks, in front of push_snapshot
-  void push_vector(const void *v, bool device, bool f32, int planes = 0);
-  void push_field_data(const void *s, const void *v, const void *j, bool device, bool f32);
+  void push_snapshot(int kind, const void *s, const void *v, const void *j, bool device, int dtype, int planes = 0);   // behind the push_* methods: one snapshot (dtype: FTKX_DTYPE_* of its arrays; planes: v is that many component pointers) -> the context(s) that read it
+  void push_scalar(const void *s, bool device, int dtype);                                         // the push_* methods' checks, in front of push_snapshot
+  void push_vector(const void *v, bool device, int dtype, int planes = 0);
+  void push_field_data(const void *s, const void *v, const void *j, bool device, int dtype);
   // extra scalar fields (set_scalar_components)
   std::vector<std::string> scalar_components;               // empty: never set (the writers' default label, no extras)
   int n_extra_expected() const { return scalar_components.empty() ? 0 : (int)scalar_components.size() - 1; }
@@ -457,6 +465,9 @@ int  ftkx_tracker_push_field_data_snapshot(ftkx_tracker *, const double *s, cons
 int  ftkx_tracker_push_scalar_field_snapshot_f32(ftkx_tracker *, const float *s, int on_device);   /* float32 snapshots, widened on the device */
 int  ftkx_tracker_push_vector_field_snapshot_f32(ftkx_tracker *, const float *v, int on_device);
 int  ftkx_tracker_push_field_data_snapshot_f32(ftkx_tracker *, const float *s, const float *v, const float *j, int on_device);
+int  ftkx_tracker_push_scalar_field_snapshot_typed(ftkx_tracker *, const void *s, int dtype, int on_device);   /* any FTKX_DTYPE_*, widened on the device */
+int  ftkx_tracker_push_vector_field_snapshot_typed(ftkx_tracker *, const void *v, int dtype, int on_device);
+int  ftkx_tracker_push_field_data_snapshot_typed(ftkx_tracker *, const void *s, const void *v, const void *j, int dtype, int on_device);
 int  ftkx_tracker_push_vector_field_components(ftkx_tracker *, const double *const *comps, int nc, int on_device);   /* one array per component, interleaved on the device */
 int  ftkx_tracker_push_vector_field_components_f32(ftkx_tracker *, const float *const *comps, int nc, int on_device);
 /* critical_point_tracker_regular::set_scalar_components: n (1 .. 3) names; and the push_* overloads that bring a snapshot's extra scalar
