@@ -173,6 +173,7 @@ class Context:
         self._keep = {}
         self._keep_aux = {}
         self._smoothing = False
+        self._vsmoothing = False
         self._perturbing = False
         self._clamping = False
 
@@ -222,6 +223,14 @@ class Context:
         rc = self._L.ftkx_set_spatial_smoothing(self._h, float(sigma), int(ksize))
         self._ck(rc)                                   # (raises: a refused setting leaves the context, and this flag, as they were)
         self._smoothing = int(ksize) != 0
+
+    def set_vector_smoothing(self, sigma, ksize=3):
+        """ftkx_set_vector_smoothing: vector snapshots pushed from now on (push_slice, push_slice_planar, temporal_push with a vector,
+        temporal_push_planar) have every component smoothed as the scalar field it is -- conv_gaussian(component, sigma, ksize, ksize // 2),
+        one kernel for the whole array; J or S beside V is refused while it is on.  A setting of its own beside set_spatial_smoothing;
+        ksize 0: off"""
+        self._ck(self._L.ftkx_set_vector_smoothing(self._h, float(sigma), int(ksize)))
+        self._vsmoothing = int(ksize) != 0
 
     def set_perturbation(self, sigma, seed=0):
         """ftkx_set_perturbation: every snapshot pushed from now on gets sigma * N(0, 1) noise added on the device, the noise of element e of
@@ -318,8 +327,8 @@ class Context:
             self._ck(self._L.ftkx_push_slice_typed(self._h, t, pv, pj, ps, dt, on_dev))
         else:
             self._ck((self._L.ftkx_push_slice_f32 if f32 else self._L.ftkx_push_slice)(self._h, t, pv, pj, ps, on_dev))
-        owned = dt != DTYPE_F64 or self._perturbing or self._clamping
-        self._keep[t] = (kv, kj, ks) if on_dev and not owned else None       # (float32, perturbation, clamp: read before the call returned, the context owns FP64 copies)
+        owned = dt != DTYPE_F64 or self._perturbing or self._clamping or self._vsmoothing
+        self._keep[t] = (kv, kj, ks) if on_dev and not owned else None       # (float32, perturbation, clamp, vector smoothing: read before the call returned, the context owns FP64 copies)
 
     def push_slice_planar(self, t, planes, J=None, S=None, on_device=None):
         """ftkx_push_slice_planar / _f32: push_slice of the vector field whose components are `planes` (see _planes: nc = nd arrays or one
@@ -720,6 +729,54 @@ class Context:
         if w.size != int(ksize) ** 3:
             raise ValueError("conv3D: ksize ** 3 weights")
         self._ck((self._L.ftkx_conv3D_f32 if f32 else self._L.ftkx_conv3D)(self._h, S_ptr, DW, DH, DD, w.ctypes.data, int(ksize), out_ptr))
+
+    # spatial smoothing of vector arrays on device pointers, every component as the scalar field it is (conv_vec_kernels.hip)
+    def _conv_vec_weights(self, who, nd, weights, ksize):
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        if w.size != int(ksize) ** nd:
+            raise ValueError("%s: ksize ** %d weights" % (who, nd))
+        return w
+
+    def conv_vec(self, V_ptr, dims, weights, ksize, out_ptr, f32=False):
+        """ftkx_conv2D_vec / ftkx_conv3D_vec (f32: a float32 source): out[c + nd * i] = conv(component c of V)[i], byte for byte what conv2D /
+        conv3D give per component; dims: (DW, DH[, DD]); V and out: device addresses of nd * DW * DH (* DD) elements"""
+        nd = len(dims)
+        w = self._conv_vec_weights("conv_vec", nd, weights, ksize)
+        d = [int(x) for x in dims]
+        if nd == 2:
+            self._ck((self._L.ftkx_conv2D_vec_f32 if f32 else self._L.ftkx_conv2D_vec)(self._h, V_ptr, d[0], d[1], w.ctypes.data, int(ksize), out_ptr))
+        elif nd == 3:
+            self._ck((self._L.ftkx_conv3D_vec_f32 if f32 else self._L.ftkx_conv3D_vec)(self._h, V_ptr, d[0], d[1], d[2], w.ctypes.data, int(ksize), out_ptr))
+        else:
+            raise ValueError("conv_vec: two or three extents")
+
+    def conv_planar(self, plane_ptrs, dims, weights, ksize, out_ptr, f32=False):
+        """ftkx_conv_planar / _f32: conv_vec of the vector array whose components are the nd planes at `plane_ptrs` (device addresses), smoothed
+        and interleaved by the one kernel"""
+        nd = len(dims)
+        w = self._conv_vec_weights("conv_planar", nd, weights, ksize)
+        if len(plane_ptrs) != nd:
+            raise ValueError("conv_planar: one plane per dimension")
+        d = [int(x) for x in dims] + [1] * (3 - nd)
+        ptrs = (C.c_void_p * nd)(*[None if p is None else int(p) for p in plane_ptrs])
+        self._ck((self._L.ftkx_conv_planar_f32 if f32 else self._L.ftkx_conv_planar)(self._h, nd, ptrs, d[0], d[1], d[2], w.ctypes.data, int(ksize), out_ptr))
+
+    def conv_vec_counts(self):
+        """(interleaved, planar, f32): launches of the vector smoothing's kernel by this context's pushes, by the source's form, and how many
+        of them read float32"""
+        a = C.c_ulonglong(0); b = C.c_ulonglong(0); c = C.c_ulonglong(0)
+        self._ck(self._L.ftkx_debug_conv_vec_counts(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return int(a.value), int(b.value), int(c.value)
+
+    def debug_conv_vec_relaunch(self, src_ptrs, dims, weights, ksize, out_ptr, reps, planar=False, f32=False):
+        """profiling aid: the vector smoothing's kernel `reps` times back to back -> device ms per launch (HIP events); src_ptrs: the nd
+        planes (planar), else [V]"""
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        d = [int(x) for x in dims] + [1] * (3 - len(dims))
+        ptrs = (C.c_void_p * len(src_ptrs))(*[int(p) for p in src_ptrs])
+        ms = (C.c_double * int(reps))()
+        self._ck(self._L.ftkx_debug_conv_vec_relaunch(self._h, len(dims), ptrs, int(bool(planar)), int(bool(f32)), d[0], d[1], d[2], w.ctypes.data, int(ksize), out_ptr, int(reps), ms))
+        return list(ms)
 
     # float32 -> FP64 on device pointers (widen_kernels.hip); conv2D / conv3D take f32=True for a float32 source
     def widen_f32(self, src_ptr, count, dst_ptr):
@@ -1156,6 +1213,11 @@ class _TrackerRegular:
         """before initialize(): every scalar snapshot is smoothed on the device like the reference stream's --spatial-smoothing-kernel
         (conv_gaussian(snapshot, sigma, ksize, ksize // 2)); ksize 0: off"""
         self._ck(self._L.ftkx_tracker_set_spatial_smoothing(self._h, float(sigma), int(ksize)))
+
+    def set_vector_spatial_smoothing(self, sigma, ksize=3):
+        """before initialize(): every vector snapshot (push_vector_field_snapshot, push_vector_field_components) has each component
+        smoothed on the device as the scalar field it is (conv_gaussian(component, sigma, ksize, ksize // 2), one kernel); ksize 0: off"""
+        self._ck(self._L.ftkx_tracker_set_vector_spatial_smoothing(self._h, float(sigma), int(ksize)))
 
     def set_perturbation(self, sigma, seed=0):
         """before initialize(): every snapshot gets sigma * N(0, 1) noise on the device like the reference stream's "perturbation", the noise

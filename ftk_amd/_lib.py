@@ -88,7 +88,7 @@ EXPORTS = [
     "ftkx_create", "ftkx_destroy", "ftkx_last_error", "ftkx_set_stream", "ftkx_set_options", "ftkx_default_options", "ftkx_set_mesh",
     "ftkx_push_slice", "ftkx_push_scalar_slice", "ftkx_drop_slice", "ftkx_slice_resolution", "ftkx_slices_resolution", "ftkx_slices_prepare", "ftkx_sweep_announce", "ftkx_set_slice_resolution", "ftkx_export_masks_size", "ftkx_export_masks", "ftkx_push_masked_slice", "ftkx_packed_masks_bytes", "ftkx_export_masks_packed", "ftkx_push_masked_slice_packed", "ftkx_sweep_cull", "ftkx_get_sparse_cells", "ftkx_patch_doubles", "ftkx_gather_patches", "ftkx_scatter_patches", "ftkx_scaling_factor",
     "ftkx_sweep", "ftkx_sweep_series", "ftkx_sweep_series_submit", "ftkx_sweep_series_complete", "ftkx_sweep_series_abort", "ftkx_series_dist_cells", "ftkx_series_dist_begin", "ftkx_series_dist_cull", "ftkx_series_dist_serve", "ftkx_series_dist_finish", "ftkx_series_dist_status", "ftkx_series_last_path", "ftkx_series_split_decision", "ftkx_sweep_enqueue", "ftkx_sweep_enqueue_many", "ftkx_sweep_collect", "ftkx_sweep_cancel", "ftkx_get_stats", "ftkx_invalidate_masks", "ftkx_debug_stream_read", "ftkx_debug_tile_repeat", "ftkx_set_profiling", "ftkx_get_kernel_times", "ftkx_extract_cp2dt", "ftkx_extract_cp3dt", "ftkx_free",
-    "ftkx_trace_curves", "ftkx_trace_curves_ctx", "ftkx_trace_curves_tags_ctx", "ftkx_trace_curves_device", "ftkx_trace_last_path", "ftkx_free_curves", "ftkx_post_process_curves", "ftkx_post_process_curves_device", "ftkx_pass2_device", "ftkx_post_process_last_path", "ftkx_free_trajectories", "ftkx_format_from_path", "ftkx_write_critical_points", "ftkx_read_critical_points", "ftkx_write_traced_critical_points", "ftkx_read_traced_critical_points", "ftkx_gradient2D", "ftkx_jacobian2D", "ftkx_gradient3D", "ftkx_jacobian3D", "ftkx_gaussian_kernel", "ftkx_conv2D", "ftkx_conv3D", "ftkx_set_spatial_smoothing", "ftkx_tracker_set_spatial_smoothing", "ftkx_debug_conv_relaunch", "ftkx_gaussian_kernel1d", "ftkx_temporal_combine", "ftkx_set_temporal_smoothing", "ftkx_temporal_push", "ftkx_temporal_flush", "ftkx_debug_temporal_relaunch", "ftkx_tracker_set_temporal_smoothing", "ftkx_tracker_snapshots_from_last_push", "ftkx_tracker_flush_temporal_smoothing", "ftkx_tracker_reset", "ftkx_version", "ftkx_device_count", "ftkx_pointer_device", "ftkx_context_device", "ftkx_last_mask_kernel", "ftkx_debug_mask_kernel_launches", "ftkx_debug_upload_counts", "ftkx_debug_mask_relaunch",
+    "ftkx_trace_curves", "ftkx_trace_curves_ctx", "ftkx_trace_curves_tags_ctx", "ftkx_trace_curves_device", "ftkx_trace_last_path", "ftkx_free_curves", "ftkx_post_process_curves", "ftkx_post_process_curves_device", "ftkx_pass2_device", "ftkx_post_process_last_path", "ftkx_free_trajectories", "ftkx_format_from_path", "ftkx_write_critical_points", "ftkx_read_critical_points", "ftkx_write_traced_critical_points", "ftkx_read_traced_critical_points", "ftkx_gradient2D", "ftkx_jacobian2D", "ftkx_gradient3D", "ftkx_jacobian3D", "ftkx_gaussian_kernel", "ftkx_conv2D", "ftkx_conv3D", "ftkx_set_spatial_smoothing", "ftkx_tracker_set_spatial_smoothing", "ftkx_conv2D_vec", "ftkx_conv3D_vec", "ftkx_conv2D_vec_f32", "ftkx_conv3D_vec_f32", "ftkx_conv_planar", "ftkx_conv_planar_f32", "ftkx_set_vector_smoothing", "ftkx_debug_conv_vec_relaunch", "ftkx_debug_conv_vec_counts", "ftkx_tracker_set_vector_spatial_smoothing", "ftkx_debug_conv_relaunch", "ftkx_gaussian_kernel1d", "ftkx_temporal_combine", "ftkx_set_temporal_smoothing", "ftkx_temporal_push", "ftkx_temporal_flush", "ftkx_debug_temporal_relaunch", "ftkx_tracker_set_temporal_smoothing", "ftkx_tracker_snapshots_from_last_push", "ftkx_tracker_flush_temporal_smoothing", "ftkx_tracker_reset", "ftkx_version", "ftkx_device_count", "ftkx_pointer_device", "ftkx_context_device", "ftkx_last_mask_kernel", "ftkx_debug_mask_kernel_launches", "ftkx_debug_upload_counts", "ftkx_debug_mask_relaunch",
     "ftkx_push_scalar_slice_f32", "ftkx_push_slice_f32", "ftkx_temporal_push_f32", "ftkx_widen_f32", "ftkx_conv2D_f32", "ftkx_conv3D_f32", "ftkx_debug_widen_relaunch", "ftkx_debug_f32_counts", "ftkx_debug_array_counts",
     "ftkx_dtype_size", "ftkx_push_scalar_slice_typed", "ftkx_push_slice_typed", "ftkx_temporal_push_typed", "ftkx_widen_typed", "ftkx_debug_narrow_relaunch", "ftkx_debug_narrow_counts",
     "ftkx_tracker_push_scalar_field_snapshot_typed", "ftkx_tracker_push_vector_field_snapshot_typed", "ftkx_tracker_push_field_data_snapshot_typed",
@@ -186,6 +186,16 @@ def load():
     L.ftkx_set_spatial_smoothing.argtypes = [vp, C.c_double, C.c_int]
     L.ftkx_debug_conv_relaunch.argtypes = [vp, C.c_int, dbl, C.c_int, C.c_int, C.c_int, dbl, C.c_int, dbl, C.c_int, C.POINTER(C.c_double)]
     L.ftkx_tracker_set_spatial_smoothing.argtypes = [vp, C.c_double, C.c_int]
+    for f in (L.ftkx_conv2D_vec, L.ftkx_conv2D_vec_f32):
+        f.argtypes = [vp, vp, C.c_int, C.c_int, dbl, C.c_int, dbl]
+    for f in (L.ftkx_conv3D_vec, L.ftkx_conv3D_vec_f32):
+        f.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, dbl, C.c_int, dbl]
+    for f in (L.ftkx_conv_planar, L.ftkx_conv_planar_f32):
+        f.argtypes = [vp, C.c_int, C.POINTER(vp), C.c_int, C.c_int, C.c_int, dbl, C.c_int, dbl]
+    L.ftkx_set_vector_smoothing.argtypes = [vp, C.c_double, C.c_int]
+    L.ftkx_debug_conv_vec_relaunch.argtypes = [vp, C.c_int, C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, dbl, C.c_int, dbl, C.c_int, C.POINTER(C.c_double)]
+    L.ftkx_debug_conv_vec_counts.argtypes = [vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
+    L.ftkx_tracker_set_vector_spatial_smoothing.argtypes = [vp, C.c_double, C.c_int]
     L.ftkx_gaussian_kernel1d.argtypes = [C.c_double, C.c_int, dbl]
     L.ftkx_temporal_combine.argtypes = [vp, C.POINTER(vp), C.c_int, dbl, C.c_size_t, dbl]
     L.ftkx_set_temporal_smoothing.argtypes = [vp, C.c_double, C.c_int, C.c_int]

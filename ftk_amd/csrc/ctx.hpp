@@ -27,6 +27,7 @@
 #include "temporal_steps.hpp"
 #include "adjust_steps.hpp"
 #include "sample_steps.hpp"
+#include "conv_vec_steps.hpp"
 
 struct ftkx_phase_clock;
 
@@ -58,6 +59,8 @@ void launch_gradient3d(const double *S, int DW, int DH, int DD, double *V, hipSt
 void launch_jacobian3d(const double *V, int DW, int DH, int DD, double *J, hipStream_t st);
 void launch_resolution(const double *p, size_t n, u64 *out2, hipStream_t st);
 template <class SRC> void launch_conv(int nd, const SRC *S, int DW, int DH, int DD, const double *d_weights, int ksize, double *out, hipStream_t st);   // conv_kernels.hip: SRC double or float
+// conv_vec_kernels.hip: every component of a vector array as the scalar field it is, interleaved FP64 out; SRC double or float
+template <class SRC> void launch_conv_vec(int nd, const ConvVecSource<SRC> &src, int DW, int DH, int DD, const double *d_weights, int ksize, double *out, hipStream_t st);
 void launch_widen(const float *src, size_t count, double *dst, hipStream_t st);   // widen_kernels.hip
 void launch_narrow(int dtype, const void *src, size_t count, double *dst, hipStream_t st);   // narrow_kernels.hip: dtype FTKX_DTYPE_F16 .. _I32
 template <class T> void launch_adjust(const T *src, size_t count, bool perturb, bool clamp, const AdjustArgs &a, double *dst, hipStream_t st);   // adjust_kernels.hip: T double or float; src == dst allowed
@@ -310,11 +313,17 @@ struct ftkx_ctx {
   ftkx_block d_expl;                // double
   int expl_ncomp = 0;
   size_t expl_n0 = 0, expl_n1 = 0;
-  // spatial smoothing (ftkx_set_spatial_smoothing): ksize 0 = off; d_conv_w holds two sets of 9^3 weights -- [0] those of the ftkx_conv2D /
-  // ftkx_conv3D call in hand (the call waits for its kernel), [1] the smoothing's, written when it is set and only read afterwards
+  // spatial smoothing (ftkx_set_spatial_smoothing): ksize 0 = off; d_conv_w holds three sets of 9^3 weights -- [0] those of the ftkx_conv2D /
+  // ftkx_conv3D / ftkx_conv*_vec / ftkx_conv_planar call in hand (the call waits for its kernel), [1] the smoothing's, [2] the vector
+  // smoothing's, each written when it is set and only read afterwards
   int smooth_ksize = 0;
   double smooth_sigma = 0;
   ftkx_block d_conv_w;              // double
+  // spatial smoothing of VECTOR snapshots, per component (ftkx_set_vector_smoothing; conv_vec_steps.hpp): a setting of its own, ksize 0 = off.
+  // The launches of its kernel by pushes, by the source's form, and how many of them read floats: ftkx_debug_conv_vec_counts.
+  int vsmooth_ksize = 0;
+  double vsmooth_sigma = 0;
+  unsigned long long conv_vec_interleaved = 0, conv_vec_planar = 0, conv_vec_f32 = 0;
   // temporal smoothing (ftkx_set_temporal_smoothing): the filter's state (temporal_steps.hpp), its weights and the ring of RAW snapshots
   // (after the spatial smoothing where that is set) -- at most ksize arrays of one size, taken from and given back to `arrays`.
   // Only kernels on the context's stream read them.  tm_next: the timestep the next emission gets.

@@ -10,6 +10,7 @@
 using namespace ftkxh;
 
 constexpr size_t kSmoothWeights = 729;      // ftkx_ctx::d_conv_w: where the smoothing's weights start
+constexpr size_t kVecSmoothWeights = 2 * kSmoothWeights;      // ... and the vector smoothing's
 static_assert(ftkx::NARROW_F64 == FTKX_DTYPE_F64 && ftkx::NARROW_F32 == FTKX_DTYPE_F32 && ftkx::NARROW_F16 == FTKX_DTYPE_F16 && ftkx::NARROW_BF16 == FTKX_DTYPE_BF16 &&
               ftkx::NARROW_U8 == FTKX_DTYPE_U8 && ftkx::NARROW_I8 == FTKX_DTYPE_I8 && ftkx::NARROW_U16 == FTKX_DTYPE_U16 && ftkx::NARROW_I16 == FTKX_DTYPE_I16 &&
               ftkx::NARROW_U32 == FTKX_DTYPE_U32 && ftkx::NARROW_I32 == FTKX_DTYPE_I32 && ftkx::NARROW_DTYPES == 10, "narrow_steps.hpp and ftkx.h number the element types alike");
@@ -76,7 +77,16 @@ struct Ingest {
   bool smooth;        // the spatial smoothing applies to this array
   bool adjust;        // perturbation or clamp applies (false for a raw array: an aux array is no snapshot of the stream's)
   bool must_own;      // never adopted (the temporal ring's slots)
+  bool vec_smooth;    // a vector snapshot under ftkx_set_vector_smoothing: every component smoothed as the scalar field it is (`smooth` is false)
 };
+
+// the vector smoothing's kernel over the context's mesh, counted by the source's form (ftkx_debug_conv_vec_counts)
+template <class T> static void queue_conv_vec(ftkx_ctx *c, const ftkx::ConvVecSource<T> &src, bool planar, double *dst)
+{
+  ftkx::launch_conv_vec<T>(c->nd, src, (int)c->ext_sz[0], (int)c->ext_sz[1], (int)c->ext_sz[2], c->d_conv_w.as<double>() + kVecSmoothWeights, c->vsmooth_ksize, dst, c->stream);
+  if (planar) c->conv_vec_planar ++; else c->conv_vec_interleaved ++;
+  if (std::is_same<T, float>::value) c->conv_vec_f32 ++;
+}
 
 // dst becomes the snapshot `planes` as a resident slice holds it: nc == 1: one (interleaved) array of n elements; nc 2 or 3: a vector
 // snapshot as one array per component, n elements each, which dst holds as the host-interleaved array of them.  An FP64 array on this
@@ -102,15 +112,20 @@ struct Ingest {
 // dst.  With smoothing, and behind the concat kernel, adjust_kernel<double> runs in place on the output.  With both settings off nothing
 // here is queued that was not queued before there were such settings.
 //
+// A vector snapshot under ftkx_set_vector_smoothing (how.vec_smooth; vec_smooth_ingest_plan): staged like any other source, then ONE kernel,
+// conv_vec_kernel, reads the interleaved array (nc == 1: n counts its elements, nd per vertex) or the planes and writes the smoothed
+// interleaved array -- no concat launch, no widened copy -- and adjust_kernel<double> follows in place.
+//
 // *waits is set where the call has to wait for the context's stream before it returns (IngestPlan::caller_waits).  After a failure dst is
 // the caller's to let go: freed, not pooled.
 template <class T> static int ingest(ftkx_ctx *c, const T *const *planes, int nc, size_t n, const Ingest &how, ftkx_block &dst, bool *waits)
 {
   constexpr bool f32 = std::is_same<T, float>::value;
   const bool planar = nc > 1;
-  bool on_this_device = ftkx::ingest_asks_where(f32, planar, how.smooth, how.adjust, how.on_device);
+  bool on_this_device = how.vec_smooth ? ftkx::vec_smooth_asks_where(planar, how.on_device) : ftkx::ingest_asks_where(f32, planar, how.smooth, how.adjust, how.on_device);
   for (int k = 0; on_this_device && k < nc; k ++) on_this_device = ftkx_pointer_device(planes[k]) == c->device;
-  const ftkx::IngestPlan p = ftkx::ingest_plan(f32, planar, how.smooth, how.adjust, how.on_device, on_this_device, how.must_own);
+  const ftkx::IngestPlan p = how.vec_smooth ? ftkx::vec_smooth_ingest_plan(f32, planar, how.adjust, how.on_device, on_this_device)
+                                            : ftkx::ingest_plan(f32, planar, how.smooth, how.adjust, how.on_device, on_this_device, how.must_own);
   if (p.caller_waits) *waits = true;
   const size_t count = n * (size_t)nc;
   if (p.adopt) { dst = ftkx_block::lent(const_cast<T *>(planes[0]), count * sizeof(double)); return FTKX_OK; }
@@ -157,6 +172,7 @@ template <class T> static int ingest(ftkx_ctx *c, const T *const *planes, int nc
     break;
   case ftkx::INGEST_ADJUST: queue_adjust<T>(c, from[0], count, how.t, out); break;
   case ftkx::INGEST_WIDEN: if constexpr (f32) { ftkx::launch_widen(from[0], count, out, c->stream); c->f32_widened ++; } break;
+  case ftkx::INGEST_CONV_VEC: queue_conv_vec<T>(c, planar ? ftkx::conv_vec_planes<T>(from, nc) : ftkx::conv_vec_interleaved<T>(from[0], c->nd), planar, out); break;
   case ftkx::INGEST_NO_KERNEL: break;
   }
   if (p.then_adjust) queue_adjust<double>(c, out, count, how.t, out);
@@ -171,11 +187,12 @@ template <class T> static int ingest(ftkx_ctx *c, const T *const *planes, int nc
 // kernel in FRONT of the chain an FP64 source takes.  It reads this device's memory only: a host source, one handed over as "device memory
 // of any device" (2) and a pointer of another device go through the context's f32_stage block as they came, count * the element's size
 // bytes, under the ordering said above (ingest).  It writes dst -- or, where smoothing is set, a pooled array that conv_kernel<double> reads
-// into dst and that goes back to the pool in stream order; adjust_kernel<double> follows in place.  Never adopted.
+// into dst (a vector under ftkx_set_vector_smoothing: conv_vec_kernel<double>) and that goes back to the pool in stream order;
+// adjust_kernel<double> follows in place.  Never adopted.
 static int ingest_narrow(ftkx_ctx *c, const void *src, int dtype, size_t count, const Ingest &how, ftkx_block &dst, bool *waits)
 {
   const bool on_this_device = ftkx::narrow_ingest_asks_where(how.on_device) && ftkx_pointer_device(src) == c->device;
-  const ftkx::NarrowIngestPlan p = ftkx::narrow_ingest_plan(how.smooth, how.adjust, how.on_device, on_this_device);
+  const ftkx::NarrowIngestPlan p = ftkx::narrow_ingest_plan(how.smooth || how.vec_smooth, how.adjust, how.on_device, on_this_device);
   if (p.caller_waits) *waits = true;
   if (int rc = take_pooled(c, count, dst)) return rc;
   double *const out = dst.as<double>();
@@ -194,7 +211,9 @@ static int ingest_narrow(ftkx_ctx *c, const void *src, int dtype, size_t count, 
   if (p.to_pooled) { if (int rc = take_pooled(c, count, tmp)) return rc; }
   ftkx::launch_narrow(dtype, from, count, p.to_pooled ? tmp.as<double>() : out, c->stream);
   c->narrow_launches[dtype] ++;
-  if (p.to_pooled)
+  if (p.to_pooled && how.vec_smooth)
+    queue_conv_vec<double>(c, ftkx::conv_vec_interleaved<double>(tmp.as<double>(), c->nd), false, out);
+  else if (p.to_pooled)
     ftkx::launch_conv<double>(c->nd, tmp.as<double>(), (int)c->ext_sz[0], (int)c->ext_sz[1], (int)c->ext_sz[2], c->d_conv_w.as<double>() + kSmoothWeights, c->smooth_ksize, out, c->stream);
   if (p.then_adjust) queue_adjust<double>(c, out, count, how.t, out);
   const hipError_t e = hipGetLastError();
@@ -246,7 +265,11 @@ template <class T> static int push_common(ftkx_ctx *c, int t, const T *V, const 
     if (int rc = planar_args<T>(c, "push", Vc, nc, n, nullptr)) return rc;
   }
   // conv_gaussian dispatches on the array's nd(): a vector field would be convolved across its components (conv.hh:213-221) -- not reproduced
-  if (c->smooth_ksize && !scalar_only) return fail(c, FTKX_E_UNSUPPORTED, "push: spatial smoothing is set and takes scalar slices only (ftkx_push_scalar_slice)");
+  // (ftkx_set_vector_smoothing is the setting for vectors: every component as the scalar field it is; where it is on it decides)
+  const bool vec_smooth = !scalar_only && c->vsmooth_ksize != 0;
+  if (c->smooth_ksize && !scalar_only && !vec_smooth) return fail(c, FTKX_E_UNSUPPORTED, "push: spatial smoothing is set and takes scalar slices only (ftkx_push_scalar_slice; vectors: ftkx_set_vector_smoothing)");
+  // a given Jacobian, or scalar, does not belong to the smoothed field
+  if (vec_smooth && (J || S)) return fail(c, FTKX_E_UNSUPPORTED, "push: vector smoothing is set and takes V alone (no J, no S beside it)");
   // the stream delivers ONE array, which perturb() and clamp() walk over (all n * nd elements of a vector field, by their flat index)
   const bool adjust = c->adj.on();
   if (adjust && !scalar_only && (J || S)) return fail(c, FTKX_E_UNSUPPORTED, "push: perturbation or clamp is set and takes V alone (no J, no S beside it)");
@@ -254,17 +277,17 @@ template <class T> static int push_common(ftkx_ctx *c, int t, const T *V, const 
   evict_slice(c, t);
   Slice s;      // (here and below: what was already taken is freed with `s`)
   bool waits = false;
-  // one interleaved array of the push (null: none); smoothing applies to S alone: vector pushes were refused above
-  auto take = [&](const T *src, size_t count, bool smooth, ftkx_block &dst) -> int {
-    return src ? ingest_array<T>(c, src, dtype, count, Ingest{on_device, t, smooth, adjust, false}, dst, &waits) : FTKX_OK;
+  // one interleaved array of the push (null: none); the scalar smoothing applies to S alone, the vector smoothing to V alone
+  auto take = [&](const T *src, size_t count, bool smooth, ftkx_block &dst, bool vsmooth = false) -> int {
+    return src ? ingest_array<T>(c, src, dtype, count, Ingest{on_device, t, smooth, adjust, false, vsmooth}, dst, &waits) : FTKX_OK;
   };
   auto take_planes = [&]() -> int {
     if constexpr (std::is_void<T>::value) return fail(c, FTKX_E_INVALID, "push: planes of narrow elements are not taken");
-    else return ingest<T>(c, Vc, nc, n, Ingest{on_device, t, false, adjust, false}, s.V, &waits);
+    else return ingest<T>(c, Vc, nc, n, Ingest{on_device, t, false, adjust, false, vec_smooth}, s.V, &waits);
   };
-  if (int rc = take(S, n, c->smooth_ksize != 0, s.S)) return rc;
+  if (int rc = take(S, n, scalar_only && c->smooth_ksize != 0, s.S)) return rc;
   if (!scalar_only) {
-    if (int rc = planar ? take_planes() : take(V, n * nd, false, s.V)) return rc;
+    if (int rc = planar ? take_planes() : take(V, n * nd, false, s.V, vec_smooth)) return rc;
     if (int rc = take(J, n * nd * nd, false, s.J)) return rc;
   }
   // scalar input: V = gradient2D/3D(S) is never materialised -- every kernel evaluates it where it needs it, with the
@@ -281,7 +304,7 @@ namespace ftkxh {
 
 // The library's own push of an array that IS a resident slice's already (slab.cpp: the upper neighbour's first slice): `full` becomes the
 // borrowed resident slice t, scalar or vector by the context's mode, behind the checks of a public on_device 1 push -- and as a raw array,
-// whatever smoothing, perturbation or clamp the context has set: its owner's push has applied them.
+// whatever smoothing (scalar or vector), perturbation or clamp the context has set: its owner's push has applied them.
 int adopt_resident_slice(ftkx_ctx *c, int t, const double *full)
 {
   if (c) c->ahead.clear();
@@ -292,7 +315,7 @@ int adopt_resident_slice(ftkx_ctx *c, int t, const double *full)
   evict_slice(c, t);
   Slice s;
   bool waits = false;
-  if (int rc = ingest<double>(c, &full, 1, n_vertices(c) * (scalar_only ? 1 : (size_t)c->nd), Ingest{1, t, false, false, false}, scalar_only ? s.S : s.V, &waits)) return rc;
+  if (int rc = ingest<double>(c, &full, 1, n_vertices(c) * (scalar_only ? 1 : (size_t)c->nd), Ingest{1, t, false, false, false, false}, scalar_only ? s.S : s.V, &waits)) return rc;
   install_slice(c, t, s, scalar_only);
   return FTKX_OK;
 }
@@ -342,7 +365,7 @@ template <class T> static int push_aux_common(ftkx_ctx *c, int t, int slot, cons
   ftkx_block b;      // (after a failure: freed, not pooled)
   bool waits = false;
   // a raw array: perturbation and clamp pass it by, and so does the smoothing
-  if (int rc = ingest<T>(c, &A, 1, n_vertices(c), Ingest{on_device, t, false, false, false}, b, &waits)) return rc;
+  if (int rc = ingest<T>(c, &A, 1, n_vertices(c), Ingest{on_device, t, false, false, false, false}, b, &waits)) return rc;
   // a device source that was not adopted is read by a copy or by the widen kernel: the call returns once it has been read
   if (waits) HIP_TRY(c, hipStreamSynchronize(c->stream));
   ftkx_block &dst = c->aux[t].A[slot - 1];
@@ -404,7 +427,8 @@ template <class T> static int temporal_push_common(ftkx_ctx *c, const T *A, int 
     if (nc != c->nd) return fail(c, FTKX_E_INVALID, "ftkx_temporal_push: %d planes for a context of %d dimensions", nc, c->nd);
     if (int rc = planar_args<T>(c, "ftkx_temporal_push", planes, nc, n_vertices(c), nullptr)) return rc;
   }
-  if (c->smooth_ksize && !scalar) return fail(c, FTKX_E_UNSUPPORTED, "ftkx_temporal_push: spatial smoothing is set and takes scalar snapshots only");
+  const bool vec_smooth = !scalar && c->vsmooth_ksize != 0;
+  if (c->smooth_ksize && !scalar && !vec_smooth) return fail(c, FTKX_E_UNSUPPORTED, "ftkx_temporal_push: spatial smoothing is set and takes scalar snapshots only (vectors: ftkx_set_vector_smoothing)");
   HIP_TRY(c, hipSetDevice(c->device));
   const size_t count = n_vertices(c) * (scalar ? 1 : (size_t)c->nd);
   if (!c->tm_ring.empty() && c->tm_ring.front().count<double>() != count) return fail(c, FTKX_E_INVALID, "ftkx_temporal_push: the mesh changed within a series");
@@ -414,7 +438,7 @@ template <class T> static int temporal_push_common(ftkx_ctx *c, const T *A, int 
   // widened where it is float32, convolved where smoothing is set, perturbed and clamped where those are set -- as raw snapshot number t0 + the
   // pushes of this series so far, which is the timestep of the emission centred on it
   if (c->tm.kind < 0 && c->tm.size == 0) { c->tm_t0 = c->tm_next; c->tm_pushed = 0; }      // the series' first snapshot
-  const Ingest how{on_device, c->tm_t0 + (int)c->tm_pushed, c->smooth_ksize != 0, c->adj.on(), true};
+  const Ingest how{on_device, c->tm_t0 + (int)c->tm_pushed, scalar && c->smooth_ksize != 0, c->adj.on(), true, vec_smooth};
   bool waits = false;
   auto take_planes = [&]() -> int {
     if constexpr (std::is_void<T>::value) return fail(c, FTKX_E_INVALID, "ftkx_temporal_push: planes of narrow elements are not taken");
@@ -446,7 +470,7 @@ static bool conv_ksize_ok(int ksize) { return ksize >= 1 && ksize <= 9 && (ksize
 
 static int conv_weights(ftkx_ctx *c, const double *weights, int n, size_t at)
 {
-  if (const int rc = c->d_conv_w.reserve(c, 2 * kSmoothWeights * sizeof(double))) return rc;
+  if (const int rc = c->d_conv_w.reserve(c, 3 * kSmoothWeights * sizeof(double))) return rc;
   HIP_TRY(c, hipMemcpyAsync(c->d_conv_w.as<double>() + at, weights, (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
   return FTKX_OK;
 }
@@ -465,6 +489,32 @@ template <class T> static int conv_common(ftkx_ctx *c, int nd, const T *S, int D
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipStreamSynchronize(c->stream));      // (the next call may overwrite the weights; the caller may read `out`)
   return FTKX_OK;
+}
+
+// The vector convolution alone on device pointers: V (interleaved, nd components) or, where V is null, nd planes; `reps` times back to back,
+// ms (nullable: reps == 1) the time of every launch.  Argument errors as conv_common's; every source array must stay clear of `out`.
+template <class T> static int conv_vec_common(ftkx_ctx *c, const char *who, int nd, const T *V, const T *const *planes, int DW, int DH, int DD, const double *weights, int ksize, double *out,
+                                              int reps, double *ms)
+{
+  DERIVE_PROLOGUE(c);
+  if (nd != 2 && nd != 3) return fail(c, FTKX_E_INVALID, "%s: nd must be 2 or 3", who);
+  if ((!V && !planes) || !out || !weights || (ms ? reps < 1 : reps != 1)) return fail(c, FTKX_E_INVALID, "%s: null argument", who);
+  if (nd == 2) DD = 1;
+  if (DW < 1 || DH < 1 || DD < 1) return fail(c, FTKX_E_INVALID, "%s: extents must be positive", who);
+  if (!conv_ksize_ok(ksize)) return fail(c, FTKX_E_INVALID, "%s: ksize must be odd and in [1, 9] (got %d)", who, ksize);
+  const size_t n = (size_t)DW * (size_t)DH * (size_t)DD;
+  if ((size_t)out & 7) return fail(c, FTKX_E_INVALID, "%s: out must be a multiple of 8", who);
+  for (int k = 0; k < (V ? 1 : nd); k ++) {
+    const T *a = V ? V : planes[k];
+    const size_t count = V ? n * (size_t)nd : n;
+    if (!a) return fail(c, FTKX_E_INVALID, "%s: plane %d is null", who, k);
+    if ((size_t)a & (sizeof(T) - 1)) return fail(c, FTKX_E_INVALID, "%s: an input is not a multiple of its element's size", who);
+    if ((const char *)a < (const char *)(out + n * (size_t)nd) && (const char *)out < (const char *)(a + count)) return fail(c, FTKX_E_INVALID, "%s: input and output overlap", who);
+  }
+  if (int rc = conv_weights(c, weights, ksize * ksize * (nd == 3 ? ksize : 1), 0)) return rc;
+  const ftkx::ConvVecSource<T> src = V ? ftkx::conv_vec_interleaved<T>(V, nd) : ftkx::conv_vec_planes<T>(planes, nd);
+  // (the stream is waited for: the next call may overwrite the weights; the caller may read `out`)
+  return timed_relaunch(c, reps, ms, [&] { ftkx::launch_conv_vec<T>(nd, src, DW, DH, DD, c->d_conv_w.as<double>(), ksize, out, c->stream); });
 }
 
 static int widen_args(ftkx_ctx *c, const char *who, const float *src, size_t count, const double *dst)
@@ -656,6 +706,55 @@ int ftkx_set_spatial_smoothing(ftkx_ctx *c, double sigma, int ksize)
   if (int rc = conv_weights(c, w, ksize * ksize * (c->nd == 3 ? ksize : 1), kSmoothWeights)) return rc;
   HIP_TRY(c, hipStreamSynchronize(c->stream));      // (`w` is this call's)
   c->smooth_ksize = ksize; c->smooth_sigma = sigma;
+  return FTKX_OK;
+}
+
+// ---- spatial smoothing of vector arrays, per component (conv_vec_kernels.hip) ------------------------------------------------------------------
+int ftkx_conv2D_vec(ftkx_ctx *c, const double *V, int DW, int DH, const double *weights, int ksize, double *out)
+{ return conv_vec_common<double>(c, "ftkx_conv2D_vec", 2, V, nullptr, DW, DH, 1, weights, ksize, out, 1, nullptr); }
+int ftkx_conv3D_vec(ftkx_ctx *c, const double *V, int DW, int DH, int DD, const double *weights, int ksize, double *out)
+{ return conv_vec_common<double>(c, "ftkx_conv3D_vec", 3, V, nullptr, DW, DH, DD, weights, ksize, out, 1, nullptr); }
+int ftkx_conv2D_vec_f32(ftkx_ctx *c, const float *V, int DW, int DH, const double *weights, int ksize, double *out)
+{ return conv_vec_common<float>(c, "ftkx_conv2D_vec_f32", 2, V, nullptr, DW, DH, 1, weights, ksize, out, 1, nullptr); }
+int ftkx_conv3D_vec_f32(ftkx_ctx *c, const float *V, int DW, int DH, int DD, const double *weights, int ksize, double *out)
+{ return conv_vec_common<float>(c, "ftkx_conv3D_vec_f32", 3, V, nullptr, DW, DH, DD, weights, ksize, out, 1, nullptr); }
+int ftkx_conv_planar(ftkx_ctx *c, int nd, const double *const *planes, int DW, int DH, int DD, const double *weights, int ksize, double *out)
+{ return conv_vec_common<double>(c, "ftkx_conv_planar", nd, nullptr, planes, DW, DH, DD, weights, ksize, out, 1, nullptr); }
+int ftkx_conv_planar_f32(ftkx_ctx *c, int nd, const float *const *planes, int DW, int DH, int DD, const double *weights, int ksize, double *out)
+{ return conv_vec_common<float>(c, "ftkx_conv_planar_f32", nd, nullptr, planes, DW, DH, DD, weights, ksize, out, 1, nullptr); }
+
+// profiling aid (tools/conv_vec_time.py): the kernel `reps` times back to back
+int ftkx_debug_conv_vec_relaunch(ftkx_ctx *c, int nd, const void *const *src, int planar, int src_is_f32, int DW, int DH, int DD, const double *weights, int ksize, double *out, int reps, double *ms)
+{
+  if (c && (!src || !ms || reps < 1)) return fail(c, FTKX_E_INVALID, "ftkx_debug_conv_vec_relaunch: bad argument");
+  if (src_is_f32) return conv_vec_common<float>(c, "ftkx_debug_conv_vec_relaunch", nd, planar || !src ? nullptr : static_cast<const float *>(src[0]), planar ? reinterpret_cast<const float *const *>(src) : nullptr,
+                                                DW, DH, DD, weights, ksize, out, reps, ms);
+  return conv_vec_common<double>(c, "ftkx_debug_conv_vec_relaunch", nd, planar || !src ? nullptr : static_cast<const double *>(src[0]), planar ? reinterpret_cast<const double *const *>(src) : nullptr,
+                                 DW, DH, DD, weights, ksize, out, reps, ms);
+}
+
+int ftkx_debug_conv_vec_counts(const ftkx_ctx *c, unsigned long long *interleaved, unsigned long long *planar, unsigned long long *f32)
+{
+  if (!c) return fail(nullptr, FTKX_E_INVALID, "null context");
+  if (interleaved) *interleaved = c->conv_vec_interleaved;
+  if (planar) *planar = c->conv_vec_planar;
+  if (f32) *f32 = c->conv_vec_f32;
+  return FTKX_OK;
+}
+
+int ftkx_set_vector_smoothing(ftkx_ctx *c, double sigma, int ksize)
+{
+  if (c) c->ahead.clear();
+  if (!c) return fail(nullptr, FTKX_E_INVALID, "null context");
+  if (int rc = settings_not_now(c, "ftkx_set_vector_smoothing")) return rc;
+  if (ksize == 0) { c->vsmooth_ksize = 0; c->vsmooth_sigma = 0; return FTKX_OK; }
+  double w[kSmoothWeights];
+  if (int rc = ftkx_gaussian_kernel(c->nd, sigma, ksize, w)) { c->err = global_error(); return rc; }
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));      // (a push queued under the old weights still reads them)
+  if (int rc = conv_weights(c, w, ksize * ksize * (c->nd == 3 ? ksize : 1), kVecSmoothWeights)) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));      // (`w` is this call's)
+  c->vsmooth_ksize = ksize; c->vsmooth_sigma = sigma;
   return FTKX_OK;
 }
 

@@ -5,7 +5,9 @@
 // The case: the source's element type (f32: float, else double), its form (planar: one array per component, else one interleaved array),
 // whether the spatial smoothing applies (smooth), whether perturbation or clamp applies (adjust: false for a raw array -- an aux array),
 // where the caller says it lies (on_device 0 host, 1 this device and borrowable, 2 device memory of any device) and whether every source
-// pointer IS device memory of the context's device (on_this_device).  planar && smooth is refused by every caller before the plan is asked.
+// pointer IS device memory of the context's device (on_this_device).  planar && smooth is never asked of ingest_plan: `smooth` is the SCALAR
+// smoothing, which takes no vectors.  A vector snapshot under ftkx_set_vector_smoothing has a plan of its own, vec_smooth_ingest_plan below
+// (tests/test_vec_smooth_plan_host.py).
 // Sources narrower than a float have a plan of their own, narrow_ingest_plan below (tests/test_narrow_plan_host.py).
 #pragma once
 
@@ -14,9 +16,10 @@ namespace ftkx {
 enum IngestStage { INGEST_STAGE_NONE = 0, INGEST_STAGE_F32, INGEST_STAGE_POOLED };       // the context's f32_stage block / a pooled field array
 enum IngestCopy { INGEST_COPY_NONE = 0, INGEST_COPY_TO_DST, INGEST_COPY_TO_STAGE };      // where the source is copied to
 // the first kernel of the chain: it writes dst.  INGEST_ADJUST is adjust_kernel<T> on the source's own type (float: in place of the widen kernel)
-enum IngestKernel { INGEST_NO_KERNEL = 0, INGEST_CONCAT, INGEST_CONV, INGEST_ADJUST, INGEST_WIDEN };
+enum IngestKernel { INGEST_NO_KERNEL = 0, INGEST_CONCAT, INGEST_CONV, INGEST_ADJUST, INGEST_WIDEN, INGEST_CONV_VEC };
 // which of the context's debug counters the chain moves, as bits (planar: planar_vec or planar_scalar, by what launch_concat returns)
-enum IngestCounter { INGEST_CNT_FROM_FLOAT = 1, INGEST_CNT_IN_PLACE = 2, INGEST_CNT_OUT_OF_PLACE = 4, INGEST_CNT_F32_WIDENED = 8, INGEST_CNT_F32_DIRECT = 16, INGEST_CNT_PLANAR = 32 };
+enum IngestCounter { INGEST_CNT_FROM_FLOAT = 1, INGEST_CNT_IN_PLACE = 2, INGEST_CNT_OUT_OF_PLACE = 4, INGEST_CNT_F32_WIDENED = 8, INGEST_CNT_F32_DIRECT = 16, INGEST_CNT_PLANAR = 32,
+                     INGEST_CNT_VEC_INTERLEAVED = 64, INGEST_CNT_VEC_PLANAR = 128, INGEST_CNT_VEC_F32 = 256 };      // ftkx_debug_conv_vec_counts
 
 struct IngestPlan {
   bool reads_here;        // a kernel may read the caller's pointers where they lie
@@ -62,9 +65,28 @@ inline IngestPlan ingest_plan(bool f32, bool planar, bool smooth, bool adjust, i
   return p;
 }
 
+// ---- vector snapshots under ftkx_set_vector_smoothing (conv_vec_steps.hpp) ------------------------------------------------------------------
+// The case: f32, planar, adjust, on_device and on_this_device as above; `smooth` is not asked (the scalar smoothing passes vectors by).  ONE
+// kernel, conv_vec_kernel, reads the source -- an interleaved array or planes, floats widened as they are staged -- and writes the smoothed,
+// interleaved FP64 array into dst: no concat launch for planes, no widened copy for floats; adjust_kernel<double> follows in place.  The
+// kernel reads this device's memory only, so where the source lies and how it is staged is what ingest_plan says for a smoothed scalar or
+// for planes: a pooled array (FP64) or the f32_stage block (floats).  Never adopted, and a device source has been read when the call returns.
+inline bool vec_smooth_asks_where(bool planar, int on_device) { return planar ? on_device == 1 : on_device != 0; }
+
+inline IngestPlan vec_smooth_ingest_plan(bool f32, bool planar, bool adjust, int on_device, bool on_this_device)
+{
+  IngestPlan p{false, false, false, INGEST_STAGE_NONE, INGEST_COPY_NONE, INGEST_CONV_VEC, adjust, 0u};
+  p.reads_here = vec_smooth_asks_where(planar, on_device) && on_this_device;
+  p.caller_waits = on_device != 0;
+  if (!p.reads_here) { p.stage = f32 ? INGEST_STAGE_F32 : INGEST_STAGE_POOLED; p.copy = INGEST_COPY_TO_STAGE; }
+  p.counters = (planar ? INGEST_CNT_VEC_PLANAR : INGEST_CNT_VEC_INTERLEAVED) | (f32 ? INGEST_CNT_VEC_F32 : 0u) | (adjust ? INGEST_CNT_IN_PLACE : 0u);
+  return p;
+}
+
 // ---- narrow sources: half, bfloat16, 8- / 16- / 32-bit integers (narrow_steps.hpp) ----------------------------------------------------------
 // They go IN FRONT of the chain above, not into it: the narrow kernel writes the FP64 array, and what follows is what follows an FP64 source
-// that was copied into the slice -- conv_kernel<double> out of a pooled array where smoothing is set, adjust_kernel<double> in place.  Neither
+// that was copied into the slice -- conv_kernel<double> (a vector under ftkx_set_vector_smoothing: conv_vec_kernel<double>, and `smooth`
+// is that setting) out of a pooled array where smoothing is set, adjust_kernel<double> in place.  Neither
 // kernel gets an instantiation per narrow type.  The case: smooth, adjust, on_device and on_this_device as above (always one interleaved
 // array; planes of narrow elements are not taken).
 struct NarrowIngestPlan {

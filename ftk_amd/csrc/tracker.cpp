@@ -495,6 +495,7 @@ void critical_point_tracker_regular::apply_configuration(ftkx_ctx *c)
   for (size_t i = 0; i < 6 && i < bounds_coords.size(); i ++) o.coords_bounds[i] = bounds_coords[i];
   check_on(c, ftkx_set_options(c, &o));
   check_on(c, ftkx_set_spatial_smoothing(c, spatial_smoothing_sigma, spatial_smoothing_ksize));
+  check_on(c, ftkx_set_vector_smoothing(c, vector_smoothing_sigma, vector_smoothing_ksize));
   check_on(c, ftkx_set_perturbation(c, perturbation_sigma, perturbation_seed));
   check_on(c, ftkx_set_clamp(c, clamp_on ? 1 : 0, clamp_lo, clamp_hi));
   check_on(c, ftkx_set_temporal_smoothing(c, temporal_smoothing_sigma, temporal_smoothing_ksize, next_push_timestep));
@@ -608,7 +609,8 @@ void critical_point_tracker_regular::push_scalar(const void *s, bool device, int
 void critical_point_tracker_regular::push_vector(const void *v, bool device, int dtype, int planes)
 {
   if (!initialized) throw ftkx_error(FTKX_E_INVALID, "push: initialize() first");
-  if (spatial_smoothing_ksize) throw ftkx_error(FTKX_E_UNSUPPORTED, "push_vector_field_snapshot: spatial smoothing takes scalar snapshots only");
+  if (spatial_smoothing_ksize && !vector_smoothing_ksize)
+    throw ftkx_error(FTKX_E_UNSUPPORTED, "push_vector_field_snapshot: spatial smoothing takes scalar snapshots only (vectors: set_vector_spatial_smoothing)");
   push_snapshot(1, nullptr, v, nullptr, device, dtype, planes);       // J derived at hits when jacobian_field_source == SOURCE_DERIVED
 }
 
@@ -616,6 +618,7 @@ void critical_point_tracker_regular::push_field_data(const void *s, const void *
 {
   if (!initialized) throw ftkx_error(FTKX_E_INVALID, "push: initialize() first");
   if (spatial_smoothing_ksize) throw ftkx_error(FTKX_E_UNSUPPORTED, "push_field_data_snapshot: spatial smoothing takes scalar snapshots only");
+  if (vector_smoothing_ksize) throw ftkx_error(FTKX_E_UNSUPPORTED, "push_field_data_snapshot: vector smoothing takes a vector snapshot alone (a given J or S does not belong to the smoothed field)");
   if (perturbation_sigma > 0 || clamp_on) throw ftkx_error(FTKX_E_UNSUPPORTED, "push_field_data_snapshot: perturbation and clamp take a scalar or a vector snapshot alone");
   push_snapshot(2, s, v, j, device, dtype);
 }
@@ -1111,6 +1114,7 @@ int ftkx_tracker_set_flags(ftkx_tracker *h, int robust, int use_tf, unsigned tf,
 }
 int ftkx_tracker_set_stream(ftkx_tracker *h, void *s) { return guarded(h, [&] { h->t->set_stream(s); }); }
 int ftkx_tracker_set_spatial_smoothing(ftkx_tracker *h, double sigma, int ksize) { return guarded(h, [&] { h->t->set_spatial_smoothing(sigma, ksize); }); }
+int ftkx_tracker_set_vector_spatial_smoothing(ftkx_tracker *h, double sigma, int ksize) { return guarded(h, [&] { h->t->set_vector_spatial_smoothing(sigma, ksize); }); }
 int ftkx_tracker_set_perturbation(ftkx_tracker *h, double sigma, unsigned long long seed) { return guarded(h, [&] { h->t->set_perturbation(sigma, seed); }); }
 int ftkx_tracker_set_clamp(ftkx_tracker *h, int on, double lo, double hi) { return guarded(h, [&] { if (on) h->t->set_clamp(lo, hi); else h->t->unset_clamp(); }); }
 int ftkx_tracker_set_temporal_smoothing(ftkx_tracker *h, double sigma, int ksize) { return guarded(h, [&] { h->t->set_temporal_smoothing(sigma, ksize); }); }

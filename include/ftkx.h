@@ -441,8 +441,9 @@ int ftkx_conv3D(ftkx_ctx *ctx, const double *S, int DW, int DH, int DD, const do
 /* ksize 0 (the default): off.  While on, ftkx_push_scalar_slice makes conv(S) the resident slice -- masks, resolution, halo export and
  * patches see the smoothed array.  A host source is staged into a pooled buffer and convolved into the slice's; with on_device = 1 the
  * caller's array is read, never written and NOT adopted: the context owns the smoothed copy and the call returns once the source has been
- * read, as with 2.  ftkx_push_slice (vector input) fails with FTKX_E_UNSUPPORTED while smoothing is on: conv_gaussian dispatches on nd()
- * and would convolve a vector field across its components.
+ * read, as with 2.  ftkx_push_slice (vector input) fails with FTKX_E_UNSUPPORTED while only this setting is on: conv_gaussian dispatches
+ * on nd() and would convolve a vector field across its components.  Vector snapshots have a setting of their own, which smooths every
+ * component as the scalar field it is: ftkx_set_vector_smoothing (below, behind the planar pushes).
  * Every push is taken for a RAW snapshot.  An array that is smoothed already -- the resident slice of another context, handed over whole
  * where a slab pass asks for its halo slice as a whole (ftkx_series_dist_status: asked < 0) -- must be pushed with smoothing switched off
  * around that push, or it is convolved twice.  ftkx_slab_* (include/ftkx_slab.h) and the tracker's slab mode do that themselves; the compact
@@ -599,6 +600,40 @@ int ftkx_concat_f32(ftkx_ctx *ctx, const float *const *planes, int nc, size_t co
 int ftkx_debug_concat_relaunch(ftkx_ctx *ctx, const void *const *planes, int nc, int planes_are_f32, size_t count, double *dst, int reps, double *ms);
 /* launches of the concat kernel by this context so far: with the 16-byte body, and vertex by vertex.  Either may be null. */
 int ftkx_debug_planar_counts(const ftkx_ctx *ctx, unsigned long long *vec_launches, unsigned long long *scalar_launches);
+
+/* ---- spatial Gaussian smoothing of VECTOR arrays, every component as the scalar field it is (conv_vec_kernels.hip) ----
+ * For an array V of nc components (nc = nd: 2 in 2D, 3 in 3D):
+ *     conv_vec(V)[c + nc * i] == conv(plane_c)[i]        with plane_c[i] = V[c + nc * i]
+ * where conv is exactly what ftkx_conv2D / ftkx_conv3D compute -- no tolerance: byte for byte that kernel's output per plane, interleaved.
+ * Components never mix.  (Not the reference's conv_gaussian on such an array, which would convolve across the component axis.)  ONE launch
+ * handles the whole array.  A float32 source is widened as it is staged; planes (ftkx_conv_planar: nd device pointers in a HOST array, DW *
+ * DH (* DD) elements each; nd 2: DD ignored) follow the same rule with plane_c given directly and give the same interleaved FP64 output.
+ * All array pointers are DEVICE pointers; out: nc * DW * DH (* DD) doubles; weights: a HOST array of ksize^nd doubles.  FTKX_E_INVALID: a
+ * null pointer, a non-positive extent, ksize even or outside [1, 9], nd not 2 or 3, an input overlapping the output.  The call returns when
+ * `out` is complete. */
+int ftkx_conv2D_vec(ftkx_ctx *ctx, const double *V, int DW, int DH, const double *weights, int ksize, double *out);
+int ftkx_conv3D_vec(ftkx_ctx *ctx, const double *V, int DW, int DH, int DD, const double *weights, int ksize, double *out);
+int ftkx_conv2D_vec_f32(ftkx_ctx *ctx, const float *V, int DW, int DH, const double *weights, int ksize, double *out);
+int ftkx_conv3D_vec_f32(ftkx_ctx *ctx, const float *V, int DW, int DH, int DD, const double *weights, int ksize, double *out);
+int ftkx_conv_planar(ftkx_ctx *ctx, int nd, const double *const *planes, int DW, int DH, int DD, const double *weights, int ksize, double *out);
+int ftkx_conv_planar_f32(ftkx_ctx *ctx, int nd, const float *const *planes, int DW, int DH, int DD, const double *weights, int ksize, double *out);
+/* ksize 0 (the default): off.  A setting of its own beside ftkx_set_spatial_smoothing, which keeps refusing vectors where it alone is set;
+ * scalar pushes are never touched by this one.  While on, ftkx_push_slice, _f32, _typed, ftkx_push_slice_planar, _f32 and -- with a vector --
+ * ftkx_temporal_push, _f32, _typed, ftkx_temporal_push_planar, _f32 make conv_vec(V), under ftkx_gaussian_kernel(nd, sigma, ksize), the
+ * resident V (the ring's snapshot): masks, resolution, halo export and patches see the smoothed array, and with derive_jacobian the Jacobian
+ * at hits comes from it.  The stream's order holds: widen -> smooth -> perturb -> clamp -> temporal ring.  Planes are smoothed and
+ * interleaved by the one kernel (no concat launch: ftkx_debug_planar_counts does not move); floats are widened as the kernel stages them;
+ * narrower types are widened into a pooled array that the FP64 kernel reads.  on_device = 1: read before the call returns, never adopted.
+ * J or S beside V: FTKX_E_UNSUPPORTED -- a given Jacobian does not belong to the smoothed field.  Every push is taken for a RAW snapshot
+ * (see ftkx_set_spatial_smoothing); the slab pass's hand-over of a whole slice sets this setting aside as it does that one.
+ * Refused while sweeps are pending or series passes are open. */
+int ftkx_set_vector_smoothing(ftkx_ctx *ctx, double sigma, int ksize);
+/* profiling aid (tools/conv_vec_time.py): the kernel launched `reps` times back to back, a pair of events around every launch; src: a HOST
+ * array of device pointers -- planar: nd planes, else src[0] is the interleaved array; ms: reps device times. */
+int ftkx_debug_conv_vec_relaunch(ftkx_ctx *ctx, int nd, const void *const *src, int planar, int src_is_f32, int DW, int DH, int DD, const double *weights, int ksize, double *out,
+                                 int reps, double *ms);
+/* launches of the kernel by this context's pushes: from an interleaved source, from planes, and how many of either read float32 */
+int ftkx_debug_conv_vec_counts(const ftkx_ctx *ctx, unsigned long long *interleaved, unsigned long long *planar, unsigned long long *f32);
 
 /* ---- perturbation and clamp of snapshots (ndarray::perturb, ndarray::clamp; the stream's "perturbation" and "clamp") ---- */
 /* The two steps ndarray_stream::modified_callback (stream.hh:1570-1604) runs between the spatial smoothing and the temporal filter:

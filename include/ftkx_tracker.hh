@@ -159,6 +159,13 @@ public:
   // ksize, ksize / 2) on the device (ftkx_set_spatial_smoothing).  Set before initialize(); ksize 0: off (the default).  Scalar input only:
   // a push that hands over a vector field while this is set throws FTKX_E_UNSUPPORTED.
   void set_spatial_smoothing(double sigma, int ksize = 3) { spatial_smoothing_sigma = sigma; spatial_smoothing_ksize = ksize; }
+  // Not in the reference (whose conv_gaussian would convolve a vector array across its components): every VECTOR snapshot pushed after
+  // initialize() -- push_vector_field_snapshot (double, float, typed), push_vector_field_components -- has each of its components smoothed
+  // as the scalar field it is, conv_gaussian(component, sigma, ksize, ksize / 2), by one kernel on the device (ftkx_set_vector_smoothing);
+  // with a derived Jacobian, the Jacobian at hits is the smoothed field's.  A setting of its own: scalar pushes pass it by.  Works in slab
+  // mode, with several devices (a halo snapshot is smoothed on both devices that receive it, alike) and in front of the temporal filter.
+  // push_field_data_snapshot throws FTKX_E_UNSUPPORTED while it is on.  Set before initialize(); ksize 0: off (the default).
+  void set_vector_spatial_smoothing(double sigma, int ksize = 3) { vector_smoothing_sigma = sigma; vector_smoothing_ksize = ksize; }
   // The stream's --temporal-smoothing-kernel / --temporal-smoothing-kernel-size (ftk::streaming_filter behind ndarray_stream; 5 is the
   // stream's default size): the snapshots pushed after initialize() are RAW and feed the filter on the device (ftkx_temporal_push, behind
   // the spatial smoothing where that is set too); the tracker sees the smoothed series.  The filter answers H - 1 = ksize / 2 pushes late:
@@ -353,6 +360,8 @@ protected:
   bool trace_on_device = false;
   double spatial_smoothing_sigma = 0;
   int spatial_smoothing_ksize = 0;
+  double vector_smoothing_sigma = 0;
+  int vector_smoothing_ksize = 0;
   double perturbation_sigma = 0, clamp_lo = 0, clamp_hi = 0;
   unsigned long long perturbation_seed = 0;
   bool clamp_on = false;
@@ -439,6 +448,7 @@ int  ftkx_tracker_set_sources(ftkx_tracker *, int scalar, int vector, int jacobi
 int  ftkx_tracker_set_flags(ftkx_tracker *, int robust, int use_type_filter, unsigned type_filter, int compute_degrees, int exact_only, int tag_mode);
 int  ftkx_tracker_set_stream(ftkx_tracker *, void *hip_stream);
 int  ftkx_tracker_set_current_timestep(ftkx_tracker *, int t);
+int  ftkx_tracker_set_vector_spatial_smoothing(ftkx_tracker *, double sigma, int ksize);   /* every component of a vector snapshot smoothed as a scalar field; ksize 0: off */
 int  ftkx_tracker_set_spatial_smoothing(ftkx_tracker *, double sigma, int ksize);   /* the stream's spatial smoothing in front of the tracker; ksize 0: off */
 int  ftkx_tracker_set_perturbation(ftkx_tracker *, double sigma, unsigned long long seed);   /* the stream's perturbation in front of the tracker; sigma 0: off */
 int  ftkx_tracker_set_clamp(ftkx_tracker *, int on, double lo, double hi);                  /* the stream's clamp in front of the tracker */
