@@ -17,7 +17,7 @@
 //   ftk_ref_driver file <in.bin> <out.bin> [nthreads]      (in.bin: see read_input())
 //   ftk_ref_driver time <in.bin> [nthreads]                (prints sweep seconds, no dump)
 //   ftk_ref_driver tables <out.txt>                         (dumps the unit-simplex tables)
-// options come from the environment (FTK_REF_NO_ROBUST, FTK_REF_TYPE_FILTER, FTK_REF_COORDS, ...); FTK_REF_RESET_RERUN: after the series,
+// options come from the environment (FTK_REF_NO_ROBUST, FTK_REF_TYPE_FILTER, FTK_REF_COORDS, FTK_REF_ARRAY_START, ...); FTK_REF_RESET_RERUN: after the series,
 // tracker.reset() and the series again -- the dump holds the second run (see run())
 #include <cmath>
 #include <cstdio>
@@ -162,23 +162,30 @@ static void run(const input_t &in, int nthreads, const char *out, bool robust, u
   const size_t DW = in.D[0], DH = in.D[1], DD = in.D[2];
   // json_interface.hh:634-656
   const bool push_all = getenv("FTK_REF_PUSH_ALL") != NULL && in.nv == 1;
+  // FTK_REF_ARRAY_START="a,b[,c]": the array lattice begins there instead of at the origin (a VTK extent, a spatial block); the domain keeps
+  // its inset from the array, so both lattices shift by the start.  Unset: all zeros
+  size_t A[3] = {0, 0, 0};
+  if (const char *as = getenv("FTK_REF_ARRAY_START")) {
+    std::string sa(as); size_t pos = 0;
+    for (int d = 0; d < in.nd && pos < sa.size(); d ++) { size_t q = sa.find(',', pos); if (q == std::string::npos) q = sa.size(); A[d] = (size_t)atoi(sa.substr(pos, q - pos).c_str()); pos = q + 1; }
+  }
   if (in.nv == 1) {
     tracker.set_scalar_field_source(ftk::SOURCE_GIVEN);
     tracker.set_vector_field_source(push_all ? ftk::SOURCE_GIVEN : ftk::SOURCE_DERIVED);
     tracker.set_jacobian_field_source(push_all ? ftk::SOURCE_GIVEN : ftk::SOURCE_DERIVED);
     tracker.set_jacobian_symmetric(true);
-    if (in.nd == 2) tracker.set_domain(ftk::lattice({2, 2}, {DW - 3, DH - 3}));
-    else tracker.set_domain(ftk::lattice({2, 2, 2}, {DW - 3, DH - 3, DD - 3}));
+    if (in.nd == 2) tracker.set_domain(ftk::lattice({A[0] + 2, A[1] + 2}, {DW - 3, DH - 3}));
+    else tracker.set_domain(ftk::lattice({A[0] + 2, A[1] + 2, A[2] + 2}, {DW - 3, DH - 3, DD - 3}));
   } else {
     tracker.set_scalar_field_source(ftk::SOURCE_NONE);
     tracker.set_vector_field_source(ftk::SOURCE_GIVEN);
     tracker.set_jacobian_field_source(ftk::SOURCE_DERIVED);
     tracker.set_jacobian_symmetric(false);
-    if (in.nd == 2) tracker.set_domain(ftk::lattice({1, 1}, {DW - 2, DH - 2}));
-    else tracker.set_domain(ftk::lattice({1, 1, 1}, {DW - 2, DH - 2, DD - 2}));
+    if (in.nd == 2) tracker.set_domain(ftk::lattice({A[0] + 1, A[1] + 1}, {DW - 2, DH - 2}));
+    else tracker.set_domain(ftk::lattice({A[0] + 1, A[1] + 1, A[2] + 1}, {DW - 2, DH - 2, DD - 2}));
   }
-  if (in.nd == 2) tracker.set_array_domain(ftk::lattice({0, 0}, {DW, DH}));
-  else tracker.set_array_domain(ftk::lattice({0, 0, 0}, {DW, DH, DD}));
+  if (in.nd == 2) tracker.set_array_domain(ftk::lattice({A[0], A[1]}, {DW, DH}));
+  else tracker.set_array_domain(ftk::lattice({A[0], A[1], A[2]}, {DW, DH, DD}));
   if (nthreads > 0) tracker.set_number_of_threads(nthreads);
   tracker.set_enable_robust_detection(robust);
   if (type_filter) tracker.set_type_filter(type_filter);

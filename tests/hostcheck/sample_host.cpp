@@ -10,7 +10,8 @@
 //   hs_reference_ok(nd, dom_sz[3], t_max)                 the bound under which FTKX_TAG_REFERENCE tags equal the 64-bit ones
 //
 // With -DSAMPLE_HOST_MAIN: a program of its own (for a sanitizer build, not for loading into Python): every simplex type at every corner of a
-// small 2D and 3D mesh under the three tag modes, the arrays allocated at exactly their size.
+// small 2D and 3D mesh under the three tag modes, the arrays allocated at exactly their size -- once with the array lattice at 0 and core =
+// domain, once with the array lattice at (5, 7, 3) and a core one vertex inside the domain on every face.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -116,18 +117,18 @@ u64 tag_of(const SampleMesh &m, const fan_table<ND + 1> &fan, const int *corner,
 }
 
 template <int ND>
-int sweep_all(const fan_table<ND + 1> &fan, int scalar_mode)
+int sweep_all(const fan_table<ND + 1> &fan, int scalar_mode, bool origin)
 {
   constexpr int N = ND + 1;
   SampleMesh m;
   memset(&m, 0, sizeof(m));
   m.scalar_mode = scalar_mode;
-  const int ext[3] = {9, 7, ND == 3 ? 6 : 1}, lo = scalar_mode ? 2 : 1;
+  const int ext[3] = {origin ? 10 : 9, origin ? 9 : 7, ND == 3 ? (origin ? 8 : 6) : 1}, lo = scalar_mode ? 2 : 1, start[3] = {5, 7, 3}, in = origin ? 1 : 0;
   size_t nv = 1;
   for (int d = 0; d < 3; d ++) {
-    m.ext_st[d] = 0; m.ext_sz[d] = ext[d];
-    m.dom_lb[d] = d < ND ? lo : 0; m.dom_sz[d] = d < ND ? ext[d] - 2 * lo : 1;
-    m.core_st[d] = m.dom_lb[d]; m.core_sz[d] = m.dom_sz[d];
+    m.ext_st[d] = origin && d < ND ? start[d] : 0; m.ext_sz[d] = ext[d];
+    m.dom_lb[d] = d < ND ? m.ext_st[d] + lo : 0; m.dom_sz[d] = d < ND ? ext[d] - 2 * lo : 1;
+    m.core_st[d] = d < ND ? m.dom_lb[d] + in : 0; m.core_sz[d] = d < ND ? m.dom_sz[d] - 2 * in : 1;
     nv *= (size_t)ext[d];
   }
   const int nt = 3, t0 = 5;
@@ -149,17 +150,18 @@ int sweep_all(const fan_table<ND + 1> &fan, int scalar_mode)
       for (int type = 0; type < fan_table<N>::NTYPES; type ++) {
         if (!fan.ordinal[type] && t == t0 + nt - 1) continue;
         int c[4] = {0, 0, 0, t};
-        // corners whose cell lies inside the array: up to the domain's last vertex but one
-        for (c[2] = m.dom_lb[2]; c[2] < m.dom_lb[2] + (ND == 3 ? m.dom_sz[2] - 1 : 1); c[2] ++)
-          for (c[1] = m.dom_lb[1]; c[1] < m.dom_lb[1] + m.dom_sz[1] - 1; c[1] ++)
-            for (c[0] = m.dom_lb[0]; c[0] < m.dom_lb[0] + m.dom_sz[0] - 1; c[0] ++) {
+        // the core's corners whose cell lies inside the array: up to the domain's last vertex but one
+        auto end = [&](int d) { const int a = m.core_st[d] + m.core_sz[d], b = m.dom_lb[d] + m.dom_sz[d] - 1; return a < b ? a : b; };
+        for (c[2] = m.core_st[2]; c[2] < (ND == 3 ? end(2) : 1); c[2] ++)
+          for (c[1] = m.core_st[1]; c[1] < end(1); c[1] ++)
+            for (c[0] = m.core_st[0]; c[0] < end(0); c[0] ++) {
               int corner[N];
               for (int d = 0; d < ND; d ++) corner[d] = c[d];
               corner[ND] = t;
               const SampleIn in{tag_of<ND>(m, fan, corner, t, type), ((unsigned)t << 1) | (fan.ordinal[type] ? 1u : 0u), 0u};
               int got[N], gtype = -1;
               if (!sample_element<ND>(m, fan, in.tag, in.aux, got, gtype) || gtype != type || memcmp(got, corner, sizeof(corner)) != 0) {
-                fprintf(stderr, "decode: nd %d mode %d t %d type %d corner %d %d %d\n", ND, mode, t, type, c[0], c[1], c[2]);
+                fprintf(stderr, "decode: nd %d origin %d mode %d t %d type %d corner %d %d %d\n", ND, (int)origin, mode, t, type, c[0], c[1], c[2]);
                 return 1;
               }
               double r[2];
@@ -172,7 +174,8 @@ int sweep_all(const fan_table<ND + 1> &fan, int scalar_mode)
 
 int main()
 {
-  if (sweep_all<2>(k_fan3, 1) || sweep_all<2>(k_fan3, 0) || sweep_all<3>(k_fan4, 1) || sweep_all<3>(k_fan4, 0)) return 1;
+  for (int origin = 0; origin < 2; origin ++)
+    if (sweep_all<2>(k_fan3, 1, origin != 0) || sweep_all<2>(k_fan3, 0, origin != 0) || sweep_all<3>(k_fan4, 1, origin != 0) || sweep_all<3>(k_fan4, 0, origin != 0)) return 1;
   printf("sample_host run complete\n");
   return 0;
 }

@@ -53,6 +53,12 @@ def mesh_ints(g, tag_mode):
     return np.array([tag_mode, 1 if g["nv"] == 1 else 0] + pad(st, 0) + pad(sz, 1) + pad(st, 0) + pad(sz, 1) + [0, 0, 0] + pad(g["dims"], 1), dtype=np.int32)
 
 
+def mesh_ints_of(tag_mode, scalar, dom, core, ext):
+    """the twenty ints of ftkx::SampleMesh for any mesh: dom, core, ext = (starts, sizes) per spatial axis, as ftkx_set_mesh takes them"""
+    pad = lambda v, fill: [int(x) for x in v] + [fill] * (3 - len(v))          # noqa: E731
+    return np.array([tag_mode, 1 if scalar else 0] + pad(dom[0], 0) + pad(dom[1], 1) + pad(core[0], 0) + pad(core[1], 1) + pad(ext[0], 0) + pad(ext[1], 1), dtype=np.int32)
+
+
 def aux_words(recs):
     """the aux word of include/ftkx.h from a record array with `ordinal` and `timestep`, or the one with `aux`"""
     if "aux" in recs.dtype.names:
@@ -77,8 +83,9 @@ def work_index_tags(g, tags, aux):
     return (lin * n_scope + local).astype(np.uint64)
 
 
-def host_sample(g, tag_mode, tags, aux, A1=None, A2=None, t0=0, nthreads=1, fields=None):
-    """hs_sample over a fixture's mesh and field arrays (fields: a list to take their place).  A1 / A2: one array per timestep, or None.
+def host_sample(g, tag_mode, tags, aux, A1=None, A2=None, t0=0, nthreads=1, fields=None, mesh=None):
+    """hs_sample over a fixture's mesh and field arrays (fields: a list to take their place; mesh: the twenty ints of another mesh than the
+    fixtures', mesh_ints_of).  A1 / A2: one array per timestep, or None.
     -> (slot 1 values or None, slot 2 values or None, ok flags, number of records that did not decode)"""
     L = host()
     steps = [np.ascontiguousarray(s, dtype=np.float64) for s in (fields if fields is not None else g["steps"])]
@@ -99,7 +106,7 @@ def host_sample(g, tag_mode, tags, aux, A1=None, A2=None, t0=0, nthreads=1, fiel
     o1 = np.full(n, 777.0) if A1 is not None else None
     o2 = np.full(n, 777.0) if A2 is not None else None
     ok = np.zeros(n, dtype=np.uint8)
-    mesh = mesh_ints(g, tag_mode)
+    mesh = mesh_ints(g, tag_mode) if mesh is None else np.ascontiguousarray(mesh, dtype=np.int32)
     slots = (1 if A1 is not None else 0) | (2 if A2 is not None else 0)
     bad = L.hs_sample(g["nd"], mesh.ctypes.data, tags.ctypes.data, aux.ctypes.data, n, int(t0), nt, f_tab if scalar else None, None if scalar else f_tab, a1, a2, slots,
                       int(nthreads), None if o1 is None else o1.ctypes.data, None if o2 is None else o2.ctypes.data, ok.ctypes.data)

@@ -52,6 +52,27 @@ def test_own_scalar_field_sampled_is_the_references_scalar0(hs, name):
     assert SC.same_doubles(o2, r["scalar"])
 
 
+@pytest.mark.parametrize("name", ["2d_scalar_40x23_ragged", "3d_scalar_40x21x11_ragged", "3d_scalar_42x19x9_aligned"])
+def test_own_scalar_field_sampled_on_a_mesh_with_an_origin(hs, oracle, name):
+    """the array lattice at (5, 7[, 3]), a core strictly inside the domain (tests/mesh_cases.py): the sample lanes subtract ext_st where they
+    index S and decode tags relative to the domain -- a case's own S sampled at the oracle's records is the oracle's scalar[0]"""
+    import mesh_cases as M
+    c = M.cases()[name]
+    r, _, _ = M.reference(c)
+    assert len(r) >= 100 and list(c.ext[0]) == [5, 7, 3][:c.nd] and c.core != c.dom
+    g = dict(nd=c.nd, nv=1, dims=list(c.dims), steps=[c.slices()[t] for t in c.slice_ts])
+    assert c.slice_ts == list(range(len(c.slice_ts)))
+    mesh = SC.mesh_ints_of(SC.TAG_EXACT64, True, c.dom, c.core, c.ext)
+    o1, o2, ok, bad = SC.host_sample(g, SC.TAG_EXACT64, r["tag"], SC.aux_words(r), A1=g["steps"], A2=g["steps"], mesh=mesh)
+    assert bad == 0 and ok.all()
+    assert SC.same_doubles(o1, r["scalar"][:, 0]), f"{name}: {int((o1.view(np.uint64) != r['scalar'][:, 0].view(np.uint64)).sum())} of {len(r)} values differ from the oracle's scalar[0]"
+    assert SC.same_doubles(o2, o1)
+    # the same tags read with the array lattice at 0 do not give these values: the origin matters to the case
+    zero = SC.mesh_ints_of(SC.TAG_EXACT64, True, c.dom, c.core, ([0] * c.nd, c.ext[1]))
+    z1, _, _, _ = SC.host_sample(g, SC.TAG_EXACT64, r["tag"], SC.aux_words(r), A1=g["steps"], mesh=zero)
+    assert not SC.same_doubles(z1, o1)
+
+
 # ---- 2. a foreign field against the pinned oracle ---------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", SC.FOREIGN)
 def test_foreign_field_is_what_the_oracle_gives_with_it_as_S(hs, oracle, name):
