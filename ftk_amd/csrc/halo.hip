@@ -93,7 +93,12 @@ size_t pad8(size_t v) { return (v + 7) / 8 * 8; }
 int factor_log2(unsigned long long f) { int b = 0; while (b < 63 && (1ull << b) < f) b ++; return b; }
 // capacity of the word list in a packed mask message: the mask kernels write a word only where its summary is 0 -- a thin shell around
 // the zero sets of the components; 1/64 of all words is generous for smooth data, and a slice that needs more is sent as it is
-size_t packed_word_capacity(const ftkx_ctx *c) { return std::max<size_t>(4096, mask_bytes(c) / 8 / 64); }
+size_t packed_word_capacity(const ftkx_ctx *c)
+{
+  const long forced = getenv("FTKX_HALO_WORDS") ? atol(getenv("FTKX_HALO_WORDS")) : 0;      // (tests: a list exactly full, one word short; read afresh by every call, on both sides of a message)
+  if (forced > 0) return (size_t)forced;
+  return std::max<size_t>(4096, mask_bytes(c) / 8 / 64);
+}
 }
 
 }  // extern "C"
@@ -251,7 +256,9 @@ int ftkx_push_masked_slice_packed(ftkx_ctx *c, int t, int scalar_input, const vo
     }
     // summaries and words: count, geometry, the sender's mask settings and factor (it must not exceed the factor the receiver was told:
     // masks serve their own factor and larger ones) and every index are checked on the device; a message that does not fit raises the
-    // flag ftkx_sweep_cull looks at
+    // flag ftkx_sweep_cull looks at.  The flag speaks of THIS message: what an earlier, refused one left standing is taken down first (as
+    // ftkx_push_masked_slice does), or a good message behind a refused one would be turned away with it
+    HIP_TRY(c, hipMemsetAsync(halo_bad_flag(c), 0, sizeof(u64), c->stream));
     ftkx::launch_scatter_packed((const u64 *)in, (const unsigned *)(in + 32 + pad8(ub)), (const u64 *)(in + 32 + pad8(ub) + pad8(cap * sizeof(unsigned))), ub, cap, m.u_rows,
                                 factor_log2(mask_factor), s.U.as<unsigned char>(), s.M.as<unsigned char>(), mask_bytes(c) / 8, halo_bad_flag(c), c->stream);
     HIP_TRY(c, hipGetLastError());

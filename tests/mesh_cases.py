@@ -133,9 +133,9 @@ def cases():
     return _cache["mesh_cases"]
 
 
-def planned(c, u_rows=None):
+def planned(c, u_rows=None, rows=False):
     """(the kernel's name, has_summary) plan_masks gives the case's shape under its FTKX_MASK_PLAN and FTKX_U_ROWS = u_rows, through
-    tests/hostcheck/hostcheck.cpp as tests/test_mask_plan.py drives it"""
+    tests/hostcheck/hostcheck.cpp as tests/test_mask_plan.py drives it; rows=True: (name, has_summary, the rows a summary byte stands for)"""
     import ctypes as C
     import os
     import subprocess
@@ -152,7 +152,7 @@ def planned(c, u_rows=None):
     out = (C.c_longlong * (14 + 2 * 47))()
     name = C.create_string_buffer(64)
     _cache["plan_lib"].hc_mask_plan(shape, c.mask_plan.encode() if c.mask_plan else None, None if u_rows is None else str(u_rows).encode(), c.n + 1, 0, out, name)
-    return name.value.decode(), bool(out[2])
+    return (name.value.decode(), bool(out[2]), int(out[3])) if rows else (name.value.decode(), bool(out[2]))
 
 
 def array_rel(c, recs):

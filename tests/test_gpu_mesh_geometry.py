@@ -13,6 +13,7 @@ import mesh_cases as M
 import one_launch_cases as K
 import sample_cases as SC
 from common import assert_records_equal
+from halo_cases import patch_addresses
 
 pytestmark = pytest.mark.gpu
 
@@ -418,15 +419,7 @@ def test_patches_round_trip_with_an_array_origin(gpu, cases, name):
 
     def where(cells):
         """array index (flat, x fastest) of every element of every cell's patch"""
-        lin = np.asarray(cells, dtype=np.int64)
-        q = np.arange(6 ** nd)
-        at = np.zeros((len(lin), 6 ** nd), dtype=np.int64)
-        stride = 1
-        for d in range(nd):
-            corner = c.core[0][d] + lin % c.core[1][d] - c.ext[0][d]; lin = lin // c.core[1][d]
-            x = np.clip(corner[:, None] - 2 + (q % 6)[None, :], 0, dims[d] - 1); q = q // 6
-            at += x * stride; stride *= dims[d]
-        return at
+        return patch_addresses(c, cells)
     B = _ctx(gpu, c)
     push(B, 1, a)
     assert B.patch_doubles() == 6 ** nd * ncomp

@@ -41,13 +41,20 @@ def _make_ctx(gpu, nd, nv, dims, stream):
 
 
 class Rank:
-    def __init__(self, gpu, torch, dev, stream, nd, nv, dims, steps, nt, world, rank):
+    def __init__(self, gpu, torch, dev, stream, nd, nv, dims, steps, nt, world, rank, make_ctx=None, cut=None):
+        """make_ctx: stream -> a context on a mesh of the caller's (None: _make_ctx -- the array at 0, core = domain); cut: the slabs' bounds
+        (0, b1, .., nt), slab r owning b[r] .. b[r + 1] - 1 (None: tslab's even partition)"""
         from ftk_amd import tslab
         self.gpu, self.torch, self.rank, self.world, self.nt = gpu, torch, rank, world, nt
-        t0, t1 = tslab.slab_range(nt, world, rank)
+        if cut is None:
+            cut = [tslab.slab_range(nt, world, r)[0] for r in range(world)] + [nt]
+            assert all(tslab.slab_range(nt, world, r) == (cut[r], cut[r + 1]) for r in range(world))
+        assert len(cut) == world + 1 and cut[0] == 0 and cut[-1] == nt
+        owner_of = lambda t: [r for r in range(world) if cut[r] <= t < cut[r + 1]][0]
+        t0, t1 = cut[rank], cut[rank + 1]
         self.own = list(range(t0, t1))
         self.scalar = nv == 1
-        self.ctx = _make_ctx(gpu, nd, nv, dims, stream) if self.own else None
+        self.ctx = (make_ctx(stream) if make_ctx is not None else _make_ctx(gpu, nd, nv, dims, stream)) if self.own else None
         self.dev_slices = {}
         for t in self.own:
             a = torch.from_numpy(np.ascontiguousarray(steps[t])).to(dev)
@@ -55,8 +62,8 @@ class Rank:
             (self.ctx.push_scalar_slice if self.scalar else self.ctx.push_slice)(t, a)
         self.open, self.stash = 0, []            # passes in flight; outcomes of passes collected early (a recovery needs the context free)
         self.t_halo = t1 if (self.own and t1 < nt) else None
-        self.lower = tslab.owner_of(t0 - 1, nt, world) if self.own and t0 > 0 else None
-        self.upper = tslab.owner_of(t1, nt, world) if self.t_halo is not None else None
+        self.lower = owner_of(t0 - 1) if self.own and t0 > 0 else None
+        self.upper = owner_of(t1) if self.t_halo is not None else None
         self.ts = np.array(self.own, dtype=np.int32)
         self.scopes = np.array([gpu.SCOPE_BOTH if t + 1 < nt else gpu.SCOPE_ORDINAL for t in self.own], dtype=np.int32)
         f64, i64, u8 = torch.float64, torch.int64, torch.uint8
@@ -74,8 +81,9 @@ class Rank:
                 self.sets.append(dict(contrib=torch.tensor([DBL_MAX, 0.0, DBL_MAX, 0.0], dtype=f64, device=dev), gathered=z(4 * world, f64)))
 
 
-def _slab_pass(ranks, k, running=None):
-    """one pass of every rank, stage by stage, the messages handed over in between (what tslab.SlabSeries.submit does over torch.distributed)"""
+def _slab_pass(ranks, k, running=None, tamper=None):
+    """one pass of every rank, stage by stage, the messages handed over in between (what tslab.SlabSeries.submit does over torch.distributed);
+    tamper(ranks, k): called with the masks delivered and not yet read (a test of the receiver's checks changes them there)"""
     torch = ranks[0].torch
     live = [r for r in ranks if r.own]
     for r in live:
@@ -87,6 +95,8 @@ def _slab_pass(ranks, k, running=None):
     for r in live:
         if r.upper is not None:
             r.sets[k]["masks_in"].copy_(ranks[r.upper].sets[k]["masks_out"])
+    if tamper is not None:
+        tamper(ranks, k)
     for r in live:
         b = r.sets[k]
         r.ctx.series_dist_cull(b["masks_in"] if r.upper is not None else None, b["req_out"] if r.upper is not None else None)
@@ -214,7 +224,8 @@ TALLY = {"ok": 0, "unsupported": 0, "recovered": 0, "records": 0}
 @pytest.mark.parametrize("seed", range(int(os.environ.get("FTKX_SLAB_FUZZ_SEEDS", "60"))))
 def test_slabs_in_one_process_add_up_to_the_whole_series(gpu, seed, monkeypatch):
     rng = np.random.default_rng(4200 + seed)
-    # (the request's capacity is read once per process: all seeds of one run share it -- small, so that recoveries happen)
+    # (the request's capacity is the default of each mesh -- FTKX_DIST_CELLS, which series.hip reads afresh on every call, is not set here:
+    # at most a sixteenth of a slice in patches, so hit-dense fields ask for the whole slice and recoveries happen)
     for case in range(4):
         nd = int(rng.choice([2, 3]))
         nv = int(rng.choice([1, 1, nd]))
@@ -241,8 +252,8 @@ def test_the_in_process_slabs_took_every_way(gpu):
 
 
 def test_small_requests_force_the_whole_slice(gpu):
-    """requests of at most two cells (FTKX_DIST_CELLS is read once per process: a child process): hit-dense data asks for the whole slice in
-    every pass -- the same records"""
+    """requests of at most two cells (FTKX_DIST_CELLS, read by series.hip on every call; set for a child process, whose contexts all see
+    it alike): hit-dense data asks for the whole slice in every pass -- the same records"""
     import subprocess
     import sys
     code = (
